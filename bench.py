@@ -2,14 +2,18 @@
 """Headline benchmark: tiles/s of the YOLOv3 hot path (1024x1024 RGB tiles, bf16 MFMA backbone+FPN, decode, merge-NMS)
 on MI355X.  One "step" = one pass over one batch of 64 device-resident synthetic tiles (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline; --dump-outputs DIR also writes the last timed step's
+detections as .npy files.  --full adds everything else: the HIP-event roofline of the dominant kernel family, the other 16-bit
+storage type, the two-batches-in-flight leg, the training and fp32 legs, the CPU baseline and the parity against it.
 
 N > 1 runs one rank per GPU either way it is started: under `python -m torch.distributed.run --nproc-per-node N` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* come from the environment), or from a plain `python bench.py --gpus N`, in which case this process starts the
 N ranks itself as child processes -- before it imports torch or touches HIP -- waits for them, forwards rank 0's JSON line and
 exits with their return code (`launch_ranks`).
 
-Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` for the dominant kernel
+Prints ONE JSON line on rank 0 (contract in the task description).  With --full it carries `roofline` for the dominant kernel
 (3x3 stride-1 MFMA convolution, BN=128 tile) timed with HIP events on the launch stream inside the timed region and
 `cpu_baseline` = the CPU oracle (torch-CPU fp32 + restated decode/NMS) on a bounded sample of the same workload.
 """
@@ -48,7 +52,7 @@ def parse():
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16",
                     help="16-bit storage type of the timed inference path: bf16 = BASELINE.json configs[1] as written (and the faster one: the "
                          "power-limited chip clocks 4 %% lower on fp16 operands); fp16 = the more faithful one (0.98 vs 0.83 of the reference's NMS "
-                         "indices).  The other type's timing and parity ride in the same line (other_dtype, parity_<other>); DESIGN.md section 2")
+                         "indices).  The other type's timing and parity ride in the --full line (other_dtype, parity_<other>); DESIGN.md section 2")
     ap.add_argument("--classes", type=int, default=3)
     ap.add_argument("--conf_thres", type=float, default=0.5)
     ap.add_argument("--nms_thres", type=float, default=0.4)
@@ -66,7 +70,29 @@ def parse():
                          "and rank 0 prints one JSON line; tests/test_dp_cpu.py drives the self-launcher through this on CPU-only boxes")
     ap.add_argument("--traffic_json", default=os.path.join(REPO, "profiles", "traffic.json"),
                     help="optional {kernel family: HBM bytes per launch} from a rocprofv3 --pmc pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (HIP events), other dtype, pipelined, train and fp32 legs, CPU baseline and parity "
+                         "(each still subject to its --no_* switch); --mode train: its CPU baseline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
+                    help="write the last timed step's merge-NMS result (rows, keep_idx, count, cand_count) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.dump_outputs and a.mode != "infer":
+        ap.error("--dump-outputs applies to --mode infer")
+    return a
+
+
+_CFG_DIR = None
+
+
+def bench_cfg(classes):
+    """Path of the generated YOLOv3 cfg, written to a temporary directory of this process: the checkout may be read-only for the
+    user who runs the benchmark, so nothing is written into the package."""
+    global _CFG_DIR
+    import tempfile
+    from amyloid_yolo_paper_amd import cfg_gen
+    if _CFG_DIR is None:
+        _CFG_DIR = tempfile.TemporaryDirectory(prefix="ay_bench_cfg_")
+    return cfg_gen.write_cfg(classes, _CFG_DIR.name)
 
 
 def csrc_sha16():
@@ -185,7 +211,7 @@ def main():
         else:
             dist.init_process_group("gloo")
 
-    from amyloid_yolo_paper_amd import _lib, build as aybuild, cfg_gen, parse_config, synth
+    from amyloid_yolo_paper_amd import _lib, build as aybuild, parse_config, synth
     from amyloid_yolo_paper_amd.models import Darknet
     from amyloid_yolo_paper_amd.utils import nms_device
 
@@ -198,7 +224,7 @@ def main():
         if USE_DIST:
             dist.barrier()
 
-    cfg = cfg_gen.write_cfg(a.classes)
+    cfg = bench_cfg(a.classes)
     defs = parse_config.parse_model_config(cfg)
     params = synth.synth_params(defs, seed=7)
     def make_model(precision):
@@ -250,12 +276,13 @@ def main():
         slot_free[slot] = done
         return res
 
+    layer_events = a.full and not a.no_layer_events
     for _ in range(a.warmup):
         res = step()
     torch.cuda.synchronize()
     if USE_DIST:
         dist.barrier()
-    if not a.no_layer_events:
+    if layer_events:
         if model.use_plan:  # HIP event pairs around the family's launches, recorded by the native plan on the stream it issues to
             model.plan_profile_begin(a.batch, a.size, set(fam), every=a.event_every)
         else:               # AY_USE_PLAN=0: the per-layer walk brackets the same launches itself
@@ -275,12 +302,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     events = []
-    if not a.no_layer_events and model.use_plan:
+    if layer_events and model.use_plan:
         per_op, n_fwd = model.plan_profile_end(a.batch, a.size)
         assert n_fwd == (a.steps + a.event_every - 1) // a.event_every   # the forwards that carried event pairs
         famset = set(fam)
         events = [ms for layer, kind, ms in per_op if layer in famset]   # per family launch: ms summed over the timed steps
-    elif not a.no_layer_events:
+    elif layer_events:
         n_fwd = a.steps
         by_layer = {}
         for layer, s, e in model.profile_events:
@@ -288,13 +315,15 @@ def main():
         events = list(by_layer.values())
         model.profile_layers = None
 
+    if a.dump_outputs and rank == 0:   # before the --full legs: they reuse the persistent NMS output buffers
+        dump_outputs(a.dump_outputs, res)
     rows, keep, count, cand = res
     cnt, cnd = count.cpu().numpy(), cand.cpu().numpy()
     # the other 16-bit storage type on the same workload, same protocol (own warm-up, barrier + synchronize around the same number
     # of steps): reported beside the headline, never in place of it
     other = "bf16" if a.dtype == "fp16" else "fp16"
     other_line = None
-    if not a.no_other_dtype:
+    if a.full and not a.no_other_dtype:
         main_model, model = model, make_model(other)
         slot_free[0] = slot_free[1] = None
         for _ in range(a.warmup):
@@ -322,7 +351,7 @@ def main():
     # the gaps in between -- which is what this leg measures.  It is reported beside the headline, never as `value`: once launches of
     # two streams overlap, the per-launch HIP-event times the roofline is built from include the other stream's work.
     pipelined = None
-    if not a.no_pipelined_leg and a.gpus == 1:
+    if a.full and not a.no_pipelined_leg and a.gpus == 1:
         try:
             pipes = [(model, torch.cuda.Stream(device=dev), 0), (make_model(a.dtype), torch.cuda.Stream(device=dev), 2)]
             torch.cuda.synchronize()
@@ -389,7 +418,7 @@ def main():
     # parity-grade fp32 path's tiles/s.  All GPU legs first, the host-heavy CPU baseline + parity legs last.  RCCL comes up only now
     # (an initialised communicator costs the inference step 3 %, see above) as a second process group next to the gloo one.
     del x, res, rows, keep, count, cand
-    if not a.no_train_leg:
+    if a.full and not a.no_train_leg:
         group = None
         try:
             if USE_DIST:
@@ -402,12 +431,12 @@ def main():
         except Exception as exc:  # the headline number stands on its own
             result["train"] = {"error": f"{type(exc).__name__}: {exc}"}
     if rank == 0:
-        if not a.no_fp32_leg and a.gpus == 1:
+        if a.full and not a.no_fp32_leg and a.gpus == 1:
             try:
                 result["fp32_path"] = measure_fp32_path(a, cfg, params, dev)
             except Exception as exc:
                 result["fp32_path"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not a.no_cpu_baseline and a.gpus == 1:
+        if a.full and not a.no_cpu_baseline and a.gpus == 1:
             result["cpu_baseline"], ref_dets, ref_tiles = cpu_baseline(a, cfg, params)
             result["parity"] = parity_vs_cpu(a, model, ref_dets, ref_tiles)     # the dtype that was timed
             result["parity_" + other] = parity_vs_cpu(a, other_model if other_line is not None else make_model(other), ref_dets, ref_tiles)  # the other 16-bit storage type, same tiles
@@ -417,18 +446,32 @@ def main():
         dist.destroy_process_group()
 
 
+def dump_outputs(path, res):
+    """--dump-outputs: the last timed step's nms_device result as its caller receives it (rows [B,max_det,7], keep_idx [B,max_det],
+    count [B], cand_count [B]).  The output buffers are persistent, so entries past an image's count hold stale values: they are
+    written as 0 (rows) and -1 (keep_idx) to make two runs comparable.  Integers go out as float64 (exact)."""
+    import numpy as np
+    rows, keep, count, cand = (t.cpu().numpy() for t in res)
+    valid = np.arange(keep.shape[1])[None, :] < count[:, None]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows.npy"), np.where(valid[..., None], rows, 0.0).astype(np.float32))
+    np.save(os.path.join(path, "keep_idx.npy"), np.where(valid, keep, -1).astype(np.float64))
+    np.save(os.path.join(path, "count.npy"), count.astype(np.float64))
+    np.save(os.path.join(path, "cand_count.npy"), cand.astype(np.float64))
+
+
 def measure_train(a, rank, world, dev, B, S, steps, warmup, group=None):
     """BASELINE.json configs[2]/[3]: random-init YOLOv3 (3 classes), batch B per GPU, synthetic boxes; one step = forward
     (train-mode BN, loss) + backward + gradient all-reduce over RCCL (N > 1, `group`) + Adam, all inside the timed region.
     Barrier + synchronize on both sides, max over ranks.  Returns the result dict (every rank)."""
     import torch
     import torch.distributed as dist
-    from amyloid_yolo_paper_amd import cfg_gen, synth
+    from amyloid_yolo_paper_amd import synth
     from amyloid_yolo_paper_amd.models import Darknet
     from amyloid_yolo_paper_amd.parallel import FlatAdam, FlatGradReducer, broadcast_parameters
     from amyloid_yolo_paper_amd.utils import weights_init_normal
     torch.manual_seed(1234)
-    model = Darknet(cfg_gen.write_cfg(a.classes), img_size=S, precision="bf16").to(dev)
+    model = Darknet(bench_cfg(a.classes), img_size=S, precision="bf16").to(dev)
     model.apply(weights_init_normal)
     broadcast_parameters(model, group=group)
     model.train()
@@ -525,7 +568,7 @@ def measure_train(a, rank, world, dev, B, S, steps, warmup, group=None):
 def bench_train(a, rank, local_rank, world, dev):
     import torch.distributed as dist
     result = measure_train(a, rank, world, dev, a.train_batch, a.train_size, a.steps, a.warmup)
-    if rank == 0 and not a.no_cpu_baseline and world == 1:
+    if rank == 0 and a.full and not a.no_cpu_baseline and world == 1:
         result["cpu_baseline"] = cpu_train_baseline(a)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -603,12 +646,12 @@ def cpu_train_baseline(a):
     """BASELINE.md section 3, training leg: the CPU oracle (fp32 torch-CPU autograd through the restated graph and loss, pinned to
     the reference's training step by tests/golden/train_*.npz), B=2 at 416^2, 1 warm-up + 4 timed steps with torch.optim.Adam."""
     import torch
-    from amyloid_yolo_paper_amd import cfg_gen, synth
+    from amyloid_yolo_paper_amd import synth
     from oracle.darknet_oracle import OracleDarknet
     cores = host_cores()
     torch.set_num_threads(cores)
     B, S = 2, 416
-    m = OracleDarknet(cfg_gen.write_cfg(a.classes))
+    m = OracleDarknet(bench_cfg(a.classes))
     g = torch.Generator().manual_seed(1234)
     for p in m.params.values():
         p["weight"] = torch.randn(p["weight"].shape, generator=g) * 0.02

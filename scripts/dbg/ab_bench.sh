@@ -5,7 +5,7 @@ cp $L ab/lib_keep.so
 for rep in 1 2; do
   for v in "$@"; do
     cp ab/lib_$v.so $L
-    timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no_cpu_baseline 2>/dev/null | python -c "
+    timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no_cpu_baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline',{})
 print('$v', d['ms_per_step'], 'ms/step', d['value'], 'tiles/s  family', r.get('avg_launch_ms'), 'ms', r.get('frac'))"

@@ -88,12 +88,28 @@ def test_model_forward(golden_dir, tmp_cfg_dir, case):
         f = m.layer_outputs[int(li)].numpy().reshape(-1)
         close(f[z["samp_idx"][k]], z["samp_val"][k])
         close(np.abs(f).max(), z["layer_amax"][k])
+    if "out" in z:   # merge-NMS on the reference's own decode output reproduces the reference's rows
+        rows_r, keep_r, _ = bo.non_max_suppression(z["out"].copy(), 0.5, 0.4)
+        for b in range(B):
+            assert (0 if rows_r[b] is None else len(rows_r[b])) == int(z[f"nms_n{b}"])
+            if rows_r[b] is not None:
+                np.testing.assert_array_equal(keep_r[b], z[f"nms_keep{b}"])
+                close(rows_r[b], z[f"nms_rows{b}"], 1e-6)
+    # ... and on the oracle's.  Its boxes are held to the decode output's bar in the decode output's own form (centre, size): a corner
+    # near 0 is the difference of a centre and a half size of ~10^2 px, where the CPU convolutions' rounding (it differs between
+    # instruction sets) passes the 1e-4 bar on the decode output and not on the corner.
     rows, keep, _ = bo.non_max_suppression(out.copy(), 0.5, 0.4)
     for b in range(B):
         assert (0 if rows[b] is None else len(rows[b])) == int(z[f"nms_n{b}"])
         if rows[b] is not None:
             np.testing.assert_array_equal(keep[b], z[f"nms_keep{b}"])
-            close(rows[b], z[f"nms_rows{b}"])
+            close(_centre_size(rows[b]), _centre_size(z[f"nms_rows{b}"]))
+
+
+def _centre_size(rows):
+    """NMS rows [n, 7] (x1, y1, x2, y2, conf, cls_conf, cls) -> (cx, cy, w, h, conf, cls_conf, cls)"""
+    r = np.asarray(rows, np.float64)
+    return np.concatenate([(r[:, :2] + r[:, 2:4]) / 2, r[:, 2:4] - r[:, :2], r[:, 4:]], axis=1)
 
 
 def test_weights_file_layout(golden_dir, tmp_cfg_dir, tmp_path):
