@@ -112,8 +112,13 @@ __global__ void __launch_bounds__(256) nms_filter_kernel(float* __restrict__ pre
             }
         }
         if (it + 1 < iters) {
+            // The decision must be workgroup-uniform (flush() is a sequence of barriers), so every wave reads kcount between two barriers:
+            // the first ends this iteration's appends, the second keeps any wave from appending the next iteration's keys before the
+            // slowest wave has read it.  kcount <= NMS_FILTER_BUF - 256 at the top of an iteration, so its <= 256 appends stay in kbuf.
             __syncthreads();
-            if (kcount > NMS_FILTER_BUF - 256) flush();   // workgroup-uniform (read behind the barrier)
+            const bool full = kcount > NMS_FILTER_BUF - 256;
+            __syncthreads();
+            if (full) flush();
         }
     }
     flush();
