@@ -33,9 +33,6 @@
 
 namespace ay {
 
-#ifndef AY_M16_PRIO
-#define AY_M16_PRIO 1
-#endif
 #ifdef AY_PHASE_CLOCK
 // instrumented build only (AY_PHASE_CLOCK=1 python build.py, AY_DBG=8 at run time): 100 MHz ticks of wave 0, summed over
 // workgroups: [0] stage loops, [1] epilogues, [2] items, [3] workgroups, [4] whole kernel per workgroup, [5] waits for landed
@@ -231,18 +228,11 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
         const int cbase = cg * BN + wm * 64;  // first channel of this wave
         const int col = (g & 1) * 16 + r;     // pixel column inside the tile row, byte half (g >> 1) * 16 of the 32-byte pixel
         constexpr int NU = MT * (NT / 2);     // 16 store units
-#ifndef AY_M16_RD
-#define AY_M16_RD 8
-#endif
-#ifndef AY_M16_EARLY
-#define AY_M16_EARLY 0
-#endif
         // residual units requested inside the last stage pair: measured SLOWER (4 units: 9 VGPRs spilled in the stage loop, 0.479 ->
-        // 0.485 ms per launch; 8 units: 28 spilled, 0.516 ms) -- the loop sits at ~246 of 256 registers -- so 0; look-ahead inside the
+        // 0.485 ms per launch; 8 units: 28 spilled, 0.516 ms) -- the loop sits at ~246 of 256 registers -- so none; look-ahead inside the
         // epilogue 4 / 8 / 16 units: 0.468 / 0.468 / 0.472 ms (same-box A/B): the residual epilogue is not a latency chain, it is the
         // HBM burst of all CUs reading residual and writing output at the same time
-        constexpr int EARLY = HAS_RES ? AY_M16_EARLY : 0;
-        constexpr int RD = AY_M16_RD;         // residual look-ahead in units inside the epilogue
+        constexpr int RD = 8;                 // residual look-ahead in units inside the epilogue
         u32x4 rres[HAS_RES ? NU : 1];
         u32x4 outv[HAS_RES ? NU : 1];
         auto unit_off = [&](int np, bool clamp, bool& ok) __attribute__((always_inline)) -> unsigned {
@@ -284,14 +274,10 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             constexpr int plist = decltype(PLIST)::value;
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-#if AY_M16_PRIO
                 __builtin_amdgcn_s_setprio(3);
-#endif
 #pragma unroll
                 for (int m = 0; m < MT; ++m) acc[m][n] = DT::mfma16(fa[cur][m], fb[n & 3], acc[m][n]);
-#if AY_M16_PRIO
                 __builtin_amdgcn_s_setprio(2);
-#endif
                 if (n < 4) {
                     fb[n & 3] = ld_b(kind, sl, n + 4);
                     // the next step's first MFMA group needs all four filter fragments: they are requested in the first half of
@@ -351,14 +337,6 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             AY_CLK(if (clk) tk_str += wall_clock64() - tkw;)
             // ---- odd stage (slot 1); the rest of stage s+2 of this item, or of stage 0 of the next, streams into slot 0
             step(I0{}, I1{}, I1{}, I1{}, I1{}, T{}, I4{}, issued, 0);
-            if constexpr (HAS_RES && EARLY > 0) {
-                // the first EARLY residual units are requested three steps (~1.4 us) before the epilogue: their round trip -- ~2 us
-                // when every CU reaches its epilogue together -- otherwise opens the epilogue with nothing to do
-                if (last_pair) {
-#pragma unroll
-                    for (int t = 0; t < EARLY; ++t) load_res(t);
-                }
-            }
             step(I1{}, I1{}, I2{}, I1{}, I0{}, T{}, I0{}, false, 0);
             step(I2{}, I1{}, I3{}, I1{}, I1{}, T{}, I0{}, false, 0);
             step(I3{}, I1{}, I0{}, I0{}, I0{}, F{}, I0{}, false, 0);
@@ -386,7 +364,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
         {
             if constexpr (HAS_RES) {
 #pragma unroll
-                for (int t = EARLY; t < RD; ++t) load_res(t);
+                for (int t = 0; t < RD; ++t) load_res(t);
             }
 #pragma unroll
             for (int np = 0; np < NT / 2; ++np) {
@@ -493,7 +471,6 @@ static int conv3x3_m16_fwd(const ay_conv_desc* d, const void* src, const void* w
     static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;
     a.dbg = dbg;
 #endif
-    a.stagger = 0;
     a.src1 = nullptr;
     a.c1 = 0;
     a.canvas_gx = 0;

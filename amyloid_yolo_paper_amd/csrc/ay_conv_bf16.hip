@@ -235,11 +235,9 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     // 16-byte cells (conflict-free ds_read_b128, as the stride-1 image is); with the plain [half][pixel] image they sit 32 bytes apart
     // and every pixel-fragment read is a 2-way bank conflict (SQ_LDS_BANK_CONFLICT = 0.32 of SQ_LDS_IDX_ACTIVE on these layers,
     // profiles/r04_pmc_sq_v1.txt).  A DMA piece still covers both halves of its pixels, so the global side fetches the same lines
-    // with the same number of requests.  -DAY_S2_DEINT=0 restores the plain image.
-#ifndef AY_S2_DEINT
-#define AY_S2_DEINT 1
-#endif
-    constexpr bool S2L = (STRIDE == 2 && KS == 3 && AY_S2_DEINT);
+    // with the same number of requests.
+    static_assert(STRIDE == 1 || KS == 3, "stride 2: 3x3 kernels only");
+    constexpr bool S2L = (STRIDE == 2);
     constexpr int NEV = TW + 1;                             // even columns of a stride-2 halo row (IN_W = 2 TW + 1)
     constexpr int PIX_SLAB = PX_PIECES * 1024;
     constexpr int W_PIECES = KK2 * 2 * BN * 16 / 1024;      // per 16-channel filter slab
@@ -458,18 +456,15 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     for (int n = 0; n < NT; ++n) {
         const int p = (wn * NT + n) * 32 + c;
         const int ty = p / TW, tx = p % TW;
-        pb[n] = (hh * IN_PIX + ty * STRIDE * IN_W + tx * STRIDE) * 16;
         if constexpr (S2L) {
             pb[n] = (ty * 2 * (2 * IN_W) + hh * NEV + tx) * 16;
             pbo[n] = (ty * 2 * (2 * IN_W) + 2 * NEV + hh * TW + tx) * 16;
+        } else {
+            pb[n] = (hh * IN_PIX + ty * IN_W + tx) * 16;
         }
     }
     const int wa = W_BASE + (hh * BN + wm * MT * 32 + c) * 16;
     const int nstages = a.cin / (16 * NK);
-
-    // de-phase the workgroups: identical items on every CU otherwise put all epilogues (the HBM-heavy phase) at the
-    // same instants and leave HBM idle during the MFMA phases
-    for (int k = 0; k < (slot & 3) * a.stagger; ++k) __builtin_amdgcn_s_sleep(127);
 
     // ---- prologue: NBUF-1 stages in flight, stage 0 landed -----------------------------------------------------
     setup_loader(item);
@@ -651,8 +646,6 @@ int conv_num_cus() {
 // baked into a captured graph node stays valid under the same rule: replay the graph on the stream it was captured on, or on
 // any stream as long as nothing else on the CAPTURE stream runs concurrently.
 unsigned* next_deal_set(hipStream_t st) {
-    static const int dynamic = getenv("AY_DYNAMIC") ? atoi(getenv("AY_DYNAMIC")) : 1;
-    if (!dynamic) return nullptr;
     struct PerDevice {
         unsigned* base = nullptr;
         hipStream_t streams[DEAL_STREAMS] = {};
@@ -678,12 +671,11 @@ unsigned* next_deal_set(hipStream_t st) {
 }
 
 // canvas tiling (ConvArgs::canvas_gx) applies to stride-1 same-size layers that save tiles that way and whose tensors stay below
-// 2 GiB (per-lane image offsets are 32-bit); AY_CANVAS=0 turns it off.
+// 2 GiB (per-lane image offsets are 32-bit).
 // Returns the number of images per canvas row (0: tile image by image) and the canvas' tile grid.
 static int canvas_plan(const ay_conv_desc* d, int th, int tw, int* tiles_x, int* tiles_y) {
-    static const int on = getenv("AY_CANVAS") ? atoi(getenv("AY_CANVAS")) : 1;
     const long long px = (long long)d->hout * d->wout;
-    if (!on || d->out_f32 || d->batch < 2) return 0;
+    if (d->out_f32 || d->batch < 2) return 0;
     if (d->stride == 1 ? (d->hin != d->hout || d->win != d->wout) : (d->hin != 2 * d->hout || d->win != 2 * d->wout)) return 0;
     if ((long long)d->hin * d->win * d->batch * d->cin * 2 >= (1ll << 31) || px * d->batch * d->cout_pad * 2 >= (1ll << 31)) return 0;
     const long long image_tiles = (long long)d->batch * ((d->hout + th - 1) / th) * ((d->wout + tw - 1) / tw);
@@ -722,7 +714,6 @@ static void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const
     a.n_cgroups = d->cout_pad / BN;
     a.leaky = d->leaky;
     a.dbg = 0;
-    a.stagger = 0;
     a.deal = nullptr;
     a.src1 = nullptr;
     a.c1 = 0;
@@ -739,8 +730,6 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
     fill_args(a, d, src, w, scale, shift, residual, out, TH, TW, BN);
     static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;
     a.dbg = dbg;
-    static const int stagger = getenv("AY_STAGGER") ? atoi(getenv("AY_STAGGER")) : 0;
-    a.stagger = stagger;
     long long nblk = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
     int ctx = 0, cty = 0;
     if (RING && (a.canvas_gx = canvas_plan(d, TH, TW, &ctx, &cty)) > 0) {
@@ -758,9 +747,8 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
     if constexpr (RING) {
         static_assert(!OUT_F32, "the ring kernel writes bf16");
         // (the 1x1 kernels once measured 5-20 % slower with dynamic dealing: that was the flat-addressed mailbox draining the DMA
-        // ring, not the counter fetch; with the LDS-typed mailbox they gain slightly, AY_DYN1=0 turns it off for them)
-        static const int dyn1 = getenv("AY_DYN1") ? atoi(getenv("AY_DYN1")) : 1;
-        if (KS == 3 || dyn1) a.deal = next_deal_set(st);
+        // ring, not the counter fetch; with the LDS-typed mailbox they gain slightly)
+        a.deal = next_deal_set(st);
         const int per_xcd = (int)((nblk + 7) / 8);
         const int cu_slots = conv_num_cus() / 8;
         dim3 pgrid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots))), block(512);
@@ -910,30 +898,16 @@ extern "C" int ay_conv_dgrad_s2_bf16(const ay_conv_desc* d, const void* dz, cons
                  d->cout_pad);
     AY_CHECK_ARG((long long)d->hin * d->win * 2 * cin_pad < (1ll << 31), "ay_conv_dgrad_s2_bf16: one image of dx exceeds 2 GiB");
     hipStream_t st = S(stream);
-    const int kin = d->cout_pad;
-    // Class pairs (AY_S2_PAIR, default on): one workgroup computes BOTH column-parity classes of a row parity -- the tile's channels are
-    // the two classes side by side -- so that a wave stores neighbouring pixels in consecutive instructions (whole lines reach HBM).
-    static const int pair = getenv("AY_S2_PAIR") ? atoi(getenv("AY_S2_PAIR")) : 1;
     // (the layers with 128 and more channels are compute-bound: a 256-wide pair tile leaves LDS for 16-channel stages only and
     // measured 2-5 % slower than one class per workgroup; they keep the class form)
-    if (pair && kin % 32 == 0 && cin_pad % 128 != 0) {
-        static const int pth16 = getenv("AY_S2_PAIR_TH16") ? atoi(getenv("AY_S2_PAIR_TH16")) : 1;   // 16x32-pixel items for the 32-channel layer
-        if (pth16 && d->hout >= 16 && cin_pad % 64 != 0) return launch_dgrad_s2<64, 1, 8, 2, 16, true>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-        if (cin_pad % 64 == 0) return launch_dgrad_s2<128, 2, 4, 2, 8, true>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-        return launch_dgrad_s2<64, 1, 8, 2, 8, true>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-    }
-    if (cin_pad % 128 == 0 && kin % 32 == 0) return launch_dgrad_s2<128, 2, 4, 2>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-    // the narrow layers (32 / 64 channels of dx: the first two stride-2 layers) have one or two stages per item and are bound by the
-    // per-item cost of the ring kernel: 16x32-pixel items (half as many): 72.5 -> 72.0 ms per training step at B=32 / 1024^2
-    // (AY_S2_TH16=0: 8x32 items)
-    static const int th16 = getenv("AY_S2_TH16") ? atoi(getenv("AY_S2_TH16")) : 1;
-    if (th16 && d->hout >= 16) {
-        if (cin_pad % 128 != 0 && cin_pad % 64 == 0 && kin % 32 == 0) return launch_dgrad_s2<64, 1, 8, 2, 16>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-        if (cin_pad % 64 != 0 && kin % 32 == 0) return launch_dgrad_s2<32, 1, 8, 2, 16>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-    }
-    if (cin_pad % 64 == 0 && kin % 32 == 0) return launch_dgrad_s2<64, 1, 8, 2>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-    if (kin % 64 == 0) return launch_dgrad_s2<32, 1, 8, 4>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
-    return launch_dgrad_s2<32, 1, 8, 2>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
+    if (cin_pad % 128 == 0) return launch_dgrad_s2<128, 2, 4, 2>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
+    // Class pairs: one workgroup computes BOTH column-parity classes of a row parity -- the tile's channels are the two classes side
+    // by side -- so that a wave stores neighbouring pixels in consecutive instructions (whole lines reach HBM).
+    if (cin_pad % 64 == 0) return launch_dgrad_s2<128, 2, 4, 2, 8, true>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
+    // the 32-channel layer is bound by the per-item cost of the ring kernel: 16x32-pixel items (half as many) where the image has
+    // the rows
+    if (d->hout >= 16) return launch_dgrad_s2<64, 1, 8, 2, 16, true>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
+    return launch_dgrad_s2<64, 1, 8, 2, 8, true>(d, dz, w_s2_packed, ones, zeros, residual, dx, cin_pad, st);
 }
 
 namespace ay {
@@ -956,13 +930,12 @@ static int conv_fwd_16(const ay_conv_desc* d, const void* src, const void* w_pac
     const int cp = d->cout_pad;
     if (d->ksize == 3 && d->stride == 1) {
         AY_CHECK_ARG(!d->out_f32, "ay_conv_fwd_bf16: 3x3 f32 output unsupported");
-        static const int tile16 = getenv("AY_TILE16") ? atoi(getenv("AY_TILE16")) : 1;
         static const int m16 = getenv("AY_M16") ? atoi(getenv("AY_M16")) : 1;
         int ctx = 0, cty = 0;
-        if (cp % 128 == 0 && tile16 && m16 && d->hout >= 16 && d->cin % 32 == 0 && canvas_plan(d, 16, 32, &ctx, &cty) == 0)
+        if (cp % 128 == 0 && m16 && d->hout >= 16 && d->cin % 32 == 0 && canvas_plan(d, 16, 32, &ctx, &cty) == 0)
             return DT::id == AY_DT_F16 ? ay_conv3x3_m16_fwd_f16(d, src, w_packed, scale, shift, residual, out, stream)
                                        : ay_conv3x3_m16_fwd_bf16(d, src, w_packed, scale, shift, residual, out, stream);  // v_mfma_f32_16x16x32_{bf16,f16}
-        if (cp % 128 == 0 && tile16 && d->hout >= 16)
+        if (cp % 128 == 0 && d->hout >= 16)
             return launch<3, 1, 128, 2, 4, 16, 32, 1, false, true, DT>(d, src, w_packed, scale, shift, residual, out, st);
         if (cp % 128 == 0) return launch<3, 1, 128, 2, 4, 8, 32, 1, false, true, DT>(d, src, w_packed, scale, shift, residual, out, st);
         if (cp % 64 == 0) return launch<3, 1, 64, 1, 8, 8, 32, 1, false, true, DT>(d, src, w_packed, scale, shift, residual, out, st);
@@ -982,8 +955,7 @@ static int conv_fwd_16(const ay_conv_desc* d, const void* src, const void* w_pac
             if (cp % 64 == 0) return launch<1, 1, 64, 1, 4, 8, 32, 4, true, false, DT>(d, src, w_packed, scale, shift, residual, out, st);
             return launch<1, 1, 32, 1, 4, 8, 32, 4, true, false, DT>(d, src, w_packed, scale, shift, residual, out, st);
         }
-        static const int bn256 = getenv("AY_BN256") ? atoi(getenv("AY_BN256")) : 1;
-        if (cp % 256 == 0 && !residual && bn256)
+        if (cp % 256 == 0 && !residual)
             return launch_ring1x1<256, 4, 2, false, DT>(d, nullptr, 0, src, w_packed, scale, shift, out, st);
         if (cp % 128 == 0) return launch<1, 1, 128, 2, 4, 8, 32, 4, false, true, DT>(d, src, w_packed, scale, shift, residual, out, st);
         if (cp % 64 == 0) return launch<1, 1, 64, 1, 8, 8, 32, 4, false, true, DT>(d, src, w_packed, scale, shift, residual, out, st);

@@ -1,7 +1,7 @@
 // fp32 parity path: the same convolutional block in the reference's own layout (nchw f32, OIHW f32
 // weights), fp32 accumulation.  Used where results must match the reference's fp32 CPU path
 // to 1e-4 (tests, precision="fp32" mode of the Darknet host class).  The cfg format's shapes (1x1 / 3x3, stride 1 / 2) run on
-// the exact-fp32 MFMA kernel of ay_conv_f32_mfma.hip; the VALU kernel below serves any other shape and AY_F32_MFMA=0.
+// the exact-fp32 MFMA kernel of ay_conv_f32_mfma.hip; the VALU kernel below serves any other shape.
 // Route concat + nearest x2 upsample (models.py:86-96,244-245) are folded into the loader.
 #include "ay_common.h"
 

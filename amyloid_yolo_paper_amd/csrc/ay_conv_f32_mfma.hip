@@ -17,8 +17,6 @@
 // Route concatenation + nearest x2 upsampling (models.py:86-96, 244-245) are folded into the loader exactly as in the VALU
 // kernel: channels [0, cin1) come from src1 (at half resolution when up1), the rest from src2.
 // Epilogue in the reference's operation order, unfused (-ffp-contract=off): y = acc * scale + shift; LeakyReLU; + residual.
-#include <stdlib.h>
-
 #include "ay_common.h"
 
 namespace ay {
@@ -235,16 +233,15 @@ static int launch_f32_mfma(const ay_conv_desc* d, const float* src1, int cin1, i
     return AY_OK;
 }
 
-// ay_conv_f32.hip: the shapes of the cfg format (1x1 / 3x3, stride 1 / 2) go to the matrix cores; anything else, and AY_F32_MFMA=0,
-// stay on the VALU kernel
+// ay_conv_f32.hip: the shapes of the cfg format (1x1 / 3x3, stride 1 / 2) go to the matrix cores; anything else stays on the VALU
+// kernel
 int conv_fwd_f32_mfma(const ay_conv_desc* d, const float* src1, int cin1, int up1, const float* src2, const float* w, const float* scale,
                       const float* shift, const float* residual, float* out, hipStream_t st, bool* taken) {
-    static const int env = getenv("AY_F32_MFMA") ? atoi(getenv("AY_F32_MFMA")) : 1;
     const int kc = d->ksize == 1 ? 16 : d->stride == 2 ? 4 : 8;
     // buffer descriptors address one image of either source and the filter tensor with 32-bit offsets; a route boundary lies
     // on a stage boundary (the cfgs' routes join 128 / 256-channel tensors)
     const bool fits = (long long)d->cin * d->hin * d->win * 4 < (1ll << 31) && (long long)d->cout * d->cin * d->ksize * d->ksize * 4 < (1ll << 31);
-    const bool on = env && fits && (cin1 == d->cin || cin1 % kc == 0);
+    const bool on = fits && (cin1 == d->cin || cin1 % kc == 0);
     *taken = true;
     if (on && d->ksize == 3 && d->stride == 1) return launch_f32_mfma<3, 1, 8>(d, src1, cin1, up1, src2, w, scale, shift, residual, out, st);
     if (on && d->ksize == 3 && d->stride == 2) return launch_f32_mfma<3, 2, 4>(d, src1, cin1, up1, src2, w, scale, shift, residual, out, st);

@@ -8,7 +8,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -144,8 +143,7 @@ extern "C" int ay_plan_create(const ay_plan_op* ops, int n_ops, const size_t* va
     }
     // ---- detection heads: a linear 1x1 convolution into an fp32 value read by the NEXT op, a decode, and by nothing else ----------
     p->fused.assign(n_ops, 0);
-    static const int fuse_heads = getenv("AY_FUSE_HEAD") ? atoi(getenv("AY_FUSE_HEAD")) : 1;
-    for (int i = 0; fuse_heads && i + 1 < n_ops; ++i) {
+    for (int i = 0; i + 1 < n_ops; ++i) {
         const ay_plan_op& o = p->ops[i];
         const ay_plan_op& y = p->ops[i + 1];
         if (o.kind == AY_OP_CONV && o.conv.out_f32 && o.conv.ksize == 1 && o.conv.stride == 1 && !o.conv.leaky && o.res == AY_PLAN_NONE &&

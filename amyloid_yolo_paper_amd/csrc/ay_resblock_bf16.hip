@@ -66,10 +66,7 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
     // phase B: as the ring kernel's 8x32 tile
     constexpr int WM = BN2 / 64, WN = 8 / WM, MT = 2, NT = (TH * TW) / (WN * 32);
     static_assert(MT * WM * 32 == BN2 && NT * WN * 32 == TH * TW, "tile split");
-#ifndef AY_RESBLOCK_RES_LDS
-#define AY_RESBLOCK_RES_LDS 1
-#endif
-    constexpr bool RES_FROM_LDS = AY_RESBLOCK_RES_LDS && MT * NT <= 4;   // 32 VGPRs of residual held from phase A to the epilogue
+    static_assert(MT * NT <= 4, "32 VGPRs of residual held from phase A to the epilogue");
 
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     __builtin_amdgcn_s_setprio(2);  // above a co-resident merge-NMS wavefront (priority 0)
@@ -232,20 +229,18 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
             // right now, so the lanes pick their residual units (store layout: 16 bytes = channels 8hh.. of one pixel) out of LDS
             // instead of re-reading them from L2 / HBM 20 us later, when 32 CUs x 150 KB per item have pushed them out of the 4-MB
             // slice (the kernel fetched its input 1.91x: profiles/r02_hbm_traffic_v7.txt)
-            if constexpr (RES_FROM_LDS) {
 #pragma unroll
-                for (int kk = 0; kk < NKA; ++kk) {
-                    const int chunk = sa * NKA + kk;           // 16-channel plane of x
-                    if ((chunk >> 2) == wm) {                  // this wave's 64 output channels (wave-uniform)
+            for (int kk = 0; kk < NKA; ++kk) {
+                const int chunk = sa * NKA + kk;           // 16-channel plane of x
+                if ((chunk >> 2) == wm) {                  // this wave's 64 output channels (wave-uniform)
 #pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-                            const uint4 v = *reinterpret_cast<const uint4*>(L + kk * XSLAB + rp[n]);
-                            // rr.r[m][n][qp], m = (chunk >> 1) & 1, qp = chunk & 1: written through constant indices
-                            if (((chunk >> 1) & 1) == 0) {
-                                if ((chunk & 1) == 0) rr.r[0][n][0] = v; else rr.r[0][n][1] = v;
-                            } else {
-                                if ((chunk & 1) == 0) rr.r[1][n][0] = v; else rr.r[1][n][1] = v;
-                            }
+                    for (int n = 0; n < NT; ++n) {
+                        const uint4 v = *reinterpret_cast<const uint4*>(L + kk * XSLAB + rp[n]);
+                        // rr.r[m][n][qp], m = (chunk >> 1) & 1, qp = chunk & 1: written through constant indices
+                        if (((chunk >> 1) & 1) == 0) {
+                            if ((chunk & 1) == 0) rr.r[0][n][0] = v; else rr.r[0][n][1] = v;
+                        } else {
+                            if ((chunk & 1) == 0) rr.r[1][n][0] = v; else rr.r[1][n][1] = v;
                         }
                     }
                 }
@@ -351,7 +346,7 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
             stage_end(issued, !(last_stage && !has_next));
             if (++cur == NBUF) cur = 0;
         }
-        conv_epilogue<BN2, MT, NT, TW, false, true, !RES_FROM_LDS, 2, false, false, DT>(a, acc, rr, b, 0, wm, wn, c, hh, y0, x0,
+        conv_epilogue<BN2, MT, NT, TW, false, true, false, 2, false, false, DT>(a, acc, rr, b, 0, wm, wn, c, hh, y0, x0,
                                                                          reinterpret_cast<const float*>(lds + OFF_SS2));
         if (!has_next) break;
         item = next_item;
@@ -407,7 +402,6 @@ static int resblock_fwd(const void* x, const void* w1_packed, const float* scale
     a.n_cgroups = 1;
     a.leaky = leaky2;
     a.dbg = 0;
-    a.stagger = 0;
     a.deal = nullptr;
     a.canvas_gx = 0;
     a.src1 = nullptr;

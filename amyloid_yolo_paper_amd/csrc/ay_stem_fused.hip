@@ -618,8 +618,8 @@ static int stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const
     a.win = w;
     a.hout = h / 2;
     a.wout = w / 2;
-    static const int v2_env = getenv("AY_STEM_V2") ? atoi(getenv("AY_STEM_V2")) : 1;   // 0: the serial-phase kernel (8x32 items)
-    const bool v2 = v2_env && w % 4 == 0 && (reinterpret_cast<uintptr_t>(x_nchw) & 15) == 0 && 3LL * h * w * 4 < 0x7fffffffLL;
+    // any other image (width not a multiple of 4, unaligned, 2 GiB and more) takes the serial-phase kernel (8x32 items)
+    const bool v2 = w % 4 == 0 && (reinterpret_cast<uintptr_t>(x_nchw) & 15) == 0 && 3LL * h * w * 4 < 0x7fffffffLL;
     a.tiles_x = (a.wout + 31) / 32;
     a.tiles_y = v2 ? (a.hout + 3) / 4 : (a.hout + 7) / 8;
     a.n_cgroups = 1;
@@ -628,7 +628,6 @@ static int stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const
     s.m_tpi = magic((unsigned)(a.tiles_x * a.tiles_y));
     a.leaky = leaky1;
     a.dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;   // read only by the instrumented build (AY_DBGBIT)
-    a.stagger = 0;
     a.deal = nullptr;
     a.canvas_gx = 0;
     a.src1 = nullptr;

@@ -23,14 +23,8 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
 // grid.x = image * chunks + chunk), so a thread keeps the parameters of its 8 channels in registers (thread parity = channel
 // half: all strides are even), and every thread has UNROLL independent 16-byte loads in flight per operand (with one load per
 // loop iteration the passes ran at ~2 TB/s: 41 % of the 1024^2 training step, profiles/r01_train_b16_s1024_kernel_stats.csv).
-#ifndef AY_BN_UNROLL
-#define AY_BN_UNROLL 4
-#endif
-#ifndef AY_BN_ROUNDS
-#define AY_BN_ROUNDS 8
-#endif
-constexpr int BN_UNROLL = AY_BN_UNROLL;   // independent 16-byte loads in flight per thread and operand
-constexpr int BN_ROUNDS = AY_BN_ROUNDS;   // rounds of BN_UNROLL units per thread and workgroup (see bn_chunks)
+constexpr int BN_UNROLL = 4;   // independent 16-byte loads in flight per thread and operand
+constexpr int BN_ROUNDS = 8;   // rounds of BN_UNROLL units per thread and workgroup (see bn_chunks)
 
 // ---- per-channel sums over (B,H,W) of a blocked bf16 tensor: sums[c] += sum z, sums[C + c] += sum z^2 (fp64 atomics, one per
 // channel and workgroup after a reduction through LDS); BWD: a = dy, zt = z: sums = (sum dpre, sum dpre * xhat)

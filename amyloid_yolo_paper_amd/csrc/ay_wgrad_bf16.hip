@@ -393,33 +393,23 @@ __global__ void __launch_bounds__(256) wgrad_reduce_scalar_kernel(const float* _
 }
 
 constexpr int WGRAD_SEGS_1X1 = 4;
-#ifndef AY_WGRAD_WIDE_SEGS
-#define AY_WGRAD_WIDE_SEGS 2
-#endif
-constexpr int WGRAD_SEGS_1X1_WIDE = AY_WGRAD_WIDE_SEGS;                     // the 128 x 128 tile of the 1x1 layers: 16 KiB per segment,
-constexpr int WGRAD_NBUF_1X1_WIDE = 8 / AY_WGRAD_WIDE_SEGS;                 // 8 segment buffers (128 KiB) either way
-#ifndef AY_WGRAD_SEGS_3X3
-#define AY_WGRAD_SEGS_3X3 2
-#endif
-constexpr int WGRAD_NBUF_3X3 = AY_WGRAD_SEGS_3X3 == 1 ? 4 : (AY_WGRAD_SEGS_3X3 == 2 ? 3 : 2);   // 6 segment buffers (126 KiB) either way
-constexpr int WGRAD_SEGS_3X3 = AY_WGRAD_SEGS_3X3;   // 3x3 stride 1: 2 segments per K step from a ring of 3 stages (126 KiB)
+constexpr int WGRAD_SEGS_1X1_WIDE = 2, WGRAD_NBUF_1X1_WIDE = 4;   // the 128 x 128 tile of the 1x1 layers: 16 KiB per segment, 8 segment buffers (128 KiB)
+constexpr int WGRAD_SEGS_3X3 = 2, WGRAD_NBUF_3X3 = 3;            // 3x3 stride 1: 2 segments per K step from a ring of 3 stages (126 KiB)
 
 // narrow layers (see the kernel template): 3x3 with at most 4 x 2 planes, 1x1 with at most 2 x 4
 static bool wgrad_narrow(const ay_conv_desc* d) {
-    static const int on = getenv("AY_WGRAD_NARROW") ? atoi(getenv("AY_WGRAD_NARROW")) : 1;
     const int CIP = (d->cin + 15) / 16;
     const int COP = (d->cout_pad > 0 ? d->cout_pad : (d->cout + 15) / 16 * 16) / 16;
-    return on && (d->ksize == 3 ? (COP <= 4 && CIP <= 2) : (COP <= 2 && CIP <= 4));
+    return d->ksize == 3 ? (COP <= 4 && CIP <= 2) : (COP <= 2 && CIP <= 4);
 }
 
 // 1x1 layers with at least 128 x 128 filters: a 128 x 128 filter tile (8 x 8 planes, one ci plane and all 8 co planes per wave: 32
 // accumulator registers -- a 1x1 has one tap).  dz is then fetched once per 128 input channels instead of once per 64: the 1x1 weight
 // gradients are bound by their operand traffic, not by the matrix pipe (256->128 at 128^2, B=32: dz read by 4 ci blocks before).
 static bool wgrad_wide1x1(const ay_conv_desc* d) {
-    static const int on = getenv("AY_WGRAD_WIDE1") ? atoi(getenv("AY_WGRAD_WIDE1")) : 1;
     const int CIP = (d->cin + 15) / 16;
     const int COP = (d->cout_pad > 0 ? d->cout_pad : (d->cout + 15) / 16 * 16) / 16;
-    return on && d->ksize == 1 && COP >= 8 && CIP >= 8;
+    return d->ksize == 1 && COP >= 8 && CIP >= 8;
 }
 
 static long long wgrad_split(const ay_conv_desc* d, int* cob, int* cib, long long* total) {
@@ -436,7 +426,7 @@ static long long wgrad_split(const ay_conv_desc* d, int* cob, int* cib, long lon
         *total = (*total + sg - 1) / sg;
     }
     if (d->ksize == 3 && d->stride == 1) *total = (*total + WGRAD_SEGS_3X3 - 1) / WGRAD_SEGS_3X3;
-    static const int wg_target = getenv("AY_WGRAD_WGS") ? atoi(getenv("AY_WGRAD_WGS")) : 256;
+    constexpr int wg_target = 256;
     long long ks = ((narrow ? 2 : 1) * wg_target + (long long)*cob * *cib - 1) / ((long long)*cob * *cib);   // ~1 workgroup per CU overall (narrow: 2) ...
     if (ks > *total / 24) ks = *total / 24;                                            // ... but >= 24 K steps each (pipeline fill, epilogue)
     if (ks > *total) ks = *total;
@@ -509,7 +499,7 @@ extern "C" int ay_conv_wgrad_bf16_ws(const ay_conv_desc* d, const void* x_blocke
     dim3 grid((unsigned)(cob * cib * ks)), block(512);
     if (wgrad_narrow(d)) {
         if (d->ksize == 3 && d->stride == 1)
-            hipLaunchKernelGGL((wgrad_bf16_kernel<3, 1, WGRAD_SEGS_3X3, WGRAD_SEGS_3X3 == 1 ? 4 : 3, 4, 2>), grid, block, 0, st, a);
+            hipLaunchKernelGGL((wgrad_bf16_kernel<3, 1, WGRAD_SEGS_3X3, WGRAD_NBUF_3X3, 4, 2>), grid, block, 0, st, a);
         else if (d->ksize == 3)
             hipLaunchKernelGGL((wgrad_bf16_kernel<3, 2, 1, 4, 4, 2>), grid, block, 0, st, a);
         else

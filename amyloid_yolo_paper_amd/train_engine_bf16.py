@@ -18,18 +18,12 @@ shape-keyed pool for the backward's gradient tensors, which are handed back as s
 optimiser step (when a parameter's version or ``parallel.WEIGHT_EPOCH`` changes), not once per forward.
 """
 import ctypes as C
-import os
 
 import torch
 
 from . import _lib
 from ._lib import ConvDesc, check, ptr
 from .train_engine import METRIC_KEYS, _ws
-
-# AY_S2_DGRAD=0: data gradient of the stride-2 layers as a stride-1 convolution over the zero-inserted output gradient (round 1)
-_S2_DGRAD = os.environ.get("AY_S2_DGRAD", "1") != "0"
-# AY_STEM_DIRECT=0: the stem through the generic kernels on a zero-padded 16-channel bf16 copy of the image (round 1)
-_STEM_DIRECT = os.environ.get("AY_STEM_DIRECT", "1") != "0"
 
 
 def _pad(v, m):
@@ -153,7 +147,7 @@ def _pack_weights(model, ctx):
             w = conv.weight.detach()
             rec = ctx.packed.setdefault(i, {})
             cpad = _pad(cout, 32)
-            stem_direct = e["src"] < 0 and _STEM_DIRECT and cout == 32 and cin == 3 and k == 3 and e["stride"] == 1
+            stem_direct = e["src"] < 0 and cout == 32 and cin == 3 and k == 3 and e["stride"] == 1
             if e["src"] < 0:
                 # the stem's generic-kernel images (16 zero-padded input channels) are built by the single-call path below; with the
                 # direct kernels only the [32][32] bf16 filter table exists
@@ -168,7 +162,7 @@ def _pack_weights(model, ctx):
             rec.update(fwd=fwd, cpad=cpad, cin_eff=cin)
             jobs.append((w.data_ptr(), fwd.data_ptr(), 0, cout, cpad, cin, 0, k, fwd.numel() // 2))
             cin_pad = _pad(cin, 32)
-            if e["stride"] == 2 and _S2_DGRAD:
+            if e["stride"] == 2:
                 dg = ctx.get(("pkd", i), (L.ay_packed_dgrad_s2_weight_bytes(cpad, cin_pad),), torch.uint8)
                 jobs.append((w.data_ptr(), dg.data_ptr(), 2, cout, cpad, cin, cin_pad, 3, dg.numel() // 2))
             else:
@@ -565,8 +559,7 @@ def train_backward_bf16(model, stt, grad_scale=None):
         pk = packed[i]
         cin_pad = pk["cin_pad"]
         kin = rec["cpad"]                       # channels of dz's planes (>= cout, multiple of 32)
-        src_dz = dz
-        if e["stride"] == 2 and _S2_DGRAD:
+        if e["stride"] == 2:
             # four stride-1 sub-convolutions of dz with a 2x2 window, one per parity class of the input pixel
             ones, zeros = model._unit(cin_pad, dev)
             first = j not in dval
@@ -576,22 +569,16 @@ def train_backward_bf16(model, stt, grad_scale=None):
                                           cin_pad, st), "ay_conv_dgrad_s2_bf16")
             pool.put(dz)
             continue
-        if e["stride"] == 2:
-            up = pool.get((B, kin // 16, hin, hin, 16))
-            check(L.ay_zero_insert_bf16(ptr(dz), ptr(up), B, kin, hout, hout, hin, hin, st), "ay_zero_insert_bf16")
-            src_dz = up
         ones, zeros = model._unit(cin_pad, dev)
         dd = ConvDesc(B, kin, cin, hin, hin, hin, hin, k, 1, 0, 0, cin_pad)
         first = j not in dval
         if first:
             dval[j] = pool.get((B, cin_pad // 16, hin, hin, 16))
         # (timed with the family where the data gradient is itself a 3x3 s1 convolution onto a multiple of 128 channels)
-        with _Timed(prof, "conv", _family(e) and e["stride"] == 1 and cin % 128 == 0):
-            check(L.ay_conv_fwd_bf16(C.byref(dd), ptr(src_dz), ptr(pk["dgrad"]), ptr(ones), ptr(zeros), None if first else ptr(dval[j]), ptr(dval[j]), st),
+        with _Timed(prof, "conv", _family(e) and cin % 128 == 0):
+            check(L.ay_conv_fwd_bf16(C.byref(dd), ptr(dz), ptr(pk["dgrad"]), ptr(ones), ptr(zeros), None if first else ptr(dval[j]), ptr(dval[j]), st),
                   "ay_conv_fwd_bf16(dgrad)")
         pool.put(dz)
-        if src_dz is not dz:
-            pool.put(src_dz)
     for t in dval.values():
         pool.put(t)
     if hook is not None:

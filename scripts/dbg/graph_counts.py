@@ -1,4 +1,4 @@
-"""Replay a captured detection step on three inputs; print NMS counts of eager steps and replays (run with AY_DYNAMIC=0)."""
+"""Replay a captured detection step on three inputs; print NMS counts of eager steps and replays."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "tests"))

@@ -1,4 +1,4 @@
-"""The body of tests/test_gpu_configs.py::test_hip_graph_of_a_detection_step_replays_after_eager_steps with prints (AY_DYNAMIC=0)."""
+"""The body of tests/test_gpu_configs.py::test_hip_graph_of_a_detection_step_replays_after_eager_steps with prints."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "tests"))

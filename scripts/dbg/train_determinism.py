@@ -1,8 +1,8 @@
 """Diagnosis of tests/test_gpu_train_bf16.py::test_bf16_train_step_tracks_fp32_step (red in GPUTEST_r01.json).
 
 (i)  two bf16 forward+backward passes on the same inputs: are loss and gradients bit-identical?  which parameters differ?
-(ii) the first-step loss / head gradients are written to an .npz so that a second process (AY_CANVAS=0) can be diffed
-     against the default:  python scripts/dbg/train_determinism.py out.npz [ref.npz]
+(ii) the first-step loss / head gradients are written to an .npz so that a second process (another build) can be diffed
+     against it:  python scripts/dbg/train_determinism.py out.npz [ref.npz]
 (iii) the 8-Adam-step sequence of the test, repeated: how far does the end loss move from run to run?
 """
 import os

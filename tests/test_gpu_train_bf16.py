@@ -329,7 +329,7 @@ def test_bf16_train_step_vs_oracle(tmp_cfg_dir):
     lr * sign(g), the 1e-7 run-to-run noise of the split-K weight-gradient atomics decides the sign of near-zero gradients,
     and the loss after 8 steps moved +-20 % between runs of one build (150, 156, 193, 204; scripts/dbg/train_determinism.py).
     The first step itself is reproducible (loss bit-identical, gradients to 2e-6) and independent of canvas tiling
-    (AY_CANVAS=0/1: identical loss, head gradients equal to 4e-8)."""
+    (measured with it off and on: identical loss, head gradients equal to 4e-8)."""
     import os
     from amyloid_yolo_paper_amd import cfg_gen, parse_config, synth
     C_, S, B = 3, 256, 4
