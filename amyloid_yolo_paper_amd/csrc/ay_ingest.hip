@@ -72,6 +72,51 @@ __global__ void __launch_bounds__(256) region_tiles_u8_kernel(const uint8_t* __r
     }
 }
 
+// The same grid with a STEP between tile origins (tile (ty, tx) starts at (ty * step, tx * step); step < tile: overlapping tiles for
+// wsi.detect_region(overlap > 0), step == tile: the grid above).  A thread produces V consecutive output pixels of one row and
+// stores them as one V-float vector per channel plane: the kernel is bound by its 12 B of stores per output pixel, and a 16-byte
+// store per lane moves them in a quarter of the store instructions of the scalar form.
+template <int V>
+__global__ void __launch_bounds__(256) region_tiles_step_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
+                                                                    int tile, int step, int tiles_y, int tiles_x, int S,
+                                                                    float* __restrict__ out) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    const int H = RH / shrink, W = RW / shrink;
+    const float scale = (float)tile / (float)S;
+    const size_t plane = (size_t)S * S;
+    const int SV = S / V;   // S % V == 0 (checked by the entry point)
+    const size_t total = (size_t)tiles_y * tiles_x * S * SV;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x0 = (int)(i % SV) * V, y = (int)((i / SV) % S);
+        const size_t t = i / ((size_t)SV * S);
+        const int ty = (int)(t / tiles_x), tx = (int)(t % tiles_x);
+        const int Y = ty * step + min((int)floorf(y * scale), tile - 1);
+        vec v[3];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int X = tx * step + min((int)floorf((x0 + k) * scale), tile - 1);
+            float px[3] = {1.0f, 1.0f, 1.0f};  // background 255
+            if (Y < H && X < W) {
+                if (shrink == 1) {
+                    const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
+                } else {
+                    const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
+                    const uint8_t* p1 = p0 + stride;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][k] = px[c];
+        }
+        float* o = out + t * 3 * plane + (size_t)y * S + x0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(vec*)(o + c * plane) = v[c];
+    }
+}
+
 }  // namespace ay
 
 extern "C" int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
@@ -88,6 +133,29 @@ extern "C" int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h
     hipLaunchKernelGGL(region_tiles_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, region_h,
                        region_w, row_stride_bytes, shrink, tile, tiles_y, tiles_x, out_size, out_nchw);
     AY_CHECK_LAUNCH("region_tiles_u8_kernel");
+    return AY_OK;
+}
+
+extern "C" int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                              int tile, int step, int tiles_y, int tiles_x, int out_size, float* out_nchw,
+                                              ay_stream_t stream) {
+    using namespace ay;
+    AY_CHECK_ARG(region_hwc_u8 && out_nchw, "ay_ingest_region_tiles_step_u8: null");
+    AY_CHECK_ARG(region_h > 0 && region_w > 0 && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2),
+                 "ay_ingest_region_tiles_step_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    AY_CHECK_ARG(tile > 0 && step > 0 && step <= tile && tiles_y > 0 && tiles_x > 0 && out_size > 0,
+                 "ay_ingest_region_tiles_step_u8: tile grid %dx%d of %d step %d -> %d", tiles_y, tiles_x, tile, step, out_size);
+    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;   // every row of every plane then starts on 16 bytes
+    const size_t total = (size_t)tiles_y * tiles_x * out_size * (out_size / (vec4 ? 4 : 1));
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    if (vec4)
+        hipLaunchKernelGGL(region_tiles_step_u8_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
+                           region_h, region_w, row_stride_bytes, shrink, tile, step, tiles_y, tiles_x, out_size, out_nchw);
+    else
+        hipLaunchKernelGGL(region_tiles_step_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
+                           region_h, region_w, row_stride_bytes, shrink, tile, step, tiles_y, tiles_x, out_size, out_nchw);
+    AY_CHECK_LAUNCH("region_tiles_step_u8_kernel");
     return AY_OK;
 }
 

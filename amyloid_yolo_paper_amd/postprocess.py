@@ -15,6 +15,8 @@ repeat until nothing changes.  The output rows are in that set's iteration order
 image) with the pair order made explicit (rows in input order, merged rows appended): the same rows as the reference whenever
 the clusters are pairs, the reference's algorithm under that order for chains of merges (whose edges depend on the order
 through the one-pixel shrink per merge)."""
+import ctypes as C
+
 import torch
 
 
@@ -103,3 +105,30 @@ def merge_detections_device(rows, count):
     _lib.check(L.ay_merge_detections(_lib.ptr(rows), _lib.ptr(count), B, M, _lib.ptr(out), _lib.ptr(out_count), _lib.stream_ptr()),
                "ay_merge_detections")
     return out, out_count
+
+
+def seam_merge_device(rows, tile_id, seam_thres=0.5, return_stats=False):
+    """Slide-level seam merge for detections of OVERLAPPING tiles (``ay_seam_merge``; ``wsi.detect_region(overlap > 0)`` calls it,
+    callers with their own tiling can).  ``rows`` [M,7] float32 CUDA tensor of (x1, y1, x2, y2, conf, cls_conf, cls_pred) in slide
+    pixels, ``tile_id`` [M] int32: which tile reported the row -> ``keep`` [M] bool on the device.
+
+    Rows are walked by descending ``conf * cls_conf`` (ties: lower index first); a row is dropped iff a row before it that was
+    KEPT has the same class, another tile id and ``inter / min(area_i, area_j) > seam_thres`` (+1 pixel convention; intersection
+    over the smaller box, so that a box truncated by a tile edge is recognised as the second sighting of the whole one).  Rows of
+    one tile never suppress each other.  Runs once per slide and synchronises with the host.  ``return_stats=True`` also returns
+    ``(rows kept, round launches taken)``."""
+    from . import _lib
+    L = _lib.lib()
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == 7
+    rows = rows.contiguous()
+    M = rows.shape[0]
+    tile_id = tile_id.to(device=rows.device, dtype=torch.int32).contiguous()
+    assert tile_id.shape == (M,)
+    keep = torch.zeros(M, device=rows.device, dtype=torch.uint8)
+    stats = torch.zeros(2, device=rows.device, dtype=torch.int32)
+    nbytes = L.ay_seam_merge_workspace_bytes(M)
+    ws = torch.empty(max(nbytes, 1), device=rows.device, dtype=torch.uint8)
+    _lib.check(L.ay_seam_merge(_lib.ptr(rows), _lib.ptr(tile_id), M, C.c_float(seam_thres), _lib.ptr(keep), _lib.ptr(stats), _lib.ptr(ws),
+                               ws.numel(), _lib.stream_ptr()), "ay_seam_merge")
+    keep = keep.bool()
+    return (keep, tuple(int(v) for v in stats.cpu())) if return_stats else keep

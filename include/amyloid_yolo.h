@@ -292,6 +292,12 @@ int ay_ingest_tiles_u8(const void* img_hwc_u8, int batch, int h, int w, int out_
 int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                               int tile, int tiles_y, int tiles_x, int out_size, float* out_nchw, ay_stream_t stream);
 
+/* The same with tile origins `step` apart: tile (ty, tx) starts at (ty * step, tx * step) on the (halved) image, 0 < step <= tile.
+ * step < tile gives tiles that overlap by tile - step pixels (wsi.tile_grid, wsi.detect_region(overlap > 0)); step == tile is
+ * ay_ingest_region_tiles_u8 bit for bit.  Stores 16 bytes per lane when out_size is a multiple of 4 and `out_nchw` is 16-byte aligned. */
+int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                   int tile, int step, int tiles_y, int tiles_x, int out_size, float* out_nchw, ay_stream_t stream);
+
 /* ---- training step, bf16 MFMA path (blocked bf16 activations and activation gradients) ------------- */
 
 /* Train-mode BatchNorm + LeakyReLU (+ fused shortcut add of `skip`) around the MFMA convolution: statistics pass (fp64
@@ -453,6 +459,38 @@ int ay_plan_forward_timed(const ay_plan* plan, const float* x_nchw, void* worksp
 int ay_merge_detections_max_rows(void);
 int ay_merge_detections(const float* rows, const int* count, int batch, int max_rows, float* rows_out, int* count_out,
                         ay_stream_t stream);
+
+/* ---- slide-level seam merge for overlapping tiles (wsi.detect_region(overlap > 0); csrc/ay_seam.hip) --------------------------
+ * THE RULE.  Input: rows [M][7] fp32 (x1, y1, x2, y2, conf, cls_conf, cls_pred) in slide pixels and tile_id [M] int32.  Output: a keep
+ * flag per row and the number kept; rows are never altered, so the result is a subset of the input, bit for bit.
+ *   score_i = conf_i * cls_conf_i (one fp32 multiply).  Rank: i comes before j iff score_i > score_j, or the scores are equal and i < j.
+ *   ov(i, j) = inter / min(area_i, area_j) in fp32 with the +1 pixel convention of bbox_iou(x1y1x2y2=True):
+ *   iw = min(x2_i, x2_j) - max(x1_i, x1_j) + 1, likewise ih, both clamped at 0, inter = iw * ih, area = (x2 - x1 + 1) * (y2 - y1 + 1),
+ *   no fused multiply-add.  Intersection over the SMALLER box, not IoU: the second sighting of an object is often a truncated box.
+ *   Walk the rows in rank order: row i is dropped iff some row j that ranks before it AND WAS KEPT has the same cls_pred, a different
+ *   tile_id and ov(i, j) > seam_thres; otherwise it is kept (exact greedy suppression: a row whose only stronger partner was itself
+ *   dropped is kept).  Rows of one tile never suppress each other.
+ *
+ * ay_seam_append: what ay_nms_merge leaves on the device for one batch (rows [batch][max_det][7], count [batch]) -> the valid rows of
+ * image b, moved to slide coordinates v = fl32(fl32(v * scale) + origin) (origins_xy [batch][2] fp32 = (x, y) of the tile's corner, on
+ * the device), appended with tile_ids[b] (device) behind the slide_count[0] rows the slide buffer holds.  Rows land in image order and,
+ * within an image, in NMS output order (one ordered prefix over count).  slide_count is int32[2] on the device, zeroed by the caller
+ * before the first append: [0] rows held, [1] AY_SEAM_FLAG_* bits.  An image with count > max_det contributes its first max_det rows
+ * and sets AY_SEAM_FLAG_MAX_DET; rows past `capacity` are not written and set AY_SEAM_FLAG_CAPACITY.  Kernel launches only, no host
+ * synchronisation; issue it on the stream of the NMS whose buffers it reads. */
+#define AY_SEAM_FLAG_MAX_DET 1
+#define AY_SEAM_FLAG_CAPACITY 2
+int ay_seam_append(const float* rows, const int32_t* count, int batch, int max_det, float scale, const float* origins_xy,
+                   const int32_t* tile_ids, float* slide_rows, int32_t* slide_tile, int32_t* slide_count, int capacity,
+                   ay_stream_t stream);
+/* ay_seam_merge applies the rule to n_rows rows: keep [n_rows] uint8 (1 = kept), stats int32[2] on the device = (rows kept, round
+ * launches taken).  Work scales with the number of neighbouring pairs (rows binned by cell, cell side from the data, boxes larger than
+ * a cell tested against everything).  Runs once per slide and SYNCHRONISES `stream` with the host (the cell side, and a "rows still
+ * undecided" word every few rounds; the number of rounds is the longest chain of suppressions and is not capped): not for graph
+ * capture.  workspace: 16-byte aligned, ay_seam_merge_workspace_bytes(n_rows) bytes.  Two runs on one input give the same bytes. */
+size_t ay_seam_merge_workspace_bytes(int n_rows);
+int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile, int n_rows, float seam_thres, uint8_t* keep, int32_t* stats,
+                  void* workspace, size_t workspace_bytes, ay_stream_t stream);
 
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call -- so a stream capture of a step (ay_plan_forward + ay_nms_merge ...)

@@ -1,6 +1,7 @@
 """Throughput of the WSI -> tile -> detection stream (§8f N4): a synthetic slide of TY x TX 1536-px tiles in host memory,
 streamed strip by strip (pinned upload on a copy stream, device-side tiling + /255 + resize to 1024), model + merge-NMS.
-usage: python scripts/bench_wsi.py [TY TX] ; prints tiles/s including the PCIe upload (this is NOT bench.py's `value`)."""
+usage: python scripts/bench_wsi.py [TY TX] [--overlap N] [--max-det D] [--reps R] ; prints tiles/s including the PCIe upload (this is NOT
+bench.py's `value`).  --overlap N: tiles that share N pixels (more tiles over the same slide) + the slide-level seam merge."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -9,7 +10,15 @@ from amyloid_yolo_paper_amd.models import Darknet
 from amyloid_yolo_paper_amd.wsi import RegionTileStream, detect_region
 import tempfile
 
-TY, TX = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (8, 32)
+argv = sys.argv[1:]
+opts = {"--overlap": 0, "--reps": 2, "--max-det": 4096}
+for o in opts:
+    if o in argv:
+        k = argv.index(o)
+        opts[o] = int(argv[k + 1])
+        del argv[k:k + 2]
+OVERLAP, REPS = opts["--overlap"], opts["--reps"]
+TY, TX = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (8, 32)
 tile, S = 1536, 1024
 dev = torch.device("cuda:0")
 from amyloid_yolo_paper_amd import parse_config
@@ -27,15 +36,24 @@ base = (base * 255).astype(np.uint8).transpose(0, 2, 3, 1)
 row = np.concatenate([base[i % 4] for i in range(TX)], 1)
 raster = np.concatenate([np.roll(row, 97 * j, 1) for j in range(TY)], 0)
 print("raster", raster.shape, "%.2f GB" % (raster.nbytes / 1e9), flush=True)
-for rep in range(2):
+if OVERLAP:   # the grid over the same slide with overlapping tiles
+    from amyloid_yolo_paper_amd.wsi import tile_grid
+    GY, GX, _ = tile_grid(raster.shape[0], raster.shape[1], tile, OVERLAP)
+    kw = dict(overlap=OVERLAP)
+    det_kw = dict(overlap=OVERLAP, max_det=opts["--max-det"])   # the synthetic tiles are dense: some overlapping tile passes 1 024 rows
+else:
+    GY, GX, kw, det_kw = TY, TX, {}, {}
+for rep in range(REPS):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     n = 0
-    for tiles, cs in RegionTileStream(raster, tile, S):
+    for tiles, cs in RegionTileStream(raster, tile, S, **kw):
         n += tiles.shape[0]
     torch.cuda.synchronize(); t1 = time.perf_counter()
     print("ingest only: %.0f tiles/s (%.1f GB/s of slide)" % (n / (t1 - t0), raster.nbytes / (t1 - t0) / 1e9), flush=True)
-for rep in range(2):
+for rep in range(REPS):
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    res = detect_region(m, raster, tile, S, conf_thres=0.5, nms_thres=0.4, batch_size=TX)
+    res = detect_region(m, raster, tile, S, conf_thres=0.5, nms_thres=0.4, batch_size=GX, **det_kw)
     torch.cuda.synchronize(); t1 = time.perf_counter()
-    print("detect_region: %.0f tiles/s (%d tiles, %d with detections)" % (TY * TX / (t1 - t0), TY * TX, len(res)), flush=True)
+    print("detect_region%s: %.0f tiles/s, %.3f s, %.2f GB/s of slide (%d tiles, %d with detections, %d rows)"
+          % ("(overlap=%d)" % OVERLAP if OVERLAP else "", GY * GX / (t1 - t0), t1 - t0, raster.nbytes / (t1 - t0) / 1e9, GY * GX, len(res),
+             sum(len(d) for _, _, d in res)), flush=True)
