@@ -1,9 +1,12 @@
 // Inference plan: the layer interpreter of the reference (Darknet.forward, models.py:237-255) as a flat op list issued
-// from native code.  The host lowers the cfg graph once (amyloid_yolo_paper_amd/models.py: Darknet._lower); this file
+// from native code.  The host lowers the cfg graph once (amyloid_yolo_paper_amd/models.py: Darknet._lower, the only place that
+// decides which ops run on which values); that op list has two executors: this file, and a host loop (Darknet._run_ops: one
+// library call per op, one tensor per value) used for fp32, kept layer outputs, bracketed events and as this file's reference
+// in the tests.  This file
 //   * checks the dataflow (every value written before it is read),
 //   * lays the values out in one arena: a value's bytes are free again once the op that reads it last has been issued --
 //     the whole plan runs on one stream, so issue order is execution order -- first-fit over [def, last use] lifetimes,
-//   * issues the ops through the same extern "C" entry points a per-layer caller uses (bit-identical results).
+//   * issues the ops through the same extern "C" entry points the host loop uses (bit-identical results).
 // Host code only; nothing here touches the device except through those entry points and HIP events.
 #include <hip/hip_runtime.h>
 
@@ -44,50 +47,45 @@ void op_reads(const ay_plan_op& o, int (&r)[3]) {
     r[2] = o.kind == AY_OP_CONV ? o.res : AY_PLAN_NONE;
 }
 
+// the 16-bit entry points of one storage type; the bfloat16 and half forms have identical signatures
+struct Entries {
+    decltype(&ay_head_decode_fwd_bf16) head_decode;
+    decltype(&ay_stem_s2_fused_fwd) stem_s2_fused;
+    decltype(&ay_stem_conv_fwd) stem;
+    decltype(&ay_conv_fwd_bf16) conv;
+    decltype(&ay_resblock_fwd_bf16) resblock;
+    decltype(&ay_conv1x1_cat_fwd_bf16) conv1x1_cat;
+};
+constexpr Entries ENTRIES_BF16 = {ay_head_decode_fwd_bf16, ay_stem_s2_fused_fwd, ay_stem_conv_fwd,
+                                  ay_conv_fwd_bf16,        ay_resblock_fwd_bf16, ay_conv1x1_cat_fwd_bf16};
+constexpr Entries ENTRIES_F16 = {ay_head_decode_fwd_f16, ay_stem_s2_fused_fwd_f16, ay_stem_conv_fwd_f16,
+                                 ay_conv_fwd_f16,        ay_resblock_fwd_f16,      ay_conv1x1_cat_fwd_f16};
+
 int issue(const ay_plan* p, size_t idx, const float* x, uint8_t* ws, float* out, ay_stream_t st) {
     const ay_plan_op& o = p->ops[idx];
+    const Entries& fn = p->dtype == AY_DT_F16 ? ENTRIES_F16 : ENTRIES_BF16;
     auto at = [&](int v) -> void* { return v >= 0 ? ws + p->offset[v] : nullptr; };
     const ay_conv_desc& d = o.conv;
     if (p->fused[idx] < 0) return AY_OK;   // a decode that went out with its head
     if (p->fused[idx] > 0) {
         const ay_plan_op& y = p->ops[p->fused[idx]];
-        return (p->dtype == AY_DT_F16 ? ay_head_decode_fwd_f16 : ay_head_decode_fwd_bf16)(
-            &d, at(o.src), o.w, o.scale, o.shift, y.num_anchors, y.num_classes, p->img_dim, y.anchors_wh, out, p->n_total, y.row_offset, st);
-    }
-    if (p->dtype == AY_DT_F16) {
-        switch (o.kind) {
-            case AY_OP_STEM_S2_FUSED:
-                return ay_stem_s2_fused_fwd_f16(x, o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst), d.batch,
-                                                p->img_dim, p->img_dim, st);
-            case AY_OP_STEM:
-                return ay_stem_conv_fwd_f16(x, static_cast<const float*>(o.w), o.scale, o.shift, at(o.dst), d.batch, p->img_dim, p->img_dim,
-                                            d.leaky, st);
-            case AY_OP_CONV:
-                return ay_conv_fwd_f16(&d, at(o.src), o.w, o.scale, o.shift, at(o.res), at(o.dst), st);
-            case AY_OP_RESBLOCK:
-                return ay_resblock_fwd_f16(at(o.src), o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst),
-                                           d.batch, d.cin, d.hout, d.wout, st);
-            case AY_OP_CONV1X1_CAT:
-                return ay_conv1x1_cat_fwd_f16(&d, at(o.src), o.c1, at(o.src2), o.w, o.scale, o.shift, at(o.dst), st);
-            default:
-                break;  // 16-bit copies and the fp32 decode: the same entry points
-        }
+        return fn.head_decode(&d, at(o.src), o.w, o.scale, o.shift, y.num_anchors, y.num_classes, p->img_dim, y.anchors_wh, out,
+                              p->n_total, y.row_offset, st);
     }
     switch (o.kind) {
         case AY_OP_STEM_S2_FUSED:
-            return ay_stem_s2_fused_fwd(x, o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst), d.batch,
-                                        p->img_dim, p->img_dim, st);
+            return fn.stem_s2_fused(x, o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst), d.batch, p->img_dim,
+                                    p->img_dim, st);
         case AY_OP_STEM:
-            return ay_stem_conv_fwd(x, static_cast<const float*>(o.w), o.scale, o.shift, at(o.dst), d.batch, p->img_dim, p->img_dim,
-                                    d.leaky, st);
+            return fn.stem(x, static_cast<const float*>(o.w), o.scale, o.shift, at(o.dst), d.batch, p->img_dim, p->img_dim, d.leaky, st);
         case AY_OP_CONV:
-            return ay_conv_fwd_bf16(&d, at(o.src), o.w, o.scale, o.shift, at(o.res), at(o.dst), st);
+            return fn.conv(&d, at(o.src), o.w, o.scale, o.shift, at(o.res), at(o.dst), st);
         case AY_OP_RESBLOCK:
-            return ay_resblock_fwd_bf16(at(o.src), o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst),
-                                        d.batch, d.cin, d.hout, d.wout, st);
+            return fn.resblock(at(o.src), o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst), d.batch, d.cin,
+                               d.hout, d.wout, st);
         case AY_OP_CONV1X1_CAT:
-            return ay_conv1x1_cat_fwd_bf16(&d, at(o.src), o.c1, at(o.src2), o.w, o.scale, o.shift, at(o.dst), st);
-        case AY_OP_CONCAT_UPSAMPLE:
+            return fn.conv1x1_cat(&d, at(o.src), o.c1, at(o.src2), o.w, o.scale, o.shift, at(o.dst), st);
+        case AY_OP_CONCAT_UPSAMPLE:  // a 16-bit copy: one entry point for both storage types
             return ay_concat_upsample_bf16(at(o.src), o.c1, o.up1, at(o.src2), o.c2, at(o.dst), d.batch, d.hout, d.wout, st);
         case AY_OP_DECODE:
             return ay_yolo_decode(static_cast<const float*>(at(o.src)), 1, out, d.batch, o.num_anchors, o.num_classes, o.grid,

@@ -3,7 +3,9 @@
 Mirrors the reference's ``models.py`` call surface -- ``Darknet(config_path, img_size)``,
 ``model(x)`` / ``model(x, targets)``, ``load_darknet_weights`` / ``save_darknet_weights``,
 ``state_dict`` key names, ``.yolo_layers[i].metrics`` -- (reference ``models.py:225-336``) while the
-forward itself is a planned sequence of calls into ``libamyloid_yolo_hip.so``:
+forward itself is a planned sequence of calls into ``libamyloid_yolo_hip.so``: the cfg graph is lowered once
+(``Darknet._lower``) to a flat op list that either the native plan (``ay_plan_*``, 16-bit inference) or a host loop
+(``Darknet._run_ops``: fp32, kept layer outputs, bracketed events, the plan's reference) executes:
 
 * ``precision="bf16"`` (default): fp32 stem -> blocked-bf16 MFMA convolutions with fused
   BN-affine/LeakyReLU/shortcut epilogues, route+upsample gather, fp32 linear heads, fused decode.
@@ -17,6 +19,7 @@ the reference's ``state_dict`` schema, optimiser hooks and ``.to(device)``); the
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -100,11 +103,21 @@ def _pad_to(v, m):
     return (v + m - 1) // m * m
 
 
+class _Lowered(NamedTuple):
+    """result of ``Darknet._lower``: the op list and what an executor needs besides it"""
+    ops: list           # _lib.PlanOp, in issue order
+    value_bytes: list   # per value: byte size (ay_plan_create), derived from ``values``
+    values: list        # per value: (layer whose output it is, tensor shape, torch dtype) of a buffer that holds it
+    op_layer: list      # per op: the layer a plain convolution (OP_CONV) was lowered from -- what profiling selects by --, else None
+    layer_value: dict   # layer -> id of the value that holds its output (materialised outputs only)
+
+
 class _Plan:
     """owner of an ``ay_plan`` handle and its workspace"""
 
-    def __init__(self, handle, workspace, ops, value_bytes):
-        self.handle, self.workspace, self.ops, self.value_bytes = handle, workspace, ops, value_bytes
+    def __init__(self, handle, workspace, low):
+        self.handle, self.workspace = handle, workspace
+        self.ops, self.op_layer, self.value_bytes = low.ops, low.op_layer, sum(low.value_bytes)
 
     def __del__(self):
         try:
@@ -131,7 +144,7 @@ class Darknet(nn.Module):
         self.fuse_block_channels = (64,)
         self._graph = self._analyse()
         self._prep = None       # packed weights / folded BN, keyed by parameter versions
-        self._act_bufs = {}      # (precision, B, S) -> per-layer device tensors
+        self._act_bufs = {}      # (precision, B, S) -> {("out", slot): output rows, value id: tensor of the host executor}
         self.keep_layer_outputs = False
         self.layer_outputs = None
         self.stem_mode = "fused_bf16"   # "fp32": separate fp32 stem kernel (layer 0 output materialised)
@@ -389,10 +402,13 @@ class Darknet(nn.Module):
     @torch.no_grad()
     def forward_device(self, x, out_slot=0):
         """x [B,3,S,S] float32 (any device) -> device tensor [B, N, 5+C] (valid until the next forward into the same
-        ``out_slot``; two slots let NMS of batch i run on a side stream while batch i+1 computes)."""
+        ``out_slot``; two slots let NMS of batch i run on a side stream while batch i+1 computes).
+
+        The op list of ``_lower`` is run by one of two executors: the native plan (16-bit inference, the timed path), or the
+        host loop ``_run_ops`` -- fp32, kept layer outputs, bracketed events, ``use_plan = False`` -- which keeps one persistent
+        tensor per value and is what the plan is tested against."""
         if not torch.cuda.is_available():
             raise _lib.AyError("no HIP device: the amyloid-yolo hot path has no CPU fallback")
-        L = _lib.lib()
         dev = torch.device("cuda", torch.cuda.current_device())
         x = x.to(device=dev, dtype=torch.float32).contiguous()
         B, Cin, S, S2 = x.shape
@@ -400,198 +416,109 @@ class Darknet(nn.Module):
         assert Cin == int(self.hyperparams["channels"])
         prep = self._prepare(dev)
         st = _lib.stream_ptr()
-        bf16 = self._mfma   # the 16-bit MFMA path, bfloat16 or half storage
-        key = (self.precision, B, S)
-        bufs = self._act_bufs.setdefault(key, {})
-        C_ = self.yolo_layers[0].num_classes
-        N = self.num_boxes(S)
+        bufs = self._act_bufs.setdefault((self.precision, B, S), {})
         okey = ("out", out_slot)
         if okey not in bufs:
-            bufs[okey] = torch.empty(B, N, 5 + C_, device=dev, dtype=torch.float32)
+            bufs[okey] = torch.empty(B, self.num_boxes(S), 5 + self.yolo_layers[0].num_classes, device=dev, dtype=torch.float32)
         out = bufs[okey]
-
-        def size_of(i):
-            return S >> self._graph[i]["log2_down"] if i >= 0 else S
-
-        def buf(i, f32=False, ch=None):
-            """persistent output buffer of layer i"""
-            if i not in bufs:
-                e = self._graph[i]
-                h = size_of(i)
-                c = e["channels"] if ch is None else ch
-                if not bf16:
-                    bufs[i] = torch.empty(B, c, h, h, device=dev, dtype=torch.float32)
-                elif f32:
-                    bufs[i] = torch.empty(B, _pad_to(c, 32) // 16, h, h, 16, device=dev, dtype=torch.float32)
-                else:
-                    bufs[i] = torch.empty(B, _pad_to(c, 16) // 16, h, h, 16, device=dev, dtype=self._act_dtype)
-            return bufs[i]
-
         prof = getattr(self, "profile_layers", None)  # bench.py: bracket these conv launches with HIP events
-        if bf16 and self.use_plan and not self.keep_layer_outputs and prof is None:
+        if self._mfma and self.use_plan and not self.keep_layer_outputs and prof is None:
             # the whole network from native code: one call, activations in one arena with lifetime reuse
             plan = self._plan(B, S, prep, dev)
-            check(L.ay_plan_forward(plan.handle, ptr(x), ptr(plan.workspace), ptr(out), st), "ay_plan_forward")
+            check(_lib.lib().ay_plan_forward(plan.handle, ptr(x), ptr(plan.workspace), ptr(out), st), "ay_plan_forward")
             return out
-
-        # values: ("t", tensor) materialised, ("up", layer) lazily upsampled view of another layer
-        val = {}
-
-        def resolve(i):
-            """materialised tensor of layer i's output"""
-            v = val[i]
-            if v[0] == "t":
-                return v[1]
-            src = resolve(v[1])  # lazy upsample -> materialise
-            c = self._graph[i]["channels"]
-            o = buf(i)
-            h = size_of(i)
-            if bf16:
-                check(L.ay_concat_upsample_bf16(ptr(src), c, 1, None, 0, ptr(o), B, h, h, st), "ay_concat_upsample_bf16")
-            else:
-                o.copy_(src.repeat_interleave(2, 2).repeat_interleave(2, 3))
-            val[i] = ("t", o)
-            return o
-
-        row = 0
-        for i, e in enumerate(self._graph):
-            t = e["type"]
-            if t == "convolutional":
-                p = prep["layers"][i]
-                hin, hout = size_of(e["src"]), size_of(i)
-                fuse = e["fuse_into_shortcut"]
-                res = resolve(self._graph[i + 1]["b"]) if fuse else None
-                is_head = not e["bn"] and not e["leaky"]
-                d = ConvDesc(B, e["cin"], e["cout"], hin, hin, hout, hout, e["k"], e["stride"], int(e["leaky"]),
-                             int(bf16 and is_head), p["cpad"])
-                tgt = i + 1 if fuse else i
-                if i in val and val[i][0] == "fused":
-                    continue  # second half of a fused residual block
-                if bf16 and e["fuse_block"] and self.fuse_blocks:
-                    p2 = prep["layers"][i + 1]
-                    e2 = self._graph[i + 1]
-                    assert L.ay_resblock_supported(e["cin"])
-                    xin = resolve(e["src"])
-                    o = buf(i + 2)
-                    check(self._fn("ay_resblock_fwd")(ptr(xin), ptr(p["packed"]), ptr(p["scale"]), ptr(p["shift"]), int(e["leaky"]),
-                                                 ptr(p2["packed"]), ptr(p2["scale"]), ptr(p2["shift"]), int(e2["leaky"]), ptr(o), B,
-                                                 e["cin"], hout, hout, st), "ay_resblock_fwd_bf16")
-                    val[i] = ("fused", None)
-                    val[i + 1] = ("fused", None)
-                    val[i + 2] = ("t", o)
-                    continue
-                if bf16 and i == 0 and self._fuse_stem and self.stem_mode == "fused_bf16":
-                    val[i] = ("fused", None)
-                    continue
-                if bf16 and i == 1 and val.get(0, (None,))[0] == "fused":
-                    p0 = prep["layers"][0]
-                    o = buf(tgt)
-                    check(self._fn("ay_stem_s2_fused_fwd")(ptr(x), ptr(p0["w0_bf16"]), ptr(p0["scale"]), ptr(p0["shift"]), int(self._graph[0]["leaky"]),
-                                                 ptr(p["packed"]), ptr(p["scale"]), ptr(p["shift"]), int(e["leaky"]), ptr(o), B, S, S, st),
-                          "ay_stem_s2_fused_fwd")
-                    val[i] = ("t", o)
-                    continue
-                if bf16:
-                    if p["stem"]:
-                        o = buf(tgt)
-                        check(self._fn("ay_stem_conv_fwd")(ptr(x), ptr(p["w"]), ptr(p["scale"]), ptr(p["shift"]), ptr(o), B, S, S,
-                                                 int(e["leaky"]), st), "ay_stem_conv_fwd")
-                    elif e["src"] >= 0 and val[e["src"]][0] == "catup":
-                        ra, rb = val[e["src"]][1]
-                        s1 = resolve(val[ra][1])      # half-resolution source of the lazy upsample
-                        s2 = resolve(rb)
-                        o = buf(tgt)
-                        check(self._fn("ay_conv1x1_cat_fwd")(C.byref(d), ptr(s1), self._graph[ra]["channels"], ptr(s2), ptr(p["packed"]),
-                                                        ptr(p["scale"]), ptr(p["shift"]), ptr(o), st), "ay_conv1x1_cat_fwd_bf16")
-                    else:
-                        src = x if e["src"] < 0 else resolve(e["src"])
-                        if e["src"] < 0:
-                            raise NotImplementedError("bf16 path expects the 3->32 3x3 stem as layer 0")
-                        o = buf(tgt, f32=is_head)
-                        timed = prof is not None and i in prof
-                        if timed:
-                            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                            ev0.record()
-                        check(self._fn("ay_conv_fwd")(C.byref(d), ptr(src), ptr(p["packed"]), ptr(p["scale"]), ptr(p["shift"]),
-                                                 ptr(res), ptr(o), st), "ay_conv_fwd_bf16")
-                        if timed:
-                            ev1.record()
-                            self.profile_events.append((i, ev0, ev1))
-                else:
-                    # route/upsample folded into the loader when the source is a lazy value
-                    s1, c1, up1, s2 = self._f32_sources(e["src"], x, val, resolve)
-                    o = buf(tgt)
-                    check(L.ay_conv_fwd_f32(C.byref(d), ptr(s1), c1, up1, ptr(s2), ptr(p["w"]), ptr(p["scale"]), ptr(p["shift"]),
-                                            ptr(res), ptr(o), st), "ay_conv_fwd_f32")
-                val[i] = ("t", o)
-                if fuse:
-                    val[i] = ("fused", None)
-                    val[i + 1] = ("t", o)
-            elif t == "shortcut":
-                if i in val:
-                    continue  # produced by the fused epilogue of the previous conv
-                raise NotImplementedError(f"layer {i}: unfused shortcut (a source other than the preceding conv)")
-            elif t == "upsample":
-                val[i] = ("up", e["src"])
-            elif t == "route":
-                srcs = e["srcs"]
-                if len(srcs) == 1:
-                    val[i] = val[srcs[0]] if val[srcs[0]][0] != "up" else ("t", resolve(srcs[0]))
-                elif len(srcs) == 2:
-                    if bf16 and self._cat_foldable(i, val):
-                        val[i] = ("catup", srcs)  # [upsampled x2 | direct]: folded into the loader of the next 1x1 conv
-                    elif bf16:
-                        a, b_ = srcs
-                        up = val[a][0] == "up"
-                        s1 = resolve(val[a][1]) if up else resolve(a)
-                        s2 = resolve(b_)
-                        o = buf(i)
-                        h = size_of(i)
-                        check(L.ay_concat_upsample_bf16(ptr(s1), self._graph[a]["channels"], int(up), ptr(s2),
-                                                        self._graph[b_]["channels"], ptr(o), B, h, h, st), "ay_concat_upsample_bf16")
-                        val[i] = ("t", o)
-                    else:
-                        val[i] = ("cat", srcs)  # consumed by the next conv's loader
-                else:
-                    raise NotImplementedError("route with more than two sources")
-            elif t == "yolo":
-                y = self.module_list[i][0]
-                head = resolve(e["src"])
-                G = size_of(i)
-                anchors = (C.c_float * (2 * y.num_anchors))(*[float(v) for a in y.anchors for v in a])
-                check(L.ay_yolo_decode(ptr(head), 1 if bf16 else 0, ptr(out), B, y.num_anchors, y.num_classes, G, S, anchors, N,
-                                       row, st), "ay_yolo_decode")
-                y.grid_size, y.img_dim = G, S
-                row += y.num_anchors * G * G
-                val[i] = ("t", head)
+        low = self._lowered(B, S, prep)
+        for v, (_, shape, dtype) in enumerate(low.values):
+            if v not in bufs or bufs[v].shape != shape or bufs[v].dtype != dtype:  # ids are per lowering: another option set reuses them
+                bufs[v] = torch.empty(shape, device=dev, dtype=dtype)
+        self._run_ops(low, x, out, bufs, prof, st)
         if self.keep_layer_outputs:
-            self.layer_outputs = {i: v[1] for i, v in val.items() if v[0] == "t"}
+            self.layer_outputs = {i: bufs[v] for i, v in low.layer_value.items()}
         return out
 
-    # ------------------------------------------------------------------ native plan
+    def _run_ops(self, low, x, out, bufs, prof, st):
+        """Host executor of a lowered op list: one library call per op, value ``v`` in the tensor ``bufs[v]``.  It decides
+        nothing; unlike ``ay_plan_create`` it does not fuse a head with its decode, so every head is materialised."""
+        L, fn, mfma = _lib.lib(), self._fn, self._mfma
+        B, _, S, _ = x.shape
+        N = out.shape[1]
+
+        def at(v):
+            return ptr(x if v == _lib.PLAN_INPUT else bufs.get(v))  # PLAN_NONE -> NULL
+
+        for o, layer in zip(low.ops, low.op_layer):
+            k, d = o.kind, o.conv
+            if k == _lib.OP_CONV:
+                timed = prof is not None and layer in prof
+                if timed:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                if mfma:
+                    check(fn("ay_conv_fwd")(C.byref(d), at(o.src), o.w, o.scale, o.shift, at(o.res), at(o.dst), st), "ay_conv_fwd_bf16")
+                else:
+                    check(L.ay_conv_fwd_f32(C.byref(d), at(o.src), o.c1, o.up1, at(o.src2), o.w, o.scale, o.shift, at(o.res),
+                                            at(o.dst), st), "ay_conv_fwd_f32")
+                if timed:
+                    ev1.record()
+                    self.profile_events.append((layer, ev0, ev1))
+            elif k == _lib.OP_STEM_S2_FUSED:
+                check(fn("ay_stem_s2_fused_fwd")(ptr(x), o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst),
+                                                 B, S, S, st), "ay_stem_s2_fused_fwd")
+            elif k == _lib.OP_STEM:
+                check(fn("ay_stem_conv_fwd")(ptr(x), o.w, o.scale, o.shift, at(o.dst), B, S, S, d.leaky, st), "ay_stem_conv_fwd")
+            elif k == _lib.OP_RESBLOCK:
+                check(fn("ay_resblock_fwd")(at(o.src), o.w, o.scale, o.shift, d.leaky, o.w2, o.scale2, o.shift2, o.leaky2, at(o.dst),
+                                            B, d.cin, d.hout, d.wout, st), "ay_resblock_fwd_bf16")
+            elif k == _lib.OP_CONV1X1_CAT:
+                check(fn("ay_conv1x1_cat_fwd")(C.byref(d), at(o.src), o.c1, at(o.src2), o.w, o.scale, o.shift, at(o.dst), st),
+                      "ay_conv1x1_cat_fwd_bf16")
+            elif k == _lib.OP_CONCAT_UPSAMPLE and mfma:
+                check(L.ay_concat_upsample_bf16(at(o.src), o.c1, o.up1, at(o.src2), o.c2, at(o.dst), B, d.hout, d.wout, st),
+                      "ay_concat_upsample_bf16")
+            elif k == _lib.OP_CONCAT_UPSAMPLE:
+                assert o.up1 == 1 and o.c2 == 0  # fp32 routes ride the convolution loader; only a lone x2 upsample is copied
+                bufs[o.dst].copy_(bufs[o.src].repeat_interleave(2, 2).repeat_interleave(2, 3))
+            elif k == _lib.OP_DECODE:
+                check(L.ay_yolo_decode(at(o.src), int(mfma), ptr(out), B, o.num_anchors, o.num_classes, o.grid, S, o.anchors_wh, N,
+                                       o.row_offset, st), "ay_yolo_decode")
+            else:
+                raise _lib.AyError(f"unknown op kind {k}")
+
+    # ------------------------------------------------------------------ lowering: cfg graph -> op list
     def _lower(self, B, S, prep):
-        """The bf16 walk of ``forward_device`` with symbolic values: the op list (``_lib.PlanOp``) and the byte size of every
-        value, for ``ay_plan_create``.  Same decisions as the per-layer walk (fused stem, fused block, route folded into the 1x1
-        loader, lazy upsample), so both issue the same kernels with the same arguments."""
-        assert self._mfma
-        ops, vbytes, val = [], [], {}
-        N = self.num_boxes(S)
+        """The one walk over ``self._graph`` that decides how the network executes (fused stem, fused residual block,
+        shortcut in the conv epilogue, lazy x2 upsample, route folded into a convolution's loader): -> ``_Lowered``, the flat
+        op list (``_lib.PlanOp``) with symbolic values, run by ``ay_plan_create`` / ``ay_plan_forward`` or by ``_run_ops``.
+
+        bf16 / fp16: the op list ``ay_plan_create`` takes.  fp32 (host executor only, ``ay_plan_create`` never sees it): every
+        convolution is an ``OP_CONV`` for ``ay_conv_fwd_f32``, whose loader reads ``src`` (``PLAN_INPUT`` = the image) with
+        ``c1`` channels, x2 nearest-upsampled when ``up1``, followed by the channels of ``src2`` when set; a lazy upsample
+        that anything else reads is an ``OP_CONCAT_UPSAMPLE`` with ``c2 = 0`` (a tensor copy)."""
+        mfma, graph = self._mfma, self._graph
+        ops, op_layer, values, val = [], [], [], {}
 
         def size_of(i):
-            return S >> self._graph[i]["log2_down"] if i >= 0 else S
+            return S >> graph[i]["log2_down"] if i >= 0 else S
 
-        def new_value(i, f32=False):
-            c, h = self._graph[i]["channels"], size_of(i)
-            vbytes.append(B * (_pad_to(c, 32) // 16) * h * h * 16 * 4 if f32 else B * (_pad_to(c, 16) // 16) * h * h * 16 * 2)
-            return len(vbytes) - 1
+        def new_value(i, head=False):
+            """value holding layer i's output: fp32 NCHW | fp32 c16 planes of a 16-bit head | 16-bit c16 planes"""
+            c, h = graph[i]["channels"], size_of(i)
+            if not mfma:
+                values.append((i, (B, c, h, h), torch.float32))
+            elif head:
+                values.append((i, (B, _pad_to(c, 32) // 16, h, h, 16), torch.float32))
+            else:
+                values.append((i, (B, _pad_to(c, 16) // 16, h, h, 16), self._act_dtype))
+            return len(values) - 1
 
-        def op(kind, **kw):
+        def op(kind, layer=None, **kw):
             o = _lib.PlanOp()
             o.kind = kind
             o.src = o.src2 = o.res = o.dst = _lib.PLAN_NONE
             for k, v in kw.items():
                 setattr(o, k, v)
             ops.append(o)
+            op_layer.append(layer)
             return o
 
         def params(o, p, second=None):
@@ -600,19 +527,21 @@ class Darknet(nn.Module):
                 o.w2, o.scale2, o.shift2 = second["packed"].data_ptr(), second["scale"].data_ptr(), second["shift"].data_ptr()
 
         def resolve(i):
+            """id of the materialised value of layer i's output"""
             v = val[i]
             if v[0] == "t":
                 return v[1]
+            assert v[0] == "up", f"layer {i}: a folded route is read by something other than a convolution"
             src = resolve(v[1])  # lazy upsample -> materialise
             h = size_of(i)
             dst = new_value(i)
-            op(_lib.OP_CONCAT_UPSAMPLE, src=src, dst=dst, c1=self._graph[i]["channels"], up1=1, c2=0,
+            op(_lib.OP_CONCAT_UPSAMPLE, src=src, dst=dst, c1=graph[i]["channels"], up1=1, c2=0,
                conv=ConvDesc(B, 0, 0, h, h, h, h, 1, 1, 0, 0, 0))
             val[i] = ("t", dst)
             return dst
 
         row = 0
-        for i, e in enumerate(self._graph):
+        for i, e in enumerate(graph):
             t = e["type"]
             if t == "convolutional":
                 if i in val and val[i][0] == "fused":
@@ -621,10 +550,11 @@ class Darknet(nn.Module):
                 hin, hout = size_of(e["src"]), size_of(i)
                 fuse = e["fuse_into_shortcut"]
                 is_head = not e["bn"] and not e["leaky"]
-                d = ConvDesc(B, e["cin"], e["cout"], hin, hin, hout, hout, e["k"], e["stride"], int(e["leaky"]), int(is_head), p["cpad"])
+                d = ConvDesc(B, e["cin"], e["cout"], hin, hin, hout, hout, e["k"], e["stride"], int(e["leaky"]), int(mfma and is_head),
+                             p["cpad"])
                 tgt = i + 1 if fuse else i
-                if e["fuse_block"] and self.fuse_blocks:
-                    p2, e2 = prep["layers"][i + 1], self._graph[i + 1]
+                if mfma and e["fuse_block"] and self.fuse_blocks:
+                    p2, e2 = prep["layers"][i + 1], graph[i + 1]
                     src = resolve(e["src"])
                     dst = new_value(i + 2)
                     o = op(_lib.OP_RESBLOCK, src=src, dst=dst, conv=d, leaky2=int(e2["leaky"]))
@@ -632,38 +562,50 @@ class Darknet(nn.Module):
                     val[i] = val[i + 1] = ("fused", None)
                     val[i + 2] = ("t", dst)
                     continue
-                if i == 0 and self._fuse_stem and self.stem_mode == "fused_bf16":
+                if mfma and i == 0 and self._fuse_stem and self.stem_mode == "fused_bf16":
                     val[i] = ("fused", None)
                     continue
                 if i == 1 and val.get(0, (None,))[0] == "fused":
                     p0 = prep["layers"][0]
                     dst = new_value(tgt)
                     o = op(_lib.OP_STEM_S2_FUSED, dst=dst, leaky2=int(e["leaky"]),
-                           conv=ConvDesc(B, 3, 32, S, S, S, S, 3, 1, int(self._graph[0]["leaky"]), 0, 32))
+                           conv=ConvDesc(B, 3, 32, S, S, S, S, 3, 1, int(graph[0]["leaky"]), 0, 32))
                     o.w, o.scale, o.shift = p0["w0_bf16"].data_ptr(), p0["scale"].data_ptr(), p0["shift"].data_ptr()
                     o.w2, o.scale2, o.shift2 = p["packed"].data_ptr(), p["scale"].data_ptr(), p["shift"].data_ptr()
                     val[i] = ("t", dst)
                     continue
-                if p["stem"]:
+                res = _lib.PLAN_NONE
+                if p["stem"]:   # 16-bit only (_prepare)
                     dst = new_value(tgt)
                     o = op(_lib.OP_STEM, dst=dst, conv=d)
-                    params(o, p)
-                elif e["src"] >= 0 and val[e["src"]][0] == "catup":
+                elif mfma and e["src"] >= 0 and val[e["src"]][0] == "cat":
                     ra, rb = val[e["src"]][1]
                     s1 = resolve(val[ra][1])  # half-resolution source of the lazy upsample
                     s2 = resolve(rb)
                     dst = new_value(tgt)
-                    o = op(_lib.OP_CONV1X1_CAT, src=s1, src2=s2, dst=dst, conv=d, c1=self._graph[ra]["channels"])
-                    params(o, p)
-                else:
+                    o = op(_lib.OP_CONV1X1_CAT, src=s1, src2=s2, dst=dst, conv=d, c1=graph[ra]["channels"])
+                elif mfma:
                     if e["src"] < 0:
                         raise NotImplementedError("bf16 path expects the 3->32 3x3 stem as layer 0")
                     src = resolve(e["src"])
-                    res = resolve(self._graph[i + 1]["b"]) if fuse else _lib.PLAN_NONE
-                    dst = new_value(tgt, f32=is_head)
-                    o = op(_lib.OP_CONV, src=src, res=res, dst=dst, conv=d)
-                    params(o, p)
-                    o._layer = i
+                    if fuse:
+                        res = resolve(graph[i + 1]["b"])
+                    dst = new_value(tgt, head=is_head)
+                    o = op(_lib.OP_CONV, layer=i, src=src, res=res, dst=dst, conv=d)
+                else:
+                    # fp32 kernel: the image, a lazy upsample or a two-source route is read by the convolution's own loader
+                    j, b_ = e["src"], None
+                    if j >= 0 and val[j][0] == "cat":
+                        j, b_ = val[j][1]
+                    up1 = int(j >= 0 and val[j][0] == "up")
+                    src = _lib.PLAN_INPUT if j < 0 else resolve(val[j][1] if up1 else j)
+                    src2 = _lib.PLAN_NONE if b_ is None else resolve(b_)
+                    if fuse:
+                        res = resolve(graph[i + 1]["b"])
+                    dst = new_value(tgt)
+                    o = op(_lib.OP_CONV, layer=i, src=src, src2=src2, res=res, dst=dst, conv=d,
+                           c1=e["cin"] if j < 0 else graph[j]["channels"], up1=up1)
+                params(o, p)
                 val[i] = ("t", dst)
                 if fuse:
                     val[i] = ("fused", None)
@@ -678,8 +620,8 @@ class Darknet(nn.Module):
                 if len(srcs) == 1:
                     val[i] = val[srcs[0]] if val[srcs[0]][0] != "up" else ("t", resolve(srcs[0]))
                 elif len(srcs) == 2:
-                    if self._cat_foldable(i, val):
-                        val[i] = ("catup", srcs)
+                    if not mfma or self._cat_foldable(i, val):
+                        val[i] = ("cat", srcs)  # [a (x2 when a lazy upsample) | b]: read by the loader of the next convolution
                     else:
                         a, b_ = srcs
                         up = val[a][0] == "up"
@@ -687,8 +629,8 @@ class Darknet(nn.Module):
                         s2 = resolve(b_)
                         h = size_of(i)
                         dst = new_value(i)
-                        op(_lib.OP_CONCAT_UPSAMPLE, src=s1, src2=s2, dst=dst, c1=self._graph[a]["channels"], up1=int(up),
-                           c2=self._graph[b_]["channels"], conv=ConvDesc(B, 0, 0, h, h, h, h, 1, 1, 0, 0, 0))
+                        op(_lib.OP_CONCAT_UPSAMPLE, src=s1, src2=s2, dst=dst, c1=graph[a]["channels"], up1=int(up),
+                           c2=graph[b_]["channels"], conv=ConvDesc(B, 0, 0, h, h, h, h, 1, 1, 0, 0, 0))
                         val[i] = ("t", dst)
                 else:
                     raise NotImplementedError("route with more than two sources")
@@ -701,26 +643,42 @@ class Darknet(nn.Module):
                        conv=ConvDesc(B, 0, 0, G, G, G, G, 1, 1, 0, 0, 0))
                 for k, v in enumerate(float(v) for a in y.anchors for v in a):
                     o.anchors_wh[k] = v
-                y.grid_size, y.img_dim = G, S
                 row += y.num_anchors * G * G
                 val[i] = ("t", head)
-        assert row == N
-        return ops, vbytes
+        assert row == self.num_boxes(S)
+        return _Lowered(ops, [int(np.prod(shape)) * dtype.itemsize for _, shape, dtype in values], values, op_layer,
+                        {i: v[1] for i, v in val.items() if v[0] == "t"})
+
+    def _lower_key(self, B, S):
+        """everything ``_lower`` reads besides the graph and the weights (``_cat_foldable`` reads ``keep_layer_outputs``)"""
+        return (B, S, self.precision, self.fuse_blocks, self.fold_routes, self.stem_mode, tuple(self.fuse_block_channels),
+                self.keep_layer_outputs)
+
+    def _lowered(self, B, S, prep):
+        """cached ``_lower``; like the plans it holds weight addresses, so it lives in ``prep`` and dies with it"""
+        cache = prep.setdefault("lowered", {})
+        key = self._lower_key(B, S)
+        if key not in cache:
+            cache[key] = self._lower(B, S, prep)
+        for y, e in zip(self.yolo_layers, (g for g in self._graph if g["type"] == "yolo")):
+            y.grid_size, y.img_dim = S >> e["log2_down"], S
+        return cache[key]
 
     def _plan(self, B, S, prep, dev):
-        """(plan handle, workspace tensor, op list) for this batch shape; plans live in ``prep`` and die with it (new weights)."""
+        """native executor (``_Plan``) of the lowering for this batch shape; plans live in ``prep`` and die with it (new weights)"""
         plans = prep.setdefault("plans", {})
-        key = (B, S, self.fuse_blocks, self.fold_routes, self.stem_mode, tuple(self.fuse_block_channels))
+        key = self._lower_key(B, S)
         if key not in plans:
+            assert self._mfma
             L = _lib.lib()
-            ops, vbytes = self._lower(B, S, prep)
-            arr = (_lib.PlanOp * len(ops))(*ops)
-            vb = (C.c_size_t * len(vbytes))(*vbytes)
+            low = self._lowered(B, S, prep)
+            arr = (_lib.PlanOp * len(low.ops))(*low.ops)
+            vb = (C.c_size_t * len(low.value_bytes))(*low.value_bytes)
             handle = C.c_void_p()
-            check(L.ay_plan_create(arr, len(ops), vb, len(vbytes), S, self.num_boxes(S), int(self.precision == "fp16"), C.byref(handle)),
+            check(L.ay_plan_create(arr, len(low.ops), vb, len(vb), S, self.num_boxes(S), int(self.precision == "fp16"), C.byref(handle)),
                   "ay_plan_create")
             ws = torch.empty(L.ay_plan_workspace_bytes(handle), device=dev, dtype=torch.uint8)
-            plans[key] = _Plan(handle, ws, ops, sum(vbytes))
+            plans[key] = _Plan(handle, ws, low)
         return plans[key]
 
     def plan_profile_begin(self, B, S, layers=None, every=1):
@@ -730,7 +688,7 @@ class Darknet(nn.Module):
         plan = self._plan(B, S, self._prepare(dev), dev)
         sel = None
         if layers is not None:
-            sel = (C.c_ubyte * len(plan.ops))(*[int(getattr(o, "_layer", None) in layers) for o in plan.ops])
+            sel = (C.c_ubyte * len(plan.ops))(*[int(layer in layers) for layer in plan.op_layer])
         check(_lib.lib().ay_plan_profile_begin_every(plan.handle, sel, int(every)), "ay_plan_profile_begin")
 
     def plan_profile_end(self, B, S):
@@ -740,7 +698,7 @@ class Darknet(nn.Module):
         ms = (C.c_float * len(plan.ops))()
         n = C.c_int(0)
         check(_lib.lib().ay_plan_profile_end(plan.handle, ms, C.byref(n)), "ay_plan_profile_end")
-        return [(getattr(o, "_layer", None), o.kind, float(ms[k])) for k, o in enumerate(plan.ops)], n.value
+        return [(layer, o.kind, float(ms[k])) for k, (o, layer) in enumerate(zip(plan.ops, plan.op_layer))], n.value
 
     def _cat_foldable(self, i, val):
         """route i = [lazily upsampled a | b] whose only consumer is the next layer, a 1x1 bf16 conv block the dual-source
@@ -754,22 +712,6 @@ class Darknet(nn.Module):
         ca, cb = self._graph[a]["channels"], self._graph[b_]["channels"]
         return (e["type"] == "convolutional" and e["k"] == 1 and e["stride"] == 1 and e["bn"] and not e["fuse_into_shortcut"]
                 and not e.get("fuse_block") and ca % 64 == 0 and cb % 64 == 0 and _pad_to(e["cout"], 32) % 128 == 0)
-
-    def _f32_sources(self, src, x, val, resolve):
-        """(src1, cin1, up1, src2) for the fp32 kernel, folding route/upsample chains."""
-        if src < 0:
-            return x, x.shape[1], 0, None
-        v = val[src]
-        if v[0] == "cat":
-            a, b_ = v[1]
-            up = val[a][0] == "up"
-            s1 = resolve(val[a][1]) if up else resolve(a)
-            return s1, self._graph[a]["channels"], int(up), resolve(b_)
-        if v[0] == "up":
-            s1 = resolve(v[1])
-            return s1, self._graph[src]["channels"], 1, None
-        t = resolve(src)
-        return t, self._graph[src]["channels"], 0, None
 
     def layer_output_nchw(self, i):
         """fp32 NCHW copy of a kept layer output (tests); needs keep_layer_outputs=True before forward."""

@@ -1,5 +1,5 @@
-"""ay_plan_* host logic without a GPU: the lowering of the cfg graph (Darknet._lower) and the arena layout of
-ay_plan_create (csrc/ay_plan.hip).  No kernel is launched: weights are host tensors standing in for device pointers."""
+"""ay_plan_* host logic without a GPU: the lowering of the cfg graph (Darknet._lower, all three precisions) and the arena
+layout of ay_plan_create (csrc/ay_plan.hip).  No kernel is launched: weights are host tensors standing in for device pointers."""
 import ctypes as C
 import os
 
@@ -17,12 +17,12 @@ def fake_prep(m):
     for i, e in enumerate(m._graph):
         if e["type"] != "convolutional":
             continue
-        first = i == 0 and e["cin"] == 3 and e["k"] == 3 and e["stride"] == 1 and e["cout"] == 32
+        first = m._mfma and i == 0 and e["cin"] == 3 and e["k"] == 3 and e["stride"] == 1 and e["cout"] == 32
         t = lambda: torch.zeros(1)
-        entry = dict(scale=t(), shift=t(), cpad=_pad_to(e["cout"], 32), w=t(), stem=first)
+        entry = dict(scale=t(), shift=t(), cpad=_pad_to(e["cout"], 32) if m._mfma else e["cout"], w=t(), stem=first)
         if first:
             entry["w0_bf16"] = t()
-        else:
+        elif m._mfma:
             entry["packed"] = t()
         prep["layers"][i] = entry
     return prep
@@ -32,8 +32,8 @@ def reads_of(o):
     r = []
     if o.kind not in (_lib.OP_STEM_S2_FUSED, _lib.OP_STEM):
         r.append(o.src)
-    if o.kind in (_lib.OP_CONV1X1_CAT, _lib.OP_CONCAT_UPSAMPLE) and o.src2 != _lib.PLAN_NONE:
-        r.append(o.src2)
+    if o.kind in (_lib.OP_CONV1X1_CAT, _lib.OP_CONCAT_UPSAMPLE, _lib.OP_CONV) and o.src2 != _lib.PLAN_NONE:
+        r.append(o.src2)   # OP_CONV: the second source of the fp32 loader (host executor only; 16-bit OP_CONV leaves it unset)
     if o.kind == _lib.OP_CONV and o.res != _lib.PLAN_NONE:
         r.append(o.res)
     return r
@@ -56,7 +56,7 @@ def test_lowering_and_arena(tmp_cfg_dir, opts):
     for k, v in opts.items():
         setattr(m, k, v)
     B, S = 4, 416
-    ops, vbytes = m._lower(B, S, fake_prep(m))
+    ops, vbytes = m._lower(B, S, fake_prep(m))[:2]
     kinds = [o.kind for o in ops]
     assert kinds.count(_lib.OP_DECODE) == 3
     if not opts or "precision" in opts:   # the half-precision plan is the same op list on the other storage type
@@ -90,6 +90,52 @@ def test_lowering_and_arena(tmp_cfg_dir, opts):
                     assert off[a] + vbytes[a] <= off[b] or off[b] + vbytes[b] <= off[a], (a, b)
     finally:
         L.ay_plan_destroy(h)
+
+
+@pytest.mark.parametrize("classes", [2, 3])
+def test_fp32_lowering_has_the_shape_of_the_fp32_walk(tmp_cfg_dir, classes):
+    """precision='fp32' lowers to what the host executor hands ay_conv_fwd_f32 / ay_yolo_decode: one OP_CONV per convolution
+    with the image, a lazy x2 upsample or a two-source route folded into its loader, no fused kernel, nothing copied."""
+    m = Darknet(cfg_gen.write_cfg(classes, tmp_cfg_dir), precision="fp32")
+    B, S = 4, 416
+    low = m._lower(B, S, fake_prep(m))
+    ops, g = low.ops, m._graph
+    assert [o.kind for o in ops].count(_lib.OP_CONV) == 75 and [o.kind for o in ops].count(_lib.OP_DECODE) == 3 and len(ops) == 78
+    assert len(low.op_layer) == len(ops) and len(low.values) == len(low.value_bytes)
+    convs = [(o, layer) for o, layer in zip(ops, low.op_layer) if o.kind == _lib.OP_CONV]
+    assert [layer for _, layer in convs] == [i for i, e in enumerate(g) if e["type"] == "convolutional"]
+    assert all(layer is None for o, layer in zip(ops, low.op_layer) if o.kind == _lib.OP_DECODE)
+    for o, layer in convs:
+        e = g[layer]
+        assert (o.conv.cin, o.conv.cout, o.conv.cout_pad, o.conv.out_f32) == (e["cin"], e["cout"], e["cout"], 0)
+    # kept outputs: every layer except the convolutions folded into a shortcut, the lazy upsamples and the two-source routes
+    want = {i for i, e in enumerate(g) if not e.get("fuse_into_shortcut") and e["type"] != "upsample"
+            and not (e["type"] == "route" and len(e["srcs"]) == 2)}
+    assert set(low.layer_value) == want and len(want) == 80
+    assert sum(o.res != _lib.PLAN_NONE for o, _ in convs) == 23
+    assert ops[0].src == _lib.PLAN_INPUT and (ops[0].c1, ops[0].up1, ops[0].src2) == (3, 0, _lib.PLAN_NONE)
+    assert all(o.src >= 0 for o in ops[1:])
+    two = [(o, layer) for o, layer in convs if o.src2 != _lib.PLAN_NONE]
+    assert len(two) == 2 and all(o.up1 == 1 for o, _ in two)
+    assert sum(o.up1 for o, _ in convs) == 2                     # no other lazy upsample
+    for o, layer in two:                                          # the two FPN routes: [upsampled | direct] == the conv's input
+        assert g[layer - 1]["type"] == "route" and o.c1 + g[low.values[o.src2][0]]["channels"] == o.conv.cin
+        assert low.values[o.src][1][2] * 2 == low.values[o.src2][1][2] == o.conv.hin
+    for o, layer in convs:
+        if o.src2 == _lib.PLAN_NONE:
+            assert o.c1 == o.conv.cin
+    born = set()
+    for i, o in enumerate(ops):
+        for v in reads_of(o):
+            assert v == _lib.PLAN_INPUT or v in born, (i, v)
+        if o.kind != _lib.OP_DECODE:
+            assert o.dst not in born, (i, o.dst)
+            born.add(o.dst)
+    assert born == set(range(len(low.values)))
+    for (layer, shape, dtype), nbytes in zip(low.values, low.value_bytes):
+        h = S >> g[layer]["log2_down"]
+        assert shape == (B, g[layer]["channels"], h, h) and dtype == torch.float32 and nbytes == B * g[layer]["channels"] * h * h * 4
+    assert [o.row_offset for o in ops if o.kind == _lib.OP_DECODE] == [0, 3 * 13 * 13, 3 * (13 * 13 + 26 * 26)]
 
 
 def test_plan_rejects_broken_dataflow():
