@@ -117,7 +117,74 @@ __global__ void __launch_bounds__(256) region_tiles_step_u8_kernel(const uint8_t
     }
 }
 
+// The cut of region_tiles_step_u8_kernel for a LIST of tile origins (wsi.RegionTileStream(tile_mask=...): only the wanted tiles of a
+// strip are cut, densely, into a batch buffer): tile t starts at origins[t] = (x, y) on the (halved) image.  Same arithmetic, same
+// 255 outside the region, same V-float stores; the origins of a full grid in grid order give the step kernel's bytes.
+template <int V>
+__global__ void __launch_bounds__(256) region_tiles_list_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
+                                                                    int tile, const int32_t* __restrict__ origins, int n, int S,
+                                                                    float* __restrict__ out) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    const int H = RH / shrink, W = RW / shrink;
+    const float scale = (float)tile / (float)S;
+    const size_t plane = (size_t)S * S;
+    const int SV = S / V;   // S % V == 0 (checked by the entry point)
+    const size_t total = (size_t)n * S * SV;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x0 = (int)(i % SV) * V, y = (int)((i / SV) % S);
+        const size_t t = i / ((size_t)SV * S);
+        const int ox = origins[2 * t], oy = origins[2 * t + 1];
+        const int Y = oy + min((int)floorf(y * scale), tile - 1);
+        vec v[3];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int X = ox + min((int)floorf((x0 + k) * scale), tile - 1);
+            float px[3] = {1.0f, 1.0f, 1.0f};  // background 255
+            if (Y >= 0 && Y < H && X >= 0 && X < W) {   // the origins come from device memory: nothing outside the region is read
+                if (shrink == 1) {
+                    const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
+                } else {
+                    const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
+                    const uint8_t* p1 = p0 + stride;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][k] = px[c];
+        }
+        float* o = out + t * 3 * plane + (size_t)y * S + x0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(vec*)(o + c * plane) = v[c];
+    }
+}
+
 }  // namespace ay
+
+extern "C" int ay_ingest_region_tiles_list_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                              int tile, const int32_t* origins_xy, int n, int out_size, float* out_nchw,
+                                              ay_stream_t stream) {
+    using namespace ay;
+    AY_CHECK_ARG(region_hwc_u8 && out_nchw && origins_xy, "ay_ingest_region_tiles_list_u8: null");
+    AY_CHECK_ARG(region_h > 0 && region_w > 0 && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2),
+                 "ay_ingest_region_tiles_list_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    AY_CHECK_ARG(tile > 0 && tile <= (1 << 24) && n > 0 && out_size > 0, "ay_ingest_region_tiles_list_u8: %d tiles of %d -> %d", n, tile,
+                 out_size);
+    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;   // every row of every plane then starts on 16 bytes
+    const size_t total = (size_t)n * out_size * (out_size / (vec4 ? 4 : 1));
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    if (vec4)
+        hipLaunchKernelGGL(region_tiles_list_u8_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
+                           region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, out_size, out_nchw);
+    else
+        hipLaunchKernelGGL(region_tiles_list_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
+                           region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, out_size, out_nchw);
+    AY_CHECK_LAUNCH("region_tiles_list_u8_kernel");
+    return AY_OK;
+}
 
 extern "C" int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                                          int tile, int tiles_y, int tiles_x, int out_size, float* out_nchw, ay_stream_t stream) {

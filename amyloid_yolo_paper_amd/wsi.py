@@ -13,8 +13,15 @@ Abutting tiles split every object that straddles a seam.  With ``overlap > 0`` t
 tile, the per-tile detections stay on the device (``utils.nms_device`` -> ``ay_seam_append``) and one slide-level pass removes
 the second sightings (``ay_seam_merge``; the rule is stated in ``include/amyloid_yolo.h``).
 
+Most of a histology slide is glass.  :func:`tissue_counts` (``ay_tile_tissue_u8``, the rule in ``include/amyloid_yolo.h``) counts the
+tissue pixels of every tile, usually on a low-resolution level, :func:`wanted_tiles` turns the counts into a ``tile_mask``, and with
+a mask the stream never stages a strip without a wanted tile, stages of any other strip only the columns between its first and its
+last wanted tile and cuts only the wanted tiles out of it (``ay_ingest_region_tiles_list_u8``); :func:`detect_region` then fills its
+batches with wanted tiles across strip boundaries.
+
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
+import math
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -39,14 +46,53 @@ def tile_grid(H, W, tile, overlap=0):
     return n(H), n(W), step
 
 
+def wanted_tiles(counts, tile, min_tissue):
+    """Tissue counts ``[tiles_y, tiles_x]`` (:func:`tissue_counts`) -> bool mask of the tiles worth reading: a tile is wanted iff
+    ``count >= max(1, ceil(min_tissue * tile * tile))`` (``include/amyloid_yolo.h``, THE TISSUE RULE).  ``tile`` is the tile side on
+    the raster that was counted (for a probe level, the divided one); ``min_tissue=0`` keeps every tile with a tissue pixel."""
+    if not 0.0 <= float(min_tissue) <= 1.0:
+        raise ValueError(f"wanted_tiles: min_tissue {min_tissue} is no fraction of a tile")
+    need = max(1, math.ceil(float(min_tissue) * int(tile) * int(tile)))
+    return np.asarray(counts) >= need
+
+
+def check_tile_mask(tile_mask, H, W, tile, overlap=0):
+    """``tile_mask`` for the ``tile_grid(H, W, tile, overlap)`` grid: a NumPy bool array ``[tiles_y, tiles_x]``, else ``ValueError``"""
+    ty, tx, _ = tile_grid(H, W, tile, overlap)
+    if not isinstance(tile_mask, np.ndarray) or tile_mask.dtype != np.bool_ or tile_mask.shape != (ty, tx):
+        raise ValueError(f"tile_mask: need a NumPy bool array of shape ({ty}, {tx}), got "
+                         f"{getattr(tile_mask, 'dtype', type(tile_mask).__name__)} {getattr(tile_mask, 'shape', '')}")
+    return tile_mask
+
+
+def probe_view(raster, tile, shrink=1, overlap=0, probe_stride=16):
+    """The low-resolution stand-in of a raster that has no pyramid level at hand: every ``probe_stride``-th pixel of the (halved)
+    slide -> ``(view, tile // d, overlap // d)``.  The view takes SINGLE source pixels (``raster[0:shrink*H:shrink*d,
+    0:shrink*W:shrink*d]``, no 2x2 mean, no averaging over the stride) and copies nothing.  ``d`` must divide ``tile`` and ``tile -
+    overlap`` (``ValueError``); the probe grid then has the shape of the full grid."""
+    d, tile, overlap = int(probe_stride), int(tile), int(overlap)
+    if d < 1 or tile % d or (tile - overlap) % d:
+        raise ValueError(f"probe_stride {d} must divide tile {tile} and tile - overlap {tile - overlap}")
+    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
+    view = raster[0:shrink * H:shrink * d, 0:shrink * W:shrink * d]
+    # ceil(ceil(x) / s) == ceil(x / s): the strided extents give the full grid's tile counts
+    assert tile_grid(view.shape[0], view.shape[1], tile // d, overlap // d)[:2] == tile_grid(H, W, tile, overlap)[:2]
+    return view, tile // d, overlap // d
+
+
 class RegionTileStream:
     """Iterates over the tile rows of ``raster`` and yields ``(tiles [n,3,S,S] float32 on the device, [(ty, tx), ...])``.
 
     ``tile`` is the tile side on the (halved, if ``shrink`` == 2) slide, ``img_size`` the network input side.  With ``overlap``
     (pixels of the halved slide, like ``tile``) strip ``j`` holds slide rows ``[j * step, j * step + tile)``, ``step = tile -
-    overlap``: consecutive strips share ``overlap`` rows, which are uploaded with both."""
+    overlap``: consecutive strips share ``overlap`` rows, which are uploaded with both.
 
-    def __init__(self, raster, tile=1536, img_size=1024, shrink=1, overlap=0):
+    ``tile_mask`` (NumPy bool ``[tiles_y, tiles_x]``, e.g. from :func:`wanted_tiles`; default: every tile): a strip without a wanted
+    tile is not staged, not uploaded and yields nothing; of any other strip only the columns from its first to its last wanted tile
+    are staged and uploaded (one contiguous block), and only its wanted tiles are cut and yielded, in grid order, with their
+    coordinates on the full grid."""
+
+    def __init__(self, raster, tile=1536, img_size=1024, shrink=1, overlap=0, tile_mask=None):
         if not torch.cuda.is_available():
             raise _lib.AyError("no HIP device: RegionTileStream has no CPU fallback")
         assert raster.ndim == 3 and raster.shape[2] == 3 and raster.dtype == np.uint8, "uint8 [H,W,3] raster"
@@ -55,6 +101,8 @@ class RegionTileStream:
         H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
         self.overlap = int(overlap)
         self.tiles_y, self.tiles_x, self.step = tile_grid(H, W, self.tile, self.overlap)
+        self.tile_mask = None if tile_mask is None else check_tile_mask(tile_mask, H, W, self.tile, self.overlap)
+        self._jobs = self._strip_jobs()
         self.dev = torch.device("cuda", torch.cuda.current_device())
         rows = self.tile * shrink
         self._pinned = [torch.empty(rows, raster.shape[1], 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -64,71 +112,189 @@ class RegionTileStream:
         self._stager = ThreadPoolExecutor(max_workers=1)    # one strip ahead of the consumer
         self._chunk = -(-rows // 4)
         self._uploaded = [None, None]   # event: strip landed in _strips[k]
-        self._consumed = [None, None]   # event: the ingest kernel that read _strips[k] is done
+        self._consumed = [None, None]   # event: every ingest kernel that read _strips[k] is done
+
+    def _strip_jobs(self):
+        """the strips that are staged: ``[(j, c0, c1)]`` = tile row and its span of SOURCE columns ``[c0, c1)`` (computed once)"""
+        if self.tile_mask is None:
+            return [(j, 0, self.raster.shape[1]) for j in range(self.tiles_y)]
+        W, out = self.raster.shape[1] // self.shrink, []
+        for j in range(self.tiles_y):
+            txs = np.flatnonzero(self.tile_mask[j])
+            if len(txs):
+                out.append((j, int(txs[0]) * self.step * self.shrink, min(int(txs[-1]) * self.step + self.tile, W) * self.shrink))
+        return out
+
+    def _staged_bytes(self):
+        """bytes of the raster that one pass stages and uploads"""
+        rows, first = self.tile * self.shrink, self.step * self.shrink
+        return sum(len(range(j * first, min(j * first + rows, self.raster.shape[0]))) * (c1 - c0) * 3 for j, c0, c1 in self._jobs)
 
     def __len__(self):
-        return self.tiles_y
+        """the number of strips the iteration yields: ``tiles_y`` without a mask, the tile rows that hold a wanted tile with one"""
+        return len(self._jobs)
 
-    def _stage(self, j):
-        """host side of strip j: raster rows -> pinned buffer (runs on the staging thread, under the consumer's GPU work)"""
-        k = j & 1
+    def _stage(self, idx, job):
+        """host side of a strip: raster rows (the job's columns) -> pinned buffer, as one contiguous block with rows ``3 * width``
+        bytes apart (runs on the staging thread, under the consumer's GPU work) -> (rows, width) of the block"""
+        k = idx & 1
+        j, c0, c1 = job
         rows = self.tile * self.shrink
         first = j * self.step * self.shrink
-        src = self.raster[first:first + rows]
-        n = src.shape[0]
+        src = self.raster[first:first + rows, c0:c1]
+        n, w = src.shape[0], src.shape[1]
         if self._uploaded[k] is not None:
             self._uploaded[k].synchronize()      # the host buffer is free again once its last copy has run
         # staging copy by NumPy (memcpy speed; torch's uint8 copy_ ran at a quarter of it), rows split over a few threads --
         # the copy releases the GIL -- so that one strip stages faster than the GPU consumes it
-        dst = self._pinned[k].numpy()
+        dst = self._pinned[k].numpy().reshape(-1)[:n * w * 3].reshape(n, w, 3)
         parts = [(a, min(a + self._chunk, n)) for a in range(0, n, self._chunk)]
         list(self._pool.map(lambda ab: np.copyto(dst[ab[0]:ab[1]], src[ab[0]:ab[1]]), parts))
-        return n
+        return n, w
 
-    def _copy_to_device(self, j, n):
-        k = j & 1
+    def _copy_to_device(self, idx, nbytes):
+        k = idx & 1
         if self._consumed[k] is not None:
             self._copy.wait_event(self._consumed[k])
         with torch.cuda.stream(self._copy):
-            self._strips[k][:n].copy_(self._pinned[k][:n], non_blocking=True)
+            self._strips[k].view(-1)[:nbytes].copy_(self._pinned[k].view(-1)[:nbytes], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._copy)
         self._uploaded[k] = ev
 
-    def __iter__(self):
-        L = _lib.lib()
+    def _strip_loop(self):
+        """The strip machinery every user shares: stage (one strip ahead, on the staging thread), pinned upload on the copy stream,
+        two buffers.  Yields ``(j, k, rows, width)`` once the current stream waits for the upload of tile row ``j`` into
+        ``_strips[k]``: a ``rows x width`` block of source pixels, rows ``3 * width`` bytes apart.  The user issues every kernel that
+        reads the block on the current stream and then calls ``_release(k)``; the buffer is refilled only behind that point."""
+        jobs = self._jobs
         main = torch.cuda.current_stream()
         dev_index = self.dev.index
 
-        def stage(j):
+        def stage(idx):
             torch.cuda.set_device(dev_index)
-            return self._stage(j)
+            return self._stage(idx, jobs[idx])
 
-        fut = self._stager.submit(stage, 0) if self.tiles_y else None
-        for j in range(self.tiles_y):
-            k = j & 1
-            valid = fut.result()
-            self._copy_to_device(j, valid)
-            if j + 1 < self.tiles_y:  # staged while the consumer's model + NMS of this strip run
-                fut = self._stager.submit(stage, j + 1)
+        fut = self._stager.submit(stage, 0) if jobs else None
+        for idx, (j, _, _) in enumerate(jobs):
+            k = idx & 1
+            n, w = fut.result()
+            self._copy_to_device(idx, n * w * 3)
+            if idx + 1 < len(jobs):  # staged while the consumer's model + NMS of this strip run
+                fut = self._stager.submit(stage, idx + 1)
             main.wait_event(self._uploaded[k])
-            out = torch.empty(self.tiles_x, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
-            if self.overlap == 0:
-                check(L.ay_ingest_region_tiles_u8(ptr(self._strips[k]), valid, self.raster.shape[1], self.raster.shape[1] * 3, self.shrink,
-                                                  self.tile, 1, self.tiles_x, self.S, ptr(out), _lib.stream_ptr()),
-                      "ay_ingest_region_tiles_u8")
+            yield j, k, n, w
+
+    def _release(self, k):
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream())
+        self._consumed[k] = done
+
+    def _wanted(self):
+        """``[(ty, tx)]`` of the tiles the stream yields, in grid order"""
+        if self.tile_mask is None:
+            return [(j, i) for j in range(self.tiles_y) for i in range(self.tiles_x)]
+        return [(int(j), int(i)) for j, i in zip(*np.nonzero(self.tile_mask))]
+
+    def _wanted_table(self):
+        """for the list ingest, on the device: the origin of every wanted tile inside its strip's block, int32 [n][2] = (x, 0) in
+        grid order, and per tile row the index of its first wanted tile (host)"""
+        span0 = {j: c0 // self.shrink for j, c0, _ in self._jobs}
+        xy = np.array([(i * self.step - span0[j], 0) for j, i in self._wanted()], np.int32).reshape(-1, 2)
+        starts = np.r_[0, np.cumsum(self.tile_mask.sum(1))]
+        return torch.from_numpy(xy).to(self.dev), starts
+
+    def _ingest_list(self, L, k, n, w, origins, m, out):
+        check(L.ay_ingest_region_tiles_list_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, self.S,
+                                               ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_list_u8")
+
+    def __iter__(self):
+        L = _lib.lib()
+        if self.tile_mask is not None:
+            table, starts = self._wanted_table()
+            coords = self._wanted()
+        for j, k, valid, width in self._strip_loop():
+            if self.tile_mask is None:
+                out = torch.empty(self.tiles_x, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
+                if self.overlap == 0:
+                    check(L.ay_ingest_region_tiles_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile, 1,
+                                                      self.tiles_x, self.S, ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_u8")
+                else:
+                    check(L.ay_ingest_region_tiles_step_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile,
+                                                           self.step, 1, self.tiles_x, self.S, ptr(out), _lib.stream_ptr()),
+                          "ay_ingest_region_tiles_step_u8")
+                self._release(k)
+                yield out, [(j, i) for i in range(self.tiles_x)]
             else:
-                check(L.ay_ingest_region_tiles_step_u8(ptr(self._strips[k]), valid, self.raster.shape[1], self.raster.shape[1] * 3,
-                                                       self.shrink, self.tile, self.step, 1, self.tiles_x, self.S, ptr(out),
-                                                       _lib.stream_ptr()), "ay_ingest_region_tiles_step_u8")
-            done = torch.cuda.Event()
-            done.record(main)
-            self._consumed[k] = done
-            yield out, [(j, i) for i in range(self.tiles_x)]
+                a, b = int(starts[j]), int(starts[j + 1])
+                out = torch.empty(b - a, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
+                self._ingest_list(L, k, valid, width, table[a:], b - a, out)
+                self._release(k)
+                yield out, coords[a:b]
+
+    def _batches(self, batch_size):
+        """The masked iteration as detect_region takes it: yields ``(tiles [n,3,S,S], w0)``, the wanted tiles ``w0 .. w0 + n`` of
+        :meth:`_wanted`, ``n == batch_size`` but for the last batch: a strip's wanted tiles are cut into the open batch buffer at its
+        fill, so that batches are filled across strip boundaries.  Every ingest of a strip is issued (into as many batch buffers as
+        it takes) and the strip released before its batches are handed out, so the refill of a strip buffer never waits for a model
+        call, also when a batch holds tiles of two strips."""
+        L = _lib.lib()
+        table, starts = self._wanted_table()
+        cur, fill, w0 = None, 0, 0
+        for j, k, valid, width in self._strip_loop():
+            a, b = int(starts[j]), int(starts[j + 1])
+            ready = []
+            while a < b:
+                if cur is None:
+                    cur, fill, w0 = torch.empty(batch_size, 3, self.S, self.S, device=self.dev, dtype=torch.float32), 0, a
+                m = min(b - a, batch_size - fill)
+                self._ingest_list(L, k, valid, width, table[a:], m, cur[fill:])
+                fill, a = fill + m, a + m
+                if fill == batch_size:
+                    ready.append((cur, w0))
+                    cur = None
+            self._release(k)
+            yield from ready
+        if cur is not None:
+            yield cur[:fill], w0
+
+
+def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
+    """Tissue pixels per tile of the ``tile_grid(H, W, tile, overlap)`` grid over ``raster`` -> NumPy int32 ``[tiles_y, tiles_x]``.
+
+    A pixel of the (halved, for ``shrink=2``: the ingest's 2x2 round-half-up means) slide is tissue iff ``min(R, G, B) < bg_level``
+    (``bg_level`` in 0 .. 256; the default suits scanned glass); pixels of a shared band count for every tile that holds them, the
+    padding outside the slide never counts (THE TISSUE RULE in ``include/amyloid_yolo.h``, ``ay_tile_tissue_u8``).  The raster goes
+    through the strips of :class:`RegionTileStream` once and the counts come back in one read.  Meant for a low-resolution level
+    of the slide, with ``tile`` and ``overlap`` divided by that level's downsample (any ``[H, W, 3]`` uint8 array, strided views
+    such as :func:`probe_view`'s included), and exact on any raster: on the full one it costs a full upload of the slide.  A strip
+    reaches the kernel with rows ``3 * width`` bytes apart: the kernel's 16-byte loads need that to be a multiple of 16 (a width
+    that is a multiple of 16 pixels) and fall back to byte loads otherwise, about three times slower on the device and the same
+    counts; on a low-resolution level either is small against the staging copy."""
+    bg_level = int(bg_level)
+    if not 0 <= bg_level <= 256:
+        raise ValueError(f"tissue_counts: bg_level {bg_level} outside 0 .. 256")
+    stream = RegionTileStream(raster, tile, tile, shrink, overlap)
+    L = _lib.lib()
+    counts = torch.empty(stream.tiles_y, stream.tiles_x, device=stream.dev, dtype=torch.int32)
+    for j, k, valid, width in stream._strip_loop():
+        check(L.ay_tile_tissue_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, stream.tile, stream.step, 1,
+                                  stream.tiles_x, bg_level, ptr(counts[j]), _lib.stream_ptr()), "ay_tile_tissue_u8")
+        stream._release(k)
+    return counts.cpu().numpy()
+
+
+def tissue_mask(raster, tile, shrink=1, overlap=0, min_tissue=0.01, bg_level=220, probe_stride=16):
+    """The ``tile_mask`` of ``detect_region(min_tissue > 0)``: ``wanted_tiles`` of the tissue counts of :func:`probe_view`
+    (``probe_stride=1``: of the raster itself, the exact rule including the 2x2 means, at the cost of a full upload of the slide)."""
+    if int(probe_stride) == 1:
+        return wanted_tiles(tissue_counts(raster, tile, shrink, overlap, bg_level), tile, min_tissue)
+    view, t, o = probe_view(raster, tile, shrink, overlap, probe_stride)
+    return wanted_tiles(tissue_counts(view, t, 1, o, bg_level), t, min_tissue)
 
 
 def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=0.8, nms_thres=0.4, batch_size=64, overlap=0,
-                  seam_thres=0.5, max_det=1024, seam_capacity=None):
+                  seam_thres=0.5, max_det=1024, seam_capacity=None, tile_mask=None, min_tissue=0.0, bg_level=220, probe_stride=16):
     """Detection over a whole raster: the loop of ``detect.py:88-105`` fed by :class:`RegionTileStream`.
 
     Returns a list of ``(ty, tx, boxes)`` with ``boxes [n,7]`` = (x1, y1, x2, y2, conf, cls_conf, cls_pred) in pixels of the
@@ -144,38 +310,65 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
     overlap))**2`` times the tiles.  On this path nothing is read back per batch: per tile at most ``max_det`` rows are kept on the
     device (a tile with more raises ``AyError`` at the end), in a slide buffer of ``seam_capacity`` rows (default: all tiles
     full, at most 4 M rows).  The result has the same form: tiles in grid order, rows of a tile in NMS output order, tiles left
-    without a row omitted."""
+    without a row omitted.
+
+    ``tile_mask`` (NumPy bool ``[tiles_y, tiles_x]`` of the ``tile_grid``; default: every tile) names the tiles worth reading:
+    the others are neither staged nor uploaded nor run (see :class:`RegionTileStream`), batches of ``batch_size`` wanted tiles are
+    filled across strip boundaries, and the result is that of the full run restricted to the wanted tiles (``(ty, tx)`` and boxes
+    on the full grid; with ``overlap`` the seam merge sees no rows of unwanted tiles).  An all-False mask returns ``[]``.
+    ``min_tissue > 0`` without a mask is the one-call form: the mask is ``tissue_mask(raster, tile, shrink, overlap, min_tissue,
+    bg_level, probe_stride)``, i.e. tiles with at least that fraction of tissue pixels (``min(R, G, B) < bg_level``) on a probe
+    that takes every ``probe_stride``-th pixel of the (halved) slide -- single source pixels, no averaging, so an object smaller
+    than ``probe_stride`` pixels that is alone in its tile can be missed; ``probe_stride`` must divide ``tile`` and ``tile -
+    overlap``.  ``probe_stride=1`` counts on the raster itself (exact, and a full upload of the slide before the detection pass)."""
+    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
+    if tile_mask is None and min_tissue > 0:
+        tile_mask = tissue_mask(raster, tile, shrink, overlap, min_tissue, bg_level, probe_stride)
+    if tile_mask is not None and not check_tile_mask(tile_mask, H, W, tile, overlap).any():
+        return []
     if overlap:
         return _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, overlap, seam_thres,
-                                      max_det, seam_capacity)
+                                      max_det, seam_capacity, tile_mask)
     results = []
     scale = float(tile) / float(img_size)
     model.eval()
-    for tiles, coords in RegionTileStream(raster, tile, img_size, shrink):
-        for s in range(0, tiles.shape[0], batch_size):
-            with torch.no_grad():  # rows stay on the device; only the detections come back
-                det = non_max_suppression(model.forward_device(tiles[s:s + batch_size]), conf_thres, nms_thres)
-            for (ty, tx), d in zip(coords[s:s + batch_size], det):
-                if d is None:
-                    continue
-                d = d.cpu()
-                d[:, :4] *= scale
-                d[:, [0, 2]] += tx * tile
-                d[:, [1, 3]] += ty * tile
-                results.append((ty, tx, d))
+
+    def run(tiles, coords):
+        with torch.no_grad():  # rows stay on the device; only the detections come back
+            det = non_max_suppression(model.forward_device(tiles), conf_thres, nms_thres)
+        for (ty, tx), d in zip(coords, det):
+            if d is None:
+                continue
+            d = d.cpu()
+            d[:, :4] *= scale
+            d[:, [0, 2]] += tx * tile
+            d[:, [1, 3]] += ty * tile
+            results.append((ty, tx, d))
+
+    stream = RegionTileStream(raster, tile, img_size, shrink, tile_mask=tile_mask)
+    if tile_mask is None:
+        for tiles, coords in stream:
+            for s in range(0, tiles.shape[0], batch_size):
+                run(tiles[s:s + batch_size], coords[s:s + batch_size])
+    else:
+        coords = stream._wanted()
+        for tiles, w0 in stream._batches(batch_size):
+            run(tiles, coords[w0:w0 + tiles.shape[0]])
     return results
 
 
 def _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, overlap, seam_thres, max_det,
-                           seam_capacity):
+                           seam_capacity, tile_mask=None):
     from .postprocess import seam_merge_device
     L = _lib.lib()
-    stream = RegionTileStream(raster, tile, img_size, shrink, overlap)
+    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask)
     dev, TX, step = stream.dev, stream.tiles_x, stream.step
-    T = stream.tiles_y * TX
-    capacity = int(seam_capacity) if seam_capacity else min(T * int(max_det), 1 << 22)
-    # per tile, on the device for the whole slide: its id (grid order) and the (x, y) of its corner
-    ids = torch.arange(T, dtype=torch.int32)
+    # per tile that runs, on the device for the whole slide: its id (grid order on the full grid) and the (x, y) of its corner
+    if tile_mask is None:
+        ids = torch.arange(stream.tiles_y * TX, dtype=torch.int32)
+    else:
+        ids = torch.from_numpy(np.flatnonzero(tile_mask.ravel()).astype(np.int32))
+    capacity = int(seam_capacity) if seam_capacity else min(len(ids) * int(max_det), 1 << 22)
     origins = torch.stack([(ids % TX) * step, (ids // TX) * step], 1).to(torch.float32).to(dev)
     ids = ids.to(dev)
     slide_rows = torch.empty(capacity, 7, device=dev, dtype=torch.float32)
@@ -183,14 +376,21 @@ def _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nm
     slide_count = torch.zeros(2, device=dev, dtype=torch.int32)
     scale = C.c_float(float(tile) / float(img_size))
     model.eval()
-    for tiles, coords in stream:
-        for s in range(0, tiles.shape[0], batch_size):
-            t0 = coords[s][0] * TX + coords[s][1]
-            with torch.no_grad():  # no read-back: the NMS result buffers are overwritten by the next batch, the append is right behind
-                rows, _, count, _ = nms_device(model.forward_device(tiles[s:s + batch_size]), conf_thres, nms_thres, int(max_det))
-            B = rows.shape[0]
-            check(L.ay_seam_append(ptr(rows), ptr(count), B, int(max_det), scale, ptr(origins[t0:t0 + B]), ptr(ids[t0:t0 + B]),
-                                   ptr(slide_rows), ptr(slide_tile), ptr(slide_count), capacity, _lib.stream_ptr()), "ay_seam_append")
+
+    def batches():   # (tiles, index of the first of them in ids / origins)
+        if tile_mask is not None:
+            yield from stream._batches(batch_size)
+            return
+        for tiles, coords in stream:
+            for s in range(0, tiles.shape[0], batch_size):
+                yield tiles[s:s + batch_size], coords[s][0] * TX + coords[s][1]
+
+    for tiles, t0 in batches():
+        with torch.no_grad():  # no read-back: the NMS result buffers are overwritten by the next batch, the append is right behind
+            rows, _, count, _ = nms_device(model.forward_device(tiles), conf_thres, nms_thres, int(max_det))
+        B = rows.shape[0]
+        check(L.ay_seam_append(ptr(rows), ptr(count), B, int(max_det), scale, ptr(origins[t0:t0 + B]), ptr(ids[t0:t0 + B]),
+                               ptr(slide_rows), ptr(slide_tile), ptr(slide_count), capacity, _lib.stream_ptr()), "ay_seam_append")
     M, flags = (int(v) for v in slide_count.cpu())
     if flags & 1:
         raise _lib.AyError(f"detect_region: a tile holds more than max_det={max_det} detections; raise max_det or conf_thres")

@@ -298,6 +298,33 @@ int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h, int regio
 int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                                    int tile, int step, int tiles_y, int tiles_x, int out_size, float* out_nchw, ay_stream_t stream);
 
+/* The same cut for a LIST of n tile origins: origins_xy [n][2] int32 ON THE DEVICE = (x, y) of a tile's corner in pixels of the
+ * (halved) region, any position (on a grid or not, repeated or not; what lies outside the region, also left of or above it, is the
+ * background 255) -> out[0..n) densely, in list order; rows of `out` behind n are not touched.  Same arithmetic and the same 16-byte
+ * stores per lane as the step form: the origins of a full grid in grid order give ay_ingest_region_tiles_step_u8 bit for bit.
+ * wsi.RegionTileStream(tile_mask=...) cuts only the wanted tiles of a strip with it. */
+int ay_ingest_region_tiles_list_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                   int tile, const int32_t* origins_xy, int n, int out_size, float* out_nchw, ay_stream_t stream);
+
+/* ---- tissue map: which tiles of a slide are worth reading (wsi.tissue_counts, wsi.wanted_tiles; csrc/ay_tissue.hip) ------------
+ * THE TISSUE RULE (exact, integer).
+ *   A pixel of the (halved, for shrink == 2) image is TISSUE iff min(R, G, B) < bg_level on its uint8 values; for shrink == 2 the
+ *   values are the 2x2 means with round-half-up of the ingest, (a + b + c + d + 2) >> 2.  bg_level is an int in [0, 256]: 0 makes
+ *   nothing tissue, 256 everything.
+ *   The TISSUE COUNT of tile (ty, tx) of a grid with origins `step` apart is the number of tissue pixels in
+ *   [ty * step, ty * step + tile) x [tx * step, tx * step + tile) that lie inside the H x W image (H = region_h / shrink, W =
+ *   region_w / shrink).  What lies outside is the ingest's 255 padding and never counts.  With step < tile a pixel in a shared band
+ *   counts for every tile that contains it.
+ *   A tile is WANTED iff count >= max(1, ceil(min_tissue * tile * tile)), the right-hand side computed once on the host
+ *   (wsi.wanted_tiles).
+ * ay_tile_tissue_u8 writes the counts [tiles_y * tiles_x] (int32, device; zeroed by a kernel of the call, not by the caller) of a
+ * resident region; tile <= 46340, so that a count fits int32.  A pure read stream over the image: a source byte comes from memory
+ * once, also where tiles overlap (neighbouring lanes and units re-read a few bytes through the cache); 16-byte loads per lane when
+ * the base and row_stride_bytes are multiples of 16, byte loads (about three times slower, same counts) for any other alignment;
+ * integer sums with one atomic per tile and workgroup: the same bits every run.  Kernel launches only. */
+int ay_tile_tissue_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int tile, int step,
+                      int tiles_y, int tiles_x, int bg_level, int32_t* counts, ay_stream_t stream);
+
 /* ---- training step, bf16 MFMA path (blocked bf16 activations and activation gradients) ------------- */
 
 /* Train-mode BatchNorm + LeakyReLU (+ fused shortcut add of `skip`) around the MFMA convolution: statistics pass (fp64

@@ -1,7 +1,13 @@
 """Throughput of the WSI -> tile -> detection stream (§8f N4): a synthetic slide of TY x TX 1536-px tiles in host memory,
 streamed strip by strip (pinned upload on a copy stream, device-side tiling + /255 + resize to 1024), model + merge-NMS.
-usage: python scripts/bench_wsi.py [TY TX] [--overlap N] [--max-det D] [--reps R] ; prints tiles/s including the PCIe upload (this is NOT
-bench.py's `value`).  --overlap N: tiles that share N pixels (more tiles over the same slide) + the slide-level seam merge."""
+usage: python scripts/bench_wsi.py [TY TX] [--overlap N] [--max-det D] [--reps R] [--blank F] [--min-tissue M] [--bg-level L]
+[--probe-stride D] ; prints tiles/s including the PCIe upload (this is NOT bench.py's `value`).
+--overlap N: tiles that share N pixels (more tiles over the same slide) + the slide-level seam merge.
+--blank F: the last round(F * TX) tile columns and the last round(F * TY) tile rows of the slide are painted 255 (glass).
+--min-tissue M (> 0): only tiles with that fraction of tissue pixels are read (wsi.tissue_mask on a --probe-stride probe, inside the
+timed call); the script prints how many tiles are wanted and the bytes staged.  The synthetic tiles have a noisy background of
+U{180..255} per channel, so runs on them use --bg-level 170 (the default 220 is for scanned glass), and a synthetic tile that drew
+no blob is rightly unwanted."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -11,11 +17,11 @@ from amyloid_yolo_paper_amd.wsi import RegionTileStream, detect_region
 import tempfile
 
 argv = sys.argv[1:]
-opts = {"--overlap": 0, "--reps": 2, "--max-det": 4096}
+opts = {"--overlap": 0, "--reps": 2, "--max-det": 4096, "--blank": 0.0, "--min-tissue": 0.0, "--bg-level": 220, "--probe-stride": 16}
 for o in opts:
     if o in argv:
         k = argv.index(o)
-        opts[o] = int(argv[k + 1])
+        opts[o] = type(opts[o])(argv[k + 1])
         del argv[k:k + 2]
 OVERLAP, REPS = opts["--overlap"], opts["--reps"]
 TY, TX = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (8, 32)
@@ -35,6 +41,9 @@ base = synth.synth_tiles(4, 1536, start=0)                       # [4,3,1536,153
 base = (base * 255).astype(np.uint8).transpose(0, 2, 3, 1)
 row = np.concatenate([base[i % 4] for i in range(TX)], 1)
 raster = np.concatenate([np.roll(row, 97 * j, 1) for j in range(TY)], 0)
+if opts["--blank"] > 0:
+    raster[:, (TX - round(opts["--blank"] * TX)) * tile:] = 255
+    raster[(TY - round(opts["--blank"] * TY)) * tile:] = 255
 print("raster", raster.shape, "%.2f GB" % (raster.nbytes / 1e9), flush=True)
 if OVERLAP:   # the grid over the same slide with overlapping tiles
     from amyloid_yolo_paper_amd.wsi import tile_grid
@@ -43,13 +52,24 @@ if OVERLAP:   # the grid over the same slide with overlapping tiles
     det_kw = dict(overlap=OVERLAP, max_det=opts["--max-det"])   # the synthetic tiles are dense: some overlapping tile passes 1 024 rows
 else:
     GY, GX, kw, det_kw = TY, TX, {}, {}
+if opts["--min-tissue"] > 0:   # the mask the timed call will compute, for the report and the ingest-only loop
+    from amyloid_yolo_paper_amd.wsi import tissue_mask
+    t0 = time.perf_counter()
+    mask = tissue_mask(raster, tile, 1, OVERLAP, opts["--min-tissue"], opts["--bg-level"], opts["--probe-stride"])
+    t1 = time.perf_counter()
+    kw = dict(kw, tile_mask=mask)
+    det_kw = dict(det_kw, min_tissue=opts["--min-tissue"], bg_level=opts["--bg-level"], probe_stride=opts["--probe-stride"])
+    probe = RegionTileStream(raster, tile, S, **kw)
+    print("tissue mask: %d of %d tiles wanted in %d of %d strips, %.3f GB of %.3f GB staged, probe %.3f s (first call)"
+          % (mask.sum(), mask.size, len(probe), GY, probe._staged_bytes() / 1e9, raster.nbytes / 1e9, t1 - t0), flush=True)
+    del probe
 for rep in range(REPS):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     n = 0
     for tiles, cs in RegionTileStream(raster, tile, S, **kw):
         n += tiles.shape[0]
     torch.cuda.synchronize(); t1 = time.perf_counter()
-    print("ingest only: %.0f tiles/s (%.1f GB/s of slide)" % (n / (t1 - t0), raster.nbytes / (t1 - t0) / 1e9), flush=True)
+    print("ingest only: %.0f tiles/s (%d tiles, %.3f s, %.1f GB/s of slide)" % (n / (t1 - t0), n, t1 - t0, raster.nbytes / (t1 - t0) / 1e9), flush=True)
 for rep in range(REPS):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     res = detect_region(m, raster, tile, S, conf_thres=0.5, nms_thres=0.4, batch_size=GX, **det_kw)

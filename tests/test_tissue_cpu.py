@@ -1,0 +1,176 @@
+"""CPU: the tissue rule's NumPy restatement on hand cases, wsi.wanted_tiles / check_tile_mask / probe_view, the test slide's
+numbers, and the two new entry points in the header and the library (no scratch memory in their kernels)."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import tissue_reference as tr
+from amyloid_yolo_paper_amd import build
+from amyloid_yolo_paper_amd.wsi import check_tile_mask, probe_view, tile_grid, wanted_tiles
+from test_gpu_seam import region_raster
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TILE, BG = 192, 170
+
+
+def white(h, w):
+    return np.full((h, w, 3), 255, np.uint8)
+
+
+# ---- the restatement on hand cases ---------------------------------------------------------------------------------------------
+def test_grid_of_the_restatement_is_the_products():
+    for H in (1, 7, 50, 333, 1000):
+        for W in (1, 20, 97, 1314):
+            for tile, overlap in ((32, 0), (32, 8), (32, 29), (192, 64), (16, 5)):
+                assert tr.grid(H, W, tile, overlap) == tile_grid(H, W, tile, overlap)
+
+
+def test_padding_never_counts():
+    r = white(40, 50)
+    r[:, :, 1] = 10                                          # every pixel is tissue
+    c = tr.tissue_counts(r, 32, bg_level=200)
+    assert c.tolist() == [[32 * 32, 32 * 18], [8 * 32, 8 * 18]]   # edge tiles count only what lies inside the image
+    assert tr.tissue_counts(white(40, 50), 32, bg_level=255).sum() == 0   # 255 is what the padding holds: never below 255
+
+
+def test_shared_band_counts_for_both_tiles():
+    r = white(32, 56)                                        # tile 32, overlap 8: origins 0 and 24, shared columns 24 .. 31
+    r[5, 26, 2] = 0                                          # in the band
+    r[6, 3, 0] = 0                                           # only in tile 0
+    r[7, 40, 1] = 0                                          # only in tile 1
+    assert tr.tissue_counts(r, 32, overlap=8, bg_level=100).tolist() == [[2, 2]]
+    assert tr.tissue_counts(r, 32, overlap=0, bg_level=100).tolist() == [[2, 1]]
+
+
+def test_counts_sum_to_the_tissue_pixels_without_overlap():
+    r = np.random.default_rng(3).integers(0, 256, size=(70, 100, 3), dtype=np.uint8)
+    c = tr.tissue_counts(r, 32, bg_level=60)
+    assert c.shape == (3, 4) and 0 < c.sum() == int((r.min(2) < 60).sum()) < 70 * 100
+    assert tr.tissue_counts(r, 32, overlap=8, bg_level=60).sum() > c.sum()
+
+
+def test_halved_means_round_across_the_level_in_both_directions():
+    r = white(4, 4)
+    r[0:2, 0:2, 0] = [[99, 99], [100, 100]]                  # sum 398: (398 + 2) >> 2 = 100, the exact mean 99.5 rounds UP: not < 100
+    r[0:2, 2:4, 1] = [[99, 99], [99, 100]]                   # sum 397: (397 + 2) >> 2 = 99 (mean 99.25): < 100
+    r[2:4, 0:2, 2] = [[100, 100], [100, 101]]                # sum 401: 100 (mean 100.25): not < 100, but < 101
+    assert tr.tissue(r, 2, 100).tolist() == [[False, True], [False, False]]
+    assert tr.tissue(r, 2, 101).tolist() == [[True, True], [True, False]]
+    assert tr.tissue_counts(r, 2, shrink=2, bg_level=100).tolist() == [[1]]
+    odd = np.concatenate([np.concatenate([r, white(4, 1)], 1), white(1, 5)], 0)   # the odd last row and column are dropped
+    assert tr.tissue_counts(odd, 2, shrink=2, bg_level=100).tolist() == [[1]]
+
+
+def test_level_0_and_256():
+    r = np.random.default_rng(4).integers(0, 256, size=(20, 30, 3), dtype=np.uint8)
+    r[0, 0] = 0
+    r[1, 1] = 255
+    assert tr.tissue_counts(r, 16, bg_level=0).sum() == 0
+    assert tr.tissue_counts(r, 16, bg_level=256).sum() == 20 * 30
+    assert tr.tissue(r, 1, 1)[0, 0] and not tr.tissue(r, 1, 255)[1, 1] and tr.tissue(r, 1, 256)[1, 1]
+
+
+# ---- wanted_tiles, the mask check, the probe -------------------------------------------------------------------------------------
+def test_wanted_tiles_threshold():
+    counts = np.array([[0, 1, 368, 369, 370]], np.int32)
+    assert wanted_tiles(counts, TILE, 0.0).tolist() == [[False, True, True, True, True]]     # one tissue pixel is enough, none is not
+    assert wanted_tiles(counts, TILE, 0.01).tolist() == [[False, False, False, True, True]]  # ceil(368.64) = 369: on the threshold is kept
+    assert wanted_tiles(counts, 12, 0.01).tolist() == [[False, False, True, True, True]]     # ceil(1.44) = 2
+    assert wanted_tiles(np.array([[36864, 36863]]), TILE, 1.0).tolist() == [[True, False]]
+    assert wanted_tiles(counts, TILE, 0.01).dtype == np.bool_
+    for m in (0.0, 0.0005, 0.01, 0.05):
+        assert np.array_equal(wanted_tiles(counts, TILE, m), tr.wanted(counts, TILE, m))
+    with pytest.raises(ValueError):
+        wanted_tiles(counts, TILE, 1.5)
+
+
+def test_mask_validation():
+    ty, tx, _ = tile_grid(1000, 1314, TILE, 64)
+    assert (ty, tx) == (8, 10)
+    good = np.zeros((8, 10), np.bool_)
+    assert check_tile_mask(good, 1000, 1314, TILE, 64) is good
+    for bad in (np.zeros((6, 7), np.bool_), np.zeros((10, 8), np.bool_), np.zeros(80, np.bool_), np.zeros((8, 10), np.uint8),
+                np.zeros((8, 10), np.int32), good.tolist(), None):
+        with pytest.raises(ValueError):
+            check_tile_mask(bad, 1000, 1314, TILE, 64)
+    with pytest.raises(ValueError):
+        check_tile_mask(good, 1000, 1314, TILE, 0)           # the 6 x 7 grid
+
+
+@pytest.mark.parametrize("shrink", [1, 2])
+def test_probe_grid_has_the_full_grids_shape(shrink):
+    for tile, overlap, d in ((192, 0, 16), (192, 64, 16), (192, 64, 32), (96, 24, 8), (1536, 128, 16), (30, 9, 3)):
+        for H, W in ((1, 1), (17, 401), (333, 718), (1000, 1314), (1001, 1315), (383, 385), (193, 191)):
+            r = np.zeros((H * shrink + (shrink - 1), W * shrink + (shrink - 1), 3), np.uint8)     # odd source extents for shrink 2
+            view, t, o = probe_view(r, tile, shrink, overlap, d)
+            assert (t, o) == (tile // d, overlap // d)
+            assert view.shape[:2] == (-(-H // d), -(-W // d)) and view.base is not None     # a view: nothing copied
+            assert tile_grid(view.shape[0], view.shape[1], t, o)[:2] == tile_grid(H, W, tile, overlap)[:2]
+    r = np.arange(10 * 12 * 3, dtype=np.uint8).reshape(10, 12, 3)
+    assert np.array_equal(probe_view(r, 8, 2, 4, 2)[0], r[0:10:4, 0:12:4])                 # single source pixels, no mean
+
+
+def test_probe_stride_must_divide():
+    r = np.zeros((100, 100, 3), np.uint8)
+    for tile, overlap, d in ((192, 0, 10), (192, 64, 48), (192, 60, 16), (192, 0, 0)):
+        with pytest.raises(ValueError):
+            probe_view(r, tile, 1, overlap, d)
+    probe_view(r, 192, 1, 64, 64)
+
+
+# ---- the test slide ----------------------------------------------------------------------------------------------------------------
+def test_slide_numbers():
+    """The issue's figures.  One of them is corrected here: at overlap 64 and min_tissue 0.0005 (19 px) the issue says 13 wanted
+    tiles, counting only the speck's two tiles on top of the 11; the rule as the issue states it also keeps the tiles (0, 4) and
+    (1, 5), whose counts 96 and 44 are at least 19: 15."""
+    s = tr.test_slide(region_raster())
+    assert s.shape == (1000, 1314, 3)
+    c0 = tr.tissue_counts(s, TILE, 1, 0, BG)
+    assert c0.tolist() == [[0, 0, 680, 4, 0, 0, 0], [0, 0, 2736, 2148, 584, 0, 0], [0, 0, 586, 984, 372, 0, 0], [0] * 7,
+                           [120, 0, 0, 0, 0, 0, 0], [0] * 7]
+    c64 = tr.tissue_counts(s, TILE, 1, 64, BG)
+    assert c64.shape == (8, 10)
+    assert [int(tr.wanted(c0, TILE, m).sum()) for m in (0.01, 0.0005, 0.05)] == [7, 8, 2]
+    assert [int(tr.wanted(c64, TILE, m).sum()) for m in (0.01, 0.0005, 0.05)] == [11, 15, 3]
+    for c in (c0, c64):                                      # no count lies on a threshold
+        assert not np.isin(c, [369, 19, 1844]).any()
+    for overlap, c, n16, n32 in ((0, c0, 7, 4), (64, c64, 11, 8)):
+        full = tr.wanted(c, TILE, 0.01)
+        p16 = tr.wanted(tr.tissue_counts(s[::16, ::16], 12, 1, overlap // 16, BG), 12, 0.01)
+        p32 = tr.wanted(tr.tissue_counts(s[::32, ::32], 6, 1, overlap // 32, BG), 6, 0.01)
+        assert np.array_equal(p16, full) and p16.sum() == n16
+        assert p32.sum() == n32 and not (p32 & ~full).any()  # the documented loss: a coarse probe only drops tiles
+    assert (tr.tissue_counts(s[::16, ::16], 12, 1, 0, BG)[tr.wanted(c0, TILE, 0.01)] == 2).sum() == 3   # on the probe's threshold: kept
+
+
+# ---- header, library, kernels --------------------------------------------------------------------------------------------------------
+def test_header_declares_the_entry_points_and_the_rule():
+    text = open(os.path.join(REPO, "include", "amyloid_yolo.h")).read()
+    assert re.search(r"#define AY_ABI_VERSION 2\b", text)
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert re.search(r"\bint ay_tile_tissue_u8\(", code) and re.search(r"\bint ay_ingest_region_tiles_list_u8\(", code)
+    assert "THE TISSUE RULE" in text and "min(R, G, B) < bg_level" in text
+
+
+def test_new_kernels_use_no_scratch(tmp_path):
+    """hipcc's resource remarks for the two sources: every instantiation of the two new kernels has ScratchSize 0"""
+    hipcc = build._hipcc()
+    found = {}
+    for src in ("ay_tissue.hip", "ay_ingest.hip"):
+        p = subprocess.run([hipcc] + build.FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                                                    os.path.join(build.CSRC, src), "-o", str(tmp_path / (src + ".o"))],
+                           capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr[-2000:]
+        name = None
+        for line in p.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+            m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+            if m and name and ("tile_tissue_u8_kernel" in name or "region_tiles_list_u8_kernel" in name):
+                found[name] = int(m.group(1))
+    assert sum("tile_tissue_u8_kernel" in n for n in found) == 4 and sum("region_tiles_list_u8_kernel" in n for n in found) == 2
+    assert all(v == 0 for v in found.values()), found
