@@ -25,6 +25,13 @@ class PlanOp(C.Structure):
                 ("w2", C.c_void_p), ("scale2", C.c_void_p), ("shift2", C.c_void_p)]
 
 
+class AugParams(C.Structure):
+    """ay_aug_params (include/amyloid_yolo.h, THE AUGMENTATION RULE): one record per image of ay_augment_ingest_u8"""
+    _fields_ = [("src_offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("inv", C.c_float * 6), ("flip", C.c_int32),
+                ("sharpen_alpha", C.c_float), ("drop_threshold", C.c_uint32), ("drop_seed", C.c_uint32),
+                ("color", C.c_float * 9), ("bright", C.c_float)]
+
+
 PLAN_INPUT, PLAN_NONE = -1, -2
 OP_STEM_S2_FUSED, OP_STEM, OP_CONV, OP_RESBLOCK, OP_CONV1X1_CAT, OP_CONCAT_UPSAMPLE, OP_DECODE = 1, 2, 3, 4, 5, 6, 7
 
@@ -88,6 +95,7 @@ _SIGS = {
     "ay_ingest_region_tiles_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _P, _P]),
     "ay_ingest_region_tiles_step_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ay_ingest_region_tiles_list_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, _I, _P, _P]),
+    "ay_augment_ingest_u8": (_I, [_P, _SZ, _P, _I, _I, _P, _P]),
     "ay_tile_tissue_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ay_build_targets_workspace_bytes": (_SZ, [_I, _I, _I]),
     "ay_build_targets": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -1,8 +1,9 @@
 """Host-side tile/label readers with the reference's conventions (reference ``utils/datasets.py``,
 ``utils/transforms.py:68-118``): PIL -> RGB uint8 -> /255 CHW float32 -> zero pad to square -> nearest resize;
 labels ``class cx cy w h`` normalised, re-normalised for the padding; ``collate_fn`` writes the sample index into
-column 0 and (optionally) re-draws the size every 10th batch.  The imgaug augmentation pipeline of the reference is
-out of scope: this loader is the deterministic DEFAULT_TRANSFORMS path."""
+column 0 and (optionally) re-draws the size every 10th batch.  This loader is the deterministic DEFAULT_TRANSFORMS path; with
+``ListDataset(raw_u8=True)`` it hands out the decoded bytes and the label rows instead, and the training augmentation (the
+reference's imgaug pipeline; parity unpinned) runs on the device: ``augment.DeviceAugmenter``."""
 import glob
 import random
 import warnings
@@ -139,12 +140,15 @@ class SizeSchedule:
 
 class ListDataset(Dataset):
     """Training / evaluation set given as a text file of image paths (reference ``utils/datasets.py:65-143``); items are
-    (path, float image [3,S',S'] padded to square, targets [n,6] with column 0 left for the sample index)."""
+    (path, float image [3,S',S'] padded to square, targets [n,6] with column 0 left for the sample index).  With ``raw_u8`` an
+    item is (path, uint8 HWC tensor, boxes [n,5] as read) and a batch is (paths, tiles, boxes, size): nothing is converted, padded
+    or resized on the host, ``augment.DeviceAugmenter`` makes the network's batch of side ``size`` on the device."""
 
-    def __init__(self, list_path, img_size=416, multiscale=True):
+    def __init__(self, list_path, img_size=416, multiscale=True, raw_u8=False):
         with open(list_path) as fh:
             self.img_files = [line.strip() for line in fh if line.strip()]
         self.schedule = SizeSchedule(img_size, multiscale)
+        self.raw_u8 = raw_u8
 
     @property
     def img_size(self):
@@ -158,6 +162,8 @@ class ListDataset(Dataset):
         sample = read_sample(path)
         if sample is None:
             return None
+        if self.raw_u8:
+            return path, torch.from_numpy(np.array(sample[0])), torch.from_numpy(np.array(sample[1], dtype=np.float64))
         img, targets = default_transform(*sample)
         return path, img, targets
 
@@ -166,6 +172,8 @@ class ListDataset(Dataset):
         size = self.schedule.next()
         kept = [item for item in batch if item is not None]
         paths = tuple(item[0] for item in kept)
+        if self.raw_u8:
+            return paths, [item[1] for item in kept], [item[2] for item in kept], size
         imgs = torch.stack([resize(item[1], size) for item in kept])
         for k, item in enumerate(kept):
             item[2][:, 0] = k

@@ -5,7 +5,12 @@ Kept from the reference: Adam with default hyper-parameters and no schedule (``:
 when ``batches_done % gradient_accumulations == 0`` (``:116-119``, i.e. after batch 0, 2, 4, ... with gradients summed,
 not averaged); per-batch metric table of the three YOLO layers (``:125-154``); ``evaluate`` at
 (iou .5, conf .5, nms .5, batch 8) every ``evaluation_interval`` epochs (``:161-169``); ``state_dict`` checkpoints
-``checkpoints/yolov3_ckpt_%d.pth`` (``:205-206``).  Not kept: TensorBoard logging and imgaug augmentation.
+``checkpoints/yolov3_ckpt_%d.pth`` (``:205-206``).  Not kept: TensorBoard logging.
+
+``augment=True`` (``--augment``) is the counterpart of the reference's imgaug pipeline (Dropout, Sharpen, Affine,
+AddToBrightness, AddToHue, Fliplr): the loader hands out the decoded uint8 tiles and label rows, and ``augment.DeviceAugmenter``
+makes the step's fp32 batch and its targets on the device in one kernel pass.  imgaug cannot be installed here, so its parity is
+unpinned; the behaviour is THE AUGMENTATION RULE of ``include/amyloid_yolo.h``.  Off by default; evaluation is never augmented.
 """
 import argparse
 import os
@@ -34,8 +39,9 @@ def format_metrics(model, epoch, epochs, batch_i, n_batches):
 def train(epochs=100, batch_size=8, gradient_accumulations=2, model_def="config/yolov3.cfg", data_config="config/coco.data",
           pretrained_weights=None, n_cpu=8, img_size=416, checkpoint_interval=1, evaluation_interval=1,
           multiscale_training=True, verbose=False, checkpoint_dir="checkpoints", max_batches=None, seed=0, precision="bf16",
-          box_loss="mse"):
-    """``precision``: "bf16" = MFMA training path (bf16 activations/gradients, fp32 master weights and statistics),
+          box_loss="mse", augment=False, augmenter=None):
+    """``augment``: train behind the device augmentation (an ``augment.DeviceAugmenter`` seeded with ``(seed, rank)``, or the
+    ``augmenter`` handed in).  ``precision``: "bf16" = MFMA training path (bf16 activations/gradients, fp32 master weights and statistics),
     "fp32" = the parity path that reproduces the reference's fp32 step to 1e-4.  ``box_loss``: "mse" (reference) | "giou"."""
     rank, local_rank, world = init_distributed()
     dev = torch.device("cuda", local_rank)
@@ -52,7 +58,10 @@ def train(epochs=100, batch_size=8, gradient_accumulations=2, model_def="config/
         else:
             model.load_darknet_weights(pretrained_weights)
     broadcast_parameters(model)
-    dataset = ListDataset(cfg["train"], multiscale=multiscale_training, img_size=img_size)
+    dataset = ListDataset(cfg["train"], multiscale=multiscale_training, img_size=img_size, raw_u8=bool(augment))
+    if augment and augmenter is None:
+        from .augment import DeviceAugmenter
+        augmenter = DeviceAugmenter(seed, rank)
     # every rank gets the same number of tiles (the tail wraps around), hence the same number of batches: optimiser steps,
     # accumulation boundaries and collectives line up on all ranks
     data = Subset(dataset, shard_indices_equal(len(dataset), rank, world)) if world > 1 else dataset
@@ -71,12 +80,17 @@ def train(epochs=100, batch_size=8, gradient_accumulations=2, model_def="config/
     for epoch in range(epochs):
         model.train()
         t0 = time.time()
-        for batch_i, (_, imgs, targets) in enumerate(loader):
+        for batch_i, batch in enumerate(loader):
+            if augment:
+                _, tiles, boxes, size = batch
+                imgs, targets = augmenter(tiles, boxes, size)      # uint8 tiles up, fp32 batch and targets made on the device
+            else:
+                imgs, targets = batch[1].to(dev), batch[2].to(dev)
             batches_done = len(loader) * epoch + batch_i          # the same on every rank (equal shards)
             step_now = batches_done % gradient_accumulations == 0  # train.py:116: after batch 0, 2, 4, ... gradients summed
             if step_now:
                 reducer.begin()                                    # buckets go out while the backward is still running
-            loss, outputs = model(imgs.to(dev), targets.to(dev))
+            loss, outputs = model(imgs, targets)
             loss.backward()
             if step_now:
                 reducer.all_reduce(average=False)      # the one exchange step of data parallelism (waits for the buckets)
@@ -127,10 +141,11 @@ def main(argv=None):
     ap.add_argument("--logdir", type=str, default="logs")
     ap.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--box_loss", type=str, default="mse", choices=["mse", "giou"])
+    ap.add_argument("--augment", default=False, action="store_true", help="device-side training augmentation (augment.py)")
     o = ap.parse_args(argv)
     train(o.epochs, o.batch_size, o.gradient_accumulations, o.model_def, o.data_config, o.pretrained_weights, o.n_cpu, o.img_size,
           o.checkpoint_interval, o.evaluation_interval, o.multiscale_training not in (False, "False"), o.verbose,
-          precision=o.precision, box_loss=o.box_loss)
+          precision=o.precision, box_loss=o.box_loss, augment=o.augment)
 
 
 if __name__ == "__main__":

@@ -306,6 +306,53 @@ int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int region_h, int 
 int ay_ingest_region_tiles_list_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                                    int tile, const int32_t* origins_xy, int n, int out_size, float* out_nchw, ay_stream_t stream);
 
+/* ---- training augmentation fused into the ingest (amyloid_yolo_paper_amd/augment.py; csrc/ay_augment.hip) -------------------
+ * The reference trains behind an imgaug pipeline (utils/augmentations.py: Dropout, Sharpen, Affine +-20 deg / +-20 %,
+ * AddToBrightness, AddToHue, Fliplr).  imgaug cannot be installed where this project is built, so PARITY WITH IMGAUG IS UNPINNED:
+ * the behaviour is defined by the rule below and restated in NumPy by tests/augment_reference.py.
+ *
+ * THE AUGMENTATION RULE (every operation IEEE fp32, in the order written, nothing fused).
+ *   One record per image (ay_aug_params, device memory).  For output pixel (x, y) of the S x S image of a record (h, w, ...):
+ *   1. Square pixel, the nearest rule of ay_ingest_tiles_u8 unchanged: D = max(h, w), scale = (float)D / (float)S,
+ *        qx = min((int)floorf(x * scale), D - 1) - left,  qy = min((int)floorf(y * scale), D - 1) - top,
+ *      left / top the centre-pad offsets of ay_ingest_tiles_u8 (h <= w: top = (w - h) / 2, left = 0; else left = (h - w) / 2).
+ *   2. Flip: if flip, qx = w - 1 - qx (the reference flips last, so the inverse mapping flips first).
+ *   3. Inverse affine about the image centre: cx = (float)(w - 1) / 2, cy = (float)(h - 1) / 2, xc = qx - cx, yc = qy - cy,
+ *        sx = ((inv[0] * xc + inv[1] * yc) + inv[2]) + cx,  sy = ((inv[3] * xc + inv[4] * yc) + inv[5]) + cy.
+ *   4. Bilinear sample of the uint8 source: x0 = floorf(sx), fx = sx - x0, the same for y; taps a, b, c, d at (y0, x0), (y0, x0+1),
+ *      (y0+1, x0), (y0+1, x0+1) as floats in 0..255, a tap outside [0, h) x [0, w) is 0 (imgaug's cval = 0, and the pad value);
+ *        t = a + fx * (b - a),  u = c + fx * (d - c),  W = t + fy * (u - t).
+ *   5. Sharpen, on the warped S x S image W: ring = the sum of the 8 neighbours of W, indices clamped at the edge of the output
+ *      image, summed rows top to bottom, left to right, centre skipped;  v = W + sharpen_alpha * (8 * W - ring).
+ *   6. Dropout: idx = y * S + x; hsh = drop_seed ^ (idx * 0x9E3779B9); hsh ^= hsh >> 16; hsh *= 0x7feb352d; hsh ^= hsh >> 15;
+ *      hsh *= 0x846ca68b; hsh ^= hsh >> 16 (all uint32); if hsh < drop_threshold, v = 0 in all three channels.
+ *   7. Colour: o_k = ((color[3k] * v_r + color[3k+1] * v_g) + color[3k+2] * v_b) + bright.
+ *   8. out = min(max(o, 0), 255) / 255.0f (evaluated as o > 0 ? o : 0, then o < 255 ? o : 255), fp32 NCHW.
+ *   With inv = (1,0,0, 0,1,0), flip = 0, sharpen_alpha = 0, drop_threshold = 0, color = I, bright = 0 every step is exact and the
+ *   output is bit-identical to ay_ingest_tiles_u8(pad_value = 0).
+ *   Departures from the reference: sharpen and dropout act on the warped image at output resolution, not on the source; brightness
+ *   is an additive offset on R, G and B; hue is a rotation about the grey axis handed over as the matrix `color` (the host computes
+ *   it in float64; the device does no trigonometry and no HSV round trip); imgaug's kernels and colour spaces are not restated. */
+typedef struct ay_aug_params {
+    int64_t src_offset;            /* byte offset of the image [h][w][3] uint8 in the source buffer (a batch may be ragged) */
+    int32_t h, w;
+    float inv[6];                  /* output -> source, about the image centre: rows (inv0 inv1 inv2), (inv3 inv4 inv5) */
+    int32_t flip;                  /* 0 | 1 */
+    float sharpen_alpha;
+    uint32_t drop_threshold;       /* floor(p * 2^32): a pixel is dropped iff its hash is below */
+    uint32_t drop_seed;
+    float color[9];                /* row-major 3 x 3 on (R, G, B) */
+    float bright;                  /* added after the matrix, in 0..255 units */
+} ay_aug_params;
+
+/* src_u8: `src_bytes` bytes of device memory holding the images one after another; params_device [batch]; out [batch][3][S][S] fp32.
+ * A record whose image does not lie inside [src_u8, src_u8 + src_bytes) (or with h, w <= 0) is treated as all padding: nothing
+ * outside the buffer is read.  One kernel: a 256-thread workgroup warps a 16 x 64 block of output pixels plus a one-pixel halo into
+ * LDS, then sharpens from there; 16-byte stores per lane when out_size is a multiple of 4 and `out_nchw` is 16-byte aligned, the
+ * scalar form with the same bits otherwise.  batch <= 65535, out_size <= 32768.  Kernel launches only. */
+int ay_augment_ingest_u8(const void* src_u8, size_t src_bytes, const ay_aug_params* params_device, int batch, int out_size,
+                         float* out_nchw, ay_stream_t stream);
+
 /* ---- tissue map: which tiles of a slide are worth reading (wsi.tissue_counts, wsi.wanted_tiles; csrc/ay_tissue.hip) ------------
  * THE TISSUE RULE (exact, integer).
  *   A pixel of the (halved, for shrink == 2) image is TISSUE iff min(R, G, B) < bg_level on its uint8 values; for shrink == 2 the
