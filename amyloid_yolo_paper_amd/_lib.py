@@ -142,6 +142,10 @@ _SIGS = {
     "ay_seam_append": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P]),
     "ay_seam_merge_workspace_bytes": (_SZ, [_I]),
     "ay_seam_merge": (_I, [_P, _P, _I, _F, _P, _P, _P, _SZ, _P]),
+    "ay_ingest_region_tiles_views_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, C.POINTER(C.c_int), _I, _I, _P, _P]),
+    "ay_unview_rows": (_I, [_P, _I, C.POINTER(C.c_int), _I, _I, _I, _I, _P]),
+    "ay_view_votes": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P, _I, _P, _P]),
+    "ay_view_select": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -30,6 +30,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr
 from .utils import nms_device, non_max_suppression
+from .views import check_views, nms_views_device
 
 
 def tile_grid(H, W, tile, overlap=0):
@@ -90,9 +91,15 @@ class RegionTileStream:
     ``tile_mask`` (NumPy bool ``[tiles_y, tiles_x]``, e.g. from :func:`wanted_tiles`; default: every tile): a strip without a wanted
     tile is not staged, not uploaded and yields nothing; of any other strip only the columns from its first to its last wanted tile
     are staged and uploaded (one contiguous block), and only its wanted tiles are cut and yielded, in grid order, with their
-    coordinates on the full grid."""
+    coordinates on the full grid.
 
-    def __init__(self, raster, tile=1536, img_size=1024, shrink=1, overlap=0, tile_mask=None):
+    ``views`` (default ``(0,)``: the tile as it lies on the slide): a list of distinct dihedral view ids 0..7 (``views.py``, THE VIEW
+    RULE in ``include/amyloid_yolo.h``).  With any other list every tile is cut in each of the ``V`` views by
+    ``ay_ingest_region_tiles_views_u8`` -- the strip is read once for all of them -- and a strip yields ``[n * V, 3, S, S]``,
+    tile-major (tile ``i`` in view ``views[j]`` is image ``i * V + j``), with the coordinates of the ``n`` tiles."""
+
+    def __init__(self, raster, tile=1536, img_size=1024, shrink=1, overlap=0, tile_mask=None, views=(0,)):
+        self.views = check_views(views)
         if not torch.cuda.is_available():
             raise _lib.AyError("no HIP device: RegionTileStream has no CPU fallback")
         assert raster.ndim == 3 and raster.shape[2] == 3 and raster.dtype == np.uint8, "uint8 [H,W,3] raster"
@@ -205,18 +212,29 @@ class RegionTileStream:
         return torch.from_numpy(xy).to(self.dev), starts
 
     def _ingest_list(self, L, k, n, w, origins, m, out):
+        """tiles ``origins[:m]`` of the block in ``_strips[k]`` -> ``out[:m * V]``, every tile in the stream's views"""
+        if self.views != (0,):
+            ids = (C.c_int * len(self.views))(*self.views)
+            check(L.ay_ingest_region_tiles_views_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, ids,
+                                                    len(ids), self.S, ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_views_u8")
+            return
         check(L.ay_ingest_region_tiles_list_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, self.S,
                                                ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_list_u8")
 
     def __iter__(self):
         L = _lib.lib()
+        V = len(self.views)
         if self.tile_mask is not None:
             table, starts = self._wanted_table()
             coords = self._wanted()
+        elif self.views != (0,):     # the views entry takes a list of origins: those of a full tile row
+            row = torch.tensor([(i * self.step, 0) for i in range(self.tiles_x)], dtype=torch.int32, device=self.dev)
         for j, k, valid, width in self._strip_loop():
             if self.tile_mask is None:
-                out = torch.empty(self.tiles_x, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
-                if self.overlap == 0:
+                out = torch.empty(self.tiles_x * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
+                if self.views != (0,):
+                    self._ingest_list(L, k, valid, width, row, self.tiles_x, out)
+                elif self.overlap == 0:
                     check(L.ay_ingest_region_tiles_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile, 1,
                                                       self.tiles_x, self.S, ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_u8")
                 else:
@@ -227,28 +245,29 @@ class RegionTileStream:
                 yield out, [(j, i) for i in range(self.tiles_x)]
             else:
                 a, b = int(starts[j]), int(starts[j + 1])
-                out = torch.empty(b - a, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
+                out = torch.empty((b - a) * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
                 self._ingest_list(L, k, valid, width, table[a:], b - a, out)
                 self._release(k)
                 yield out, coords[a:b]
 
     def _batches(self, batch_size):
-        """The masked iteration as detect_region takes it: yields ``(tiles [n,3,S,S], w0)``, the wanted tiles ``w0 .. w0 + n`` of
+        """The masked iteration as detect_region takes it: yields ``(tiles [n * V,3,S,S], w0)``, the wanted tiles ``w0 .. w0 + n`` of
         :meth:`_wanted`, ``n == batch_size`` but for the last batch: a strip's wanted tiles are cut into the open batch buffer at its
         fill, so that batches are filled across strip boundaries.  Every ingest of a strip is issued (into as many batch buffers as
         it takes) and the strip released before its batches are handed out, so the refill of a strip buffer never waits for a model
         call, also when a batch holds tiles of two strips."""
         L = _lib.lib()
         table, starts = self._wanted_table()
+        V = len(self.views)
         cur, fill, w0 = None, 0, 0
         for j, k, valid, width in self._strip_loop():
             a, b = int(starts[j]), int(starts[j + 1])
             ready = []
             while a < b:
                 if cur is None:
-                    cur, fill, w0 = torch.empty(batch_size, 3, self.S, self.S, device=self.dev, dtype=torch.float32), 0, a
+                    cur, fill, w0 = torch.empty(batch_size * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32), 0, a
                 m = min(b - a, batch_size - fill)
-                self._ingest_list(L, k, valid, width, table[a:], m, cur[fill:])
+                self._ingest_list(L, k, valid, width, table[a:], m, cur[fill * V:])
                 fill, a = fill + m, a + m
                 if fill == batch_size:
                     ready.append((cur, w0))
@@ -256,7 +275,7 @@ class RegionTileStream:
             self._release(k)
             yield from ready
         if cur is not None:
-            yield cur[:fill], w0
+            yield cur[:fill * V], w0
 
 
 def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
@@ -294,7 +313,8 @@ def tissue_mask(raster, tile, shrink=1, overlap=0, min_tissue=0.01, bg_level=220
 
 
 def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=0.8, nms_thres=0.4, batch_size=64, overlap=0,
-                  seam_thres=0.5, max_det=1024, seam_capacity=None, tile_mask=None, min_tissue=0.0, bg_level=220, probe_stride=16):
+                  seam_thres=0.5, max_det=1024, seam_capacity=None, tile_mask=None, min_tissue=0.0, bg_level=220, probe_stride=16,
+                  views=(0,), min_views=1, vote_thres=None):
     """Detection over a whole raster: the loop of ``detect.py:88-105`` fed by :class:`RegionTileStream`.
 
     Returns a list of ``(ty, tx, boxes)`` with ``boxes [n,7]`` = (x1, y1, x2, y2, conf, cls_conf, cls_pred) in pixels of the
@@ -320,7 +340,28 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
     bg_level, probe_stride)``, i.e. tiles with at least that fraction of tissue pixels (``min(R, G, B) < bg_level``) on a probe
     that takes every ``probe_stride``-th pixel of the (halved) slide -- single source pixels, no averaging, so an object smaller
     than ``probe_stride`` pixels that is alone in its tile can be missed; ``probe_stride`` must divide ``tile`` and ``tile -
-    overlap``.  ``probe_stride=1`` counts on the raster itself (exact, and a full upload of the slide before the detection pass)."""
+    overlap``.  ``probe_stride=1`` counts on the raster itself (exact, and a full upload of the slide before the detection pass).
+
+    ``views`` (default ``(0,)``; ``views.ALL_VIEWS``, ``views.FLIPS`` or any list of distinct ids 0..7) is test-time augmentation
+    over the orientations of the square: every tile is cut in each of the ``V`` views on the device (one read of the strip for all of
+    them, THE VIEW RULE in ``include/amyloid_yolo.h``), the network runs on all of them, the boxes are mapped back to the tile's
+    frame (exact in fp32) and the rows of all views of a tile go through ONE merge-NMS, so a sighting that several views share comes
+    out once, with the confidence-weighted box of its cluster.  ``min_views > 1`` (at most ``V``) then keeps a detection only if at
+    least that many views hold a row of its class above ``conf_thres`` whose IoU with it exceeds ``vote_thres`` (default:
+    ``nms_thres``; THE VOTE RULE).  Cost: ``V`` times the network (a model call takes ``max(1, batch_size // V)`` tiles, at most
+    ``batch_size`` images; the ingest and the post-processing stay small against it), and on both paths at most ``max_det``
+    detections per tile (``AyError`` beyond).  What the votes can do: remove rows that only a few orientations report, which for an
+    orientation-free object are mostly false alarms.  What they cannot do: they never add a detection, they do not re-score or move
+    a box, and an error the network makes in every orientation gets every vote.  The views only agree as far as the model is
+    equivariant: for a model that is not (one trained without ``augment=True``), the merged boxes and the votes depend on which
+    views are listed and on their order only through the rows the network returns -- the same list always gives the same bytes,
+    another list may give another result.  With the defaults nothing of this is called and the result is unchanged, bit for bit."""
+    views = check_views(views)
+    if isinstance(min_views, bool) or int(min_views) != min_views or not 1 <= int(min_views) <= len(views):
+        raise ValueError(f"detect_region: min_views {min_views!r} outside 1 .. {len(views)} (the number of views)")
+    if vote_thres is not None and not 0.0 <= float(vote_thres) <= 1.0:      # a NaN fails both comparisons
+        raise ValueError(f"detect_region: vote_thres {vote_thres!r} is no IoU in 0 .. 1")
+    tta = None if views == (0,) and int(min_views) == 1 else (views, int(min_views), vote_thres)
     H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
     if tile_mask is None and min_tissue > 0:
         tile_mask = tissue_mask(raster, tile, shrink, overlap, min_tissue, bg_level, probe_stride)
@@ -328,7 +369,9 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
         return []
     if overlap:
         return _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, overlap, seam_thres,
-                                      max_det, seam_capacity, tile_mask)
+                                      max_det, seam_capacity, tile_mask, tta)
+    if tta is not None:
+        return _detect_region_views(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, max_det, tile_mask, tta)
     results = []
     scale = float(tile) / float(img_size)
     model.eval()
@@ -357,11 +400,53 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
     return results
 
 
+def _detect_region_views(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, max_det, tile_mask, tta):
+    """the abutting path with views: per model call ``max(1, batch_size // V)`` tiles in V views, ``nms_views_device``, and the rows of
+    the batch read back -- the arithmetic on them is that of the path without views"""
+    views, min_views, vote_thres = tta
+    V, max_det = len(views), int(max_det)
+    per_call = max(1, int(batch_size) // V)
+    results = []
+    scale = float(tile) / float(img_size)
+    model.eval()
+
+    def run(tiles, coords):
+        with torch.no_grad():
+            rows, _, count, _ = nms_views_device(model.forward_device(tiles), views, conf_thres, nms_thres, max_det, min_views,
+                                                 vote_thres, img_dim=img_size)
+            count_h, rows_h = count.cpu().tolist(), rows.cpu()
+        if max(count_h) > max_det:
+            raise _lib.AyError(f"detect_region: a tile holds more than max_det={max_det} detections; raise max_det or conf_thres")
+        for (ty, tx), n, d in zip(coords, count_h, rows_h):
+            if n == 0:
+                continue
+            d = d[:n].clone()
+            d[:, :4] *= scale
+            d[:, [0, 2]] += tx * tile
+            d[:, [1, 3]] += ty * tile
+            results.append((ty, tx, d))
+
+    stream = RegionTileStream(raster, tile, img_size, shrink, tile_mask=tile_mask, views=views)
+    if tile_mask is None:
+        for tiles, coords in stream:
+            for s in range(0, len(coords), per_call):
+                run(tiles[s * V:(s + per_call) * V], coords[s:s + per_call])
+    else:
+        coords = stream._wanted()
+        for tiles, w0 in stream._batches(per_call):
+            run(tiles, coords[w0:w0 + tiles.shape[0] // V])
+    return results
+
+
 def _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, overlap, seam_thres, max_det,
-                           seam_capacity, tile_mask=None):
+                           seam_capacity, tile_mask=None, tta=None):
     from .postprocess import seam_merge_device
     L = _lib.lib()
-    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask)
+    views, min_views, vote_thres = tta if tta is not None else ((0,), 1, None)
+    V = len(views)
+    if tta is not None:
+        batch_size = max(1, int(batch_size) // V)     # tiles per model call: at most batch_size images
+    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask, views)
     dev, TX, step = stream.dev, stream.tiles_x, stream.step
     # per tile that runs, on the device for the whole slide: its id (grid order on the full grid) and the (x, y) of its corner
     if tile_mask is None:
@@ -377,17 +462,21 @@ def _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nm
     scale = C.c_float(float(tile) / float(img_size))
     model.eval()
 
-    def batches():   # (tiles, index of the first of them in ids / origins)
+    def batches():   # (tiles [n * V ...], index of the first of the n in ids / origins)
         if tile_mask is not None:
             yield from stream._batches(batch_size)
             return
         for tiles, coords in stream:
-            for s in range(0, tiles.shape[0], batch_size):
-                yield tiles[s:s + batch_size], coords[s][0] * TX + coords[s][1]
+            for s in range(0, len(coords), batch_size):
+                yield tiles[s * V:(s + batch_size) * V], coords[s][0] * TX + coords[s][1]
 
     for tiles, t0 in batches():
         with torch.no_grad():  # no read-back: the NMS result buffers are overwritten by the next batch, the append is right behind
-            rows, _, count, _ = nms_device(model.forward_device(tiles), conf_thres, nms_thres, int(max_det))
+            if tta is None:
+                rows, _, count, _ = nms_device(model.forward_device(tiles), conf_thres, nms_thres, int(max_det))
+            else:             # rows and count in nms_device's form, one image per TILE
+                rows, _, count, _ = nms_views_device(model.forward_device(tiles), views, conf_thres, nms_thres, int(max_det), min_views,
+                                                     vote_thres, img_dim=img_size)
         B = rows.shape[0]
         check(L.ay_seam_append(ptr(rows), ptr(count), B, int(max_det), scale, ptr(origins[t0:t0 + B]), ptr(ids[t0:t0 + B]),
                                ptr(slide_rows), ptr(slide_tile), ptr(slide_count), capacity, _lib.stream_ptr()), "ay_seam_append")

@@ -566,6 +566,51 @@ size_t ay_seam_merge_workspace_bytes(int n_rows);
 int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile, int n_rows, float seam_thres, uint8_t* keep, int32_t* stats,
                   void* workspace, size_t workspace_bytes, ay_stream_t stream);
 
+/* ---- dihedral test-time views (wsi.detect_region(views=...), amyloid_yolo_paper_amd/views.py; csrc/ay_views.hip) ----------------
+ * Plaques have no orientation: a tile can be run in several of the 8 orientations of the square, the boxes mapped back and merged,
+ * and a detection kept only if enough orientations support it.  Both rules are exact and restated in NumPy by
+ * tests/views_reference.py.
+ *
+ * THE VIEW RULE.  A view id v is in 0 .. 7 with FX = v & 1, FY = (v >> 1) & 1, T = (v >> 2) & 1.  Let I0 be the S x S image that
+ *   ay_ingest_region_tiles_list_u8 produces for a tile origin.  View v of that tile is defined on the OUTPUT grid, after the nearest
+ *   resize, so it is a pure permutation of I0's bits:
+ *     out_v[c][y][x] = I0[c][sy][sx],  (a, b) = T ? (y, x) : (x, y),  sx = FX ? S-1-a : a,  sy = FY ? S-1-b : b.
+ *   View 0 is I0; in torch terms: flip I0 along x and / or y, then transpose if T.
+ *   A decoded row (cx, cy, w, h, conf, cls...) of view v goes back to the frame of I0 in fp32, one operation each:
+ *     (a, b) = T ? (cy, cx) : (cx, cy),  X = FX ? (float)S - a : a,  Y = FY ? (float)S - b : b,  (W, H) = T ? (h, w) : (w, h);
+ *   confidence and class scores are copied untouched.  (In the decode pixel x covers [x, x+1): hence S - a, not S-1-a.)
+ *
+ * THE VOTE RULE.  After the merge-NMS over the concatenated rows of all views of a tile (n_views * N rows per image, view j of the list
+ *   in rows [j*N, (j+1)*N)), `pred` holds corners in place.  View j votes for emitted detection d of image b iff some row r of that
+ *   range satisfies all of: conf >= conf_thres; its arg-max class (first maximum) equals (int)rows[d][6]; its IoU with rows[d][0:4] is
+ *   strictly greater than vote_thres -- the +1-pixel IoU in the operation order of ay_box_iou mode 0 on corners.  votes[b][d] is the bit
+ *   mask over j; entries at or behind min(count[b], max_det) are 0.  The result does not depend on any order.
+ *
+ * ay_ingest_region_tiles_views_u8: the list cut in n_views views; `views` is a HOST array of 1 .. 8 distinct ids (else AY_ERR_ARG),
+ *   origins_xy [n][2] on the device with the list form's semantics, out [n][n_views][3][S][S] fp32, TILE-major.  views = {0} gives
+ *   ay_ingest_region_tiles_list_u8 bit for bit.  A workgroup computes a 32 x 32 block of I0 once, holds it in LDS (rows padded to 33
+ *   floats) and stores it into every view from there, row-contiguously also for the transposed views: the slide bytes are fetched
+ *   once for all views.  16-byte stores per lane when out_size is a multiple of 4 and `out_nchw` is 16-byte aligned, the scalar form
+ *   with the same bits otherwise.
+ * ay_unview_rows: the box rule, in place on pred [n_images][n_rows][5 + num_classes], image i in view views[i % n_views] (host array).
+ *   Runs behind the forward and BEFORE ay_nms_filter / ay_nms_merge (it needs cx, cy, w, h); pred seen as [n_images / n_views][n_views *
+ *   n_rows][5 + C] is then the per-tile concatenation, without a copy.
+ * ay_view_votes: the vote rule; votes int32 [batch][max_det], zeroed by a kernel of the call; integer OR atomics, the same bits every
+ *   run.
+ * ay_view_select: per image a stable in-place compaction of the rows (and of keep_idx, which may be null) whose vote mask has at least
+ *   min_views bits set; count[b] becomes the number kept, but an image with count[b] > max_det keeps its count (its first max_det rows
+ *   are compacted), so that the caller's overflow check still fires.  `votes` is left as it is.
+ * All four: kernel launches only, no scratch. */
+int ay_ingest_region_tiles_views_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                    int tile, const int32_t* origins_xy, int n, const int* views, int n_views, int out_size,
+                                    float* out_nchw, ay_stream_t stream);
+int ay_unview_rows(float* pred, int n_images, const int* views, int n_views, int n_rows, int num_classes, int img_dim,
+                   ay_stream_t stream);
+int ay_view_votes(const float* pred, int batch, int n_views, int n_rows_per_view, int num_classes, float conf_thres, float vote_thres,
+                  const float* rows, const int32_t* count, int max_det, int32_t* votes, ay_stream_t stream);
+int ay_view_select(float* rows, int32_t* keep_idx, int32_t* count, const int32_t* votes, int batch, int max_det, int min_views,
+                   ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call -- so a stream capture of a step (ay_plan_forward + ay_nms_merge ...)
  * replays like any other graph (scripts/micro/graph_sync.hip, graph_coherence.hip, graph_input_coherence.hip: every wait covers a
