@@ -36,8 +36,9 @@ namespace ay {
 #ifdef AY_PHASE_CLOCK
 // instrumented build only (AY_PHASE_CLOCK=1 python build.py, AY_DBG=8 at run time): 100 MHz ticks of wave 0, summed over
 // workgroups: [0] stage loops, [1] epilogues, [2] items, [3] workgroups, [4] whole kernel per workgroup, [5] waits for landed
-// stages (vmcnt + barrier, both kinds), [6] slowest workgroup, [7] straddle step + its barrier
-__device__ unsigned long long g_phase_ticks_m16[8];
+// stages (vmcnt + barrier, both kinds), [6] slowest workgroup, [7] straddle step + its barrier, [8] the part of [5] spent in the
+// first wait of an item (end of its first even stage: the only wait with the previous item's output stores in front of it)
+__device__ unsigned long long g_phase_ticks_m16[10];
 #define AY_CLK(...) __VA_ARGS__
 #else
 #define AY_CLK(...)
@@ -197,7 +198,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
     asm volatile("" ::: "memory");
 
     int par = 0;
-    AY_CLK(const bool clk = (a.dbg & 8) && wave == 0; unsigned long long tk_stage = 0, tk_epi = 0, tk_items = 0, tk_wait = 0, tk_str = 0, tk0 = 0, tkw = 0;
+    AY_CLK(const bool clk = (a.dbg & 8) && wave == 0; unsigned long long tk_stage = 0, tk_epi = 0, tk_items = 0, tk_wait = 0, tk_wait0 = 0, tk_str = 0, tk0 = 0, tkw = 0;
            const unsigned long long tk_begin = wall_clock64();)
     while (true) {
         AY_CLK(if (clk) tk0 = wall_clock64();)
@@ -326,7 +327,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the odd stage has landed
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            AY_CLK(if (clk) { const unsigned long long t = wall_clock64(); tk_wait += t - tkw; tkw = t; })
+            AY_CLK(if (clk) { const unsigned long long t = wall_clock64(); tk_wait += t - tkw; if (s == 0) tk_wait0 += t - tkw; tkw = t; })
             // ---- tap 8 of both stages in one K32-step.  Every wave is through with the filter taps 0..7 of slot 0 (barrier
             // above), the straddle reads tap 8 and the pixels only: the next stage's taps 0..7 stream into slot 0 already
             const bool issued = !ld_done;
@@ -429,7 +430,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
         const unsigned long long tot = wall_clock64() - tk_begin;
         atomicAdd(&g_phase_ticks_m16[0], tk_stage); atomicAdd(&g_phase_ticks_m16[1], tk_epi); atomicAdd(&g_phase_ticks_m16[2], tk_items);
         atomicAdd(&g_phase_ticks_m16[3], 1ull); atomicAdd(&g_phase_ticks_m16[4], tot); atomicAdd(&g_phase_ticks_m16[5], tk_wait);
-        atomicMax(&g_phase_ticks_m16[6], tot); atomicAdd(&g_phase_ticks_m16[7], tk_str);
+        atomicMax(&g_phase_ticks_m16[6], tot); atomicAdd(&g_phase_ticks_m16[7], tk_str); atomicAdd(&g_phase_ticks_m16[8], tk_wait0);
     })
 }
 
@@ -448,6 +449,8 @@ static int conv3x3_m16_fwd(const ay_conv_desc* d, const void* src, const void* w
     AY_CHECK_ARG((long long)d->hout * d->wout * 2 * d->cout_pad < (1ll << 31),
                  "ay_conv3x3_m16_fwd_bf16: one image's output (%dx%dx%d) exceeds the 2 GiB a store descriptor addresses", d->hout, d->wout,
                  d->cout_pad);
+    AY_CHECK_ARG((long long)d->hin * d->win * 2 * d->cin < (1ll << 31),
+                 "ay_conv3x3_m16_fwd_bf16: one image's input (%dx%dx%d) exceeds the 2 GiB a load descriptor addresses", d->hin, d->win, d->cin);
     ConvArgs a;
     a.src = (const uint8_t*)src;
     a.w = (const uint8_t*)w_packed;
@@ -491,14 +494,15 @@ static int conv3x3_m16_fwd(const ay_conv_desc* d, const void* src, const void* w
     AY_CHECK_LAUNCH("conv3x3_m16_ring_kernel");
 #ifdef AY_PHASE_CLOCK
     if (a.dbg & 8) {  // timing experiments only: synchronous phase report per launch
-        unsigned long long t[8] = {0};
+        unsigned long long t[10] = {0};
         (void)hipStreamSynchronize(st);
         (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_phase_ticks_m16), sizeof(t));
+        const int nwait = d->cin / 16 - 1;  // waits of an item that is not a workgroup's last, the first one included
         if (t[3])
-            fprintf(stderr, "[ay phase m16] cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (of it waits for landed stages %.2f, straddle+barrier %.2f; %d stages), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
-                    d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[2] / t[3], t[0] * 0.01 / t[2], t[5] * 0.01 / t[2], t[7] * 0.01 / t[2],
-                    d->cin / 16, t[1] * 0.01 / t[2], t[4] * 0.01 / t[3], t[6] * 0.01);
-        unsigned long long z[8] = {0};
+            fprintf(stderr, "[ay phase m16] cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (of it waits for landed stages %.2f = first wait %.2f + others %.2f each, straddle+barrier %.2f; %d stages), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
+                    d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[2] / t[3], t[0] * 0.01 / t[2], t[5] * 0.01 / t[2], t[8] * 0.01 / t[2],
+                    nwait ? (t[5] - t[8]) * 0.01 / t[2] / nwait : 0.0, t[7] * 0.01 / t[2], d->cin / 16, t[1] * 0.01 / t[2], t[4] * 0.01 / t[3], t[6] * 0.01);
+        unsigned long long z[10] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks_m16), z, sizeof(z));
     }
 #endif

@@ -193,16 +193,19 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(ConvArgs a, DecodeArg
 
 // ---------------------------------------------------------------------------------------------------------
 // Ring kernel: persistent, ALL staging by LDS-DMA into a ring of NBUF stage buffers, counted vmcnt, raw s_barrier.
-//   * input pixels too go global -> LDS by DMA: lanes whose pixel falls outside the image (3x3 halo at the border,
-//     ragged tiles) read from a 64-byte page of zeros instead (the DMA source address is per lane);
+//   * input pixels too go global -> LDS by DMA.  Every piece is a `buffer_load_dwordx4 ... lds` (dma16_buf): a wave-uniform
+//     descriptor, a scalar offset (the stage) and ONE 32-bit offset per lane; lanes whose pixel falls outside the image (3x3
+//     halo at the border, ragged tiles) and the padding of the piece lists carry the offset 0x80000000, which is out of range
+//     for every descriptor and reads as zero -- no 64-bit address per lane, no page of zeros, no select per piece;
 //   * stage g+NBUF-1 is issued before the MFMAs of stage g: NBUF-1 stages of DMA in flight per CU, which is what
 //     the latency-bound layers (1x1, small Cin) need (ablation in DESIGN.md: staging alone ran at one stage/us);
-//   * every wave issues the same number PW of 1-KiB DMA pieces per stage (the piece list is padded with dummy
-//     pieces that copy zeros into a scratch KiB), so "stage g+1 has landed" is one constant `s_waitcnt vmcnt(PW)`.
-__device__ __attribute__((aligned(64))) uint32_t g_zero_page[16];  // zero-initialised by the loader
+//   * three slots: every wave issues the same number PW of 1-KiB DMA pieces per stage (the piece list is padded with dummy
+//     pieces that copy zeros into a scratch KiB), so "stage g+1 has landed" is one constant `s_waitcnt vmcnt(PW)`; two slots:
+//     every wait is `vmcnt(0)` and the padding pieces are skipped.
 // AY_DBG&8: phase clock of the ring kernel, summed over workgroups (wave 0): [0] stage loops, [1] epilogues, [2] items,
-// [3] workgroups, [4] whole-kernel ticks per workgroup, [5] first stages, [6] slowest workgroup; 100 MHz ticks (s_memrealtime)
-__device__ unsigned long long g_phase_ticks[8];
+// [3] workgroups, [4] whole-kernel ticks per workgroup, [5] first stages, [6] slowest workgroup, [7] stage-end waits (last MFMA
+// group to the barrier's return) of the first stage of an item, [8] of all other stages, [9] their number; 100 MHz ticks (s_memrealtime)
+__device__ unsigned long long g_phase_ticks[10];
 // dynamic item dealing: 64 rotating sets of {8 per-XCD item counters, exit counter}; zero at load, reset by the last workgroup
 constexpr int DEAL_SETS = 64, DEAL_STREAMS = 16;
 __device__ unsigned g_deal[DEAL_STREAMS * DEAL_SETS][16];
@@ -244,9 +247,8 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     constexpr int W_SLAB = W_PIECES * 1024;
     constexpr int W_BASE = NK * PIX_SLAB;
     constexpr int BUF_BYTES = NK * (PIX_SLAB + W_SLAB);
-    constexpr int NPIECE = NK * (PX_PIECES + W_PIECES);     // + the piece(s) that carry this item's scale/shift
-    constexpr int SSP = BN > 128 ? 2 : 1;                   // BN <= 128: one piece [scale | shift]; 256: a scale piece, a shift piece
-    constexpr int SSR = SSP * 1024;                         // bytes of one scale/shift region
+    constexpr int SSP = 2;                                  // a scale piece and a shift piece (one descriptor each), as in the m16 kernel
+    constexpr int SSR = SSP * 1024;                         // bytes of one scale/shift region [scale BN | 0 .. 1 KiB][shift BN | 0]
     // Piece i of a wave has the same KIND in every wave: i < PWP pixel pieces (global piece i*8 + wave of the pixel slabs), the
     // rest filter-side (filter pieces, then the scale/shift piece(s)); each list is padded to a multiple of 8 with dummy pieces
     // that copy zeros into a scratch KiB.  With the kind depending on the wave (one list i*8 + wave over all pieces) every DMA
@@ -254,8 +256,12 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     constexpr int PWP = (NK * PX_PIECES + 7) / 8;
     constexpr int PWW = (NK * W_PIECES + SSP + 7) / 8;
     constexpr int PW = PWP + PWW;                           // pieces per wave per stage (dummy-padded)
+    // Three slots: a stage is waited for with a COUNTED `s_waitcnt vmcnt(PW)` while the next one stays in flight, so every wave
+    // issues exactly PW pieces per stage, padding included.  Two slots: every wait is `vmcnt(0)`, nothing counts pieces, and a wave
+    // skips its padding pieces and re-sends the scale/shift pieces only with an item's first stage (9-11 % fewer DMA instructions).
+    constexpr bool COUNTED = (NBUF == 3);
     constexpr int DUMMY_BASE = NBUF * BUF_BYTES;
-    constexpr int SS_BASE = DUMMY_BASE + 1024;              // 4 x 1 KiB [scale 128][shift 128], by item index & 3 (the loader
+    constexpr int SS_BASE = DUMMY_BASE + 1024;              // 4 x 2 KiB [scale][shift], by item index & 3 (the loader
                                                             // runs at most NBUF-1 <= 2 items ahead of the epilogue)
     constexpr int MBOX_BASE = NBUF * BUF_BYTES + 1024 + 4 * SSR;  // 8 ints: item ids by sequence number & 7
     constexpr int LDS_BYTES = MBOX_BASE + 64;
@@ -324,29 +330,56 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     const int CP = a.cout_pad;
     const size_t w_stage_stride = (size_t)NK * KK2 * 2 * CP * 16;
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    const uint8_t* zero_page = reinterpret_cast<const uint8_t*>(g_zero_page);
     const unsigned lds_base = lds_addr_of(lds);
 
     // ---- loader: piece i of this wave is global piece q = i*8 + wave ------------------------------------------
-    // kind: pixel piece (kk, j) | filter piece (kk, j) | dummy.  Per lane: byte offset from the item's base, or -1.
-    int src_off[PW];
+    // kind: pixel piece (kk, j) | filter piece (kk, j) | scale piece | shift piece | dummy.  Per lane: ONE 32-bit byte offset per
+    // piece, or OOB where the lane has nothing to fetch.  Pixel offsets are relative to image b of the source (canvas mode: to the
+    // tensor, the lane's image rides in the offset) and change with the item; the filter-side offsets never change: the item's
+    // channel group, its parity class and the stage ride in the descriptor base and the scalar offset.
+    constexpr unsigned OOB = 0x80000000u;
+    unsigned src_off[PWP];
     // CAT (models.py:244-245 route of [upsampled x2 | direct] folded into this 1x1): stages below c1 channels read `src1`
     // at half resolution (pixel (y>>1, x>>1)), the rest `src`; c1 is a multiple of the stage's NK*16 channels
-    int src_off1[CAT ? PW : 1];
-    const uint8_t* ld_src1 = nullptr;
-    const size_t in_plane1 = (size_t)(a.hin >> 1) * (a.win >> 1) * 32;
+    unsigned src_off1[CAT ? PWP : 1];
+    const unsigned in_plane1 = (unsigned)(a.hin >> 1) * (unsigned)(a.win >> 1) * 32u;
     const int s1_stages = CAT ? a.c1 / (16 * NK) : 0;
+    const int src_planes = (a.cin - (CAT ? a.c1 : 0)) / 16;
+    // descriptor ranges (host-checked to stay below 2 GiB): one image's planes; canvas mode: the whole tensor
+    const int src_bytes = (int)((unsigned)src_planes * (unsigned)in_plane * (CANVAS ? (unsigned)a.batch : 1u));
+    const int src1_bytes = CAT ? (int)((unsigned)(a.c1 / 16) * in_plane1) : 0;
+    constexpr int BNR = PAIR ? BN / 2 : BN;   // real channels of the group
+    const uint8_t* ld_src1 = nullptr;
     const uint8_t* ld_src = nullptr;
     const uint8_t* ld_w = nullptr;
+    int ld_ch = 0;  // first real channel of the loader's group: its scales and shifts
     int ld_item = item, ld_s = 0, ld_par = 0;
     bool ld_done = false;
-    const float* ld_ss = nullptr;  // per-lane source of the scale/shift piece (nullptr: zero page)
+    unsigned w_off[PWW];
+#pragma unroll
+    for (int i = 0; i < PWW; ++i) {
+        const int qq = i * 8 + wave;   // filter piece; qq >= NK * W_PIECES: scale, shift or padding
+        const int u = qq * 64 + lane;  // unit inside the stage's filter image [kk][tap][half][BN]
+        const int r = u % BN, th = u / BN;
+        unsigned off = OOB;
+        if (qq < NK * W_PIECES) {
+            if constexpr (PAIR)   // rows BN/2.. of the tile: the second class's image, w_class_stride further on
+                off = (unsigned)((th * CP + r % (BN / 2)) * 16) + (unsigned)(r / (BN / 2)) * a.w_class_stride;
+            else
+                off = (unsigned)((th * CP + r) * 16);
+        } else if (qq < NK * W_PIECES + SSP && lane < BN / 4) {
+            // lane l carries scales (piece NK * W_PIECES) / shifts (the next one) 4l..4l+3 of the tile's BN channels (PAIR: tile
+            // channel t is real channel t % BNR of the group); the descriptor starts at the group's first channel
+            off = (unsigned)(((lane * 4) % BNR) * 4);
+        }
+        w_off[i] = off;
+    }
     auto setup_loader = [&](int it) __attribute__((always_inline)) {
         int cg = it % a.n_cgroups;
         const int pt = it / a.n_cgroups;
         const int b = pt / tiles_per_img;
         const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
-        ld_src = a.src + (size_t)b * ((a.cin - (CAT ? a.c1 : 0)) / 16) * in_plane;
+        ld_src = a.src + (size_t)b * src_planes * in_plane;
         if constexpr (CAT) ld_src1 = a.src1 + (size_t)b * (a.c1 / 16) * in_plane1;
         const uint8_t* wbase = a.w;
         if constexpr (PAIR) {   // classes (2 py, 2 py + 1): two consecutive filter images
@@ -356,79 +389,64 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
             wbase += (size_t)(cg & 3) * a.w_class_stride;
             cg >>= 2;
         }
-        constexpr int BNR = PAIR ? BN / 2 : BN;   // real channels of the group
         ld_w = wbase + (size_t)cg * BNR * 16;
-        // lanes 0..BN/4-1 fetch 4 scales each, lanes 32..32+BN/4-1 the shifts: LDS image [scale | pad to 128][shift]
-        // (PAIR: tile channel t is real channel t % BNR of the group)
-        if constexpr (SSP == 1)
-            ld_ss = (lane & 31) < BN / 4 ? ((lane < 32 ? a.scale : a.shift) + (size_t)cg * BNR + ((lane & 31) * 4) % BNR) : nullptr;
-        else  // 256 channels: lane l carries scales (piece NPIECE) / shifts (piece NPIECE + 1) 4l..4l+3
-            ld_ss = a.scale + (size_t)cg * BNR + (lane * 4) % BNR;
+        ld_ch = cg * BNR;
 #pragma unroll
-        for (int i = 0; i < PW; ++i) {
-            int off = -1, off1 = -1;
-            if (i < PWP) {
-                const int q = i * 8 + wave;  // pixel piece; q >= NK * PX_PIECES: padding
-                const int kk = q / PX_PIECES, j = q % PX_PIECES;
-                const int u = j * 64 + lane;           // unit inside the slab, LDS order [half][IN_PIX] (S2L: see above)
-                int h = u / IN_PIX, P = u % IN_PIX;
-                if constexpr (S2L) {
-                    const int r = u / (2 * IN_W), v = u % (2 * IN_W);
-                    const bool ev = v < 2 * NEV;
-                    const int w2 = ev ? v : v - 2 * NEV;
-                    const int per = ev ? NEV : TW;
-                    h = r < IN_H ? w2 / per : 2;       // units past the image: padding of the piece list
-                    P = r * IN_W + 2 * (w2 % per) + (ev ? 0 : 1);
-                }
-                int iy = y0 * STRIDE - PAD + P / IN_W;
-                int ix = x0 * STRIDE - PAD + P % IN_W;
-                bool inside = iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win;
-                int img = 0;  // canvas mode: this lane's image; its planes lie img * (cin/16) planes further on
-                if constexpr (CANVAS) inside = canvas_px_in<STRIDE>(a, iy, ix, img, iy, ix);
-                if (q < NK * PX_PIECES && h < 2 && inside) {
-                    off = (int)(kk * in_plane) + (iy * a.win + ix) * 32 + h * 16 + img * (a.cin / 16) * (int)in_plane;
-                    off1 = (int)(kk * in_plane1) + ((iy >> 1) * (a.win >> 1) + (ix >> 1)) * 32 + h * 16;
-                }
-            } else {
-                const int qq = (i - PWP) * 8 + wave;   // filter piece; qq >= NK * W_PIECES: scale/shift or padding
-                const int u = qq * 64 + lane;          // unit inside the stage's filter image [kk][tap][half][BN]
-                const int r = u % BN, th = u / BN;
-                if (qq < NK * W_PIECES) {
-                    if constexpr (PAIR)   // rows BN/2.. of the tile: the second class's image, w_class_stride further on
-                        off = (th * CP + r % (BN / 2)) * 16 + (r / (BN / 2)) * (int)a.w_class_stride;
-                    else
-                        off = (th * CP + r) * 16;
-                }
+        for (int i = 0; i < PWP; ++i) {
+            unsigned off = OOB, off1 = OOB;
+            const int q = i * 8 + wave;  // pixel piece; q >= NK * PX_PIECES: padding
+            const int kk = q / PX_PIECES, j = q % PX_PIECES;
+            const int u = j * 64 + lane;           // unit inside the slab, LDS order [half][IN_PIX] (S2L: see above)
+            int h = u / IN_PIX, P = u % IN_PIX;
+            if constexpr (S2L) {
+                const int r = u / (2 * IN_W), v = u % (2 * IN_W);
+                const bool ev = v < 2 * NEV;
+                const int w2 = ev ? v : v - 2 * NEV;
+                const int per = ev ? NEV : TW;
+                h = r < IN_H ? w2 / per : 2;       // units past the image: padding of the piece list
+                P = r * IN_W + 2 * (w2 % per) + (ev ? 0 : 1);
+            }
+            int iy = y0 * STRIDE - PAD + P / IN_W;
+            int ix = x0 * STRIDE - PAD + P % IN_W;
+            bool inside = iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win;
+            int img = 0;  // canvas mode: this lane's image; its planes lie img * (cin/16) planes further on
+            if constexpr (CANVAS) inside = canvas_px_in<STRIDE>(a, iy, ix, img, iy, ix);
+            if (q < NK * PX_PIECES && h < 2 && inside) {
+                off = (unsigned)kk * (unsigned)in_plane + (unsigned)((iy * a.win + ix) * 32 + h * 16) + (unsigned)img * (unsigned)(a.cin / 16) * (unsigned)in_plane;
+                off1 = (unsigned)kk * in_plane1 + (unsigned)(((iy >> 1) * (a.win >> 1) + (ix >> 1)) * 32 + h * 16);
             }
             src_off[i] = off;
             if constexpr (CAT) src_off1[i] = off1;
         }
     };
     auto issue_piece = [&](int i, int buf) __attribute__((always_inline)) {  // DMA piece i of the loader's current stage into ring slot `buf`
-        const uint8_t* zp = zero_page + (lane & 3) * 16;
-        const uint8_t* g;
-        int dst;
-        if (i < PWP) {  // `i` is a constant after unrolling: one kind per call site, the rest is selects
+        if (i < PWP) {  // `i` is a constant after unrolling: one kind per call site
             const bool from1 = CAT && ld_s < s1_stages;  // wave-uniform
-            const uint8_t* sp = from1 ? ld_src1 + (size_t)ld_s * NK * in_plane1 : ld_src + (size_t)(ld_s - s1_stages) * NK * in_plane;
             const int q = i * 8 + wave;  // wave-uniform
-            const int off0 = src_off[i], off1 = src_off1[CAT ? i : 0];  // both read by value: a select between the arrays
-            const int off = from1 ? off1 : off0;                        // puts them on the stack (seen: 64 B of scratch)
-            g = off >= 0 ? sp + off : zp;
-            dst = q < NK * PX_PIECES ? buf * BUF_BYTES + (q / PX_PIECES) * PIX_SLAB + (q % PX_PIECES) * 1024 : DUMMY_BASE;
+            if (!COUNTED && q >= NK * PX_PIECES) return;  // padding of the piece list
+            const unsigned off0 = src_off[i], off1 = src_off1[CAT ? i : 0];  // both read by value: a select between the arrays
+            const unsigned off = from1 ? off1 : off0;                        // puts them on the stack (seen: 64 B of scratch)
+            const __amdgpu_buffer_rsrc_t rs =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(from1 ? ld_src1 : ld_src), 0, from1 ? src1_bytes : src_bytes, 0x00020000);
+            const unsigned so = from1 ? (unsigned)(ld_s * NK) * in_plane1 : (unsigned)((ld_s - s1_stages) * NK) * (unsigned)in_plane;
+            const int dst = q < NK * PX_PIECES ? buf * BUF_BYTES + q * 1024 : DUMMY_BASE;  // (PIX_SLAB = PX_PIECES KiB: slab kk, piece j)
+            dma16_buf(rs, off, so, lds_base + dst);
         } else {
-            const uint8_t* wp = ld_w + (size_t)ld_s * w_stage_stride;
             const int qq = (i - PWP) * 8 + wave;  // wave-uniform
-            const bool is_w = qq < NK * W_PIECES;
-            const bool is_ss = qq >= NK * W_PIECES && qq < NK * W_PIECES + SSP;
-            // scale/shift piece(s): lane pointer ld_ss (nullptr: lane carries nothing); the shift array at the same lane offset
-            const float* ssp = (SSP == 2 && qq == NK * W_PIECES + 1) ? ld_ss + (a.shift - a.scale) : ld_ss;
-            const uint8_t* gss = (is_ss && ld_ss != nullptr) ? reinterpret_cast<const uint8_t*>(ssp) : zp;
-            g = is_w ? wp + src_off[i] : gss;
-            dst = is_w ? buf * BUF_BYTES + W_BASE + qq * 1024
-                       : (is_ss ? SS_BASE + ld_par * SSR + (qq - NK * W_PIECES) * 1024 : DUMMY_BASE);
+            // (call sites whose eight pieces are all filter pieces fold to the first branch)
+            const bool is_w = (i - PWP) * 8 + 7 < NK * W_PIECES || qq < NK * W_PIECES;
+            if (is_w) {
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(ld_w), 0, 0x7fffffff, 0x00020000);
+                dma16_buf(rs, w_off[i - PWP], (unsigned)ld_s * (unsigned)w_stage_stride, lds_base + buf * BUF_BYTES + W_BASE + qq * 1024);
+            } else {
+                // scale piece | shift piece | padding (every lane out of range)
+                const bool is_ss = qq < NK * W_PIECES + SSP;
+                if (!COUNTED && !(is_ss && ld_s == 0)) return;  // padding; the scales and shifts of an item travel with its first stage
+                const float* base = (qq == NK * W_PIECES ? a.scale : a.shift) + ld_ch;
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, BNR * 4, 0x00020000);
+                dma16_buf(rs, w_off[i - PWP], 0u, lds_base + (is_ss ? SS_BASE + ld_par * SSR + (qq - NK * W_PIECES) * 1024 : DUMMY_BASE));
+            }
         }
-        dma16(g, lds_base + __builtin_amdgcn_readfirstlane(dst));
     };
     auto advance_loader = [&]() __attribute__((always_inline)) {
         if (++ld_s == a.cin / (16 * NK)) {
@@ -486,7 +504,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     int par = 0;  // scale/shift region of the item the MFMAs work on
     // phase clock (instrumented build only, see AY_DBGBIT): wave-uniform tick counters
     const bool clk = AY_DBGBIT(a, 8) && wave == 0;
-    unsigned long long tk_stage = 0, tk_epi = 0, tk_items = 0, tk0 = 0, tk_begin = 0, tk_s0 = 0;
+    unsigned long long tk_stage = 0, tk_epi = 0, tk_items = 0, tk0 = 0, tk_begin = 0, tk_s0 = 0, tk_w0 = 0, tk_w = 0, tk_nw = 0, tkw = 0;
     if (clk) tk_begin = wall_clock64();
     while (true) {
         if (clk) tk0 = wall_clock64();
@@ -514,9 +532,12 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
         for (int s = 0; s < nstages; ++s) {
             const bool last_stage = (s + 1 == nstages);
             // stage g+NBUF-1 -> the slot that was read during stage g-1 (every wave passed the barrier since)
-            // the PW DMA pieces of stage g+NBUF-1 are issued one by one behind the MFMA groups of this stage (an LDS-DMA
-            // issue costs the wave 60-180 cycles; behind 4-8 queued MFMAs it is hidden, in a burst at the stage start
-            // both waves of a SIMD pay it at the same time)
+            // the PW DMA pieces of stage g+NBUF-1 are issued behind the MFMA groups of this stage (an LDS-DMA issue costs the
+            // wave issue slots; behind 4-8 queued MFMAs it is hidden, in a burst at the stage start both waves of a SIMD pay it
+            // at the same time).  Three slots: spread over all steps, the stage has a whole further stage to land.  Two slots:
+            // the stage is waited for at the end of this one, and a piece lands ~1.1 us after its issue under load, so all of
+            // it goes out behind the first NE steps (3x3: two pieces per tap, five of nine taps in the stride-2 kernel; otherwise
+            // the first half of the steps).
             const bool issued = !ld_done && !AY_DBGBIT(a, 1);
             int slot_ld = cur + (NBUF - 1);
             if (slot_ld >= NBUF) slot_ld -= NBUF;
@@ -525,6 +546,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
 
             const uint8_t* L = lds + cur * BUF_BYTES;
             constexpr int NSTEP = NK * KK2;
+            constexpr int NE = NBUF == 3 ? NSTEP : (KS == 3 ? (PW + 1) / 2 : (NSTEP + 1) / 2);  // steps that carry DMA issue
             vec8 af[2][MT], bfr[2][NT];
             auto load_frags = [&](int t, vec8 (&fa)[MT], vec8 (&fb)[NT]) __attribute__((always_inline)) {
                 const int kk = t / KK2, tap = t % KK2;
@@ -558,9 +580,10 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
                 if (issued) {
 #pragma unroll
                     for (int i = 0; i < PW; ++i)  // constant trip count: src_off[] must stay in registers
-                        if (i >= t * PW / NSTEP && i < (t + 1) * PW / NSTEP) issue_piece(i, slot_ld);
+                        if (i >= t * PW / NE && i < (t + 1) * PW / NE) issue_piece(i, slot_ld);
                 }
             }
+            if (clk) tkw = wall_clock64();
             if (issued) advance_loader();
             // stage g+1 must have landed before anyone reads it: everything but the stage(s) issued after it
             if (!(last_stage && !has_next)) {
@@ -574,6 +597,13 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
                 }
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
+                if (clk) {
+                    const unsigned long long t = wall_clock64() - tkw;
+                    if (s == 0)
+                        tk_w0 += t;
+                    else
+                        tk_w += t, ++tk_nw;
+                }
             }
             if (++cur == NBUF) cur = 0;
             if (clk && s == 0) tk_s0 += wall_clock64() - tk0;
@@ -609,6 +639,9 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
         atomicAdd(&g_phase_ticks[4], wall_clock64() - tk_begin);
         atomicAdd(&g_phase_ticks[5], tk_s0);
         atomicMax(&g_phase_ticks[6], wall_clock64() - tk_begin);
+        atomicAdd(&g_phase_ticks[7], tk_w0);
+        atomicAdd(&g_phase_ticks[8], tk_w);
+        atomicAdd(&g_phase_ticks[9], tk_nw);
     }
 }
 
@@ -616,7 +649,7 @@ template <int KS, int STRIDE, int BN, int TH, int TW, int NK>
 constexpr int ring_depth() {
     constexpr int in_pix = ((TH - 1) * STRIDE + KS) * ((TW - 1) * STRIDE + KS);
     constexpr int buf = NK * (((2 * in_pix + 63) / 64) * 1024 + KS * KS * 2 * BN * 16);
-    return (3 * buf + 1024 + 4 * (BN > 128 ? 2048 : 1024) + 64 <= 160 * 1024) ? 3 : 2;
+    return (3 * buf + 1024 + 4 * 2048 + 64 <= 160 * 1024) ? 3 : 2;
 }
 
 static int current_device() {
@@ -775,14 +808,15 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
     AY_CHECK_LAUNCH("conv_bf16_kernel");
 #ifdef AY_PHASE_CLOCK
     if (RING && (dbg & 8)) {  // timing experiments only: synchronous phase report per launch
-        unsigned long long t[8] = {0};
+        unsigned long long t[10] = {0};
         (void)hipStreamSynchronize(st);
         (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_phase_ticks), sizeof(t));
         if (t[3])
-            fprintf(stderr, "[ay phase] k%d s%d BN%d tile%dx%d cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (first stage %.2f of %d), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
+            fprintf(stderr, "[ay phase] k%d s%d BN%d tile%dx%d cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (first stage %.2f of %d; stage-end wait: first stage %.2f, other stages %.2f each), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
                     KS, STRIDE, BN, TH, TW, d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[2] / t[3], t[0] * 0.01 / t[2],
-                    t[5] * 0.01 / t[2], d->cin / (16 * NK), t[1] * 0.01 / t[2], t[4] * 0.01 / t[3], t[6] * 0.01);
-        unsigned long long z[8] = {0};
+                    t[5] * 0.01 / t[2], d->cin / (16 * NK), t[7] * 0.01 / t[2], t[9] ? t[8] * 0.01 / t[9] : 0.0, t[1] * 0.01 / t[2], t[4] * 0.01 / t[3],
+                    t[6] * 0.01);
+        unsigned long long z[10] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), z, sizeof(z));
     }
 #endif
@@ -875,6 +909,9 @@ static int conv1x1_cat_fwd(const ay_conv_desc* d, const void* src1_halfres, int 
                  c1, d->cin - c1);
     AY_CHECK_ARG(d->cout_pad % 128 == 0 && d->cout_pad >= d->cout, "ay_conv1x1_cat_fwd_bf16: cout_pad %d (multiple of 128)", d->cout_pad);
     AY_CHECK_ARG(d->hin % 2 == 0 && d->win % 2 == 0 && d->hout == d->hin && d->wout == d->win, "ay_conv1x1_cat_fwd_bf16: even sizes");
+    AY_CHECK_ARG((long long)d->hin * d->win * 2 * d->cin < (1ll << 31) && (long long)d->hout * d->wout * 2 * d->cout_pad < (1ll << 31),
+                 "ay_conv1x1_cat_fwd_bf16: one image (%dx%d, %d -> %d channels) exceeds the 2 GiB a buffer descriptor addresses", d->hin, d->win,
+                 d->cin, d->cout_pad);
     return launch_ring1x1<128, 2, 4, true, DT>(d, src1_halfres, c1, src2, w_packed, scale, shift, out, S(stream));
 }
 }  // namespace ay
@@ -897,6 +934,7 @@ extern "C" int ay_conv_dgrad_s2_bf16(const ay_conv_desc* d, const void* dz, cons
     AY_CHECK_ARG(d->cout_pad % 32 == 0 && cin_pad % 32 == 0 && cin_pad >= d->cin, "ay_conv_dgrad_s2_bf16: channels %d(%d) <- %d", d->cin, cin_pad,
                  d->cout_pad);
     AY_CHECK_ARG((long long)d->hin * d->win * 2 * cin_pad < (1ll << 31), "ay_conv_dgrad_s2_bf16: one image of dx exceeds 2 GiB");
+    AY_CHECK_ARG((long long)d->hout * d->wout * 2 * d->cout_pad < (1ll << 31), "ay_conv_dgrad_s2_bf16: one image of dz exceeds 2 GiB");
     hipStream_t st = S(stream);
     // (the layers with 128 and more channels are compute-bound: a 256-wide pair tile leaves LDS for 16-channel stages only and
     // measured 2-5 % slower than one class per workgroup; they keep the class form)
@@ -926,6 +964,8 @@ static int conv_fwd_16(const ay_conv_desc* d, const void* src, const void* w_pac
     AY_CHECK_ARG((long long)d->hout * d->wout * 2 * d->cout_pad < (1ll << 31),
                  "ay_conv_fwd_bf16: one image's output (%dx%dx%d) exceeds the 2 GiB a store descriptor addresses", d->hout, d->wout,
                  d->cout_pad);
+    AY_CHECK_ARG((long long)d->hin * d->win * 2 * d->cin < (1ll << 31),
+                 "ay_conv_fwd_bf16: one image's input (%dx%dx%d) exceeds the 2 GiB a load descriptor addresses", d->hin, d->win, d->cin);
     hipStream_t st = S(stream);
     const int cp = d->cout_pad;
     if (d->ksize == 3 && d->stride == 1) {

@@ -138,8 +138,8 @@ __device__ __forceinline__ void residual_prefetch(const ConvArgs& a, ResRegs<MT,
 
 // RES_INLINE: the residual is loaded here, RD 32-pixel blocks ahead of its use (large wave tiles cannot hold all of it).
 // SS_MODE 1|2 (ss_lds != nullptr; 0 = from global memory): per-channel scale/shift of this workgroup's BN channels staged in
-// LDS as [scale BN | pad to 128][shift] (shift at float offset max(BN, 128)), so the epilogue issues no vector-memory loads
-// that would have to wait behind its own stores.
+// LDS as [scale BN | pad][shift] (mode 2: shift at float offset max(BN, 128); mode 1: at 256, a DMA piece each), so the
+// epilogue issues no vector-memory loads that would have to wait behind its own stores.
 // Deferred stores (residual loaded here): see below; they go out as unconditional buffer stores -- out-of-image lanes carry an
 // offset past num_records and the hardware drops them -- so that the compiler can count them (a store under `if (ok)` sits in
 // its own basic block and forces conservative waits).  The plane offset rides in the VECTOR offset: with it in the scalar-offset
@@ -167,7 +167,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
     // first real channel and parity class of this wave's m-th block of 32 tile channels (PAIR: see pair_block)
     auto blk_of = [&](int m, int& chf, int& clm) __attribute__((always_inline)) { pair_block<BN, PAIR>(cg, wm * MT + m, cls, chf, clm); };
     const int lbase = wm * MT * 32;  // channel index inside the workgroup's BN channels
-    constexpr int SHO = BN > 128 ? BN : 128;  // float offset of the shifts in the LDS scale/shift image
+    // float offset of the shifts in the LDS scale/shift image (SS_MODE 1, the ring kernel: a scale KiB, then a shift KiB)
+    constexpr int SHO = SS_MODE == 1 ? 256 : (BN > 128 ? BN : 128);
     const float slope = a.leaky ? 0.1f : 1.0f;
     // buffer descriptor over image b's output; offsets >= num_records are dropped, so the out-of-image sentinel 0x80000000
     // (+ a plane offset) needs an image below 2 GiB: host check
