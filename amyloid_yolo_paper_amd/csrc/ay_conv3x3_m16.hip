@@ -1,7 +1,7 @@
 // 3x3 stride-1 convolution, 128 output channels x 16x32 pixels per workgroup, on v_mfma_f32_16x16x32_bf16.
 //
 // Same persistent all-DMA ring structure as conv_bf16_ring_kernel<3,1,128,2,4,16,32,1,2> (ay_conv_bf16.hip: LDS-DMA staging with
-// counted waits, items dealt per XCD through atomic counters and an LDS mailbox, fused BN-affine + LeakyReLU (+ shortcut)
+// counted waits, items dealt by ItemDealer (ay_conv_common.h), fused BN-affine + LeakyReLU (+ shortcut)
 // epilogue; reference models.py:26-45, 246-248) with the matrix instruction changed: on non-trivial operands the chip holds
 // a higher clock on the 16x16x32 shape than on 32x32x16 (scripts/micro/mfma_shape.hip on this kernel's wave tile, every
 // operand re-read from LDS: 1 773 vs 1 610 TFLOP/s on network-like data, 1 814 vs 1 637 on uniform random, 2 243 vs 2 392 on
@@ -25,8 +25,6 @@
 // LDS pixel image [half][624 px][16 B]: 624 = 18 x 34 rounded up to a multiple of 16 keeps the two halves' lanes of one
 // ds_read_b128 lane group on disjoint banks.
 // C/D layout of 16x16: col (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "ay_conv_common.h"
@@ -76,38 +74,16 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
     const int wm = wave & 1, wn = wave >> 1;
     const int r = lane & 15, g = lane >> 4, h = g & 1, hi = g >> 1;
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd;
-    const int last = min(first + per_xcd, n_items);
-    int item = first + slot;
-    // ---- item dealing: as conv_bf16_ring_kernel (static first items, then the XCD's atomic counter through an LDS mailbox)
-    const bool dyn = a.deal != nullptr;
-    auto leave = [&]() __attribute__((always_inline)) {
-        if (dyn && tid == 0) {
-            const unsigned d = atomicAdd(a.deal + 8, 1u);
-            if (d == gridDim.x - 1) {  // last workgroup out: hand the counter set back zeroed
-#pragma unroll
-                for (int i = 0; i < 9; ++i) atomicExch(a.deal + i, 0u);
-            }
-        }
-    };
+    const ItemRange rg(n_items);
+    const int last = rg.last;
+    int item = rg.first_item();
+    // item dealing (ItemDealer): dynamic with a counter set in a.deal, static without; fetch-ahead distance 3 items
+    const ItemDealer dealer(rg, a.deal, lds + MBOX_BASE, 3);
     if (item >= last) {
-        leave();
+        dealer.leave();
         return;
     }
-    typedef volatile __attribute__((address_space(3))) int lds_vint;
-    lds_vint* mbox = (lds_vint*)(__attribute__((address_space(3))) int*)(lds + MBOX_BASE);
-    constexpr int D = 3;  // fetch-ahead distance in items
-    auto fetch_id = [&](int prev) __attribute__((always_inline)) -> int {  // thread 0 only
-        if (prev >= last) return last;
-        if (!dyn) return prev + slots;
-        // whatever the counter holds, the id stays inside this XCD's range or reads as "no more items"
-        const unsigned n = atomicAdd(a.deal + xcd, 1u);
-        return n < (unsigned)(last - first) ? first + D * slots + (int)n : last;
-    };
-    if (tid < D) mbox[tid] = min(item + tid * slots, last);
-    __syncthreads();
+    dealer.post_first();
     int seq_l = 0, seq_c = 0;
 
     const size_t in_plane = (size_t)a.hin * a.win * 32;
@@ -172,7 +148,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             ld_s = 0;
             ld_par = (ld_par + 1) & 3;
             ++seq_l;
-            ld_item = __builtin_amdgcn_readfirstlane(mbox[seq_l & 7]);
+            ld_item = dealer.id_at(seq_l);
             if (ld_item < last)
                 setup_loader(ld_item);
             else
@@ -206,7 +182,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
         const int pt = item / a.n_cgroups;
         const int b = pt / tiles_per_img;
         const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
-        const int next_item = __builtin_amdgcn_readfirstlane(mbox[(seq_c + 1) & 7]);
+        const int next_item = dealer.id_at(seq_c + 1);
         const bool has_next = next_item < last;
 
         f32x4 acc[MT][NT];
@@ -353,8 +329,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
         }
         AY_CLK(if (clk) { const unsigned long long t = wall_clock64(); tk_stage += t - tk0; tk0 = t; })
 
-        int fetched = last;
-        if (tid == 0) fetched = fetch_id(mbox[(seq_c + D - 1) & 7]);
+        const int fetched = dealer.fetch(seq_c);
 
         // ---- epilogue: affine + leaky (+ residual) -> bf16 -> 16-byte stores --------------------------------------------
         // A store unit = (m, row pair np): the accumulator tiles (m, 2np) and (m, 2np+1) are the two halves of one 32-pixel
@@ -415,17 +390,14 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
                 }
             }
         }
-        if (tid == 0) {
-            mbox[(seq_c + D) & 7] = fetched;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
+        dealer.post(seq_c, fetched);
         AY_CLK(if (clk) { tk_epi += wall_clock64() - tk0; ++tk_items; })
         if (!has_next) break;
         item = next_item;
         ++seq_c;
         par = (par + 1) & 3;
     }
-    leave();
+    dealer.leave();
     AY_CLK(if (clk && lane == 0) {
         const unsigned long long tot = wall_clock64() - tk_begin;
         atomicAdd(&g_phase_ticks_m16[0], tk_stage); atomicAdd(&g_phase_ticks_m16[1], tk_epi); atomicAdd(&g_phase_ticks_m16[2], tk_items);
@@ -452,46 +424,14 @@ static int conv3x3_m16_fwd(const ay_conv_desc* d, const void* src, const void* w
     AY_CHECK_ARG((long long)d->hin * d->win * 2 * d->cin < (1ll << 31),
                  "ay_conv3x3_m16_fwd_bf16: one image's input (%dx%dx%d) exceeds the 2 GiB a load descriptor addresses", d->hin, d->win, d->cin);
     ConvArgs a;
-    a.src = (const uint8_t*)src;
-    a.w = (const uint8_t*)w_packed;
-    a.scale = scale;
-    a.shift = shift;
-    a.residual = (const uint8_t*)residual;
-    a.out = (uint8_t*)out;
-    a.batch = d->batch;
-    a.cin = d->cin;
-    a.cout_pad = d->cout_pad;
-    a.hin = d->hin;
-    a.win = d->win;
-    a.hout = d->hout;
-    a.wout = d->wout;
-    a.tiles_x = (d->wout + 31) / 32;
-    a.tiles_y = (d->hout + 15) / 16;
-    a.n_cgroups = d->cout_pad / 128;
-    a.leaky = d->leaky;
-    a.dbg = 0;
-#ifdef AY_PHASE_CLOCK
-    static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;
-    a.dbg = dbg;
-#endif
-    a.src1 = nullptr;
-    a.c1 = 0;
-    a.canvas_gx = 0;
+    fill_args(a, d, src, w_packed, scale, shift, residual, out, 16, 32, 128);
+    a.dbg = conv_dbg();
     hipStream_t st = S(stream);
-    a.deal = next_deal_set(st);
     const long long nblk = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        set_error("conv grid out of range (%lld)", nblk);
-        return AY_ERR_ARG;
-    }
-    const int per_xcd = (int)((nblk + 7) / 8);
-    const int cu_slots = conv_num_cus() / 8;
-    dim3 pgrid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots)));
-    if (residual)
-        hipLaunchKernelGGL((conv3x3_m16_ring_kernel<true, DT>), pgrid, dim3(512), 0, st, a, (int)nblk);
-    else
-        hipLaunchKernelGGL((conv3x3_m16_ring_kernel<false, DT>), pgrid, dim3(512), 0, st, a, (int)nblk);
-    AY_CHECK_LAUNCH("conv3x3_m16_ring_kernel");
+    // dynamic dealing
+    if (int rc = launch_ring(residual ? conv3x3_m16_ring_kernel<true, DT> : conv3x3_m16_ring_kernel<false, DT>, a, nblk, true, st, "conv",
+                             "conv3x3_m16_ring_kernel"))
+        return rc;
 #ifdef AY_PHASE_CLOCK
     if (a.dbg & 8) {  // timing experiments only: synchronous phase report per launch
         unsigned long long t[10] = {0};

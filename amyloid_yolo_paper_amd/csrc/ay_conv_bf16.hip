@@ -282,48 +282,16 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     const int wm = wave % WM, wn = wave / WM;
     const int c = lane & 31, hh = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd;
-    const int last = min(first + per_xcd, n_items);
-    int item = first + slot;
-    // ---- item dealing --------------------------------------------------------------------------------------------
-    // A workgroup's first item is static; the following ones come from its XCD's atomic counter (a.deal), so that a slow
-    // CU (HBM channel luck, a neighbour kernel on the CU) simply takes fewer items instead of setting the kernel time.
-    // Item ids travel through an 8-entry LDS mailbox indexed by sequence number: thread 0 fetches id[c+D] at the start of the
-    // epilogue of item c (the atomic's latency hides under it) and posts it at its end; the stage barriers publish it long
-    // before the loader (at most 2 item boundaries ahead) or the MFMA side need it.  Without counters the same mailbox
-    // carries the static ids.
-    constexpr bool MAILBOX = true;  // (false: plain strided dealing without any mailbox traffic)
-    const bool dyn = MAILBOX && a.deal != nullptr;
-    auto leave = [&]() __attribute__((always_inline)) {
-        if (dyn && tid == 0) {
-            const unsigned d = atomicAdd(a.deal + 8, 1u);
-            if (d == gridDim.x - 1) {  // last workgroup out: hand the counter set back zeroed
-#pragma unroll
-                for (int i = 0; i < 9; ++i) atomicExch(a.deal + i, 0u);
-            }
-        }
-    };
+    const ItemRange rg(n_items);
+    const int last = rg.last;
+    int item = rg.first_item();
+    // item dealing (ItemDealer): dynamic with a counter set in a.deal, static without; fetch-ahead distance in items
+    const ItemDealer dealer(rg, a.deal, lds + MBOX_BASE, (a.cin / (16 * NK)) >= 2 ? 3 : 5);
     if (item >= last) {
-        leave();
+        dealer.leave();
         return;
     }
-    // explicit LDS address space: through a generic pointer these volatile accesses become flat_load/flat_store, which count on
-    // vmcnt as well, and hipcc then waits vmcnt(0) -- draining the DMA ring -- at every mailbox access
-    typedef volatile __attribute__((address_space(3))) int lds_vint;
-    lds_vint* mbox = (lds_vint*)(__attribute__((address_space(3))) int*)(lds + MBOX_BASE);
-    const int D = (a.cin / (16 * NK)) >= 2 ? 3 : 5;  // fetch-ahead distance in items
-    auto fetch_id = [&](int prev) __attribute__((always_inline)) -> int {  // thread 0 only
-        if (prev >= last) return last;
-        if (!dyn) return prev + slots;
-        // whatever the counter holds, the id stays inside this XCD's range or reads as "no more items"
-        const unsigned n = atomicAdd(a.deal + xcd, 1u);
-        return n < (unsigned)(last - first) ? first + D * slots + (int)n : last;
-    };
-    if (MAILBOX && tid < D) mbox[tid] = min(item + tid * slots, last);  // the first D items of a workgroup are static (no atomics, no
-                                                             // wait in the prologue); id[c+D] is posted by the epilogue of item c
-    if constexpr (MAILBOX) __syncthreads();  // ids 0..D-1 posted (a single-stage item makes the loader ask for id 1 already in the prologue below)
+    dealer.post_first();
     int seq_l = 0, seq_c = 0;  // sequence numbers of the loader's / the MFMA side's current item
 
     const size_t in_plane = (size_t)a.hin * a.win * 32;
@@ -453,10 +421,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
             ld_s = 0;
             ld_par = (ld_par + 1) & 3;
             ++seq_l;
-            if constexpr (MAILBOX)
-                ld_item = __builtin_amdgcn_readfirstlane(mbox[seq_l & 7]);
-            else
-                ld_item += slots;
+            ld_item = dealer.id_at(seq_l);
             if (ld_item < last)
                 setup_loader(ld_item);
             else
@@ -517,7 +482,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
         const int pt = item / a.n_cgroups;
         const int b = pt / tiles_per_img;
         const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
-        const int next_item = MAILBOX ? __builtin_amdgcn_readfirstlane(mbox[(seq_c + 1) & 7]) : item + slots;
+        const int next_item = dealer.id_at(seq_c + 1);
         const bool has_next = next_item < last;
 
         f32x16 acc[MT][NT];
@@ -613,14 +578,10 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
             tk_stage += t - tk0;
             tk0 = t;
         }
-        int fetched = last;
-        if (MAILBOX && tid == 0) fetched = fetch_id(mbox[(seq_c + D - 1) & 7]);  // id[c+D]; consumed after the epilogue
+        const int fetched = dealer.fetch(seq_c);  // id[c+D]; posted after the epilogue
         conv_epilogue<BN, MT, NT, TW, false, HAS_RES, (MT * NT > 4), 1, CANVAS, UP2, DT, PAIR>(a, acc, rr, b, cg, wm, wn, c, hh, y0, x0,
                                                                             reinterpret_cast<const float*>(lds + SS_BASE + par * SSR), cls);
-        if (MAILBOX && tid == 0) {
-            mbox[(seq_c + D) & 7] = fetched;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
+        dealer.post(seq_c, fetched);
         if (clk) {
             tk_epi += wall_clock64() - tk0;
             ++tk_items;
@@ -630,7 +591,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
         ++seq_c;
         par = (par + 1) & 3;
     }
-    leave();
+    dealer.leave();
     if (clk && lane == 0) {
         atomicAdd(&g_phase_ticks[0], tk_stage);
         atomicAdd(&g_phase_ticks[1], tk_epi);
@@ -727,8 +688,9 @@ static int canvas_plan(const ay_conv_desc* d, int th, int tw, int* tiles_x, int*
     return best * 10 <= image_tiles * 9 ? best_gx : 0;  // worth it from a tenth fewer tiles
 }
 
-static void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* w, const float* scale, const float* shift,
-                      const void* residual, void* out, int TH, int TW, int BN) {
+void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* w, const float* scale, const float* shift,
+               const void* residual, void* out, int TH, int TW, int BN) {
+    a = ConvArgs{};
     a.src = (const uint8_t*)src;
     a.w = (const uint8_t*)w;
     a.scale = scale;
@@ -747,11 +709,36 @@ static void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const
     a.n_cgroups = d->cout_pad / BN;
     a.leaky = d->leaky;
     a.dbg = 0;
-    a.deal = nullptr;
     a.src1 = nullptr;
     a.c1 = 0;
+    a.deal = nullptr;
     a.canvas_gx = 0;
     a.w_class_stride = 0;
+}
+
+int conv_dbg() {
+    static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;
+    return dbg;
+}
+
+unsigned persistent_grid(long long n_items, int wgs_per_cu) {
+    if (n_items <= 0 || n_items > 0x7fffffffLL) return 0;
+    const long long per_xcd = (n_items + 7) / 8;
+    const long long cu_slots = (long long)wgs_per_cu * (conv_num_cus() / 8);
+    return (unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots));
+}
+
+// The tile grid of `a` and its number of items.  canvas_ok: images that leave much of their tiles empty (canvas_plan) are tiled as a
+// canvas of canvas_gx images per row with one-pixel gutters instead; the kernel's item decode then yields image 0 and (y0, x0) on
+// the canvas.
+static long long plan_tiles(ConvArgs& a, const ay_conv_desc* d, int th, int tw, bool canvas_ok) {
+    int ctx = 0, cty = 0;
+    if (canvas_ok && (a.canvas_gx = canvas_plan(d, th, tw, &ctx, &cty)) > 0) {
+        a.tiles_x = ctx;
+        a.tiles_y = cty;
+        return (long long)ctx * cty * a.n_cgroups;
+    }
+    return (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
 }
 
 // RING = false: the 4-wave register-staged kernel (fp32-output heads, cout_pad not a multiple of 64); RING = true: the persistent
@@ -761,40 +748,28 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
                   const void* residual, void* out, hipStream_t st) {
     ConvArgs a;
     fill_args(a, d, src, w, scale, shift, residual, out, TH, TW, BN);
-    static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;
-    a.dbg = dbg;
-    long long nblk = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
-    int ctx = 0, cty = 0;
-    if (RING && (a.canvas_gx = canvas_plan(d, TH, TW, &ctx, &cty)) > 0) {
-        // images that leave much of their tiles empty: tile a canvas of gx images per row with one-pixel gutters instead
-        a.tiles_x = ctx;
-        a.tiles_y = cty;
-        nblk = (long long)ctx * cty * a.n_cgroups;  // the kernel's item decode then yields image 0 and (y0, x0) on the canvas
-    } else {
-        a.canvas_gx = 0;
-    }
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        set_error("conv grid out of range (%lld)", nblk);
-        return AY_ERR_ARG;
-    }
+    a.dbg = conv_dbg();
+    const long long nblk = plan_tiles(a, d, TH, TW, RING);
     if constexpr (RING) {
         static_assert(!OUT_F32, "the ring kernel writes bf16");
-        // (the 1x1 kernels once measured 5-20 % slower with dynamic dealing: that was the flat-addressed mailbox draining the DMA
-        // ring, not the counter fetch; with the LDS-typed mailbox they gain slightly)
-        a.deal = next_deal_set(st);
-        const int per_xcd = (int)((nblk + 7) / 8);
-        const int cu_slots = conv_num_cus() / 8;
-        dim3 pgrid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots))), block(512);
         constexpr int NBUF = ring_depth<KS, STRIDE, BN, TH, TW, NK>();
+        void (*kernel)(ConvArgs, int);
         if (a.canvas_gx && residual)
-            hipLaunchKernelGGL((conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, true, false, true, DT>), pgrid, block, 0, st, a, (int)nblk);
+            kernel = conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, true, false, true, DT>;
         else if (a.canvas_gx)
-            hipLaunchKernelGGL((conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, false, false, true, DT>), pgrid, block, 0, st, a, (int)nblk);
+            kernel = conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, false, false, true, DT>;
         else if (residual)
-            hipLaunchKernelGGL((conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, true, false, false, DT>), pgrid, block, 0, st, a, (int)nblk);
+            kernel = conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, true, false, false, DT>;
         else
-            hipLaunchKernelGGL((conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, false, false, false, DT>), pgrid, block, 0, st, a, (int)nblk);
+            kernel = conv_bf16_ring_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, NBUF, false, false, false, DT>;
+        // dynamic dealing (the 1x1 kernels once measured 5-20 % slower with it: that was the flat-addressed mailbox draining the DMA
+        // ring, not the counter fetch; with the LDS-typed mailbox they gain slightly)
+        if (int rc = launch_ring(kernel, a, nblk, true, st, "conv", "conv_bf16_kernel")) return rc;
     } else {
+        if (nblk <= 0 || nblk > 0x7fffffffLL) {
+            set_error("conv grid out of range (%lld)", nblk);
+            return AY_ERR_ARG;
+        }
         dim3 grid((unsigned)nblk), block(256);
         if constexpr (OUT_F32) {
             hipLaunchKernelGGL((conv_bf16_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, true, false, DT>), grid, block, 0, st, a, DecodeArgs{});
@@ -804,10 +779,10 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
             else
                 hipLaunchKernelGGL((conv_bf16_kernel<KS, STRIDE, BN, WM, WN, TH, TW, NK, false, false, DT>), grid, block, 0, st, a, DecodeArgs{});
         }
+        AY_CHECK_LAUNCH("conv_bf16_kernel");
     }
-    AY_CHECK_LAUNCH("conv_bf16_kernel");
 #ifdef AY_PHASE_CLOCK
-    if (RING && (dbg & 8)) {  // timing experiments only: synchronous phase report per launch
+    if (RING && (a.dbg & 8)) {  // timing experiments only: synchronous phase report per launch
         unsigned long long t[10] = {0};
         (void)hipStreamSynchronize(st);
         (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_phase_ticks), sizeof(t));
@@ -825,7 +800,7 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
 
 // 1x1 ring kernel launched directly (no residual): CAT = over the route [nearest-x2-upsampled src1 | src2]
 // (models.py:86-96,244-245) without materialising it; BN = 256 = all of a 256-channel group per workgroup (twice the MFMAs per
-// stage barrier of the 128-channel tile, input pixels read once per 256 instead of per 128 output channels)
+// stage barrier of the 128-channel tile, input pixels read once per 256 instead of per 128 output channels).  Static dealing.
 template <int BN, int WM, int WN, bool CAT, typename DT = Bf16>
 static int launch_ring1x1(const ay_conv_desc* d, const void* src1, int c1, const void* src2, const void* w, const float* scale,
                           const float* shift, void* out, hipStream_t st) {
@@ -834,35 +809,16 @@ static int launch_ring1x1(const ay_conv_desc* d, const void* src1, int c1, const
     fill_args(a, d, src2, w, scale, shift, nullptr, out, TH, TW, BN);
     a.src1 = (const uint8_t*)src1;
     a.c1 = c1;
-    long long nblk = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
-    a.canvas_gx = 0;
-    int ctx = 0, cty = 0;
-    if (!CAT && (a.canvas_gx = canvas_plan(d, TH, TW, &ctx, &cty)) > 0) {
-        a.tiles_x = ctx;
-        a.tiles_y = cty;
-        nblk = (long long)ctx * cty * a.n_cgroups;
-    } else {
-        a.canvas_gx = 0;
-    }
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        set_error("conv grid out of range (%lld)", nblk);
-        return AY_ERR_ARG;
-    }
-    const int per_xcd = (int)((nblk + 7) / 8);
-    const int cu_slots = conv_num_cus() / 8;
-    dim3 pgrid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots)));
+    const long long nblk = plan_tiles(a, d, TH, TW, !CAT);
     constexpr int NBUF = ring_depth<1, 1, BN, TH, TW, NK>();
-    if (a.canvas_gx)
-        hipLaunchKernelGGL((conv_bf16_ring_kernel<1, 1, BN, WM, WN, TH, TW, NK, NBUF, false, false, !CAT, DT>), pgrid, dim3(512), 0, st, a, (int)nblk);
-    else
-        hipLaunchKernelGGL((conv_bf16_ring_kernel<1, 1, BN, WM, WN, TH, TW, NK, NBUF, false, CAT, false, DT>), pgrid, dim3(512), 0, st, a, (int)nblk);
-    AY_CHECK_LAUNCH("conv_bf16_ring_kernel<1x1>");
-    return AY_OK;
+    void (*kernel)(ConvArgs, int) = conv_bf16_ring_kernel<1, 1, BN, WM, WN, TH, TW, NK, NBUF, false, CAT, false, DT>;
+    if (a.canvas_gx) kernel = conv_bf16_ring_kernel<1, 1, BN, WM, WN, TH, TW, NK, NBUF, false, false, !CAT, DT>;
+    return launch_ring(kernel, a, nblk, false, st, "conv", "conv_bf16_ring_kernel<1x1>");
 }
 
 // Data gradient of a 3x3 stride-2 convolution as four 2x2-window stride-1 convolutions over dz, one per parity class of the
 // output pixel: the ring kernel with KS = 2, classes riding in the channel-group index (class fastest, so the four classes of a
-// tile -- which interleave in the same 128-byte lines of dx -- run side by side)
+// tile -- which interleave in the same 128-byte lines of dx -- run side by side).  Dynamic dealing.
 template <int BN, int WM, int WN, int NK, int TH = 8, bool PAIR = false>
 static int launch_dgrad_s2(const ay_conv_desc* d, const void* dz, const void* w, const float* scale, const float* shift,
                            const void* residual, void* dx, int cin_pad, hipStream_t st) {
@@ -879,22 +835,11 @@ static int launch_dgrad_s2(const ay_conv_desc* d, const void* dz, const void* w,
     // only the row parity
     a.n_cgroups = PAIR ? 2 * (cin_pad / (BN / 2)) : 4 * (cin_pad / BN);
     a.w_class_stride = (unsigned)((size_t)(d->cout_pad / 16) * 4 * 2 * cin_pad * 16);
-    const long long nblk = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) {
-        set_error("dgrad grid out of range (%lld)", nblk);
-        return AY_ERR_ARG;
-    }
-    a.deal = next_deal_set(st);
-    const int per_xcd = (int)((nblk + 7) / 8);
-    const int cu_slots = conv_num_cus() / 8;
-    dim3 pgrid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots))), block(512);
     constexpr int NBUF = ring_depth<2, 1, BN, TH, TW, NK>();
-    if (residual)
-        hipLaunchKernelGGL((conv_bf16_ring_kernel<2, 1, BN, WM, WN, TH, TW, NK, NBUF, true, false, false, Bf16, PAIR>), pgrid, block, 0, st, a, (int)nblk);
-    else
-        hipLaunchKernelGGL((conv_bf16_ring_kernel<2, 1, BN, WM, WN, TH, TW, NK, NBUF, false, false, false, Bf16, PAIR>), pgrid, block, 0, st, a, (int)nblk);
-    AY_CHECK_LAUNCH("conv_bf16_ring_kernel(dgrad s2)");
-    return AY_OK;
+    void (*kernel)(ConvArgs, int) = conv_bf16_ring_kernel<2, 1, BN, WM, WN, TH, TW, NK, NBUF, false, false, false, Bf16, PAIR>;
+    if (residual) kernel = conv_bf16_ring_kernel<2, 1, BN, WM, WN, TH, TW, NK, NBUF, true, false, false, Bf16, PAIR>;
+    const long long nblk = plan_tiles(a, &dd, TH, TW, false);
+    return launch_ring(kernel, a, nblk, true, st, "dgrad", "conv_bf16_ring_kernel(dgrad s2)");
 }
 
 }  // namespace ay
@@ -1030,7 +975,7 @@ static int head_decode_fwd(const ay_conv_desc* d, const void* src, const void* w
     dd.K = K;
     dd.stride = (float)((double)img_dim / (double)d->hout);   // Python float division, then cast (models.py:119): as ay_yolo_decode
     for (int i = 0; i < num_anchors; ++i) dd.aw[i] = anchors_wh[2 * i], dd.ah[i] = anchors_wh[2 * i + 1];
-    const long long nblk = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
+    const long long nblk = plan_tiles(a, d, 8, 32, false);
     AY_CHECK_ARG(nblk > 0 && nblk <= 0x7fffffffLL, "ay_head_decode_fwd: grid out of range");
     dim3 grid((unsigned)nblk), block(256);
     if (d->cin % 64 == 0)

@@ -50,6 +50,74 @@ struct DecodeArgs {
     float aw[6], ah[6]; // anchors in pixels
 };
 
+// ---- persistent kernels: which items a workgroup works on ---------------------------------------------------------------
+// A persistent launch has 8 * slots workgroups (persistent_grid); workgroup blockIdx.x runs on XCD blockIdx.x & 7 and is that
+// XCD's workgroup number `slot`.  The n_items items are cut into 8 consecutive ranges, one per XCD (neighbouring items share
+// input lines, and an XCD has its own L2); the XCD's workgroups share [first, last).  Static dealing: first_item(), then every
+// slots-th item below `last`.  A workgroup with first_item() >= last has nothing to do.
+struct ItemRange {
+    int xcd, slot, slots, first, last;
+    __device__ __forceinline__ explicit ItemRange(int n_items) {
+        xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
+        const int per_xcd = (n_items + 7) >> 3;
+        first = xcd * per_xcd;
+        last = min(first + per_xcd, n_items);
+    }
+    __device__ __forceinline__ int first_item() const { return first + slot; }
+};
+
+// Item dealing of the ring kernels.  A workgroup's first D items are static (no atomics, no wait in the prologue); the following
+// ones come from its XCD's atomic counter in the counter set `deal` (next_deal_set), so that a slow CU (HBM channel luck, a
+// neighbour kernel on the CU) simply takes fewer items instead of setting the kernel time.  Item ids travel through an 8-entry LDS
+// mailbox indexed by sequence number: thread 0 fetches id[c+D] at the start of the epilogue of item c (the atomic's latency hides
+// under it) and posts it at its end; the stage barriers publish it long before the loader (at most 2 item boundaries ahead) or the
+// MFMA side need it.  Without a counter set (deal == nullptr: static dealing) the same mailbox carries the static ids.  An id
+// >= rg.last reads as "no more items".
+struct ItemDealer {
+    // explicit LDS address space: through a generic pointer these volatile accesses become flat_load/flat_store, which count on
+    // vmcnt as well, and hipcc then waits vmcnt(0) -- draining the DMA ring -- at every mailbox access
+    typedef volatile __attribute__((address_space(3))) int lds_vint;
+    const ItemRange& rg;
+    unsigned* deal;  // {8 per-XCD item counters, exit counter} or nullptr
+    lds_vint* mbox;  // 8 ints of the workgroup's LDS
+    int D;           // fetch-ahead distance in items
+    __device__ __forceinline__ ItemDealer(const ItemRange& rg, unsigned* deal, void* mbox_lds, int D)
+        : rg(rg), deal(deal), mbox((lds_vint*)(__attribute__((address_space(3))) int*)mbox_lds), D(D) {}
+    // the workgroup is through with the launch; the last one out hands the counter set back zeroed
+    __device__ __forceinline__ void leave() const {
+        if (deal != nullptr && threadIdx.x == 0) {
+            const unsigned d = atomicAdd(deal + 8, 1u);
+            if (d == gridDim.x - 1) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) atomicExch(deal + i, 0u);
+            }
+        }
+    }
+    // ids 0..D-1, then a barrier (a single-stage item makes the loader ask for id 1 already in the prologue)
+    __device__ __forceinline__ void post_first() const {
+        if ((int)threadIdx.x < D) mbox[threadIdx.x] = min(rg.first_item() + (int)threadIdx.x * rg.slots, rg.last);
+        __syncthreads();
+    }
+    // the id with sequence number s, wave-uniform
+    __device__ __forceinline__ int id_at(int s) const { return __builtin_amdgcn_readfirstlane(mbox[s & 7]); }
+    // thread 0: id[c+D], to be posted after the epilogue of item c; every other thread: rg.last
+    __device__ __forceinline__ int fetch(int c) const {
+        if (threadIdx.x != 0) return rg.last;
+        const int prev = mbox[(c + D - 1) & 7];
+        if (prev >= rg.last) return rg.last;
+        if (deal == nullptr) return prev + rg.slots;
+        // whatever the counter holds, the id stays inside this XCD's range or reads as "no more items"
+        const unsigned n = atomicAdd(deal + rg.xcd, 1u);
+        return n < (unsigned)(rg.last - rg.first) ? rg.first + D * rg.slots + (int)n : rg.last;
+    }
+    __device__ __forceinline__ void post(int c, int id) const {
+        if (threadIdx.x == 0) {
+            mbox[(c + D) & 7] = id;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+    }
+};
+
 // canvas pixel -> image pixel; false: gutter / beyond the batch (reads as zero, is never stored)
 __device__ __forceinline__ bool canvas_px(const ConvArgs& a, int cy, int cx, int& b, int& y, int& x) {
     const int H1 = a.hout + 1, W1 = a.wout + 1;
@@ -375,8 +443,34 @@ __device__ __forceinline__ void head_decode_epilogue(const ConvArgs& a, const De
     }
 }
 
+// ---- host side of the launches (defined in ay_conv_bf16.hip) -------------------------------------------------------------
 int conv_num_cus();
-// counter set for the dynamic item dealing of the next ring-kernel launch on `st` (nullptr: static dealing); ay_conv_bf16.hip
+// AY_DBG, read once (timing experiments: only the instrumented build's kernels look at ConvArgs::dbg)
+int conv_dbg();
+// counter set for the dynamic item dealing of the next ring-kernel launch on `st` (nullptr: static dealing)
 unsigned* next_deal_set(hipStream_t st);
+// THE initialiser of ConvArgs: every field, for the convolution `d` tiled TH x TW pixels by BN channels image by image; static
+// dealing, no debug bits.  A launcher overrides only what differs.
+void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* w, const float* scale, const float* shift,
+               const void* residual, void* out, int TH, int TW, int BN);
+// workgroups of a persistent launch over n_items items: 8 XCDs x min(items per XCD, wgs_per_cu x CUs per XCD); 0: n_items is
+// not in 1 .. 0x7fffffff
+unsigned persistent_grid(long long n_items, int wgs_per_cu = 1);
+
+// One launch of a persistent ring kernel (512 threads) over n_items items of `a`: the counter set (dynamic dealing) or none
+// (static dealing: each workgroup takes every slots-th item of its XCD's range), the grid, the launch.  `what` names the launch
+// in the grid error, `kernel_name` in a launch error.
+inline int launch_ring(void (*kernel)(ConvArgs, int), ConvArgs a, long long n_items, bool dynamic, hipStream_t st, const char* what,
+                       const char* kernel_name) {
+    const unsigned grid = persistent_grid(n_items);
+    if (!grid) {
+        set_error("%s grid out of range (%lld)", what, n_items);
+        return AY_ERR_ARG;
+    }
+    a.deal = dynamic ? next_deal_set(st) : nullptr;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), 0, st, a, (int)n_items);
+    AY_CHECK_LAUNCH(kernel_name);
+    return AY_OK;
+}
 
 }  // namespace ay

@@ -78,11 +78,9 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
     const int wma = wave % WMA, wna = wave / WMA;
     const int wm = wave % WM, wn = wave / WM;
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd;
-    const int last = min(first + per_xcd, n_items);
-    int item = first + slot;
+    const ItemRange rg(n_items);  // static dealing
+    const int slots = rg.slots, last = rg.last;
+    int item = rg.first_item();
     if (item >= last) return;
 
     const int H = a.hout, W = a.wout;
@@ -354,11 +352,10 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
 }
 
 template <int CM, int TH, int NKA, int NBUF, typename DT>
-static int launch_resblock(const ResBlockArgs& s, int n_items, hipStream_t st) {
-    const int per_xcd = (n_items + 7) / 8;
-    const int cu_slots = conv_num_cus() / 8;
-    dim3 grid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots)));
-    hipLaunchKernelGGL((resblock_bf16_kernel<CM, TH, NKA, NBUF, DT>), grid, dim3(512), 0, st, s, n_items);
+static int launch_resblock(const ResBlockArgs& s, long long n_items, hipStream_t st) {
+    const unsigned grid = persistent_grid(n_items);
+    AY_CHECK_ARG(grid, "ay_resblock_fwd_bf16: grid");
+    hipLaunchKernelGGL((resblock_bf16_kernel<CM, TH, NKA, NBUF, DT>), dim3(grid), dim3(512), 0, st, s, (int)n_items);
     AY_CHECK_LAUNCH("resblock_bf16_kernel");
     return AY_OK;
 }
@@ -383,32 +380,16 @@ static int resblock_fwd(const void* x, const void* w1_packed, const float* scale
     s.scale1 = scale1;
     s.shift1 = shift1;
     s.leaky1 = leaky1;
-    ConvArgs& a = s.c2;
-    a.src = nullptr;
-    a.w = (const uint8_t*)w2_packed;
-    a.scale = scale2;
-    a.shift = shift2;
-    a.residual = (const uint8_t*)x;
-    a.out = (uint8_t*)out;
-    a.batch = batch;
-    a.cin = channels / 2;
-    a.cout_pad = channels;
-    a.hin = a.hout = h;
-    a.win = a.wout = w;
+    // the 3x3 as a convolution of `mid` (never in memory: no src) with the shortcut x; one channel group
     // C = 64: 16x32 tile, one x chunk per stage, 4-deep ring (HBM-latency bound: 3 stages in flight); C = 128: 8x32, 3-deep
-    const int th = channels == 64 ? 16 : 8;
-    a.tiles_x = (w + 31) / 32;
-    a.tiles_y = (h + th - 1) / th;
-    a.n_cgroups = 1;
-    a.leaky = leaky2;
-    a.dbg = 0;
-    a.deal = nullptr;
-    a.canvas_gx = 0;
-    a.src1 = nullptr;
-    a.c1 = 0;
+    ay_conv_desc d2{};
+    d2.batch = batch, d2.cin = channels / 2, d2.cout = d2.cout_pad = channels;
+    d2.hin = d2.hout = h, d2.win = d2.wout = w;
+    d2.ksize = 3, d2.stride = 1, d2.leaky = leaky2;
+    ConvArgs& a = s.c2;
+    fill_args(a, &d2, nullptr, w2_packed, scale2, shift2, x, out, channels == 64 ? 16 : 8, 32, channels);
     const long long n_items = (long long)a.tiles_x * a.tiles_y * batch;
-    AY_CHECK_ARG(n_items > 0 && n_items < 0x7fffffffLL, "ay_resblock_fwd_bf16: grid");
-    return channels == 128 ? launch_resblock<64, 8, 2, 3, DT>(s, (int)n_items, S(stream)) : launch_resblock<32, 16, 1, 4, DT>(s, (int)n_items, S(stream));
+    return channels == 128 ? launch_resblock<64, 8, 2, 3, DT>(s, n_items, S(stream)) : launch_resblock<32, 16, 1, 4, DT>(s, n_items, S(stream));
 }
 }  // namespace ay
 

@@ -72,11 +72,9 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
     const int c = lane & 31, hh = lane >> 5;
     const ConvArgs& a = s.c1;
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd;
-    const int last = min(first + per_xcd, n_items);
-    int item = first + slot;
+    const ItemRange rg(n_items);  // static dealing
+    const int slots = rg.slots, last = rg.last;
+    int item = rg.first_item();
     if (item >= last) return;
     const int tiles_per_img = a.tiles_x * a.tiles_y;
 
@@ -336,16 +334,13 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
     const int c = lane & 31, hh = lane >> 5;
     const ConvArgs& a = s.c1;
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd;
-    const int last = min(first + per_xcd, n_items);
-    if (first + slot >= last) return;
-    const int nk = (last - (first + slot) + slots - 1) / slots;   // items of this workgroup: first + slot + k * slots, k < nk
+    const ItemRange rg(n_items);  // static dealing
+    if (rg.first_item() >= rg.last) return;
+    const int nk = (rg.last - rg.first_item() + rg.slots - 1) / rg.slots;   // items of this workgroup: first_item() + k * slots, k < nk
     const unsigned tiles_per_img = (unsigned)(a.tiles_x * a.tiles_y);
     struct Coord { int b, y0, x0; };
     auto coord_of = [&](int k) __attribute__((always_inline)) {   // item k of this workgroup -> image, tile origin
-        const unsigned it = (unsigned)(first + slot + k * slots);
+        const unsigned it = (unsigned)(rg.first_item() + k * rg.slots);
         unsigned b = __umulhi(it, s.m_tpi), r = it - b * tiles_per_img;
         if (r >= tiles_per_img) ++b, r -= tiles_per_img;
         unsigned ty = __umulhi(r, s.m_tx), tx = r - ty * (unsigned)a.tiles_x;
@@ -604,46 +599,29 @@ static int stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const
     s.leaky0 = leaky0;
     s.H = h;
     s.W = w;
-    ConvArgs& a = s.c1;
-    a.src = nullptr;
-    a.w = (const uint8_t*)w1_packed;
-    a.scale = scale1;
-    a.shift = shift1;
-    a.residual = nullptr;
-    a.out = (uint8_t*)out_blocked;
-    a.batch = batch;
-    a.cin = 32;
-    a.cout_pad = 64;
-    a.hin = h;
-    a.win = w;
-    a.hout = h / 2;
-    a.wout = w / 2;
     // any other image (width not a multiple of 4, unaligned, 2 GiB and more) takes the serial-phase kernel (8x32 items)
     const bool v2 = w % 4 == 0 && (reinterpret_cast<uintptr_t>(x_nchw) & 15) == 0 && 3LL * h * w * 4 < 0x7fffffffLL;
-    a.tiles_x = (a.wout + 31) / 32;
-    a.tiles_y = v2 ? (a.hout + 3) / 4 : (a.hout + 7) / 8;
-    a.n_cgroups = 1;
+    // layer 1: 3x3 stride 2 over the stem's 32 channels (never in memory: no src), 64 filters in one channel group
+    ay_conv_desc d1{};
+    d1.batch = batch, d1.cin = 32, d1.cout = d1.cout_pad = 64;
+    d1.hin = h, d1.win = w, d1.hout = h / 2, d1.wout = w / 2;
+    d1.ksize = 3, d1.stride = 2, d1.leaky = leaky1;
+    ConvArgs& a = s.c1;
+    fill_args(a, &d1, nullptr, w1_packed, scale1, shift1, nullptr, out_blocked, v2 ? 4 : 8, 32, 64);
+    a.dbg = conv_dbg();
     auto magic = [](unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ULL / d); };
     s.m_tx = magic((unsigned)a.tiles_x);
     s.m_tpi = magic((unsigned)(a.tiles_x * a.tiles_y));
-    a.leaky = leaky1;
-    a.dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;   // read only by the instrumented build (AY_DBGBIT)
-    a.deal = nullptr;
-    a.canvas_gx = 0;
-    a.src1 = nullptr;
-    a.c1 = 0;
     const long long n_items = (long long)a.tiles_x * a.tiles_y * batch;
-    AY_CHECK_ARG(n_items > 0 && n_items < 0x7fffffffLL, "ay_stem_s2_fused_fwd: grid");
-    const int per_xcd = (int)((n_items + 7) / 8);
-    const int cu_slots = conv_num_cus() / 8;
-    dim3 grid((unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots)));
+    const dim3 grid(persistent_grid(n_items));   // static dealing
+    AY_CHECK_ARG(grid.x, "ay_stem_s2_fused_fwd: grid");
     if (v2)
         hipLaunchKernelGGL(stem_s2_fused_v2_kernel<DT>, grid, dim3(1024), 0, S(stream), s, (int)n_items);
     else
         hipLaunchKernelGGL(stem_s2_fused_kernel<DT>, grid, dim3(1024), 0, S(stream), s, (int)n_items);
     AY_CHECK_LAUNCH("stem_s2_fused_kernel");
 #ifdef AY_PHASE_CLOCK
-    if (getenv("AY_DBG") && (atoi(getenv("AY_DBG")) & 8)) {
+    if (conv_dbg() & 8) {
         unsigned long long t[8] = {0}, z[8] = {0};
         (void)hipStreamSynchronize(S(stream));
         (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_stem_ticks), sizeof(t));

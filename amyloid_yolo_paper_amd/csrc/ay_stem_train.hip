@@ -77,15 +77,13 @@ __global__ void __launch_bounds__(512, 4) stem_train_fwd_kernel(stemtr::Args a, 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hh = lane >> 5;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd, last = min(first + per_xcd, n_items);
-    if (first + slot >= last) {
+    const ItemRange rg(n_items);  // static dealing
+    if (rg.first_item() >= rg.last) {
         if (STATS && tid < 64) a.stat_slab[(size_t)blockIdx.x * 64 + tid] = 0.f;
         return;
     }
-    const int nk = (last - (first + slot) + slots - 1) / slots;
-    auto item_at = [&](int k) { return (unsigned)(first + slot + k * slots); };
+    const int nk = (rg.last - rg.first_item() + rg.slots - 1) / rg.slots;
+    auto item_at = [&](int k) { return (unsigned)(rg.first_item() + k * rg.slots); };
     const unsigned lds_base = lds_addr_of(lds);
     const int plane_elems = a.H * a.W;
 
@@ -285,11 +283,9 @@ __global__ void __launch_bounds__(512) stem_train_wgrad_kernel(stemtr::Args a, i
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (n_items + 7) >> 3;
-    const int first = xcd * per_xcd, last = min(first + per_xcd, n_items);
-    const int nk = first + slot < last ? (last - (first + slot) + slots - 1) / slots : 0;
-    auto item_at = [&](int k) { return (unsigned)(first + slot + k * slots); };
+    const ItemRange rg(n_items);  // static dealing
+    const int nk = rg.first_item() < rg.last ? (rg.last - rg.first_item() + rg.slots - 1) / rg.slots : 0;
+    auto item_at = [&](int k) { return (unsigned)(rg.first_item() + k * rg.slots); };
     const unsigned lds_base = lds_addr_of(lds);
     const int plane_elems = a.H * a.W;
     const unsigned dz_plane_bytes = (unsigned)plane_elems * 32u;
@@ -446,11 +442,8 @@ static bool stem_train_setup(stemtr::Args& a, const float* x, int batch, int h, 
     a.m_tx = magic((unsigned)a.tiles_x);
     a.m_tpi = magic((unsigned)(a.tiles_x * a.tiles_y));
     *n_items = (long long)a.tiles_x * a.tiles_y * batch;
-    if (*n_items <= 0 || *n_items >= 0x7fffffffLL) return false;
-    const int per_xcd = (int)((*n_items + 7) / 8);
-    const int cu_slots = wgs_per_cu * conv_num_cus() / 8;
-    *grid = (unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots));
-    return true;
+    *grid = persistent_grid(*n_items, wgs_per_cu);
+    return *grid != 0;
 }
 
 }  // namespace ay
