@@ -55,7 +55,9 @@ const char* ay_last_error(void);
 typedef struct ay_conv_desc {
     int32_t batch;
     int32_t cin, cout;         /* logical channels */
-    int32_t hin, win;          /* input spatial size */
+    int32_t hin, win;          /* input spatial size; hin != win is pinned bit for bit by tests/test_gpu_conv_exact.py for the
+                                  convolution, data- and weight-gradient, fused-block and stem entry points (16-bit and fp32);
+                                  ay_head_decode_fwd_* refuses a rectangle */
     int32_t hout, wout;        /* output spatial size = floor((hin + 2*pad - k)/stride) + 1, pad=(k-1)/2 */
     int32_t ksize, stride;     /* 1|3 ; 1|2 */
     int32_t leaky;             /* 1: LeakyReLU(0.1) after the affine */
