@@ -1,5 +1,7 @@
 """Detection statistics (reference ``utils/utils.py:69-190``): greedy true-positive matching on the device
-(``ay_match_detections``), VOC-style AP per class on the host (a sort and two cumulative sums over the detections)."""
+(``ay_match_detections``), VOC-style AP per class on the host (a sort and two cumulative sums over the detections).
+Slide level: ``match_slide`` / ``slide_statistics`` (``ay_slide_match``) match one image of any size, a whole slide's detections
+against its annotations, where the per-tile kernel's 2048 targets per image do not reach."""
 import numpy as np
 import torch
 
@@ -88,3 +90,85 @@ def ap_per_class(tp, conf, pred_cls, target_cls):
             ap[k], prec[k], rec[k] = average_precision(tp[a:b], n_truth)
     f1 = 2 * prec * rec / (prec + rec + 1e-16)
     return prec, rec, ap, f1, truth_ids.astype("int32")
+
+
+# ---- slide level: one image of any size (THE SLIDE MATCH RULE, include/amyloid_yolo.h) ----------------------------------------
+def _slide_array(a, cols, dev):
+    t = a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
+    return t.to(device=dev, dtype=torch.float32).reshape(-1, cols).contiguous()
+
+
+def match_slide(rows, targets, iou_thres=0.5, roi=None, cell_side=None):
+    """True-positive matching of a whole slide's detections against its annotations on the device (``ay_slide_match``): the rule of
+    ``get_batch_statistics`` for ONE image of any size, with no cap on the number of targets.
+
+    ``rows`` [M,7] = (x1, y1, x2, y2, conf, cls_conf, cls_pred) and ``targets`` [T,5] = (class, x1, y1, x2, y2), both in slide
+    pixels, tensors or arrays on the host or the device; ``iou_thres`` a float or a sequence of K <= 16 values in (0, 1]; ``roi`` =
+    (x1, y1, x2, y2): rows and targets whose centre lies outside the closed rectangle are ignored, as if deleted.  Rows need not
+    be sorted: they are ranked by ``conf * cls_conf`` (ties: lower index first).  Scores must be >= 0 and not NaN, coordinates
+    finite, classes integers in 0 .. 4095 (``AyError`` for a target class outside).
+
+    Returns a dict of device tensors: ``tp`` uint8 [K,M], ``best_iou`` float32 [M], ``best_target`` int32 [M] (-1: no target with a
+    positive IoU), ``claim`` int32 [K,T] (the row that claimed the target, -1: missed), ``row_ignored`` / ``target_ignored`` bool,
+    ``eligible`` / ``claimed`` int32 [K] (rows that reached threshold k with a label present; targets claimed = true positives),
+    ``oversize`` (targets larger than a grid cell, which every row tests).  ``cell_side`` overrides the side of the binning grid
+    (default: from the targets); the result does not depend on it.  Synchronises with the host."""
+    import ctypes as C
+
+    from . import _lib
+    from ._lib import check, ptr
+    from .utils import _to_dev
+    dev = _to_dev(torch.zeros(1)).device
+    rows, targets = _slide_array(rows, 7, dev), _slide_array(targets, 5, dev)
+    M, T = int(rows.shape[0]), int(targets.shape[0])
+    thr = [float(v) for v in np.atleast_1d(np.asarray(iou_thres, np.float64))]
+    K = len(thr)
+    thr_c = (C.c_float * max(K, 1))(*thr)
+    roi_c = None if roi is None else (C.c_float * 4)(*[float(v) for v in roi])
+    tp = torch.zeros(K, M, device=dev, dtype=torch.uint8)
+    best_iou = torch.zeros(M, device=dev, dtype=torch.float32)
+    best_target = torch.full((M,), -1, device=dev, dtype=torch.int32)
+    claim = torch.full((K, T), -1, device=dev, dtype=torch.int32)
+    row_ign = torch.zeros(M, device=dev, dtype=torch.uint8)
+    tgt_ign = torch.zeros(T, device=dev, dtype=torch.uint8)
+    stats = torch.zeros(2 * K + 2, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    ws = torch.empty(max(int(L.ay_slide_match_workspace_bytes(M, T, K)), 1), device=dev, dtype=torch.uint8)
+    check(L.ay_slide_match(ptr(rows) if M else None, M, ptr(targets) if T else None, T, thr_c, K, roi_c,
+                           C.c_float(0.0 if cell_side is None else float(cell_side)), ptr(tp) if M else None, ptr(best_iou) if M else None,
+                           ptr(best_target) if M else None, ptr(claim) if T else None, ptr(row_ign) if M else None,
+                           ptr(tgt_ign) if T else None, ptr(stats), ptr(ws), ws.numel(), _lib.stream_ptr()), "ay_slide_match")
+    st = stats.cpu().numpy()
+    if int(st[2 * K]) & 1:   # AY_SLIDE_FLAG_CLASS
+        raise _lib.AyError("ay_slide_match: a target's class is no integer in 0 .. 4095")
+    return {"tp": tp, "best_iou": best_iou, "best_target": best_target, "claim": claim, "row_ignored": row_ign.bool(),
+            "target_ignored": tgt_ign.bool(), "eligible": torch.from_numpy(st[0:2 * K:2].copy()),
+            "claimed": torch.from_numpy(st[1:2 * K:2].copy()), "oversize": int(st[2 * K + 1])}
+
+
+def slide_statistics(rows, targets, iou_thres=0.5, roi=None, match=None):
+    """Precision / recall / AP of a whole slide's detections (``match_slide`` + ``ap_per_class``).
+
+    Arguments as for :func:`match_slide` (``match`` replaces the device call by a function of the same signature that returns at
+    least ``tp``, ``claim``, ``row_ignored`` and ``target_ignored``: the tests pass the NumPy restatement).  Returns a dict:
+    ``iou_thres`` (the K thresholds); ``metrics``: per threshold ``(precision, recall, AP, f1, ap_class)`` of
+    ``ap_per_class(tp, conf, cls_pred, target classes)`` over the non-ignored rows and targets; ``missed``: per threshold the
+    indices of the non-ignored targets that no row claimed; ``false_alarms``: per threshold the indices of the non-ignored rows
+    that are no true positive; ``counts``: per threshold a dict with ``rows``, ``targets`` (non-ignored), ``tp``, ``missed`` and
+    ``false_alarms``.  All indices refer to the arrays as given."""
+    m = (match or match_slide)(rows, targets, iou_thres, roi)
+    host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    rows_h, targets_h = host(rows).astype(np.float32).reshape(-1, 7), host(targets).astype(np.float32).reshape(-1, 5)
+    tp, claim = host(m["tp"]), host(m["claim"])
+    live_r, live_t = ~host(m["row_ignored"]).astype(bool), ~host(m["target_ignored"]).astype(bool)
+    thr = [float(v) for v in np.atleast_1d(np.asarray(iou_thres, np.float64))]
+    out = {"iou_thres": thr, "metrics": [], "missed": [], "false_alarms": [], "counts": []}
+    for k in range(len(thr)):
+        out["metrics"].append(ap_per_class(tp[k][live_r], rows_h[live_r, 4], rows_h[live_r, 6], targets_h[live_t, 0]))
+        missed = np.flatnonzero(live_t & (claim[k] == -1))
+        alarms = np.flatnonzero(live_r & (tp[k] == 0))
+        out["missed"].append(missed)
+        out["false_alarms"].append(alarms)
+        out["counts"].append({"rows": int(live_r.sum()), "targets": int(live_t.sum()), "tp": int(tp[k][live_r].sum()),
+                              "missed": int(missed.size), "false_alarms": int(alarms.size)})
+    return out

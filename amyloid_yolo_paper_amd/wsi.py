@@ -493,3 +493,25 @@ def _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nm
     starts = np.flatnonzero(np.r_[True, kept_tile[1:] != kept_tile[:-1]])
     ends = np.r_[starts[1:], len(kept_tile)]
     return [(int(kept_tile[a]) // TX, int(kept_tile[a]) % TX, kept[a:b].clone()) for a, b in zip(starts, ends)]
+
+
+def evaluate_region(model, raster, targets, iou_thres=0.5, roi=None, **detect_region_kwargs):
+    """Slide-level precision / recall / AP of :func:`detect_region` against the annotations of the slide.
+
+    Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged, concatenates its ``(ty, tx, boxes)`` result in that
+    order into ``rows`` [M,7] and returns ``stats.slide_statistics(rows, targets, iou_thres, roi)`` with ``rows`` added to the
+    dict.  ``targets`` [T,5] = (class, x1, y1, x2, y2) are in pixels of the (halved) slide, like the boxes ``detect_region``
+    returns; ``roi`` = (x1, y1, x2, y2) restricts the evaluation to the annotated part of the slide (rows and targets whose centre
+    lies outside are ignored).  The slide is ONE image: an annotation on a tile seam stays one target (cutting the annotations
+    back into tiles would make it two truncated ones), and there is no cap on their number (THE SLIDE MATCH RULE,
+    ``include/amyloid_yolo.h``).
+
+    What the number is for: comparing settings of ``overlap`` / ``seam_thres``, ``views`` / ``min_views`` / ``vote_thres``,
+    ``min_tissue`` and ``conf_thres`` on an annotated slide -- each of them changes which rows come out, and this says whether the
+    change helped.  ``missed`` and ``false_alarms`` index ``targets`` and ``rows`` for a look at the cases themselves."""
+    from .stats import slide_statistics
+    res = detect_region(model, raster, **detect_region_kwargs)
+    rows = torch.cat([d for _, _, d in res]) if res else torch.zeros(0, 7)
+    out = slide_statistics(rows, targets, iou_thres, roi)
+    out["rows"] = rows
+    return out

@@ -613,10 +613,57 @@ int ay_view_votes(const float* pred, int batch, int n_views, int n_rows_per_view
 int ay_view_select(float* rows, int32_t* keep_idx, int32_t* count, const int32_t* votes, int batch, int max_det, int min_views,
                    ay_stream_t stream);
 
+/* ---- slide-level evaluation: detections of a whole slide against its annotations (stats.match_slide; csrc/ay_slidematch.hip) ------
+ * The true-positive rule of get_batch_statistics (utils/utils.py:154-190) for one image of any size.  ay_match_detections walks an
+ * image's detections with one wavefront and holds 2048 targets; a slide has 10^4 .. 10^5 annotated objects and a few 10^5 rows.
+ *
+ * THE SLIDE MATCH RULE.  Input: rows [M][7] fp32 (x1, y1, x2, y2, conf, cls_conf, cls_pred) and targets [T][5] fp32 (class, x1, y1, x2,
+ *   y2), both in slide pixels; K thresholds with 0 < thr_k <= 1, 1 <= K <= AY_SLIDE_MAX_THRES; optionally a region of interest
+ *   roi = (rx1, ry1, rx2, ry2).  tests/slide_match_reference.py restates the rule in NumPy as the reference writes it.
+ *   ROI: a row or target is IGNORED iff a roi is given and its centre (fl32((x1 + x2) * 0.5f), fl32((y1 + y2) * 0.5f)) lies outside
+ *     the closed rectangle.  Ignored rows and targets take no part, as if deleted before the rule ran; indices in all outputs still
+ *     refer to the original arrays.
+ *   Rank (the seam rule's): score_i = conf_i * cls_conf_i, one fp32 multiply; row i comes before j iff score_i > score_j, or the
+ *     scores are equal and i < j.  A NaN or negative score is a caller error (the result is then unspecified, but in bounds); so is
+ *     a coordinate that is not finite.
+ *   IoU: iou_p1_s of csrc/ay_stats.hip exactly: +1 pixel convention, inter / (a1 + a2 - inter + 1e-16f), fp32, no fused multiply-add.
+ *   Best target: for a non-ignored row, best_target is the lowest-index non-ignored target among those with the largest IoU (torch's
+ *     first maximum) and best_iou that value; if no target has a positive IoU, best_target = -1 and best_iou = 0 (thr > 0: this never
+ *     changes a flag).  Ignored rows get -1 and 0.
+ *   Eligibility: a row is eligible at k iff it is not ignored, its cls_pred equals the class of at least one non-ignored target (the
+ *     reference's `pred_label not in target_labels`) and best_iou >= thr_k.  As in the reference, the row's label is NOT compared
+ *     with the label of its best target: a row whose best target has another class still claims it.
+ *   Claim and flags: claim[k][g] is the first eligible-at-k row in rank order whose best_target is g, or -1;
+ *     tp[k][i] = 1 iff claim[k][best_target_i] == i.  This equals the reference's sequential walk in rank order with its claimed set,
+ *     including the early exit once every target is claimed: a row's candidate is its own first maximum whatever earlier rows did,
+ *     so the walk is an argmax per row and a minimum per target.
+ *   The result is exact for any box sizes, has no cap on M or T other than int32 and memory, and is the same bytes on every run.
+ *   Classes are integers in 0 .. AY_SLIDE_MAX_CLASSES - 1 (class presence is a flag array on the device): a non-ignored target with
+ *     another class value sets AY_SLIDE_FLAG_CLASS and matches no label; a row with such a cls_pred is simply never eligible.
+ *
+ * ay_slide_match: rows, targets and every output on the device; iou_thres (n_thres floats) and roi (4 floats, or NULL) on the HOST.
+ *   tp uint8 [n_thres][n_rows], best_iou fp32 [n_rows], best_target int32 [n_rows], claim int32 [n_thres][n_targets], row_ignored uint8
+ *   [n_rows], target_ignored uint8 [n_targets], stats int32 [2 * n_thres + 2] = per k (rows eligible at k, targets claimed at k), then
+ *   AY_SLIDE_FLAG_* bits, then the number of targets on the oversize list.  n_rows == 0 or n_targets == 0 is legal (every flag 0, every
+ *   claim -1; arrays of length 0 may be NULL).  The non-ignored targets are binned by the cell of their centre; a target larger than a
+ *   cell goes to an oversize list that every row tests in full.  cell_side <= 0: the side comes from the targets (a reduction, read by
+ *   the host); cell_side >= 2: that side.  Either way it is doubled until the grid over the targets' extent stays bounded, and the
+ *   result does not depend on it.  With n_targets > 0 the call SYNCHRONISES `stream` with the host once (the grid): not for graph
+ *   capture.  workspace: 16-byte aligned, ay_slide_match_workspace_bytes(n_rows, n_targets, n_thres) bytes.  No scratch. */
+#define AY_SLIDE_MAX_THRES 16
+#define AY_SLIDE_MAX_CLASSES 4096
+#define AY_SLIDE_FLAG_CLASS 1
+size_t ay_slide_match_workspace_bytes(int n_rows, int n_targets, int n_thres);
+int ay_slide_match(const float* rows, int n_rows, const float* targets, int n_targets, const float* iou_thres, int n_thres,
+                   const float* roi, float cell_side, uint8_t* tp, float* best_iou, int32_t* best_target, int32_t* claim,
+                   uint8_t* row_ignored, uint8_t* target_ignored, int32_t* stats, void* workspace, size_t workspace_bytes,
+                   ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
- * no host copy, no memset node, no symbol access inside a call -- so a stream capture of a step (ay_plan_forward + ay_nms_merge ...)
- * replays like any other graph (scripts/micro/graph_sync.hip, graph_coherence.hip, graph_input_coherence.hip: every wait covers a
- * replayed graph, a kernel behind a replay sees its writes, a replay sees eager writes to its inputs).  The persistent kernels rely on
+ * no host copy, no memset node, no symbol access inside a call (the once-per-slide calls ay_seam_merge and ay_slide_match excepted:
+ * they memset, read a few words back and synchronise the stream, and are not for capture) -- so a stream capture of a step
+ * (ay_plan_forward + ay_nms_merge ...) replays like any other graph (scripts/micro/graph_sync.hip, graph_coherence.hip,
+ * graph_input_coherence.hip: every wait covers a replayed graph, a kernel behind a replay sees its writes, a replay sees eager writes to its inputs).  The persistent kernels rely on
  * stream order between launches (a launch hands its work-counter set back zeroed for a later launch on that stream, the plan's
  * arena reuses a block once its last reader has been issued): replay a graph on ONE stream at a time and do not run other library
  * work on the capture stream concurrently.  ay_stream_fence records a library-owned event on `stream` and makes the stream wait for
