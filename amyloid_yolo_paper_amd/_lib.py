@@ -32,6 +32,12 @@ class AugParams(C.Structure):
                 ("color", C.c_float * 9), ("bright", C.c_float)]
 
 
+class AugWindowParams(C.Structure):
+    """ay_aug_window_params (include/amyloid_yolo.h, THE WINDOW RULE): one record per image of ay_augment_ingest_window_u8"""
+    _fields_ = [("src_offset", C.c_int64), ("row_stride", C.c_int64), ("bh", C.c_int32), ("bw", C.c_int32), ("x0", C.c_int32),
+                ("y0", C.c_int32), ("context", C.c_int32), ("fill", C.c_float), ("aug", AugParams)]
+
+
 PLAN_INPUT, PLAN_NONE = -1, -2
 OP_STEM_S2_FUSED, OP_STEM, OP_CONV, OP_RESBLOCK, OP_CONV1X1_CAT, OP_CONCAT_UPSAMPLE, OP_DECODE = 1, 2, 3, 4, 5, 6, 7
 
@@ -96,6 +102,7 @@ _SIGS = {
     "ay_ingest_region_tiles_step_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ay_ingest_region_tiles_list_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, _I, _P, _P]),
     "ay_augment_ingest_u8": (_I, [_P, _SZ, _P, _I, _I, _P, _P]),
+    "ay_augment_ingest_window_u8": (_I, [_P, _SZ, _P, _I, _I, _P, _P]),
     "ay_tile_tissue_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ay_build_targets_workspace_bytes": (_SZ, [_I, _I, _I]),
     "ay_build_targets": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),

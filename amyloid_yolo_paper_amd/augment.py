@@ -29,7 +29,15 @@ from ._lib import AyError, check
 AUG_DTYPE = np.dtype([("src_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("inv", "<f4", (6,)), ("flip", "<i4"),
                       ("sharpen_alpha", "<f4"), ("drop_threshold", "<u4"), ("drop_seed", "<u4"), ("color", "<f4", (9,)),
                       ("bright", "<f4")], align=True)
+# numpy mirror of ay_aug_window_params (THE WINDOW RULE; _lib.AugWindowParams is the ctypes mirror)
+AUG_WINDOW_DTYPE = np.dtype([("src_offset", "<i8"), ("row_stride", "<i8"), ("bh", "<i4"), ("bw", "<i4"), ("x0", "<i4"), ("y0", "<i4"),
+                             ("context", "<i4"), ("fill", "<f4"), ("aug", AUG_DTYPE)], align=True)
 HUE_UNIT_DEGREES = 360.0 / 255.0
+# footprint(): what the fp32 evaluation of step 3 can differ by from its float64 value, in pixels.  With every coordinate below 2^17
+# in magnitude (sizes up to 32768, the kernel's limit, turned and shifted within the default ranges) each of the six fp32 roundings
+# of sx is at most half an ulp of 2^17 = 2^-8, and rounding the three float64 coefficients to fp32 moves sx by at most 3 * 2^-24 *
+# 2^17: 6 * 2^-8 + 3 * 2^-7 = 0.047 < 1/16.
+FOOTPRINT_MARGIN = 0.0625
 
 
 @dataclass
@@ -140,11 +148,13 @@ def sample_params(rng, sizes, ranges=None):
     return make_table(sizes, A if B else None, flip, alpha, p, seed, hue, bright)
 
 
-def transform_labels(boxes, h, w, rec):
+def transform_labels(boxes, h, w, rec, min_visible=0.0):
     """Labels ``class cx cy w h`` (normalised to the h x w tile) moved with the image: in continuous coordinates (pixel i spans
     [i, i+1), centre (w/2, h/2)) the four corners go through rec.A, then through the flip x -> w - x; the axis-aligned bounding
     box of the result (as imgaug does) is clipped to the image, a box whose clipped width or height is <= 0 is dropped, and what
-    remains gets the pad offsets and the re-normalisation by D = max(h, w) of ``datasets.default_transform``.  -> float64 [m,5]"""
+    remains gets the pad offsets and the re-normalisation by D = max(h, w) of ``datasets.default_transform``.  -> float64 [m,5]
+    ``min_visible`` > 0 also drops a box whose clipped area is below that fraction of the area of its unclipped transformed bounding
+    box (what the clip left of it is too little to be called the object); the default drops nothing more."""
     b = np.array(boxes, dtype=np.float64, copy=True).reshape(-1, 5)
     if not len(b):
         return b
@@ -161,6 +171,9 @@ def transform_labels(boxes, h, w, rec):
     x1, x2 = np.clip(px.min(1), 0.0, w), np.clip(px.max(1), 0.0, w)
     y1, y2 = np.clip(py.min(1), 0.0, h), np.clip(py.max(1), 0.0, h)
     keep = (x2 - x1 > 0) & (y2 - y1 > 0)
+    if min_visible > 0.0:
+        full = (px.max(1) - px.min(1)) * (py.max(1) - py.min(1))
+        keep &= (x2 - x1) * (y2 - y1) >= min_visible * full
     b, x1, x2, y1, y2 = b[keep], x1[keep], x2[keep], y1[keep], y2[keep]
     D = max(h, w)
     p1 = abs(h - w) // 2
@@ -223,6 +236,104 @@ def augment_ingest_device(tiles, params, img_size, out=None):
     check(_lib.lib().ay_augment_ingest_u8(C.c_void_p(src_ptr), n_img, C.c_void_p(table_ptr), B, img_size, _lib.ptr(out),
                                           _lib.stream_ptr()), "ay_augment_ingest_u8")
     return out
+
+
+class WindowTable:
+    """the window records of a batch: `dev` (structured array of AUG_WINDOW_DTYPE, what ay_augment_ingest_window_u8 reads) and `A`
+    (float64 [B,2,3], the forward matrices for the labels)"""
+
+    def __init__(self, dev, A):
+        self.dev, self.A = dev, A
+
+    def __len__(self):
+        return len(self.dev)
+
+    def __getitem__(self, i):
+        return AugRecord(self.A[i], self.dev[i]["aug"])
+
+
+def make_window_table(table, blocks, origins, context=True, fill=255.0, src_offsets=None, row_strides=None):
+    """Window records (THE WINDOW RULE) from an AugTable whose ``h, w`` are the windows' sizes: ``blocks`` [(bh, bw), ...] are the
+    pixels that may be read and ``origins`` [(x0, y0), ...] the windows' origins in block pixels.  ``row_strides`` default to
+    ``3 * bw`` and ``src_offsets`` to the blocks lying one after another (empty blocks take no room)."""
+    B = len(table)
+    assert len(blocks) == B and len(origins) == B
+    dev = np.zeros(B, AUG_WINDOW_DTYPE)
+    dev["aug"] = table.dev
+    dev["aug"]["src_offset"] = 0
+    off = 0
+    for i, ((bh, bw), (x0, y0)) in enumerate(zip(blocks, origins)):
+        r = dev[i]
+        r["bh"], r["bw"], r["x0"], r["y0"] = bh, bw, x0, y0
+        r["row_stride"] = 3 * max(int(bw), 0) if row_strides is None else row_strides[i]
+        r["src_offset"] = off if src_offsets is None else src_offsets[i]
+        if bh > 0 and bw > 0:
+            off += (int(bh) - 1) * int(r["row_stride"]) + 3 * int(bw)
+    dev["context"] = np.asarray(context, dtype=bool).astype(np.int32)
+    dev["fill"] = fill
+    return WindowTable(dev, np.array(table.A, dtype=np.float64, copy=True))
+
+
+def footprint(rec, tile, img_size):
+    """The integer bounding box ``(x1, y1, x2, y2)`` (half open, in window coordinates, of any sign) of every tap step 4 can touch
+    for this record on an ``(h, w) = tile`` window (an int for a square one) at output size ``img_size``.  Steps 1-2 give integer
+    positions inside ``[-left, D - 1 - left] x [-top, D - 1 - top]`` (mirrored by the flip); step 3 is affine, so its extremes lie
+    at the corners of that rectangle; they are computed here in float64 from the float64 inverse of ``rec.A`` and widened by
+    ``FOOTPRINT_MARGIN`` for the kernel's fp32 evaluation; the taps are ``floor`` and ``floor + 1`` of the result."""
+    h, w = (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))
+    assert 0 < h <= 32768 and 0 < w <= 32768 and img_size > 0
+    D = max(h, w)
+    top = (w - h) // 2 if h <= w else 0
+    left = (h - w) // 2 if h > w else 0
+    qx = np.array([-left, D - 1 - left], dtype=np.float64)
+    if rec.flip:
+        qx = (w - 1) - qx
+    qy = np.array([-top, D - 1 - top], dtype=np.float64)
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    inv = inverse_matrix(rec.A)
+    xc, yc = np.meshgrid(qx - cx, qy - cy)
+    sx = inv[0, 0] * xc + inv[0, 1] * yc + inv[0, 2] + cx
+    sy = inv[1, 0] * xc + inv[1, 1] * yc + inv[1, 2] + cy
+    m = FOOTPRINT_MARGIN
+    return (int(math.floor(sx.min() - m)), int(math.floor(sy.min() - m)),
+            int(math.floor(sx.max() + m)) + 2, int(math.floor(sy.max() + m)) + 2)
+
+
+def launch_windows(src_ptr, src_bytes, table_ptr, B, img_size, out):
+    """one call of ``ay_augment_ingest_window_u8`` on the current stream (raw device addresses)"""
+    assert out.shape == (B, 3, img_size, img_size) and out.is_contiguous() and out.dtype == torch.float32 and out.is_cuda
+    check(_lib.lib().ay_augment_ingest_window_u8(C.c_void_p(src_ptr), src_bytes, C.c_void_p(table_ptr), B, img_size, _lib.ptr(out),
+                                                 _lib.stream_ptr()), "ay_augment_ingest_window_u8")
+    return out
+
+
+def augment_ingest_windows_device(src, table, img_size, out=None):
+    """Windows of one source buffer -> float32 [B,3,S,S] on the current HIP device (``ay_augment_ingest_window_u8``).  ``src``: a
+    uint8 tensor of any shape, taken as its bytes; on the device it is read in place and only the records go up, on the host
+    (pinned or not) it goes up in ONE copy with the records behind it.  ``table``: a WindowTable or a structured array of
+    AUG_WINDOW_DTYPE, used as it is (``src_offset`` counts from the first byte of ``src``).  No CPU fallback."""
+    if not torch.cuda.is_available():
+        raise AyError("no HIP device: augment_ingest_windows_device has no CPU fallback")
+    src = torch.as_tensor(src)
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.numel() > 0, "a contiguous uint8 buffer"
+    recs = np.array(table.dev if isinstance(table, WindowTable) else table, dtype=AUG_WINDOW_DTYPE, copy=True)
+    B, n = len(recs), src.numel()
+    assert B > 0 and recs.ndim == 1
+    rec_bytes = torch.from_numpy(recs.view(np.uint8).reshape(-1))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if src.is_cuda:
+        resident, tab_dev = src, rec_bytes.to(dev, non_blocking=True)
+        src_ptr, table_ptr = src.data_ptr(), tab_dev.data_ptr()
+    else:
+        tab = (n + 15) // 16 * 16              # the table starts on 16 bytes behind the pixels
+        host = torch.empty(tab + rec_bytes.numel(), dtype=torch.uint8, pin_memory=True)
+        host[:n].copy_(src.reshape(-1))
+        host[tab:].copy_(rec_bytes)
+        resident = host.to(dev, non_blocking=True)
+        src_ptr, table_ptr = resident.data_ptr(), resident.data_ptr() + tab
+    if out is None:
+        out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
+    return launch_windows(src_ptr, n, table_ptr, B, img_size, out)
 
 
 class DeviceAugmenter:

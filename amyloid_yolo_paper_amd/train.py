@@ -39,8 +39,14 @@ def format_metrics(model, epoch, epochs, batch_i, n_batches):
 def train(epochs=100, batch_size=8, gradient_accumulations=2, model_def="config/yolov3.cfg", data_config="config/coco.data",
           pretrained_weights=None, n_cpu=8, img_size=416, checkpoint_interval=1, evaluation_interval=1,
           multiscale_training=True, verbose=False, checkpoint_dir="checkpoints", max_batches=None, seed=0, precision="bf16",
-          box_loss="mse", augment=False, augmenter=None):
-    """``augment``: train behind the device augmentation (an ``augment.DeviceAugmenter`` seeded with ``(seed, rank)``, or the
+          box_loss="mse", augment=False, augmenter=None, source=None):
+    """``source``: an iterable with ``__len__`` that yields ``(imgs [B,3,S,S] fp32, targets [n,6])`` on the device, e.g. a
+    ``wsi.SlideSampler`` over annotated slides; it replaces the ``ListDataset`` / ``DataLoader`` / augmenter trio (``data_config``
+    is still read for the class names and the validation list; ``batch_size``, ``img_size``, ``n_cpu``, ``augment`` then say nothing
+    about the training batches).  One pass over it is an epoch, ``len(source)`` its number of batches.  With ``world > 1`` the caller
+    gives every rank a source of its own with the same number of batches (``SlideSampler(rank=rank, batches=...)``), so that
+    optimiser steps and collectives line up.
+    ``augment``: train behind the device augmentation (an ``augment.DeviceAugmenter`` seeded with ``(seed, rank)``, or the
     ``augmenter`` handed in).  ``precision``: "bf16" = MFMA training path (bf16 activations/gradients, fp32 master weights and statistics),
     "fp32" = the parity path that reproduces the reference's fp32 step to 1e-4.  ``box_loss``: "mse" (reference) | "giou"."""
     rank, local_rank, world = init_distributed()
@@ -58,14 +64,17 @@ def train(epochs=100, batch_size=8, gradient_accumulations=2, model_def="config/
         else:
             model.load_darknet_weights(pretrained_weights)
     broadcast_parameters(model)
-    dataset = ListDataset(cfg["train"], multiscale=multiscale_training, img_size=img_size, raw_u8=bool(augment))
-    if augment and augmenter is None:
-        from .augment import DeviceAugmenter
-        augmenter = DeviceAugmenter(seed, rank)
-    # every rank gets the same number of tiles (the tail wraps around), hence the same number of batches: optimiser steps,
-    # accumulation boundaries and collectives line up on all ranks
-    data = Subset(dataset, shard_indices_equal(len(dataset), rank, world)) if world > 1 else dataset
-    loader = DataLoader(data, batch_size=batch_size, shuffle=True, num_workers=n_cpu, pin_memory=True, collate_fn=dataset.collate_fn)
+    if source is not None:
+        loader = source
+    else:
+        dataset = ListDataset(cfg["train"], multiscale=multiscale_training, img_size=img_size, raw_u8=bool(augment))
+        if augment and augmenter is None:
+            from .augment import DeviceAugmenter
+            augmenter = DeviceAugmenter(seed, rank)
+        # every rank gets the same number of tiles (the tail wraps around), hence the same number of batches: optimiser steps,
+        # accumulation boundaries and collectives line up on all ranks
+        data = Subset(dataset, shard_indices_equal(len(dataset), rank, world)) if world > 1 else dataset
+        loader = DataLoader(data, batch_size=batch_size, shuffle=True, num_workers=n_cpu, pin_memory=True, collate_fn=dataset.collate_fn)
     # one exchange per optimiser step over a flat gradient buffer, overlapped with the backward on the bf16 path; the update is
     # torch.optim.Adam's (train.py:81: default hyper-parameters, no schedule) as one kernel over the flat buffers -- the step
     # bench.py --mode train times
@@ -81,7 +90,9 @@ def train(epochs=100, batch_size=8, gradient_accumulations=2, model_def="config/
         model.train()
         t0 = time.time()
         for batch_i, batch in enumerate(loader):
-            if augment:
+            if source is not None:
+                imgs, targets = batch                              # made on the device by the source
+            elif augment:
                 _, tiles, boxes, size = batch
                 imgs, targets = augmenter(tiles, boxes, size)      # uint8 tiles up, fp32 batch and targets made on the device
             else:

@@ -355,6 +355,41 @@ typedef struct ay_aug_params {
 int ay_augment_ingest_u8(const void* src_u8, size_t src_bytes, const ay_aug_params* params_device, int batch, int out_size,
                          float* out_nchw, ay_stream_t stream);
 
+/* THE WINDOW RULE (training windows cut out of an annotated slide: wsi.SlideSampler), as a difference to THE AUGMENTATION RULE.
+ *   One record per image (ay_aug_window_params).  The BLOCK is the bh x bw pixels that may be read: pixel (0, 0) at byte
+ *   src_offset of the source buffer, rows row_stride bytes apart (>= 3 * bw, no multiple of anything).  The WINDOW is the h x w
+ *   (aug.h, aug.w) pixels whose origin lies at block pixel (x0, y0), of any sign: it may leave the block on every side.
+ *   Steps 1-3 and 5-8 are unchanged, with (h, w) the window.  Step 4 computes x0 = floorf(sx), y0 = floorf(sy), fx, fy and the tap
+ *   positions (ty, tx) in WINDOW coordinates as before; the value of a tap is
+ *     - if context == 0 and (ty, tx) lies outside [0, h) x [0, w): 0 (the tile rule);
+ *     - else, with (by, bx) = (y0 + ty, x0 + tx) computed without overflow: the source byte of block pixel (by, bx) if it lies
+ *       inside [0, bh) x [0, bw), otherwise `fill`.
+ *   So with context == 1 a rotated or shifted window shows the real surroundings it has on the slide instead of black wedges, and
+ *   `fill` (the slide's background) only beyond the block.
+ *   Consequences:
+ *     - context == 0, x0 == y0 == 0, bh == h, bw == w, row_stride == 3 * w: ay_augment_ingest_u8 bit for bit.
+ *     - context == 0 and the window inside a larger block: ay_augment_ingest_u8 on the cut-out tile, bit for bit.
+ *     - context == 1: the output depends on the block only through the pixels the taps touch; any sub-block that holds them (and
+ *       has `fill` semantics beyond the same outer edge) gives the same bytes.
+ *     - A block without pixels (bh <= 0 or bw <= 0) has every tap outside: `fill` (context == 1, or inside the window), else 0.
+ *   Safety: a record with h, w <= 0, a negative src_offset or row_stride, or a block (with pixels) that does not lie inside
+ *   [src_u8, src_u8 + src_bytes) -- src_offset + (bh - 1) * row_stride + 3 * bw <= src_bytes, evaluated without overflow --
+ *   reads nothing and yields the all-padding image of ay_augment_ingest_u8 (W = 0).  Tap positions are clamped in block
+ *   coordinates before any address is formed, so every float in `inv` (inf and NaN included) reads inside the block. */
+typedef struct ay_aug_window_params {
+    int64_t src_offset;            /* byte offset of block pixel (0, 0) in the source buffer */
+    int64_t row_stride;            /* bytes between block rows */
+    int32_t bh, bw;                /* the block: the pixels that may be read */
+    int32_t x0, y0;                /* the window's origin in block pixels, of any sign */
+    int32_t context;               /* 0: outside the window is 0 | 1: outside the window is the block, then `fill` */
+    float fill;                    /* 0..255: the value of a tap outside the block */
+    ay_aug_params aug;             /* h, w = the window's size; its src_offset is ignored */
+} ay_aug_window_params;
+
+/* ay_augment_ingest_u8 under THE WINDOW RULE: the same kernel body with another tap fetch, the same argument checks and limits. */
+int ay_augment_ingest_window_u8(const void* src_u8, size_t src_bytes, const ay_aug_window_params* params_device, int batch,
+                                int out_size, float* out_nchw, ay_stream_t stream);
+
 /* ---- tissue map: which tiles of a slide are worth reading (wsi.tissue_counts, wsi.wanted_tiles; csrc/ay_tissue.hip) ------------
  * THE TISSUE RULE (exact, integer).
  *   A pixel of the (halved, for shrink == 2) image is TISSUE iff min(R, G, B) < bg_level on its uint8 values; for shrink == 2 the
