@@ -135,6 +135,28 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
 
+// The tap of the whole-slide cut (ay_ingest.hip, ay_views.hip): pixel (X, Y) of the (halved, for shrink == 2) H x W slide that the
+// region `reg` (rows `stride` bytes apart) holds -> px[3] in 0 .. 1; the background 255 = 1.0 outside.  shrink == 2 is the 2x2 mean
+// with round-half-up in uint8.  X and Y are origin + offset added in `unsigned` (int32 origin, 0 <= offset < 2^24): a sum below 0
+// or beyond 2^31 - 1 wraps to a value >= 2^31 > W, H, so the one unsigned comparison per axis gates every read for any origin, and
+// no signed sum can overflow.
+__device__ __forceinline__ void region_tap(const uint8_t* __restrict__ reg, size_t stride, int shrink, int H, int W, unsigned X,
+                                           unsigned Y, float px[3]) {
+    px[0] = px[1] = px[2] = 1.0f;
+    if (Y < (unsigned)H && X < (unsigned)W) {
+        if (shrink == 1) {
+            const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
+        } else {
+            const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
+            const uint8_t* p1 = p0 + stride;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
+        }
+    }
+}
+
 static inline hipStream_t S(ay_stream_t s) { return (hipStream_t)s; }
 
 }  // namespace ay

@@ -40,74 +40,46 @@ __global__ void __launch_bounds__(256) ingest_u8_kernel(const uint8_t* __restric
 // (a full-width strip of the slide: one contiguous upload), optionally after the 40x -> 20x halving, then the N1 chain
 // (/255, nearest resize to the network size).  The halving is a 2x2 mean with round-half-up in uint8: pyvips' resize(0.5) is a
 // lanczos3 reduce and the reference then goes through JPEG Q=90, neither is restated (parity unpinned).
-__global__ void __launch_bounds__(256) region_tiles_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
-                                                               int tile, int tiles_y, int tiles_x, int S, float* __restrict__ out) {
-    const int H = RH / shrink, W = RW / shrink;  // the (halved) image the tile grid lies on
-    const float scale = (float)tile / (float)S;
-    const size_t plane = (size_t)S * S;
-    const size_t total = (size_t)tiles_y * tiles_x * plane;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % S), y = (int)((i / S) % S);
-        const size_t t = i / plane;
-        const int ty = (int)(t / tiles_x), tx = (int)(t % tiles_x);
-        const int Y = ty * tile + min((int)floorf(y * scale), tile - 1);
-        const int X = tx * tile + min((int)floorf(x * scale), tile - 1);
-        float v[3] = {1.0f, 1.0f, 1.0f};  // background 255
-        if (Y < H && X < W) {
-            if (shrink == 1) {
-                const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = (float)p[c] / 255.0f;
-            } else {
-                const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
-                const uint8_t* p1 = p0 + stride;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
-            }
-        }
-        float* o = out + t * 3 * plane + (size_t)y * S + x;
-        o[0] = v[0];
-        o[plane] = v[1];
-        o[2 * plane] = v[2];
+//
+// ONE cut for every region entry point.  Tile t has its origin at Origins::at(t) on the (halved) slide and a side of `tile`; a thread
+// produces V consecutive output pixels of one row (region_tap of ay_common.h per pixel) and stores them as one V-float vector per
+// channel plane: the kernel is bound by its 12 B of stores per output pixel, and a 16-byte store per lane moves them in a quarter of
+// the store instructions of the scalar form.
+struct GridOrigins {   // tile (ty, tx) of a tiles_x-wide grid starts at (tx * step, ty * step); step == tile: dzsave's abutting grid
+    int tiles_x, step;
+    __device__ __forceinline__ void at(size_t t, unsigned& x, unsigned& y) const {
+        x = (unsigned)(t % tiles_x) * (unsigned)step;
+        y = (unsigned)(t / tiles_x) * (unsigned)step;
     }
-}
+};
+struct ListOrigins {   // tile t starts at xy[t] = (x, y), any int32 pair (wsi.RegionTileStream(tile_mask=...): only the wanted tiles)
+    const int32_t* __restrict__ xy;
+    __device__ __forceinline__ void at(size_t t, unsigned& x, unsigned& y) const {
+        x = (unsigned)xy[2 * t];
+        y = (unsigned)xy[2 * t + 1];
+    }
+};
 
-// The same grid with a STEP between tile origins (tile (ty, tx) starts at (ty * step, tx * step); step < tile: overlapping tiles for
-// wsi.detect_region(overlap > 0), step == tile: the grid above).  A thread produces V consecutive output pixels of one row and
-// stores them as one V-float vector per channel plane: the kernel is bound by its 12 B of stores per output pixel, and a 16-byte
-// store per lane moves them in a quarter of the store instructions of the scalar form.
-template <int V>
-__global__ void __launch_bounds__(256) region_tiles_step_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
-                                                                    int tile, int step, int tiles_y, int tiles_x, int S,
-                                                                    float* __restrict__ out) {
+template <int V, typename Origins>
+__global__ void __launch_bounds__(256) region_tiles_cut_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
+                                                                   int tile, Origins origins, size_t n, int S, float* __restrict__ out) {
     typedef float vec __attribute__((ext_vector_type(V)));
-    const int H = RH / shrink, W = RW / shrink;
+    const int H = RH / shrink, W = RW / shrink;  // the (halved) image the tiles lie on
     const float scale = (float)tile / (float)S;
     const size_t plane = (size_t)S * S;
-    const int SV = S / V;   // S % V == 0 (checked by the entry point)
-    const size_t total = (size_t)tiles_y * tiles_x * S * SV;
+    const int SV = S / V;   // S % V == 0 (launch_cut)
+    const size_t total = n * S * SV;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int x0 = (int)(i % SV) * V, y = (int)((i / SV) % S);
         const size_t t = i / ((size_t)SV * S);
-        const int ty = (int)(t / tiles_x), tx = (int)(t % tiles_x);
-        const int Y = ty * step + min((int)floorf(y * scale), tile - 1);
+        unsigned ox, oy;
+        origins.at(t, ox, oy);
+        const unsigned Y = oy + (unsigned)min((int)floorf(y * scale), tile - 1);
         vec v[3];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            const int X = tx * step + min((int)floorf((x0 + k) * scale), tile - 1);
-            float px[3] = {1.0f, 1.0f, 1.0f};  // background 255
-            if (Y < H && X < W) {
-                if (shrink == 1) {
-                    const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
-                } else {
-                    const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
-                    const uint8_t* p1 = p0 + stride;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
-                }
-            }
+            float px[3];
+            region_tap(reg, stride, shrink, H, W, ox + (unsigned)min((int)floorf((x0 + k) * scale), tile - 1), Y, px);
 #pragma unroll
             for (int c = 0; c < 3; ++c) v[c][k] = px[c];
         }
@@ -117,48 +89,22 @@ __global__ void __launch_bounds__(256) region_tiles_step_u8_kernel(const uint8_t
     }
 }
 
-// The cut of region_tiles_step_u8_kernel for a LIST of tile origins (wsi.RegionTileStream(tile_mask=...): only the wanted tiles of a
-// strip are cut, densely, into a batch buffer): tile t starts at origins[t] = (x, y) on the (halved) image.  Same arithmetic, same
-// 255 outside the region, same V-float stores; the origins of a full grid in grid order give the step kernel's bytes.
-template <int V>
-__global__ void __launch_bounds__(256) region_tiles_list_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
-                                                                    int tile, const int32_t* __restrict__ origins, int n, int S,
-                                                                    float* __restrict__ out) {
-    typedef float vec __attribute__((ext_vector_type(V)));
-    const int H = RH / shrink, W = RW / shrink;
-    const float scale = (float)tile / (float)S;
-    const size_t plane = (size_t)S * S;
-    const int SV = S / V;   // S % V == 0 (checked by the entry point)
-    const size_t total = (size_t)n * S * SV;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x0 = (int)(i % SV) * V, y = (int)((i / SV) % S);
-        const size_t t = i / ((size_t)SV * S);
-        const int ox = origins[2 * t], oy = origins[2 * t + 1];
-        const int Y = oy + min((int)floorf(y * scale), tile - 1);
-        vec v[3];
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const int X = ox + min((int)floorf((x0 + k) * scale), tile - 1);
-            float px[3] = {1.0f, 1.0f, 1.0f};  // background 255
-            if (Y >= 0 && Y < H && X >= 0 && X < W) {   // the origins come from device memory: nothing outside the region is read
-                if (shrink == 1) {
-                    const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
-                } else {
-                    const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
-                    const uint8_t* p1 = p0 + stride;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c][k] = px[c];
-        }
-        float* o = out + t * 3 * plane + (size_t)y * S + x0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(vec*)(o + c * plane) = v[c];
-    }
+// the launch of the three region entry points: 16-byte stores where every row of every plane starts on 16 bytes, scalar ones otherwise
+template <typename Origins>
+static int launch_cut(const void* reg, int RH, int RW, size_t stride, int shrink, int tile, Origins origins, size_t n, int out_size,
+                      float* out, ay_stream_t stream) {
+    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    const size_t total = n * out_size * (out_size / (vec4 ? 4 : 1));
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    if (vec4)
+        hipLaunchKernelGGL((region_tiles_cut_u8_kernel<4, Origins>), dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)reg, RH,
+                           RW, stride, shrink, tile, origins, n, out_size, out);
+    else
+        hipLaunchKernelGGL((region_tiles_cut_u8_kernel<1, Origins>), dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)reg, RH,
+                           RW, stride, shrink, tile, origins, n, out_size, out);
+    AY_CHECK_LAUNCH("region_tiles_cut_u8_kernel");
+    return AY_OK;
 }
 
 }  // namespace ay
@@ -172,18 +118,8 @@ extern "C" int ay_ingest_region_tiles_list_u8(const void* region_hwc_u8, int reg
                  "ay_ingest_region_tiles_list_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
     AY_CHECK_ARG(tile > 0 && tile <= (1 << 24) && n > 0 && out_size > 0, "ay_ingest_region_tiles_list_u8: %d tiles of %d -> %d", n, tile,
                  out_size);
-    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;   // every row of every plane then starts on 16 bytes
-    const size_t total = (size_t)n * out_size * (out_size / (vec4 ? 4 : 1));
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (vec4)
-        hipLaunchKernelGGL(region_tiles_list_u8_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
-                           region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, out_size, out_nchw);
-    else
-        hipLaunchKernelGGL(region_tiles_list_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
-                           region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, out_size, out_nchw);
-    AY_CHECK_LAUNCH("region_tiles_list_u8_kernel");
-    return AY_OK;
+    return launch_cut(region_hwc_u8, region_h, region_w, row_stride_bytes, shrink, tile, ListOrigins{origins_xy}, (size_t)n, out_size,
+                      out_nchw, stream);
 }
 
 extern "C" int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
@@ -194,13 +130,8 @@ extern "C" int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h
                  "ay_ingest_region_tiles_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
     AY_CHECK_ARG(tile > 0 && tiles_y > 0 && tiles_x > 0 && out_size > 0, "ay_ingest_region_tiles_u8: tile grid %dx%d of %d -> %d",
                  tiles_y, tiles_x, tile, out_size);
-    const size_t total = (size_t)tiles_y * tiles_x * out_size * out_size;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(region_tiles_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, region_h,
-                       region_w, row_stride_bytes, shrink, tile, tiles_y, tiles_x, out_size, out_nchw);
-    AY_CHECK_LAUNCH("region_tiles_u8_kernel");
-    return AY_OK;
+    return launch_cut(region_hwc_u8, region_h, region_w, row_stride_bytes, shrink, tile, GridOrigins{tiles_x, tile},
+                      (size_t)tiles_y * tiles_x, out_size, out_nchw, stream);
 }
 
 extern "C" int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
@@ -212,18 +143,8 @@ extern "C" int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int reg
                  "ay_ingest_region_tiles_step_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
     AY_CHECK_ARG(tile > 0 && step > 0 && step <= tile && tiles_y > 0 && tiles_x > 0 && out_size > 0,
                  "ay_ingest_region_tiles_step_u8: tile grid %dx%d of %d step %d -> %d", tiles_y, tiles_x, tile, step, out_size);
-    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;   // every row of every plane then starts on 16 bytes
-    const size_t total = (size_t)tiles_y * tiles_x * out_size * (out_size / (vec4 ? 4 : 1));
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (vec4)
-        hipLaunchKernelGGL(region_tiles_step_u8_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
-                           region_h, region_w, row_stride_bytes, shrink, tile, step, tiles_y, tiles_x, out_size, out_nchw);
-    else
-        hipLaunchKernelGGL(region_tiles_step_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
-                           region_h, region_w, row_stride_bytes, shrink, tile, step, tiles_y, tiles_x, out_size, out_nchw);
-    AY_CHECK_LAUNCH("region_tiles_step_u8_kernel");
-    return AY_OK;
+    return launch_cut(region_hwc_u8, region_h, region_w, row_stride_bytes, shrink, tile, GridOrigins{tiles_x, step},
+                      (size_t)tiles_y * tiles_x, out_size, out_nchw, stream);
 }
 
 extern "C" int ay_ingest_tiles_u8(const void* img_hwc_u8, int batch, int h, int w, int out_size, float pad_value, float* out_nchw,

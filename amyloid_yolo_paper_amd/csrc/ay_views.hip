@@ -1,9 +1,9 @@
 // Dihedral test-time views for whole-slide detection (wsi.detect_region(views=...); THE VIEW RULE and THE VOTE RULE are stated in
 // include/amyloid_yolo.h and restated in NumPy by tests/views_reference.py).
 //
-//   region_tiles_views_u8_kernel   the cut of region_tiles_list_u8_kernel, written in every requested view.  A workgroup computes one
-//                                  32 x 32 block of I0 (the image the list kernel would write: region bytes, the 2x2 means for shrink
-//                                  == 2, /255, nearest resize) ONCE, keeps it in LDS and stores it into each view from there: the
+//   region_tiles_views_u8_kernel   the list cut of ay_ingest.hip (region_tiles_cut_u8_kernel), written in every requested view.  A
+//                                  workgroup computes one 32 x 32 block of I0 (the image the cut kernel would write, pixel by pixel
+//                                  through the same region_tap of ay_common.h, after the nearest resize) ONCE, keeps it in LDS and stores it into each view from there: the
 //                                  slide bytes are fetched once for all views.  A view is a permutation of I0, so the block lands in
 //                                  each view as one rectangle, written row by row: lanes run along the OUTPUT row also for the
 //                                  transposed views, whose LDS reads then walk a column of the block.  LDS rows are 33 floats apart:
@@ -61,26 +61,14 @@ __global__ void __launch_bounds__(256) region_tiles_views_u8_kernel(const uint8_
         const int rem = (int)(b % per_tile);
         const int r0 = (rem / nb) * VIEW_BLOCK, c0 = (rem % nb) * VIEW_BLOCK;      // the block of I0: rows r0 .., columns c0 ..
         const int h = min(VIEW_BLOCK, S - r0), w = min(VIEW_BLOCK, S - c0);
-        const long long ox = origins[2 * t], oy = origins[2 * t + 1];
-        // ---- I0, with the arithmetic of region_tiles_list_u8_kernel ----
+        const unsigned ox = (unsigned)origins[2 * t], oy = (unsigned)origins[2 * t + 1];
+        // ---- I0: the tap of the cut kernel (region_tap, ay_common.h) ----
         for (int i = tid; i < VIEW_BLOCK * VIEW_BLOCK; i += 256) {
             const int ly = i >> 5, lx = i & 31;
             if (ly >= h || lx >= w) continue;
-            const long long Y = oy + min((int)floorf((r0 + ly) * scale), tile - 1);
-            const long long X = ox + min((int)floorf((c0 + lx) * scale), tile - 1);
-            float px[3] = {1.0f, 1.0f, 1.0f};  // background 255
-            if (Y >= 0 && Y < H && X >= 0 && X < W) {   // the origins come from device memory: nothing outside the region is read
-                if (shrink == 1) {
-                    const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
-                } else {
-                    const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
-                    const uint8_t* p1 = p0 + stride;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
-                }
-            }
+            float px[3];
+            region_tap(reg, stride, shrink, H, W, ox + (unsigned)min((int)floorf((c0 + lx) * scale), tile - 1),
+                       oy + (unsigned)min((int)floorf((r0 + ly) * scale), tile - 1), px);
 #pragma unroll
             for (int c = 0; c < 3; ++c) blk[c][ly][lx] = px[c];
         }

@@ -4,20 +4,21 @@ reference (``crop.py:13-25`` writes 1536-px JPEG tiles with pyvips ``dzsave``, `
 A slide (any ``[H, W, 3]`` uint8 array: a NumPy memmap of a decoded level, a pyvips/openslide region fetched by the caller)
 is walked in full-width strips of one tile row.  A strip is one contiguous slice of the raster: it goes to the device in a
 single copy from a pinned staging buffer on a copy stream (two buffers, so strip i+1 uploads while strip i computes), and
-``ay_ingest_region_tiles_u8`` cuts the row of tiles out of it on the device -- dzsave's 'google' layout: a ``tile`` grid from
-the top-left corner, edge tiles padded with the background 255 -- with the optional 40x -> 20x halving (``crop.py:44-47``)
-and the detect-time ``/255`` + nearest resize fused in.  Detections come back in slide coordinates.
+``ay_ingest_region_tiles_step_u8`` cuts the row of tiles out of it on the device -- at ``step == tile`` dzsave's 'google' layout:
+a ``tile`` grid from the top-left corner, edge tiles padded with the background 255 -- with the optional 40x -> 20x halving
+(``crop.py:44-47``) and the detect-time ``/255`` + nearest resize fused in.  Detections come back in slide coordinates.
 
 Abutting tiles split every object that straddles a seam.  With ``overlap > 0`` the tile origins are ``tile - overlap`` apart
-(:func:`tile_grid`, ``ay_ingest_region_tiles_step_u8``), every object no larger than ``overlap`` is seen whole by at least one
+(:func:`tile_grid`, the ``step`` of the same entry point), every object no larger than ``overlap`` is seen whole by at least one
 tile, the per-tile detections stay on the device (``utils.nms_device`` -> ``ay_seam_append``) and one slide-level pass removes
 the second sightings (``ay_seam_merge``; the rule is stated in ``include/amyloid_yolo.h``).
 
 Most of a histology slide is glass.  :func:`tissue_counts` (``ay_tile_tissue_u8``, the rule in ``include/amyloid_yolo.h``) counts the
 tissue pixels of every tile, usually on a low-resolution level, :func:`wanted_tiles` turns the counts into a ``tile_mask``, and with
 a mask the stream never stages a strip without a wanted tile, stages of any other strip only the columns between its first and its
-last wanted tile and cuts only the wanted tiles out of it (``ay_ingest_region_tiles_list_u8``); :func:`detect_region` then fills its
-batches with wanted tiles across strip boundaries.
+last wanted tile and cuts only the wanted tiles out of it (``ay_ingest_region_tiles_list_u8``, the same cut with the origins read
+from a list); its batches are then filled with wanted tiles across strip boundaries.  Every mode of :func:`detect_region` takes its
+model calls from one generator, :meth:`RegionTileStream.batches`.
 
 Training reads the same rasters: :class:`SlideSampler` draws windows centred on annotations, hard cases and tissue out of annotated
 slides and cuts them with the fused augmentation kernel under THE WINDOW RULE (``ay_augment_ingest_window_u8``), for
@@ -238,10 +239,7 @@ class RegionTileStream:
                 out = torch.empty(self.tiles_x * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
                 if self.views != (0,):
                     self._ingest_list(L, k, valid, width, row, self.tiles_x, out)
-                elif self.overlap == 0:
-                    check(L.ay_ingest_region_tiles_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile, 1,
-                                                      self.tiles_x, self.S, ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_u8")
-                else:
+                else:    # the grid origins are computed, not read: faster than the list entry; overlap == 0 is step == tile
                     check(L.ay_ingest_region_tiles_step_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile,
                                                            self.step, 1, self.tiles_x, self.S, ptr(out), _lib.stream_ptr()),
                           "ay_ingest_region_tiles_step_u8")
@@ -254,8 +252,21 @@ class RegionTileStream:
                 self._release(k)
                 yield out, coords[a:b]
 
+    def batches(self, per_call):
+        """The iteration as detect_region takes it, one item per model call: ``(tiles [n * V,3,S,S], [(ty, tx)] * n)`` with ``n <=
+        per_call``.  Without a mask the tiles of a strip in slices of ``per_call``, never across strips; with one, :meth:`_batches`."""
+        V = len(self.views)
+        if self.tile_mask is None:
+            for tiles, coords in self:
+                for s in range(0, len(coords), per_call):
+                    yield tiles[s * V:(s + per_call) * V], coords[s:s + per_call]
+        else:
+            coords = self._wanted()
+            for tiles, w0 in self._batches(per_call):
+                yield tiles, coords[w0:w0 + tiles.shape[0] // V]
+
     def _batches(self, batch_size):
-        """The masked iteration as detect_region takes it: yields ``(tiles [n * V,3,S,S], w0)``, the wanted tiles ``w0 .. w0 + n`` of
+        """The masked iteration of :meth:`batches`: yields ``(tiles [n * V,3,S,S], w0)``, the wanted tiles ``w0 .. w0 + n`` of
         :meth:`_wanted`, ``n == batch_size`` but for the last batch: a strip's wanted tiles are cut into the open batch buffer at its
         fill, so that batches are filled across strip boundaries.  Every ingest of a strip is issued (into as many batch buffers as
         it takes) and the strip released before its batches are handed out, so the refill of a strip buffer never waits for a model
@@ -371,119 +382,67 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
         tile_mask = tissue_mask(raster, tile, shrink, overlap, min_tissue, bg_level, probe_stride)
     if tile_mask is not None and not check_tile_mask(tile_mask, H, W, tile, overlap).any():
         return []
+    per_call = int(batch_size) if tta is None else max(1, int(batch_size) // len(views))   # tiles per model call: at most batch_size images
+    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask, views)
+    model.eval()
     if overlap:
-        return _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, overlap, seam_thres,
-                                      max_det, seam_capacity, tile_mask, tta)
-    if tta is not None:
-        return _detect_region_views(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, max_det, tile_mask, tta)
+        return _detect_region_overlap(model, stream, per_call, conf_thres, nms_thres, seam_thres, int(max_det), seam_capacity, tta)
     results = []
-    scale = float(tile) / float(img_size)
-    model.eval()
-
-    def run(tiles, coords):
+    for tiles, coords in stream.batches(per_call):
         with torch.no_grad():  # rows stay on the device; only the detections come back
-            det = non_max_suppression(model.forward_device(tiles), conf_thres, nms_thres)
-        for (ty, tx), d in zip(coords, det):
-            if d is None:
-                continue
-            d = d.cpu()
-            d[:, :4] *= scale
-            d[:, [0, 2]] += tx * tile
-            d[:, [1, 3]] += ty * tile
-            results.append((ty, tx, d))
-
-    stream = RegionTileStream(raster, tile, img_size, shrink, tile_mask=tile_mask)
-    if tile_mask is None:
-        for tiles, coords in stream:
-            for s in range(0, tiles.shape[0], batch_size):
-                run(tiles[s:s + batch_size], coords[s:s + batch_size])
-    else:
-        coords = stream._wanted()
-        for tiles, w0 in stream._batches(batch_size):
-            run(tiles, coords[w0:w0 + tiles.shape[0]])
+            pred = model.forward_device(tiles)
+            if tta is None:    # a read-back per tile, no cap on the rows of a tile
+                det = [None if d is None else d.cpu() for d in non_max_suppression(pred, conf_thres, nms_thres)]
+            else:              # V views per tile through one merge-NMS; one read-back per batch
+                rows, _, count, _ = nms_views_device(pred, views, conf_thres, nms_thres, int(max_det), int(min_views), vote_thres,
+                                                     img_dim=img_size)
+                count_h, rows_h = count.cpu().tolist(), rows.cpu()
+                if max(count_h) > int(max_det):
+                    raise _lib.AyError(f"detect_region: a tile holds more than max_det={max_det} detections; raise max_det or conf_thres")
+                det = [d[:n].clone() if n else None for n, d in zip(count_h, rows_h)]
+        results += [(ty, tx, _to_slide(d, ty, tx, stream)) for (ty, tx), d in zip(coords, det) if d is not None]
     return results
 
 
-def _detect_region_views(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, max_det, tile_mask, tta):
-    """the abutting path with views: per model call ``max(1, batch_size // V)`` tiles in V views, ``nms_views_device``, and the rows of
-    the batch read back -- the arithmetic on them is that of the path without views"""
-    views, min_views, vote_thres = tta
-    V, max_det = len(views), int(max_det)
-    per_call = max(1, int(batch_size) // V)
-    results = []
-    scale = float(tile) / float(img_size)
-    model.eval()
-
-    def run(tiles, coords):
-        with torch.no_grad():
-            rows, _, count, _ = nms_views_device(model.forward_device(tiles), views, conf_thres, nms_thres, max_det, min_views,
-                                                 vote_thres, img_dim=img_size)
-            count_h, rows_h = count.cpu().tolist(), rows.cpu()
-        if max(count_h) > max_det:
-            raise _lib.AyError(f"detect_region: a tile holds more than max_det={max_det} detections; raise max_det or conf_thres")
-        for (ty, tx), n, d in zip(coords, count_h, rows_h):
-            if n == 0:
-                continue
-            d = d[:n].clone()
-            d[:, :4] *= scale
-            d[:, [0, 2]] += tx * tile
-            d[:, [1, 3]] += ty * tile
-            results.append((ty, tx, d))
-
-    stream = RegionTileStream(raster, tile, img_size, shrink, tile_mask=tile_mask, views=views)
-    if tile_mask is None:
-        for tiles, coords in stream:
-            for s in range(0, len(coords), per_call):
-                run(tiles[s * V:(s + per_call) * V], coords[s:s + per_call])
-    else:
-        coords = stream._wanted()
-        for tiles, w0 in stream._batches(per_call):
-            run(tiles, coords[w0:w0 + tiles.shape[0] // V])
-    return results
+def _to_slide(rows, ty, tx, stream):
+    """rows of tile ``(ty, tx)`` of an abutting grid, boxes in network pixels -> in pixels of the (halved) slide, in place (fp32)"""
+    rows[:, :4] *= float(stream.tile) / float(stream.S)
+    rows[:, [0, 2]] += tx * stream.tile
+    rows[:, [1, 3]] += ty * stream.tile
+    return rows
 
 
-def _detect_region_overlap(model, raster, tile, img_size, shrink, conf_thres, nms_thres, batch_size, overlap, seam_thres, max_det,
-                           seam_capacity, tile_mask=None, tta=None):
+def _detect_region_overlap(model, stream, per_call, conf_thres, nms_thres, seam_thres, max_det, seam_capacity, tta):
+    """the path with overlapping tiles: the rows of every model call are appended to a slide buffer on the device (``ay_seam_append``
+    scales and shifts them, the arithmetic of :func:`_to_slide` at ``step`` between origins), one seam merge and one read-back at the end"""
     from .postprocess import seam_merge_device
     L = _lib.lib()
-    views, min_views, vote_thres = tta if tta is not None else ((0,), 1, None)
-    V = len(views)
-    if tta is not None:
-        batch_size = max(1, int(batch_size) // V)     # tiles per model call: at most batch_size images
-    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask, views)
     dev, TX, step = stream.dev, stream.tiles_x, stream.step
     # per tile that runs, on the device for the whole slide: its id (grid order on the full grid) and the (x, y) of its corner
-    if tile_mask is None:
+    if stream.tile_mask is None:
         ids = torch.arange(stream.tiles_y * TX, dtype=torch.int32)
     else:
-        ids = torch.from_numpy(np.flatnonzero(tile_mask.ravel()).astype(np.int32))
-    capacity = int(seam_capacity) if seam_capacity else min(len(ids) * int(max_det), 1 << 22)
+        ids = torch.from_numpy(np.flatnonzero(stream.tile_mask.ravel()).astype(np.int32))
+    capacity = int(seam_capacity) if seam_capacity else min(len(ids) * max_det, 1 << 22)
     origins = torch.stack([(ids % TX) * step, (ids // TX) * step], 1).to(torch.float32).to(dev)
     ids = ids.to(dev)
     slide_rows = torch.empty(capacity, 7, device=dev, dtype=torch.float32)
     slide_tile = torch.empty(capacity, device=dev, dtype=torch.int32)
     slide_count = torch.zeros(2, device=dev, dtype=torch.int32)
-    scale = C.c_float(float(tile) / float(img_size))
-    model.eval()
-
-    def batches():   # (tiles [n * V ...], index of the first of the n in ids / origins)
-        if tile_mask is not None:
-            yield from stream._batches(batch_size)
-            return
-        for tiles, coords in stream:
-            for s in range(0, len(coords), batch_size):
-                yield tiles[s * V:(s + batch_size) * V], coords[s][0] * TX + coords[s][1]
-
-    for tiles, t0 in batches():
+    scale = C.c_float(float(stream.tile) / float(stream.S))
+    t0 = 0   # tiles run so far: the batches come in the order of ids / origins
+    for tiles, coords in stream.batches(per_call):
         with torch.no_grad():  # no read-back: the NMS result buffers are overwritten by the next batch, the append is right behind
             if tta is None:
-                rows, _, count, _ = nms_device(model.forward_device(tiles), conf_thres, nms_thres, int(max_det))
+                rows, _, count, _ = nms_device(model.forward_device(tiles), conf_thres, nms_thres, max_det)
             else:             # rows and count in nms_device's form, one image per TILE
-                rows, _, count, _ = nms_views_device(model.forward_device(tiles), views, conf_thres, nms_thres, int(max_det), min_views,
-                                                     vote_thres, img_dim=img_size)
+                views, min_views, vote_thres = tta
+                rows, _, count, _ = nms_views_device(model.forward_device(tiles), views, conf_thres, nms_thres, max_det, min_views,
+                                                     vote_thres, img_dim=stream.S)
         B = rows.shape[0]
-        check(L.ay_seam_append(ptr(rows), ptr(count), B, int(max_det), scale, ptr(origins[t0:t0 + B]), ptr(ids[t0:t0 + B]),
+        check(L.ay_seam_append(ptr(rows), ptr(count), B, max_det, scale, ptr(origins[t0:t0 + B]), ptr(ids[t0:t0 + B]),
                                ptr(slide_rows), ptr(slide_tile), ptr(slide_count), capacity, _lib.stream_ptr()), "ay_seam_append")
+        t0 += B
     M, flags = (int(v) for v in slide_count.cpu())
     if flags & 1:
         raise _lib.AyError(f"detect_region: a tile holds more than max_det={max_det} detections; raise max_det or conf_thres")

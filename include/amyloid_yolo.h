@@ -290,20 +290,23 @@ int ay_ingest_tiles_u8(const void* img_hwc_u8, int batch, int h, int w, int out_
  * lays over the slide, cut out of a resident uint8 HWC region (rows `row_stride_bytes` apart; region_h x region_w source pixels),
  * edge tiles padded with the background 255; shrink 2 = the 40x -> 20x halving first (2x2 mean, round half up; the grid then lies
  * on the region_h/2 x region_w/2 image); then x/255 and the nearest resize to out_size as in ay_ingest_tiles_u8.
- * out [tiles_y*tiles_x][3][out_size][out_size] fp32. */
+ * out [tiles_y*tiles_x][3][out_size][out_size] fp32.  The three entry points below are ONE cut (one kernel, one pixel rule, the tile
+ * origins computed or read from a list); this one is ay_ingest_region_tiles_step_u8 at step == tile: the same launch, the same stores. */
 int ay_ingest_region_tiles_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                               int tile, int tiles_y, int tiles_x, int out_size, float* out_nchw, ay_stream_t stream);
 
 /* The same with tile origins `step` apart: tile (ty, tx) starts at (ty * step, tx * step) on the (halved) image, 0 < step <= tile.
  * step < tile gives tiles that overlap by tile - step pixels (wsi.tile_grid, wsi.detect_region(overlap > 0)); step == tile is
- * ay_ingest_region_tiles_u8 bit for bit.  Stores 16 bytes per lane when out_size is a multiple of 4 and `out_nchw` is 16-byte aligned. */
+ * ay_ingest_region_tiles_u8.  Stores 16 bytes per lane when out_size is a multiple of 4 and `out_nchw` is 16-byte aligned, 4 bytes
+ * with the same bits otherwise. */
 int ay_ingest_region_tiles_step_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                                    int tile, int step, int tiles_y, int tiles_x, int out_size, float* out_nchw, ay_stream_t stream);
 
 /* The same cut for a LIST of n tile origins: origins_xy [n][2] int32 ON THE DEVICE = (x, y) of a tile's corner in pixels of the
  * (halved) region, any position (on a grid or not, repeated or not; what lies outside the region, also left of or above it, is the
- * background 255) -> out[0..n) densely, in list order; rows of `out` behind n are not touched.  Same arithmetic and the same 16-byte
- * stores per lane as the step form: the origins of a full grid in grid order give ay_ingest_region_tiles_step_u8 bit for bit.
+ * background 255, for every int32 origin: origin + offset is formed without signed overflow and nothing outside the region is read)
+ * -> out[0..n) densely, in list order; rows of `out` behind n are not touched.  The same kernel and the same stores as the step form,
+ * only the origins are read: those of a full grid in grid order give ay_ingest_region_tiles_step_u8 bit for bit.
  * wsi.RegionTileStream(tile_mask=...) cuts only the wanted tiles of a strip with it. */
 int ay_ingest_region_tiles_list_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                                    int tile, const int32_t* origins_xy, int n, int out_size, float* out_nchw, ay_stream_t stream);
@@ -625,7 +628,8 @@ int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile, int n_rows
  *
  * ay_ingest_region_tiles_views_u8: the list cut in n_views views; `views` is a HOST array of 1 .. 8 distinct ids (else AY_ERR_ARG),
  *   origins_xy [n][2] on the device with the list form's semantics, out [n][n_views][3][S][S] fp32, TILE-major.  views = {0} gives
- *   ay_ingest_region_tiles_list_u8 bit for bit.  A workgroup computes a 32 x 32 block of I0 once, holds it in LDS (rows padded to 33
+ *   ay_ingest_region_tiles_list_u8 bit for bit (the pixel rule is the one function both kernels call).  A workgroup computes a 32 x 32
+ *   block of I0 once, holds it in LDS (rows padded to 33
  *   floats) and stores it into every view from there, row-contiguously also for the transposed views: the slide bytes are fetched
  *   once for all views.  16-byte stores per lane when out_size is a multiple of 4 and `out_nchw` is 16-byte aligned, the scalar form
  *   with the same bits otherwise.

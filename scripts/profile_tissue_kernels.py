@@ -1,6 +1,7 @@
 """Kernel timings of the tissue path on one strip of the scripts/bench_wsi.py slide (1536 rows x 32 tiles of 1536 px, 226 MB, resident
-on the device): ay_tile_tissue_u8 (16-byte loads, byte loads, shrink 2, abutting and overlapping grid), ay_ingest_region_tiles_step_u8
-and ay_ingest_region_tiles_list_u8 on the full grid; 3 repeats x (1 warm call + 10 calls between two events) each.
+on the device): ay_tile_tissue_u8 (16-byte loads, byte loads, shrink 2, abutting and overlapping grid), ay_ingest_region_tiles_step_u8,
+ay_ingest_region_tiles_u8 (the step entry at step == tile) and ay_ingest_region_tiles_list_u8 on the full grid (one kernel,
+region_tiles_cut_u8_kernel<V, Origins>, in a trace); 3 repeats x (1 warm call + 10 calls between two events) each.
 usage: python scripts/profile_tissue_kernels.py
        rocprofv3 --kernel-trace --stats -d DIR -o tk --output-format csv -- python scripts/profile_tissue_kernels.py
        python scripts/profile_tissue_kernels.py --trace DIR     (per kernel, the dispatch durations of DIR's kernel trace; no GPU)"""
@@ -41,6 +42,7 @@ runs = {
  "tissue bytewise base+1": lambda: check(L.ay_tile_tissue_u8(ptr(off[1:]), tile, W, W * 3, 1, tile, tile, 1, TX, 170, ptr(counts), sp())),
  "tissue wide shrink=2 (16 tiles of 1536 on 768 rows)": lambda: check(L.ay_tile_tissue_u8(ptr(strip), tile, W, W * 3, 2, tile, tile, 1, 16, 170, ptr(counts), sp())),
  "step ingest step=tile": lambda: check(L.ay_ingest_region_tiles_step_u8(ptr(strip), tile, W, W * 3, 1, tile, tile, 1, TX, S, ptr(out), sp())),
+ "grid ingest (the entry without a step)": lambda: check(L.ay_ingest_region_tiles_u8(ptr(strip), tile, W, W * 3, 1, tile, 1, TX, S, ptr(out), sp())),
  "list ingest full grid": lambda: check(L.ay_ingest_region_tiles_list_u8(ptr(strip), tile, W, W * 3, 1, tile, ptr(origins), TX, S, ptr(out2), sp())),
 }
 for rep in range(3):

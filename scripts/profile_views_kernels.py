@@ -1,6 +1,7 @@
 """Kernel timings of the dihedral-views path.  (1) On one strip of the scripts/bench_wsi.py slide (1536 rows x 32 tiles of 1536 px,
 226 MB, resident on the device): ay_ingest_region_tiles_list_u8 on 8 tiles against ay_ingest_region_tiles_views_u8 on the same tiles
-at V = 1, 4, 8, and the transposed views alone.  (2) At B = 8 tiles x 8 views of 1024^2 (64 512 rows per view, 3 classes, about 230
+at V = 1, 4, 8, and the transposed views alone (region_tiles_cut_u8_kernel<V, ay::ListOrigins> and region_tiles_views_u8_kernel<V> in a
+trace).  (2) At B = 8 tiles x 8 views of 1024^2 (64 512 rows per view, 3 classes, about 230
 candidates per view): ay_unview_rows, the merge-NMS of the concatenated rows, ay_view_votes and ay_view_select.  3 repeats x (1 warm
 call + 10 calls between two events) each.
 usage: python scripts/profile_views_kernels.py

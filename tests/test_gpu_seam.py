@@ -86,6 +86,32 @@ def test_strided_ingest(dev, case):
     assert torch.equal(torch.cat(got), want)
 
 
+@pytest.mark.parametrize("case", INGEST_CASES, ids=str)
+def test_stores_of_the_three_entries(dev, case):
+    """The grid (step == tile), step and list entries share one cut: each writes the tiles exactly, into an output that starts on a
+    16-byte boundary (16-byte stores where out_size % 4 == 0) and into one that starts one float behind it (scalar stores), and
+    touches none of the 16 guard floats before and behind it."""
+    H, W, tile, S, shrink, overlap = case
+    r = np.random.default_rng(H * 1000 + W + overlap).integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+    want, (ty, tx, step) = cpu_tiles(r, tile, S, shrink, overlap)
+    L, sp = _lib.lib(), _lib.stream_ptr()
+    rd = torch.from_numpy(r).to(dev)
+    org = torch.tensor([(i * step, j * step) for j in range(ty) for i in range(tx)], dtype=torch.int32, device=dev)
+    entries = {"step": lambda o: L.ay_ingest_region_tiles_step_u8(ptr(rd), H, W, W * 3, shrink, tile, step, ty, tx, S, o, sp),
+               "list": lambda o: L.ay_ingest_region_tiles_list_u8(ptr(rd), H, W, W * 3, shrink, tile, ptr(org), ty * tx, S, o, sp)}
+    if overlap == 0:
+        entries["grid"] = lambda o: L.ay_ingest_region_tiles_u8(ptr(rd), H, W, W * 3, shrink, tile, ty, tx, S, o, sp)
+    n, G = want.numel(), 16
+    for name, call in entries.items():
+        for shift in (0, 1):
+            buf = torch.full((G + shift + n + G,), -7.0, device=dev)
+            assert buf.data_ptr() % 16 == 0
+            check(call(ptr(buf[G + shift:])), name)
+            got = buf.cpu()
+            assert torch.equal(got[G + shift:G + shift + n].view_as(want), want), (name, shift)
+            assert (got[:G + shift] == -7.0).all() and (got[G + shift + n:] == -7.0).all(), (name, shift)
+
+
 # ---- 2. ay_seam_merge ------------------------------------------------------------------------------------------------------
 def device_merge(dev, rows, tile_id, thres=0.5):
     rows = torch.from_numpy(np.ascontiguousarray(np.asarray(rows, np.float32).reshape(-1, 7))).to(dev)

@@ -4,6 +4,7 @@ detect_region with a tile_mask.  Every comparison is exact: integer counts, or t
 Yardsticks: tests/tissue_reference.py (the rule restated in NumPy) for the counts; the step ingest and tiles cut on the CPU +
 oracle/ingest_oracle.ingest for the list ingest and the masked stream; the unmasked detect_region for the masked one; model +
 non_max_suppression on CPU-cut tiles filtered by tests/seam_reference.py for the masked overlap path."""
+import ctypes as C
 import math
 
 import numpy as np
@@ -12,6 +13,7 @@ import torch
 
 import seam_reference as sr
 import tissue_reference as tr
+import views_reference as vr
 from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd._lib import check, ptr
 from amyloid_yolo_paper_amd.wsi import RegionTileStream, detect_region, tile_grid, tissue_counts
@@ -135,6 +137,37 @@ def test_list_ingest(dev, case):
     got = torch.full((len(origins) + 3, 3, S_, S_), -7.0, device=dev)
     list_ingest(dev, rd, H, W, shrink, tile, origins, S_, got)
     assert torch.equal(got[: len(origins)].cpu(), torch.stack(crops)) and (got[len(origins):] == -7.0).all()
+
+
+@pytest.mark.parametrize("shrink", [1, 2])
+def test_list_and_views_ingest_at_extreme_origins(dev, shrink):
+    """Origins at both ends of int32 through the list entry and the views entry: origin + offset is formed without signed overflow
+    and the bounds test gates every read, so such a tile is all background, and a tile at (1, 2) in the same call is its CPU crop."""
+    H, W, tile, S_ = 70, 100, 32, 32
+    r = np.random.default_rng(7 + shrink).integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+    rd = torch.from_numpy(r).to(dev)
+    rr = halve(r) if shrink == 2 else r
+    far = [(2**31 - 1, 0), (0, 2**31 - 1), (-2**31, 0), (0, -2**31), (2**31 - 32, 3)]
+    origins = far + [(1, 2)]
+    t = np.full((tile, tile, 3), 255, np.uint8)
+    c = rr[2:2 + tile, 1:1 + tile]
+    t[:c.shape[0], :c.shape[1]] = c
+    crop = ingest(t, S_)
+    assert not (crop == 1.0).all()
+    got = torch.full((len(origins) + 1, 3, S_, S_), -7.0, device=dev)
+    list_ingest(dev, rd, H, W, shrink, tile, origins, S_, got)
+    got = got.cpu()
+    assert (got[:len(far)] == 1.0).all() and torch.equal(got[len(far)], crop) and (got[len(far) + 1:] == -7.0).all()
+    views = (0, 5)
+    o = torch.tensor(origins, dtype=torch.int32, device=dev)
+    ids = (C.c_int * len(views))(*views)
+    got = torch.full(((len(origins) + 1) * len(views), 3, S_, S_), -7.0, device=dev)
+    check(_lib.lib().ay_ingest_region_tiles_views_u8(ptr(rd), H, W, W * 3, shrink, tile, ptr(o), len(origins), ids, len(views), S_, ptr(got),
+                                                     _lib.stream_ptr()), "ay_ingest_region_tiles_views_u8")
+    got = got.cpu()
+    assert (got[:len(far) * 2] == 1.0).all() and (got[len(origins) * 2:] == -7.0).all()
+    for i, v in enumerate(views):      # tile-major: the views of the last tile lie one after another
+        assert torch.equal(got[len(far) * 2 + i], torch.from_numpy(vr.view_image_fast(crop.numpy(), v))), v
 
 
 # ---- 3. wsi.tissue_counts through the strip stream ---------------------------------------------------------------------------------

@@ -156,7 +156,8 @@ def test_header_declares_the_entry_points_and_the_rule():
 
 
 def test_new_kernels_use_no_scratch(tmp_path):
-    """hipcc's resource remarks for the two sources: every instantiation of the two new kernels has ScratchSize 0"""
+    """hipcc's resource remarks for the two sources: every instantiation of the tissue kernel and of the one cut kernel (both store widths,
+    grid and list origins) has ScratchSize 0"""
     hipcc = build._hipcc()
     found = {}
     for src in ("ay_tissue.hip", "ay_ingest.hip"):
@@ -170,7 +171,7 @@ def test_new_kernels_use_no_scratch(tmp_path):
             if m:
                 name = m.group(1)
             m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-            if m and name and ("tile_tissue_u8_kernel" in name or "region_tiles_list_u8_kernel" in name):
+            if m and name and ("tile_tissue_u8_kernel" in name or "region_tiles_cut_u8_kernel" in name):
                 found[name] = int(m.group(1))
-    assert sum("tile_tissue_u8_kernel" in n for n in found) == 4 and sum("region_tiles_list_u8_kernel" in n for n in found) == 2
+    assert sum("tile_tissue_u8_kernel" in n for n in found) == 4 and sum("region_tiles_cut_u8_kernel" in n for n in found) == 4
     assert all(v == 0 for v in found.values()), found
