@@ -117,6 +117,7 @@ _SIGS = {
     "ay_slice_accumulate_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ay_zero_insert_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ay_pack_dgrad_weights_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ay_packed_dgrad_weight_bytes": (_SZ, [_I, _I, _I]),
     "ay_pack_batch_block": (_I, []),
     "ay_pack_batch_bf16": (_I, [_P, _P, _I, _P]),
     "ay_stem_train_fwd_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),

@@ -1,7 +1,7 @@
 // Weight packing, BN folding, the fp32 stem convolution, route/upsample gather and layout converters.
 #include <stdarg.h>
 
-#include "ay_common.h"
+#include "ay_pack.h"
 
 namespace ay {
 
@@ -13,27 +13,18 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// OIHW f32 -> [cin/16][tap][half][cout_pad][8] bf16
+// the one kernel behind the single-call filter packers: element i of the image <- its source value (ay_pack.h)
 template <typename DT>
-__global__ void pack_weights_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cout, int cout_pad,
-                                    int cin, int ks) {
+__global__ void pack_filter_kernel(const PackJob jb) {
     DT::enter();
-    const int kk2 = ks * ks;
-    const size_t total = (size_t)(cin / 16) * kk2 * 2 * cout_pad * 8;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(i % 8);
-        size_t t = i / 8;
-        const int co = (int)(t % cout_pad);
-        t /= cout_pad;
-        const int half = (int)(t % 2);
-        t /= 2;
-        const int tap = (int)(t % kk2);
-        const int chunk = (int)(t / kk2);
-        const int ci = chunk * 16 + half * 8 + j;
-        float v = 0.f;
-        if (co < cout) v = w[((size_t)co * cin + ci) * kk2 + tap];
-        out[i] = DT::from_f32(v);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < jb.total; i += (size_t)gridDim.x * blockDim.x)
+        jb.dst[i] = DT::from_f32(packed_filter_value(jb, i));
+}
+void launch_pack_filter(const PackJob& jb, int act_dtype, unsigned grid, hipStream_t stream) {
+    if (act_dtype == AY_DT_F16)
+        hipLaunchKernelGGL(pack_filter_kernel<F16>, dim3(grid), dim3(256), 0, stream, jb);
+    else
+        hipLaunchKernelGGL(pack_filter_kernel<Bf16>, dim3(grid), dim3(256), 0, stream, jb);
 }
 
 __global__ void fold_bn_kernel(const float* gamma, const float* beta, const float* mean, const float* var,
@@ -184,13 +175,18 @@ extern "C" const char* ay_last_error(void) { return ay::g_err; }
 extern "C" size_t ay_packed_weight_bytes(int cout_pad, int cin, int ksize) {
     return (size_t)(cin / 16) * ksize * ksize * 2 * cout_pad * 8 * 2;
 }
+extern "C" size_t ay_packed_dgrad_weight_bytes(int cout, int cin_pad, int ksize) {
+    return (size_t)((cout + 15) / 16) * ksize * ksize * 2 * cin_pad * 8 * 2;
+}
+extern "C" size_t ay_packed_dgrad_s2_weight_bytes(int cout_pad, int cin_pad) {
+    return (size_t)4 * (cout_pad / 16) * 4 * 2 * cin_pad * 8 * 2;
+}
 
 template <typename DT>
 static int pack_conv_weights(const float* w_oihw, void* packed, int cout, int cout_pad, int cin, int ksize, ay_stream_t stream) {
     AY_CHECK_ARG(w_oihw && packed && cin % 16 == 0 && cout_pad >= cout && cout_pad % 16 == 0, "ay_pack_conv_weights: bad args");
     const size_t total = ay_packed_weight_bytes(cout_pad, cin, ksize) / 2;
-    hipLaunchKernelGGL(pack_weights_kernel<DT>, dim3(grid_for(total, 256)), dim3(256), 0, S(stream), w_oihw, (uint16_t*)packed, cout,
-                       cout_pad, cin, ksize);
+    launch_pack_filter(PackJob{w_oihw, (uint16_t*)packed, 0, cout, cout_pad, cin, 0, ksize, total}, DT::id, grid_for(total, 256), S(stream));
     AY_CHECK_LAUNCH("pack_weights_kernel");
     return AY_OK;
 }

@@ -3,7 +3,7 @@
 // convolution (models.py:43-45), its backward, gradient plumbing for shortcut / route / upsample (models.py:86-96,244-248),
 // filter re-packing that turns the forward convolution kernel into the data-gradient kernel, and zero insertion for the
 // stride-2 data gradient.  All of these are bandwidth-bound elementwise / reduction passes over [B][C/16][H][W][16] bf16.
-#include "ay_common.h"
+#include "ay_pack.h"
 
 namespace ay {
 
@@ -26,6 +26,48 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
 constexpr int BN_UNROLL = 4;   // independent 16-byte loads in flight per thread and operand
 constexpr int BN_ROUNDS = 8;   // rounds of BN_UNROLL units per thread and workgroup (see bn_chunks)
 
+// parameters of a thread's 8 channels c0 .. c0 + 7; a channel beyond C (ragged last plane) reads channel C - 1: its results are masked
+// or never stored
+template <typename T>
+__device__ __forceinline__ void bn_load8(const T* __restrict__ p, int c0, int C, float (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)p[c0 + j < C ? c0 + j : C - 1];
+}
+
+// The stream of one workgroup over its (image, plane) slice: BN_UNROLL guarded 16-byte loads per operand issued before any use (zero
+// fill out of range), then body(fa, fb) on the 8 floats of each unit; STORE: what body left in fa goes to out where the unit exists.
+// B_OPTIONAL: operand b may be NULL (then fb = 0)
+template <bool B_OPTIONAL, bool STORE, typename Body>
+__device__ __forceinline__ void bn_for_each_unit(const uint4* __restrict__ a, const uint4* __restrict__ b, uint4* __restrict__ out, int CP,
+                                                 int HW, int chunks, Body body) {
+    const int units = HW * 2;
+    const int img = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    const int stride = chunks * 256;
+    const size_t base = ((size_t)img * CP + blockIdx.y) * units;
+    for (int u0 = chunk * 256 + threadIdx.x; u0 < units; u0 += stride * BN_UNROLL) {
+        uint4 va[BN_UNROLL], vb[BN_UNROLL];
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            const int u = u0 + k * stride;
+            va[k] = make_uint4(0, 0, 0, 0);
+            vb[k] = make_uint4(0, 0, 0, 0);
+            if (u < units) {
+                va[k] = a[base + u];
+                if (!B_OPTIONAL || b) vb[k] = b[base + u];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            const int u = u0 + k * stride;
+            float fa[8], fb[8];
+            unpack8(va[k], fa);
+            unpack8(vb[k], fb);
+            body(fa, fb);
+            if (STORE && u < units) out[base + u] = pack8(fa);
+        }
+    }
+}
+
 // ---- per-channel sums over (B,H,W) of a blocked bf16 tensor: sums[c] += sum z, sums[C + c] += sum z^2 (fp64 atomics, one per
 // channel and workgroup after a reduction through LDS); BWD: a = dy, zt = z: sums = (sum dpre, sum dpre * xhat)
 template <bool BWD>
@@ -35,61 +77,29 @@ __global__ void __launch_bounds__(256) bn_sums_kernel(const uint4* __restrict__ 
                                                       double* __restrict__ sums, int C, int HW, int chunks) {
     __shared__ float red[4][2][16];
     const int plane = blockIdx.y;
-    const int CP = gridDim.y;
-    const int half = threadIdx.x & 1;
-    const int c0 = plane * 16 + half * 8;
-    float s1[8], s2[8], mu[8], is[8], ga[8], be[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        s1[j] = s2[j] = 0.f;
-        if (BWD) {
-            const int c = c0 + j < C ? c0 + j : C - 1;
-            mu[j] = mean[c];
-            is[j] = invstd[c];
-            ga[j] = gamma[c];
-            be[j] = beta[c];
-        }
+    const int c0 = plane * 16 + (threadIdx.x & 1) * 8;
+    float s1[8] = {}, s2[8] = {}, mu[8], is[8], ga[8], be[8];
+    if (BWD) {
+        bn_load8(mean, c0, C, mu);
+        bn_load8(invstd, c0, C, is);
+        bn_load8(gamma, c0, C, ga);
+        bn_load8(beta, c0, C, be);
     }
-    const int units = HW * 2;
-    const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
-    const int stride = chunks * 256;
-    const size_t base = ((size_t)b * CP + plane) * units;
-    for (int u0 = chunk * 256 + threadIdx.x; u0 < units; u0 += stride * BN_UNROLL) {
-        uint4 va[BN_UNROLL], vz[BN_UNROLL];
+    bn_for_each_unit<!BWD, false>(a, BWD ? zt : nullptr, nullptr, gridDim.y, HW, chunks, [&](float (&f)[8], float (&z)[8]) {
 #pragma unroll
-        for (int k = 0; k < BN_UNROLL; ++k) {
-            const int u = u0 + k * stride;
-            va[k] = make_uint4(0, 0, 0, 0);
-            vz[k] = make_uint4(0, 0, 0, 0);
-            if (u < units) {
-                va[k] = a[base + u];
-                if (BWD) vz[k] = zt[base + u];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < BN_UNROLL; ++k) {
-            float f[8];
-            unpack8(va[k], f);
-            if (!BWD) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    s1[j] += f[j];
-                    s2[j] += f[j] * f[j];
-                }
+        for (int j = 0; j < 8; ++j) {
+            if constexpr (!BWD) {
+                s1[j] += f[j];
+                s2[j] += f[j] * f[j];
             } else {  // a zero dy (the fill of an out-of-range unit) adds nothing to either sum
-                float z[8];
-                unpack8(vz[k], z);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float xh = (z[j] - mu[j]) * is[j];
-                    const float pre = xh * ga[j] + be[j];
-                    const float d = (leaky && !(pre > 0.f)) ? 0.1f * f[j] : f[j];
-                    s1[j] += d;
-                    s2[j] += d * xh;
-                }
+                const float xh = (z[j] - mu[j]) * is[j];
+                const float pre = xh * ga[j] + be[j];
+                const float d = (leaky && !(pre > 0.f)) ? 0.1f * f[j] : f[j];
+                s1[j] += d;
+                s2[j] += d * xh;
             }
         }
-    }
+    });
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
 #pragma unroll
@@ -125,9 +135,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const uint4* __restrict__
                                                        float* __restrict__ save_mean, float* __restrict__ save_invstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta, int leaky,
                                                        const uint4* __restrict__ skip, uint4* __restrict__ y, int C, int CP, int HW, int chunks) {
-    const int plane = blockIdx.y;
-    const int half = threadIdx.x & 1;
-    const int c0 = plane * 16 + half * 8;
+    const int c0 = blockIdx.y * 16 + (threadIdx.x & 1) * 8;
     float mu[8], is[8], ga[8], be[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -147,38 +155,15 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const uint4* __restrict__
             running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unbiased;
         }
     }
-    const int units = HW * 2;
-    const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
-    const int stride = chunks * 256;
-    const size_t base = ((size_t)b * CP + plane) * units;
-    for (int u0 = chunk * 256 + threadIdx.x; u0 < units; u0 += stride * BN_UNROLL) {
-        uint4 vz[BN_UNROLL], vs[BN_UNROLL];
+    bn_for_each_unit<true, true>(z, skip, y, CP, HW, chunks, [&](float (&f)[8], float (&sk)[8]) {
 #pragma unroll
-        for (int k = 0; k < BN_UNROLL; ++k) {
-            const int u = u0 + k * stride;
-            vz[k] = make_uint4(0, 0, 0, 0);
-            vs[k] = make_uint4(0, 0, 0, 0);
-            if (u < units) {
-                vz[k] = z[base + u];
-                if (skip) vs[k] = skip[base + u];
-            }
+        for (int j = 0; j < 8; ++j) {
+            float v = (f[j] - mu[j]) * is[j] * ga[j] + be[j];
+            if (leaky) v = v > 0.f ? v : 0.1f * v;
+            if (skip) v += sk[j];
+            f[j] = c0 + j < C ? v : 0.f;
         }
-#pragma unroll
-        for (int k = 0; k < BN_UNROLL; ++k) {
-            const int u = u0 + k * stride;
-            float f[8], sk[8];
-            unpack8(vz[k], f);
-            unpack8(vs[k], sk);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float v = (f[j] - mu[j]) * is[j] * ga[j] + be[j];
-                if (leaky) v = v > 0.f ? v : 0.1f * v;
-                if (skip) v += sk[j];
-                f[j] = c0 + j < C ? v : 0.f;
-            }
-            if (u < units) y[base + u] = pack8(f);
-        }
-    }
+    });
 }
 
 // dz = gamma*invstd/n * (n*dpre - dbeta - xhat*dgamma), dpre = dy * leaky'(pre)
@@ -188,59 +173,34 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const uint4* __restri
                                                            const double* __restrict__ sums, float n, uint4* __restrict__ dz, int C, int CP,
                                                            int HW, int chunks, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            int accumulate) {
-    const int plane = blockIdx.y;
-    const int half = threadIdx.x & 1;
-    const int c0 = plane * 16 + half * 8;
+    const int c0 = blockIdx.y * 16 + (threadIdx.x & 1) * 8;
     float mu[8], is[8], ga[8], be[8], sb[8], sg[8];
+    bn_load8(mean, c0, C, mu);
+    bn_load8(invstd, c0, C, is);
+    bn_load8(gamma, c0, C, ga);
+    bn_load8(beta, c0, C, be);
+    bn_load8(sums, c0, C, sb);
+    bn_load8(sums + C, c0, C, sg);
+    // the parameter gradients (accumulate != 0: ADDED, gradient accumulation over batches, train.py:116-119): workgroup 0 of the plane
+    if (blockIdx.x == 0 && threadIdx.x < 2) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int c = c0 + j < C ? c0 + j : C - 1;
-        mu[j] = mean[c];
-        is[j] = invstd[c];
-        ga[j] = gamma[c];
-        be[j] = beta[c];
-        sb[j] = (float)sums[c];
-        sg[j] = (float)sums[C + c];
-        // the parameter gradients (accumulate != 0: ADDED, gradient accumulation over batches, train.py:116-119): workgroup 0 of the plane
-        if (blockIdx.x == 0 && threadIdx.x < 2 && c0 + j < C) {
-            dbeta[c] = (accumulate ? dbeta[c] : 0.f) + sb[j];
-            dgamma[c] = (accumulate ? dgamma[c] : 0.f) + sg[j];
-        }
-    }
-    const int units = HW * 2;
-    const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
-    const int stride = chunks * 256;
-    const size_t base = ((size_t)b * CP + plane) * units;
-    for (int u0 = chunk * 256 + threadIdx.x; u0 < units; u0 += stride * BN_UNROLL) {
-        uint4 vd[BN_UNROLL], vz[BN_UNROLL];
-#pragma unroll
-        for (int k = 0; k < BN_UNROLL; ++k) {
-            const int u = u0 + k * stride;
-            vd[k] = make_uint4(0, 0, 0, 0);
-            vz[k] = make_uint4(0, 0, 0, 0);
-            if (u < units) {
-                vd[k] = dy[base + u];
-                vz[k] = z[base + u];
+        for (int j = 0; j < 8; ++j)
+            if (c0 + j < C) {
+                dbeta[c0 + j] = (accumulate ? dbeta[c0 + j] : 0.f) + sb[j];
+                dgamma[c0 + j] = (accumulate ? dgamma[c0 + j] : 0.f) + sg[j];
             }
-        }
-#pragma unroll
-        for (int k = 0; k < BN_UNROLL; ++k) {
-            const int u = u0 + k * stride;
-            float d[8], zz[8];
-            unpack8(vd[k], d);
-            unpack8(vz[k], zz);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float xh = (zz[j] - mu[j]) * is[j];
-                const float pre = xh * ga[j] + be[j];
-                const float dp = (leaky && !(pre > 0.f)) ? 0.1f * d[j] : d[j];
-                const float k2 = ga[j] * is[j] / n;
-                const float v = k2 * (n * dp - sb[j] - xh * sg[j]);
-                d[j] = c0 + j < C ? v : 0.f;
-            }
-            if (u < units) dz[base + u] = pack8(d);
-        }
     }
+    bn_for_each_unit<false, true>(dy, z, dz, CP, HW, chunks, [&](float (&d)[8], float (&zz)[8]) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float xh = (zz[j] - mu[j]) * is[j];
+            const float pre = xh * ga[j] + be[j];
+            const float dp = (leaky && !(pre > 0.f)) ? 0.1f * d[j] : d[j];
+            const float k2 = ga[j] * is[j] / n;
+            const float v = k2 * (n * dp - sb[j] - xh * sg[j]);
+            d[j] = c0 + j < C ? v : 0.f;
+        }
+    });
 }
 
 // dst += src (bf16, fp32 add, one rounding)
@@ -303,119 +263,14 @@ __global__ void zero_insert_kernel(const uint4* __restrict__ in, uint4* __restri
     }
 }
 
-// filters for the data gradient: the forward kernel computes dx = conv(dz, W') with W'[ci][co][kh][kw] = W[co][ci][k-1-kh][k-1-kw];
-// packed as [Cout/16 (K chunks)][tap][half][CinPad][8] bf16
-__global__ void pack_dgrad_weights_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cout, int cout_pad16, int cin,
-                                          int cin_pad, int ks) {
-    const int kk2 = ks * ks;
-    const size_t total = (size_t)(cout_pad16 / 16) * kk2 * 2 * cin_pad * 8;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(i % 8);
-        size_t t = i / 8;
-        const int ci = (int)(t % cin_pad);
-        t /= cin_pad;
-        const int half = (int)(t % 2);
-        t /= 2;
-        const int tap = (int)(t % kk2);
-        const int chunk = (int)(t / kk2);
-        const int co = chunk * 16 + half * 8 + j;
-        const int kh = tap / ks, kw = tap % ks;
-        float v = 0.f;
-        if (co < cout && ci < cin) v = w[(((size_t)co * cin + ci) * ks + (ks - 1 - kh)) * ks + (ks - 1 - kw)];
-        out[i] = f2bf(v);
-    }
-}
-
-// filter images of the four parity classes of a stride-2 data gradient: [class py*2+px][cout_pad/16][window tap oy*2+ox][half][cin_pad][8];
-// window row oy of class py holds filter row kh: py = 0: oy 0 -> kh 1, oy 1 -> none; py = 1: oy 0 -> kh 2, oy 1 -> kh 0 (columns alike)
-__global__ void pack_dgrad_s2_weights_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cout, int cout_pad, int cin,
-                                             int cin_pad) {
-    const size_t per_class = (size_t)(cout_pad / 16) * 4 * 2 * cin_pad * 8;
-    const size_t total = 4 * per_class;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int cls = (int)(i / per_class);
-        size_t t = i % per_class;
-        const int j = (int)(t % 8);
-        t /= 8;
-        const int ci = (int)(t % cin_pad);
-        t /= cin_pad;
-        const int half = (int)(t % 2);
-        t /= 2;
-        const int tap = (int)(t % 4);
-        const int chunk = (int)(t / 4);
-        const int co = chunk * 16 + half * 8 + j;
-        const int py = cls >> 1, px = cls & 1, oy = tap >> 1, ox = tap & 1;
-        const int kh = py ? (oy ? 0 : 2) : (oy ? -1 : 1);
-        const int kw = px ? (ox ? 0 : 2) : (ox ? -1 : 1);
-        float v = 0.f;
-        if (co < cout && ci < cin && kh >= 0 && kw >= 0) v = w[(((size_t)co * cin + ci) * 3 + kh) * 3 + kw];
-        out[i] = f2bf(v);
-    }
-}
-
 // ---- all filter images of a training step in ONE launch.  A step re-packs ~75 forward and ~70 data-gradient images (the weights
 // changed); as separate launches that is ~145 kernels of a few microseconds each -- 0.84 ms of a 23-ms step at 416^2 for 0.5 GB of
 // traffic.  ay_pack_batch_bf16 walks a job table (device memory, built once per weight layout by the caller): workgroup w takes
 // PACK_BLOCK consecutive elements of job work[w].job starting at work[w].first.
 constexpr int PACK_BLOCK = 2048;
-struct PackJob {             // mirrors ay_pack_job (include/amyloid_yolo.h)
-    const float* src;        // OIHW fp32 filters
-    uint16_t* dst;           // packed bf16 image
-    int32_t kind;            // 0: forward image (ay_pack_conv_weights_bf16), 1: data gradient (ay_pack_dgrad_weights_bf16), 2: stride-2 parity classes
-    int32_t cout, cout_pad, cin, cin_pad, ksize;
-    uint64_t total;          // elements of dst
-};
 struct PackWork {
     uint32_t job, first_block;
 };
-
-__device__ __forceinline__ uint16_t pack_elem(const PackJob& jb, size_t i) {
-    const float* w = jb.src;
-    if (jb.kind == 0) {   // [cin/16][tap][half][cout_pad][8]; cin here = channels of the source tensor (multiple of 16)
-        const int kk2 = jb.ksize * jb.ksize;
-        const int j = (int)(i % 8);
-        size_t t = i / 8;
-        const int co = (int)(t % jb.cout_pad);
-        t /= jb.cout_pad;
-        const int half = (int)(t % 2);
-        t /= 2;
-        const int tap = (int)(t % kk2);
-        const int chunk = (int)(t / kk2);
-        const int ci = chunk * 16 + half * 8 + j;
-        return f2bf(co < jb.cout ? w[((size_t)co * jb.cin + ci) * kk2 + tap] : 0.f);
-    }
-    if (jb.kind == 1) {   // [cout_pad/16][tap][half][cin_pad][8], flipped taps, transposed channels
-        const int ks = jb.ksize, kk2 = ks * ks;
-        const int j = (int)(i % 8);
-        size_t t = i / 8;
-        const int ci = (int)(t % jb.cin_pad);
-        t /= jb.cin_pad;
-        const int half = (int)(t % 2);
-        t /= 2;
-        const int tap = (int)(t % kk2);
-        const int chunk = (int)(t / kk2);
-        const int co = chunk * 16 + half * 8 + j;
-        const int kh = tap / ks, kw = tap % ks;
-        return f2bf(co < jb.cout && ci < jb.cin ? w[(((size_t)co * jb.cin + ci) * ks + (ks - 1 - kh)) * ks + (ks - 1 - kw)] : 0.f);
-    }
-    // kind 2: [class][cout_pad/16][window tap][half][cin_pad][8]
-    const size_t per_class = (size_t)(jb.cout_pad / 16) * 4 * 2 * jb.cin_pad * 8;
-    const int cls = (int)(i / per_class);
-    size_t t = i % per_class;
-    const int j = (int)(t % 8);
-    t /= 8;
-    const int ci = (int)(t % jb.cin_pad);
-    t /= jb.cin_pad;
-    const int half = (int)(t % 2);
-    t /= 2;
-    const int tap = (int)(t % 4);
-    const int chunk = (int)(t / 4);
-    const int co = chunk * 16 + half * 8 + j;
-    const int py = cls >> 1, px = cls & 1, oy = tap >> 1, ox = tap & 1;
-    const int kh = py ? (oy ? 0 : 2) : (oy ? -1 : 1);
-    const int kw = px ? (ox ? 0 : 2) : (ox ? -1 : 1);
-    return f2bf(co < jb.cout && ci < jb.cin && kh >= 0 && kw >= 0 ? w[(((size_t)co * jb.cin + ci) * 3 + kh) * 3 + kw] : 0.f);
-}
 
 __global__ void __launch_bounds__(256) pack_batch_kernel(const PackJob* __restrict__ jobs, const PackWork* __restrict__ work) {
     const PackWork wk = work[blockIdx.x];
@@ -424,7 +279,7 @@ __global__ void __launch_bounds__(256) pack_batch_kernel(const PackJob* __restri
 #pragma unroll
     for (int r = 0; r < PACK_BLOCK / 256; ++r) {
         const size_t i = base + (size_t)r * 256 + threadIdx.x;
-        if (i < jb.total) jb.dst[i] = pack_elem(jb, i);
+        if (i < jb.total) jb.dst[i] = f2bf(packed_filter_value(jb, i));
     }
 }
 
@@ -577,25 +432,18 @@ extern "C" int ay_pack_batch_bf16(const void* jobs_device, const void* work_devi
     return AY_OK;
 }
 
-extern "C" size_t ay_packed_dgrad_s2_weight_bytes(int cout_pad, int cin_pad) {
-    return (size_t)4 * (cout_pad / 16) * 4 * 2 * cin_pad * 8 * 2;
-}
-
 extern "C" int ay_pack_dgrad_s2_weights_bf16(const float* w_oihw, void* packed, int cout, int cout_pad, int cin, int cin_pad, ay_stream_t stream) {
     AY_CHECK_ARG(w_oihw && packed && cin_pad >= cin && cin_pad % 32 == 0 && cout_pad >= cout && cout_pad % 16 == 0, "ay_pack_dgrad_s2_weights_bf16: bad args");
-    const size_t total = (size_t)4 * (cout_pad / 16) * 4 * 2 * cin_pad * 8;
-    hipLaunchKernelGGL(pack_dgrad_s2_weights_kernel, dim3(gridu(total)), dim3(256), 0, S(stream), w_oihw, (uint16_t*)packed, cout, cout_pad, cin,
-                       cin_pad);
+    const size_t total = ay_packed_dgrad_s2_weight_bytes(cout_pad, cin_pad) / 2;
+    launch_pack_filter(PackJob{w_oihw, (uint16_t*)packed, 2, cout, cout_pad, cin, cin_pad, 3, total}, AY_DT_BF16, gridu(total), S(stream));
     AY_CHECK_LAUNCH("pack_dgrad_s2_weights_kernel");
     return AY_OK;
 }
 
 extern "C" int ay_pack_dgrad_weights_bf16(const float* w_oihw, void* packed, int cout, int cin, int cin_pad, int ksize, ay_stream_t stream) {
     AY_CHECK_ARG(w_oihw && packed && cin_pad >= cin && cin_pad % 32 == 0, "ay_pack_dgrad_weights_bf16: bad args");
-    const int cout_pad16 = (cout + 15) / 16 * 16;
-    const size_t total = (size_t)(cout_pad16 / 16) * ksize * ksize * 2 * cin_pad * 8;
-    hipLaunchKernelGGL(pack_dgrad_weights_kernel, dim3(gridu(total)), dim3(256), 0, S(stream), w_oihw, (uint16_t*)packed, cout, cout_pad16, cin,
-                       cin_pad, ksize);
+    const size_t total = ay_packed_dgrad_weight_bytes(cout, cin_pad, ksize) / 2;
+    launch_pack_filter(PackJob{w_oihw, (uint16_t*)packed, 1, cout, (cout + 15) / 16 * 16, cin, cin_pad, ksize, total}, AY_DT_BF16, gridu(total), S(stream));
     AY_CHECK_LAUNCH("pack_dgrad_weights_kernel");
     return AY_OK;
 }

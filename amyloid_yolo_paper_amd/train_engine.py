@@ -39,6 +39,52 @@ def _ws(model, nbytes, dev):
     return ws
 
 
+def size_of(graph, S, i):
+    """side of layer i's output at input size S (i < 0: the input)"""
+    return S >> graph[i]["log2_down"] if i >= 0 else S
+
+
+def yolo_head_step(model, L, st, i, head, out, row, tg, B, S, G, alloc):
+    """YOLO layer i on its fp32 NCHW `head` tensor: decodes into rows [row, row + rows_added) of `out` and, with targets `tg`, runs the
+    loss forward + backward.  ``alloc(kind, shape)`` gives the fp32 tensors "dhead" and "sums".  Returns (rows_added, dhead | None,
+    sums | None)."""
+    y = model.module_list[i][0]
+    anchors = (C.c_float * (2 * y.num_anchors))(*[float(v) for a in y.anchors for v in a])
+    check(L.ay_yolo_decode(ptr(head), 0, ptr(out), B, y.num_anchors, y.num_classes, G, S, anchors, out.shape[1], row, st), "ay_yolo_decode")
+    y.grid_size, y.img_dim = G, S
+    dhead = sums = None
+    if tg is not None:
+        dhead = alloc("dhead", tuple(head.shape))
+        sums = alloc("sums", (16,))
+        nb = L.ay_yolo_loss_workspace_bytes(B, y.num_anchors, y.num_classes, G)
+        ws = _ws(model, nb, head.device)
+        loss_fn = L.ay_yolo_loss_giou_fwd_bwd if getattr(model, 'box_loss', 'mse') == 'giou' else L.ay_yolo_loss_fwd_bwd
+        check(loss_fn(ptr(head), ptr(tg), tg.shape[0], B, y.num_anchors, y.num_classes, G, S, anchors, C.c_float(y.ignore_thres),
+                      C.c_float(1.0), ptr(dhead), ptr(sums), ptr(ws), ws.numel(), st), "ay_yolo_loss_fwd_bwd")
+    return y.num_anchors * G * G, dhead, sums
+
+
+def loss_and_metrics(sums_all, n_classes, collect):
+    """sums_all: [(yolo module, its 16 device sums, grid size)] -> the loss (device scalar): six terms per layer, scalar glue on the
+    device.  collect: also fills every module's ``metrics``, through the step's only host synchronisation (the reference: 39,
+    models.py:205-220)."""
+    allsums = torch.stack([s for _, s, _ in sums_all])  # [heads, 16]
+    n_obj, n_noobj = allsums[:, 7], allsums[:, 8]
+    lx, ly, lw, lh = (allsums[:, k] / n_obj for k in range(4))
+    lconf = allsums[:, 4] / n_obj + 100.0 * allsums[:, 5] / n_noobj
+    lcls = allsums[:, 6] / (n_obj * n_classes)
+    per_layer = lx + ly + lw + lh + lconf + lcls
+    loss = per_layer.sum()
+    if collect:
+        h = torch.stack([per_layer, lx, ly, lw, lh, lconf, lcls, 100.0 * allsums[:, 9] / n_obj, allsums[:, 13] / (n_obj + 1e-16),
+                         allsums[:, 14] / (n_obj + 1e-16), allsums[:, 13] / (allsums[:, 12] + 1e-16), allsums[:, 10] / n_obj,
+                         allsums[:, 11] / n_noobj], 1).cpu().numpy()
+        for li, (y, _, G) in enumerate(sums_all):
+            y.metrics = {k: float(h[li, j]) for j, k in enumerate(METRIC_KEYS[:-1])}
+            y.metrics["grid_size"] = G
+    return loss
+
+
 def train_forward(model, x, targets):
     """Runs the plan in fp32 NCHW.  Returns (loss tensor [device scalar] | None, outputs [B,N,5+C] device, state)."""
     L = _lib.lib()
@@ -56,14 +102,11 @@ def train_forward(model, x, targets):
     out = torch.empty(B, N, 5 + Ccls, device=dev, dtype=torch.float32)
     tg = None if targets is None else targets.detach().to(device=dev, dtype=torch.float32).contiguous()
 
-    def size_of(i):
-        return S >> graph[i]["log2_down"] if i >= 0 else S
-
     def resolve(i):
         v = val[i]
         if isinstance(v, tuple):  # lazy nearest x2 upsample
             src = resolve(v[1])
-            c, h = graph[i]["channels"], size_of(i)
+            c, h = graph[i]["channels"], size_of(graph, S, i)
             o = torch.empty(B, c, h, h, device=dev, dtype=torch.float32)
             check(L.ay_copy_channels_f32(ptr(src), ptr(o), B, c, c, 0, h, h, 1, st), "ay_copy_channels_f32")
             val[i] = o
@@ -79,7 +122,7 @@ def train_forward(model, x, targets):
             m = model.module_list[i]
             conv = m[0]
             src = x if e["src"] < 0 else resolve(e["src"])
-            hin, hout = size_of(e["src"]), size_of(i)
+            hin, hout = size_of(graph, S, e["src"]), size_of(graph, S, i)
             cout = e["cout"]
             w = conv.weight.detach()
             d = ConvDesc(B, e["cin"], cout, hin, hin, hout, hout, e["k"], e["stride"], 0, 0, cout)
@@ -131,7 +174,7 @@ def train_forward(model, x, targets):
                 val[i] = val[srcs[0]]
                 stt.route[i] = [(srcs[0], graph[srcs[0]]["channels"], 0)]
             else:
-                h, ctot = size_of(i), e["channels"]
+                h, ctot = size_of(graph, S, i), e["channels"]
                 o = torch.empty(B, ctot, h, h, device=dev, dtype=torch.float32)
                 c0, parts = 0, []
                 for j in srcs:
@@ -145,39 +188,17 @@ def train_forward(model, x, targets):
                 val[i] = o
                 stt.route[i] = parts
         elif t == "yolo":
-            y = model.module_list[i][0]
             head = resolve(e["src"])
-            G = size_of(i)
-            anchors = (C.c_float * (2 * y.num_anchors))(*[float(v) for a in y.anchors for v in a])
-            check(L.ay_yolo_decode(ptr(head), 0, ptr(out), B, y.num_anchors, y.num_classes, G, S, anchors, N, row, st), "ay_yolo_decode")
-            y.grid_size, y.img_dim = G, S
-            row += y.num_anchors * G * G
+            G = size_of(graph, S, i)
+            rows, dhead, sums = yolo_head_step(model, L, st, i, head, out, row, tg, B, S, G,
+                                               lambda kind, shape: torch.empty(shape, device=dev, dtype=torch.float32))
+            row += rows
             if tg is not None:
-                dhead = torch.empty_like(head)
-                sums = torch.empty(16, device=dev, dtype=torch.float32)
-                nb = L.ay_yolo_loss_workspace_bytes(B, y.num_anchors, y.num_classes, G)
-                ws = _ws(model, nb, dev)
-                check((L.ay_yolo_loss_giou_fwd_bwd if getattr(model, 'box_loss', 'mse') == 'giou' else L.ay_yolo_loss_fwd_bwd)(ptr(head), ptr(tg), tg.shape[0], B, y.num_anchors, y.num_classes, G, S, anchors,
-                                             C.c_float(y.ignore_thres), C.c_float(1.0), ptr(dhead), ptr(sums), ptr(ws), ws.numel(), st),
-                      "ay_yolo_loss_fwd_bwd")
                 stt.dhead[i] = dhead
-                sums_all.append((y, sums, G))
+                sums_all.append((model.module_list[i][0], sums, G))
             val[i] = head
     if tg is not None:
-        # six terms per layer from the device sums (scalar glue on the device; the sums came from the HIP loss kernel)
-        allsums = torch.stack([s for _, s, _ in sums_all])  # [3,16]
-        n_obj, n_noobj = allsums[:, 7], allsums[:, 8]
-        lx, ly, lw, lh = (allsums[:, k] / n_obj for k in range(4))
-        lconf = allsums[:, 4] / n_obj + 100.0 * allsums[:, 5] / n_noobj
-        lcls = allsums[:, 6] / (n_obj * Ccls)
-        per_layer = lx + ly + lw + lh + lconf + lcls
-        loss = per_layer.sum()
-        h = torch.stack([per_layer, lx, ly, lw, lh, lconf, lcls, 100.0 * allsums[:, 9] / n_obj, allsums[:, 13] / (n_obj + 1e-16),
-                         allsums[:, 14] / (n_obj + 1e-16), allsums[:, 13] / (allsums[:, 12] + 1e-16), allsums[:, 10] / n_obj,
-                         allsums[:, 11] / n_noobj], 1).cpu().numpy()  # the one host sync of the step (reference: 39)
-        for li, (y, _, G) in enumerate(sums_all):
-            y.metrics = {k: float(h[li, j]) for j, k in enumerate(METRIC_KEYS[:-1])}
-            y.metrics["grid_size"] = G
+        loss = loss_and_metrics(sums_all, Ccls, True)
     return loss, out, stt
 
 

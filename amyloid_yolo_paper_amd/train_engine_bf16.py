@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, check, ptr
-from .train_engine import METRIC_KEYS, _ws
+from .train_engine import loss_and_metrics, size_of, yolo_head_step
 
 
 def _pad(v, m):
@@ -118,6 +118,13 @@ class _Ctx:
             self.buf[key] = t
         return t
 
+    def scratch(self, key, nbytes, floor=0):
+        """a byte buffer that only grows: at least nbytes, max(nbytes, floor) when it has to be (re)allocated"""
+        t = self.buf.get(key)
+        if t is None or t.numel() < nbytes:
+            t = self.buf[key] = torch.empty(max(nbytes, floor), device=self.dev, dtype=torch.uint8)
+        return t
+
     def bytes(self):
         return sum(t.numel() * t.element_size() for t in self.buf.values()) + self.pool.bytes
 
@@ -166,9 +173,9 @@ def _pack_weights(model, ctx):
                 dg = ctx.get(("pkd", i), (L.ay_packed_dgrad_s2_weight_bytes(cpad, cin_pad),), torch.uint8)
                 jobs.append((w.data_ptr(), dg.data_ptr(), 2, cout, cpad, cin, cin_pad, 3, dg.numel() // 2))
             else:
-                dg = ctx.get(("pkd", i), ((cpad // 16) * k * k * 2 * cin_pad * 8 * 2,), torch.uint8, zero=True)  # rows of the pad planes stay zero
-                cp16 = _pad(cout, 16)
-                jobs.append((w.data_ptr(), dg.data_ptr(), 1, cout, cp16, cin, cin_pad, k, (cp16 // 16) * k * k * 2 * cin_pad * 8))
+                # cpad / 16 chunks of filters, of which the job writes the first ceil(cout / 16): rows of the pad planes stay zero
+                dg = ctx.get(("pkd", i), (L.ay_packed_dgrad_weight_bytes(cpad, cin_pad, k),), torch.uint8, zero=True)
+                jobs.append((w.data_ptr(), dg.data_ptr(), 1, cout, _pad(cout, 16), cin, cin_pad, k, L.ay_packed_dgrad_weight_bytes(cout, cin_pad, k) // 2))
             rec.update(dgrad=dg, cin_pad=cin_pad)
         job_dt = np.dtype([("src", "<u8"), ("dst", "<u8"), ("kind", "<i4"), ("cout", "<i4"), ("cout_pad", "<i4"), ("cin", "<i4"),
                            ("cin_pad", "<i4"), ("ksize", "<i4"), ("total", "<u8")])
@@ -225,9 +232,6 @@ def train_forward_bf16(model, x, targets):
     out = ctx.get("out", (B, N, 5 + Ccls), torch.float32)
     tg = None if targets is None else targets.detach().to(device=dev, dtype=torch.float32).contiguous()
 
-    def size_of(i):
-        return S >> graph[i]["log2_down"] if i >= 0 else S
-
     def blocked(key, c, h, dtype=torch.bfloat16, pad=16):
         return ctx.get(key, (B, _pad(c, pad) // 16, h, h, 16), dtype)
 
@@ -235,7 +239,7 @@ def train_forward_bf16(model, x, targets):
         v = val[i]
         if isinstance(v, tuple):
             src = resolve(v[1])
-            c, h = graph[i]["channels"], size_of(i)
+            c, h = graph[i]["channels"], size_of(graph, S, i)
             o = blocked(("up", i), c, h)
             check(L.ay_concat_upsample_bf16(ptr(src), c, 1, None, 0, ptr(o), B, h, h, st), "ay_concat_upsample_bf16")
             val[i] = o
@@ -266,7 +270,7 @@ def train_forward_bf16(model, x, targets):
         if t == "convolutional":
             m = model.module_list[i]
             conv = m[0]
-            hin, hout = size_of(e["src"]), size_of(i)
+            hin, hout = size_of(graph, S, e["src"]), size_of(graph, S, i)
             cout, cin, k = e["cout"], e["cin"], e["k"]
             pk = packed[i]
             cpad, cin_eff = pk["cpad"], pk["cin_eff"]
@@ -303,9 +307,7 @@ def train_forward_bf16(model, x, targets):
                 # forward + the layer's BatchNorm batch statistics in one kernel (the sums land in the layer's fp64 workspace)
                 ws = bn_ws(i, False)
                 nws = L.ay_stem_train_stats_workspace_bytes()
-                sws = ctx.buf.get("stem_stats_ws")
-                if sws is None or sws.numel() < nws:
-                    sws = ctx.buf["stem_stats_ws"] = torch.empty(nws, device=dev, dtype=torch.uint8)
+                sws = ctx.scratch("stem_stats_ws", nws)
                 check(L.ay_stem_train_fwd_stats_bf16(ptr(x), ptr(pk["stem_w0"]), ptr(z), ptr(ws), ptr(sws), sws.numel(), B, hin, hin, st),
                       "ay_stem_train_fwd_stats_bf16")
                 stats_done = True
@@ -342,7 +344,7 @@ def train_forward_bf16(model, x, targets):
                 stt.route[i] = [(srcs[0], graph[srcs[0]]["channels"], 0)]
             else:
                 assert len(srcs) == 2, "route with more than two sources"
-                h = size_of(i)
+                h = size_of(graph, S, i)
                 a, b_ = srcs
                 up = isinstance(val[a], tuple)
                 base = val[a][1] if up else a
@@ -353,23 +355,14 @@ def train_forward_bf16(model, x, targets):
                 val[i] = o
                 stt.route[i] = [(base, graph[a]["channels"], int(up)), (b_, graph[b_]["channels"], 0)]
         elif t == "yolo":
-            y = model.module_list[i][0]
             head = val[e["src"]]
-            G = size_of(i)
-            anchors = (C.c_float * (2 * y.num_anchors))(*[float(v) for a in y.anchors for v in a])
-            check(L.ay_yolo_decode(ptr(head), 0, ptr(out), B, y.num_anchors, y.num_classes, G, S, anchors, N, row, st), "ay_yolo_decode")
-            y.grid_size, y.img_dim = G, S
-            row += y.num_anchors * G * G
+            G = size_of(graph, S, i)
+            rows, dhead, sums = yolo_head_step(model, L, st, i, head, out, row, tg, B, S, G,
+                                               lambda kind, shape: ctx.get((kind, i), shape, torch.float32))
+            row += rows
             if tg is not None:
-                dhead = ctx.get(("dhead", i), tuple(head.shape), torch.float32)
-                sums = ctx.get(("sums", i), (16,), torch.float32)
-                nb = L.ay_yolo_loss_workspace_bytes(B, y.num_anchors, y.num_classes, G)
-                ws = _ws(model, nb, dev)
-                check((L.ay_yolo_loss_giou_fwd_bwd if getattr(model, 'box_loss', 'mse') == 'giou' else L.ay_yolo_loss_fwd_bwd)(ptr(head), ptr(tg), tg.shape[0], B, y.num_anchors, y.num_classes, G, S, anchors,
-                                             C.c_float(y.ignore_thres), C.c_float(1.0), ptr(dhead), ptr(sums), ptr(ws), ws.numel(), st),
-                      "ay_yolo_loss_fwd_bwd")
                 stt.dhead[i] = dhead
-                sums_all.append((y, sums, G))
+                sums_all.append((model.module_list[i][0], sums, G))
             val[i] = head
     if nbt:
         # num_batches_tracked += 1 for every BatchNorm that ran (models.py:43 semantics of nn.BatchNorm2d in train mode): the counters
@@ -382,22 +375,7 @@ def train_forward_bf16(model, x, targets):
                 b._buffers["num_batches_tracked"] = flat[k_]
             model._nbt_flat = flat
         flat.add_(1)
-    loss = None
-    if tg is not None:
-        allsums = torch.stack([s for _, s, _ in sums_all])
-        n_obj, n_noobj = allsums[:, 7], allsums[:, 8]
-        lx, ly, lw, lh = (allsums[:, k] / n_obj for k in range(4))
-        lconf = allsums[:, 4] / n_obj + 100.0 * allsums[:, 5] / n_noobj
-        lcls = allsums[:, 6] / (n_obj * Ccls)
-        per_layer = lx + ly + lw + lh + lconf + lcls
-        loss = per_layer.sum()
-        if getattr(model, "collect_metrics", True):   # one host sync per step (the reference: 39, models.py:205-220)
-            h = torch.stack([per_layer, lx, ly, lw, lh, lconf, lcls, 100.0 * allsums[:, 9] / n_obj, allsums[:, 13] / (n_obj + 1e-16),
-                             allsums[:, 14] / (n_obj + 1e-16), allsums[:, 13] / (allsums[:, 12] + 1e-16), allsums[:, 10] / n_obj,
-                             allsums[:, 11] / n_noobj], 1).cpu().numpy()
-            for li, (y, _, G) in enumerate(sums_all):
-                y.metrics = {k: float(h[li, j]) for j, k in enumerate(METRIC_KEYS[:-1])}
-                y.metrics["grid_size"] = G
+    loss = None if tg is None else loss_and_metrics(sums_all, Ccls, getattr(model, "collect_metrics", True))
     return loss, out, stt
 
 
@@ -424,9 +402,6 @@ def train_backward_bf16(model, stt, grad_scale=None):
     hook = getattr(model, "_grad_ready", None)
     keep_dz = getattr(model, "_dbg_keep_dz", None)
     prof = getattr(model, "_train_prof", None)
-
-    def size_of(i):
-        return S >> graph[i]["log2_down"] if i >= 0 else S
 
     def acc(j, t, own):
         """accumulate the blocked-bf16 gradient t into layer j's output gradient; `own`: t came from the pool and may be kept"""
@@ -459,7 +434,7 @@ def train_backward_bf16(model, stt, grad_scale=None):
                 continue
             d = dval.pop(i)
             parts = stt.route[i]
-            h = size_of(i)
+            h = size_of(graph, S, i)
             ctot = e["channels"]
             if len(parts) == 1 and parts[0][2] == 0 and parts[0][1] == ctot:
                 acc(parts[0][0], d, True)
@@ -478,7 +453,7 @@ def train_backward_bf16(model, stt, grad_scale=None):
         if t == "upsample":
             if i in dval:
                 d = dval.pop(i)
-                c, h = e["channels"], size_of(i)
+                c, h = e["channels"], size_of(graph, S, i)
                 first = e["src"] not in dval
                 if first:
                     dval[e["src"]] = pool.get((B, c // 16, h // 2, h // 2, 16))
@@ -529,9 +504,7 @@ def train_backward_bf16(model, stt, grad_scale=None):
         # ---- weight gradient (matrix cores, K = pixels), added into conv.weight.grad
         if rec.get("stem_direct"):
             nws = L.ay_stem_train_wgrad_workspace_bytes()
-            wws = ctx.buf.get("wgrad_ws")
-            if wws is None or wws.numel() < nws:
-                wws = ctx.buf["wgrad_ws"] = torch.empty(max(nws, 1 << 20), device=dev, dtype=torch.uint8)
+            wws = ctx.scratch("wgrad_ws", nws, 1 << 20)
             check(L.ay_stem_train_wgrad_bf16(ptr(rec["x"]), ptr(dz), ptr(conv.weight.grad), 1, ptr(wws), wws.numel(), B, hin, hin, st),
                   "ay_stem_train_wgrad_bf16")
             if hook is not None:
@@ -544,9 +517,7 @@ def train_backward_bf16(model, stt, grad_scale=None):
             d_w = d
         # split-K partial filters go to slabs in a workspace and are summed in a fixed order (reproducible; no fp32 atomics)
         nws = L.ay_conv_wgrad_workspace_bytes(C.byref(d_w))
-        wws = ctx.buf.get("wgrad_ws")
-        if wws is None or wws.numel() < nws:
-            wws = ctx.buf["wgrad_ws"] = torch.empty(max(nws, 1 << 20), device=dev, dtype=torch.uint8)
+        wws = ctx.scratch("wgrad_ws", nws, 1 << 20)
         with _Timed(prof, "wgrad", _family(e)):
             check(L.ay_conv_wgrad_bf16_ws(C.byref(d_w), ptr(rec["x"]), ptr(dz), ptr(conv.weight.grad), 1, ptr(wws), wws.numel(), st), "ay_conv_wgrad_bf16")
         if hook is not None:

@@ -448,6 +448,7 @@ int ay_zero_insert_bf16(const void* in, void* out, int batch, int channels, int 
 /* filters that make ay_conv_fwd_bf16 compute the data gradient: W'[ci][co][kh][kw] = W[co][ci][k-1-kh][k-1-kw], packed
  * [ceil(cout/16)][k*k][2][cin_pad][8]; use with desc{cin=ceil16(cout), cout=cin, cout_pad=cin_pad, stride 1}. */
 int ay_pack_dgrad_weights_bf16(const float* w_oihw, void* packed, int cout, int cin, int cin_pad, int ksize, ay_stream_t stream);
+size_t ay_packed_dgrad_weight_bytes(int cout, int cin_pad, int ksize);
 /* Every filter image a training step needs, re-packed in ONE launch after the optimiser moved the weights (the reference has no
  * counterpart: its convolutions read nn.Conv2d.weight directly; this replaces ~145 ay_pack_*_bf16 launches per step).  `jobs` and
  * `work` live in DEVICE memory and are built once per weight layout: job j packs `total` elements of image kind `kind` (0 =

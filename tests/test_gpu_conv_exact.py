@@ -431,7 +431,7 @@ def run_dgrad_s1(dev, case):
     cpad, cin_pad = _ceil(cout, 32), _ceil(cin, 32)
     dzb = blocked("bf16", r["dz"], dev, cpad)
     wd = r["w"].to(dev)
-    packed = torch.empty((cpad // 16) * k * k * 2 * cin_pad * 8 * 2, device=dev, dtype=torch.uint8)
+    packed = torch.empty(L.ay_packed_dgrad_weight_bytes(cpad, cin_pad, k), device=dev, dtype=torch.uint8)
     check(L.ay_pack_dgrad_weights_bf16(ptr(wd), ptr(packed), cout, cin, cin_pad, k, st))
     ones, zeros = torch.ones(cin_pad, device=dev), torch.zeros(cin_pad, device=dev)
     dx = Guarded((B, cin_pad // 16, H, W, 16), "bf16", dev)

@@ -108,7 +108,7 @@ def test_dgrad_through_forward_kernel(case):
         dzb = up
     wd = w.to(dev)
     kin = (cout + 15) // 16 * 16
-    packed = torch.empty((kin // 16) * k * k * 2 * cin_pad * 8 * 2, device=dev, dtype=torch.uint8)
+    packed = torch.empty(L.ay_packed_dgrad_weight_bytes(cout, cin_pad, k), device=dev, dtype=torch.uint8)
     check(L.ay_pack_dgrad_weights_bf16(ptr(wd), ptr(packed), cout, cin, cin_pad, k, st))
     ones, zeros = torch.ones(cin_pad, device=dev), torch.zeros(cin_pad, device=dev)
     dx = to_blocked(prev, dev, cin_pad)

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd._lib import ConvDesc, check, ptr
+import pack_reference
 from test_gpu_train_bf16 import bf, from_blocked, to_blocked
 
 pytestmark = pytest.mark.gpu
@@ -335,8 +336,9 @@ def test_wgrad_split_k_slices_of_8(case):
 def test_pack_batch_against_single_packers():
     """ay_pack_batch_bf16 (one launch over a job table, what a training step uses) against ay_pack_conv_weights_bf16,
     ay_pack_dgrad_weights_bf16 and ay_pack_dgrad_s2_weights_bf16: byte equality over what those write, bytes past a job's total
-    untouched.  Jobs with padded output and input channels, totals below one block and off a multiple of it; work items in a
-    scrambled order (they are independent)."""
+    untouched; and the single packers (ay_pack_conv_weights_f16 too) byte for byte against the documented layouts built in NumPy
+    (tests/pack_reference.py).  Jobs with padded output and input channels, totals below one block and off a multiple of it; work
+    items in a scrambled order (they are independent)."""
     L, dev, st = _lib.lib(), _dev(), _lib.stream_ptr()
     blk = L.ay_pack_batch_block()
     g = torch.Generator().manual_seed(5)
@@ -352,7 +354,7 @@ def test_pack_batch_against_single_packers():
             nbytes = L.ay_packed_weight_bytes(cout_pad, cin, k)
         elif kind == 1:
             assert cout_pad == (cout + 15) // 16 * 16
-            nbytes = (cout_pad // 16) * k * k * 2 * cin_pad * 8 * 2
+            nbytes = L.ay_packed_dgrad_weight_bytes(cout, cin_pad, k)
         else:
             nbytes = L.ay_packed_dgrad_s2_weight_bytes(cout_pad, cin_pad)
         single = torch.full((nbytes + TAIL,), 0xFF, device=dev, dtype=torch.uint8)
@@ -384,6 +386,19 @@ def test_pack_batch_against_single_packers():
         assert bool((b_[: 2 * t].view(torch.int16) != -1).all())            # ... every one of them (0xFFFF is no packed value)
         assert torch.equal(a[: 2 * t], b_[: 2 * t]), (spec, int((a[: 2 * t] != b_[: 2 * t]).sum()))
         assert bool((a[2 * t:] == 0xFF).all()), (spec, "bytes past the job's total were written")
+        kind, cout, cout_pad, cin, cin_pad, k = spec
+        wn = w.cpu().numpy()
+        ref = (pack_reference.forward_image(wn, cout_pad) if kind == 0 else pack_reference.dgrad_image(wn, cin_pad) if kind == 1
+               else pack_reference.dgrad_s2_images(wn, cout_pad, cin_pad))
+        assert np.array_equal(b_[: 2 * t].numpy().view(np.uint16), pack_reference.bits(ref)), (spec, "single packer against the documented layout")
+    cout, cout_pad, cin, k = 12, 16, 16, 3           # the IEEE-half forward image
+    w = torch.randn(cout, cin, k, k, generator=g)
+    nbytes = L.ay_packed_weight_bytes(cout_pad, cin, k)
+    half = torch.full((nbytes + TAIL,), 0xFF, device=dev, dtype=torch.uint8)
+    check(L.ay_pack_conv_weights_f16(ptr(w.to(dev)), ptr(half), cout, cout_pad, cin, k, st))
+    half = half.cpu()
+    assert bool((half[nbytes:] == 0xFF).all())
+    assert np.array_equal(half[:nbytes].numpy().view(np.uint16), pack_reference.bits(pack_reference.forward_image(w.numpy(), cout_pad), "f16"))
 
 
 # ------------------------------------------------------------------------------------------------------------ bias gradient
