@@ -2,7 +2,7 @@
 product), and the case lists the exact tests share (tests/test_conv_exact_cpu.py, tests/test_gpu_conv_exact.py).
 
 The technique (the one rocBLAS uses for its GEMM tests): with integer activations in [-4, 4], filters in [-2, 2] and output
-gradients in [-4, 4] every product and every partial sum of a convolution is an integer far below 2^24, hence exactly
+gradients in [-4, 4] ([-64, 64] for the accumulating 1x1 data gradients, see dgrad_reference) every product and every partial sum of a convolution is an integer far below 2^24, hence exactly
 representable in fp32 -- ANY summation order (MFMA 32x32x16, 16x16x32, 32x32x2 f32, split-K slabs, fp32 atomics, an fmaf chain)
 leaves the same fp32 accumulator, and a float64 convolution gives that accumulator exactly.  The epilogue the kernels promise
 (csrc/ay_common.h, csrc/ay_conv_common.h: IEEE operations in a fixed order, ONE rounding per stored activation, to nearest even)
@@ -228,6 +228,11 @@ RECT_CONV_CASES = [
 M16_CASES = [(32, 128, 3, 1, 33, 33, True, False, False, 2), (128, 256, 3, 1, 16, 16, True, True, False, 2)]
 M16_RECT_CASES = [(64, 128, 3, 1, 18, 37, True, True, False, 2), (32, 128, 3, 1, 37, 18, False, False, False, 1)]
 
+# square cases beyond CONV_CASES of test_gpu_parity (same form as RECT_CONV_CASES)
+SQUARE_CONV_CASES = [
+    (256, 128, 1, 1, 32, 32, True, False, False, 1),    # 1x1 ring kernel, BN=128, tiled image by image (one image), not route-folding
+]
+
 
 def _out_hw(k, stride, H, W):
     pad = (k - 1) // 2
@@ -418,14 +423,14 @@ def wgrad_case(c):
 
 
 @functools.lru_cache(maxsize=None)
-def grad_reference(case):
+def grad_reference(case, dz_range=4):
     """float64 autograd of F.conv2d on integer x, w, dz: -> dict(x, w, dz, dw, dx, bits_dw, bits_dx); dw and dx are exact integers"""
     cin, cout, k, s, H, W, B = case
     g = gen(cin, cout, k, s, H, W, B, 23)
     x = activations(g, (B, cin, H, W))
     w = filters(g, (cout, cin, k, k))
     Ho, Wo = _out_hw(k, s, H, W)
-    dz = activations(g, (B, cout, Ho, Wo))
+    dz = ints(g, (B, cout, Ho, Wo), dz_range)
     x64, w64 = x.double().requires_grad_(True), w.double().requires_grad_(True)
     F.conv2d(x64, w64, None, s, (k - 1) // 2).backward(dz.double())
     xa, wa = x.abs().double().requires_grad_(True), w.abs().double().requires_grad_(True)
@@ -441,21 +446,40 @@ DGRAD_S2_CASES = [
     (64, 256, 24, 24, False), (48, 256, 14, 40, True),
     (128, 256, 24, 24, True), (128, 512, 40, 14, False),
 ]
-DGRAD_S1_CASES = [(32, 256, 3, 13, 13, True), (64, 256, 3, 13, 40, True), (128, 512, 1, 40, 13, False)]   # cin, cout, k, H, W, has_prev
+# The 1x1 data gradient of a residual block [1x1 C -> C/2, 3x3 C/2 -> C + shortcut] ACCUMULATES: the shortcut's backward has put dy into
+# dx before it, so every bf16 training step runs the 1x1 forward kernels with a residual, in place (train_engine_bf16.py,
+# `residual = out = dval[j]`).  cin, cout = C, C/2 as in the network: the forward kernel then sees C/2 -> C channels.
+DGRAD_S1_ACC_1X1_CASES = [
+    (64, 32, 1, 13, 40, True),        # 32 input channels (not a multiple of 64): the register-staged NK=1 kernel with a residual
+    (128, 64, 1, 40, 13, True),       # BN=128 ring kernel, residual, canvas (6 tiles against 10)
+    (128, 64, 1, 32, 32, True),       # the same, tiled image by image (no canvas saves a tenth of 8 tiles)
+    (256, 128, 1, 13, 13, True),      # canvas; cout_pad % 256 == 0, turned away from the 256-wide tile by the residual
+    (256, 128, 1, 32, 20, True),      # the same, image by image
+    (512, 256, 1, 13, 13, True),      # canvas, four channel groups of 128, K loop of 4 stages
+]
+DGRAD_S1_CASES = [(32, 256, 3, 13, 13, True), (64, 256, 3, 13, 40, True), (128, 512, 1, 40, 13, False)] + DGRAD_S1_ACC_1X1_CASES   # cin, cout, k, H, W, has_prev
+ACC_1X1_DZ_RANGE = 64
 
 
 def dgrad_reference(case, stride):
-    """data gradient (+ a gradient already accumulated, integers in [-8, 8]) rounded once to bfloat16"""
+    """data gradient (+ a gradient already accumulated, integers in [-8, 8]) rounded once to bfloat16.
+
+    The accumulating 1x1 cases draw dz from [-64, 64]: with dz in [-4, 4] and the network's cout = cin / 2 their sums stay below 256,
+    bfloat16 holds every one of them and no rounding would be tested.  Filters stay in [-2, 2]; sum |w| |dz| <= 256 * 2 * 64 = 2^15."""
     if stride == 2:
         cin, cout, H, W, has_prev = case
         k = 3
     else:
         cin, cout, k, H, W, has_prev = case
-    r = grad_reference((cin, cout, k, stride, H, W, 2))
+    wide = stride == 1 and k == 1 and has_prev
+    key = (cin, cout, k, stride, H, W, 2)
+    r = grad_reference(key, ACC_1X1_DZ_RANGE) if wide else grad_reference(key)
     prev = residuals(gen(cin, cout, H, W, 29), r["dx"].shape) if has_prev else None
     o = r["dx"] + prev if has_prev else r["dx"]
+    if has_prev:
+        assert torch.equal(o.double(), r["dx"].double() + prev.double()), "dx + prev is not exact in fp32"
     inexact, ties = rounding_stats(o, "bf16")
-    return dict(w=r["w"], dz=r["dz"], prev=prev, out=round_store(o, "bf16"), o=o, bits=r["bits_dx"], inexact=inexact, ties=ties)
+    return dict(w=r["w"], dz=r["dz"], dx=r["dx"], prev=prev, out=round_store(o, "bf16"), o=o, bits=r["bits_dx"], inexact=inexact, ties=ties)
 
 
 STEM_TRAIN_CASES = [(2, 40, 72), (1, 24, 24), (2, 13, 132)]   # B, H, W (W % 4 == 0)

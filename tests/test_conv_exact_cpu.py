@@ -18,7 +18,7 @@ import conv_exact_reference as R
 from test_gpu_parity import CONV_CASES, F32_CASES
 from test_gpu_train_bf16 import WGRAD_CASES
 
-SINGLE = [R.conv_case(c) for c in CONV_CASES] + R.RECT_CONV_CASES
+SINGLE = [R.conv_case(c) for c in CONV_CASES] + R.SQUARE_CONV_CASES + R.RECT_CONV_CASES
 SINGLE += [c for c in R.M16_CASES + R.M16_RECT_CASES if c not in SINGLE]      # the direct ay_conv3x3_m16_fwd_* calls
 FP32 = [R.f32_case(c) for c in F32_CASES] + R.RECT_F32_CASES
 GRADS = [R.wgrad_case(c) for c in WGRAD_CASES] + R.RECT_WGRAD_CASES + R.F32_GRAD_CASES
@@ -130,6 +130,24 @@ def test_data_gradient_reference(case):
     assert r["bits"] <= R.HEADROOM_BITS
     assert r["ties"] >= R.MIN_TIES, r["ties"]       # sums beyond 256 meet bfloat16's rounding; no LeakyReLU here
     assert torch.equal(r["out"], r["out"].to(torch.bfloat16).float())
+
+
+@pytest.mark.parametrize("case", R.DGRAD_S1_ACC_1X1_CASES, ids=ids)
+def test_accumulating_1x1_data_gradient_reference(case):
+    """the 1x1 data gradient onto a gradient already in dx: dx + prev is exact in fp32 and meets bfloat16's rounding (ties), and the
+    two wrong kernels an exact comparison must tell from the right one each differ from it in at least 100 values"""
+    cin, cout, k, H, W, has_prev = case
+    assert k == 1 and has_prev
+    r = R.dgrad_reference(case, 1)
+    assert r["bits"] <= R.HEADROOM_BITS
+    for t in (r["dz"], r["w"], r["prev"]):      # operands are exact in bfloat16
+        assert torch.equal(t, t.to(torch.bfloat16).float())
+    assert torch.equal(R.to_f32_exact(r["dx"].double() + r["prev"].double(), "dx + prev"), r["o"])
+    assert r["ties"] >= R.MIN_TIES, r["ties"]
+    rounds_first = R.round_store(R.round_store(r["dx"], "bf16") + r["prev"], "bf16")      # (a) rounds before the residual add
+    drops_residual = R.round_store(r["dx"], "bf16")                                         # (b) no residual
+    assert int((rounds_first != r["out"]).sum()) >= 100, int((rounds_first != r["out"]).sum())
+    assert int((drops_residual != r["out"]).sum()) >= 100, int((drops_residual != r["out"]).sum())
 
 
 @pytest.mark.parametrize("case", R.STEM_TRAIN_CASES, ids=ids)

@@ -14,12 +14,24 @@ rectangular cases as two runs).  It shows the 16x16x32 kernel with and without r
 fused-stem kernels in both types, the stem and training-stem kernels, the five fp32 MFMA forms, every register-staged
 conv_bf16_kernel that conv_fwd_16 can select, the 256-wide 1x1 ring kernel with and without canvas, the route-folding 1x1
 (launch_ring1x1<128, ..., true>), all seven weight-gradient instantiations, and launch_dgrad_s2 for cin_pad 128 and 64 with and
-without a gradient in dx and for cin_pad 32 in its 16-row and 8-row forms, each with and without one.  Of the other ring kernels
-(nine tile shapes x residual x canvas x type) the trace shows all but these, which no case selects:
-  * a residual on a stride-2 or a 1x1 layer (BN 128 / 64 / 32): no layer of the network adds a shortcut there and CONV_CASES has no
-    such case; these forms have never been run and are not first run here.
-  * the 1x1 ring kernel with BN=128 tiled image by image appears only in its route-folding form: every plain 1x1 case of that
-    width has two or more small images and takes the canvas;
+without a gradient in dx and for cin_pad 32 in its 16-row and 8-row forms, each with and without one.
+
+A residual on a 1x1 layer: no layer of the network adds a shortcut there in the FORWARD pass, but every bf16 training step does in
+the BACKWARD pass.  train_backward_bf16 computes a stride-1 data gradient as ay_conv_fwd_bf16 on re-packed filters with
+residual == out == the gradient already in dx, and in a residual block [1x1 C -> C/2, 3x3 C/2 -> C + shortcut] the shortcut has put
+dy there before the 1x1 layer's data gradient arrives.  So the 1x1 forward kernels run with a residual, in place, once per residual
+block and step (profiles/train_step_kernels.txt: a traced training step, with the module that compares each kernel exactly):
+  * C = 128 ... 1024: conv_bf16_ring_kernel<1, 1, 128, 2, 4, 8, 32, 4, 3, true, false, CANVAS> with and without canvas (a residual
+    keeps cout_pad % 256 == 0 away from the 256-wide tile);
+  * C = 64 (32 input channels, no multiple of 64): the register-staged conv_bf16_kernel<1, 1, 32, 1, 4, 8, 32, 1, false, true>.
+DGRAD_S1_ACC_1X1_CASES pins them: six shapes (both kernels; the ring kernel on a canvas and image by image, at 128, 256 and 512
+channels), dz in [-64, 64] so that the sums meet bfloat16's rounding, each run in place and with the residual in a buffer of its own
+(which comes back unchanged), both equal to the reference and to each other bit for bit.  SQUARE_CONV_CASES adds the plain BN=128 1x1
+ring kernel tiled image by image, which appeared only in its route-folding form before.
+Of the ring kernels (nine tile shapes x residual x canvas x type) the trace still lacks these, which nothing selects:
+  * a residual on a stride-2 layer (BN 128 / 64), and on a 1x1 layer in the forms the data gradient does not take (BN 64 / 32 ring
+    tiles, the half type): no layer of the network adds a shortcut there in either pass and no case does; these forms remain unused
+    and untested, and are not first run here.
 The slab reduction of ay_conv_wgrad_bf16_ws takes one lane group per slab, at most 16 / 8 / 4 by the filter count (below 256 K /
 below 1 M / from 1 M weights), and the slab count is at most a 24th of the K steps (B * hout * ceil(wout / 32) / segments per step).
 The trace shows wgrad_reduce_kernel<1>, <2> (2 and 3 slabs) and <16> (the 128 x 96 case: 384 K steps, 16 slabs).  <8> and <4> need
@@ -138,9 +150,9 @@ def run_conv(dev, case, dtype, entry="ay_conv_fwd", cpad_mult=32):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("case", [R.conv_case(c) for c in CONV_CASES], ids=ids)
+@pytest.mark.parametrize("case", [R.conv_case(c) for c in CONV_CASES] + R.SQUARE_CONV_CASES, ids=ids)
 def test_conv_fwd_exact(dev, case, dtype):
-    """every branch of conv_fwd_16 (CONV_CASES of test_gpu_parity): the reference's bits, padded channels exact zeros"""
+    """every branch of conv_fwd_16 (CONV_CASES of test_gpu_parity, SQUARE_CONV_CASES): the reference's bits, padded channels exact zeros"""
     run_conv(dev, case, dtype)
 
 
@@ -434,19 +446,37 @@ def run_dgrad_s1(dev, case):
     packed = torch.empty(L.ay_packed_dgrad_weight_bytes(cpad, cin_pad, k), device=dev, dtype=torch.uint8)
     check(L.ay_pack_dgrad_weights_bf16(ptr(wd), ptr(packed), cout, cin, cin_pad, k, st))
     ones, zeros = torch.ones(cin_pad, device=dev), torch.zeros(cin_pad, device=dev)
-    dx = Guarded((B, cin_pad // 16, H, W, 16), "bf16", dev)
+    shape = (B, cin_pad // 16, H, W, 16)
+    d = ConvDesc(B, cpad, cin, H, W, H, W, k, 1, 0, 0, cin_pad)
+    want = with_zero_channels(r["out"], cin_pad)
+    # in place, as train_backward_bf16 issues it: the gradient already in dx is the residual operand AND the output
+    dx = Guarded(shape, "bf16", dev)
     if has_prev:
         dx.t.copy_(blocked("bf16", r["prev"], dev, cin_pad))
-    d = ConvDesc(B, cpad, cin, H, W, H, W, k, 1, 0, 0, cin_pad)
     check(L.ay_conv_fwd_bf16(C.byref(d), ptr(dzb), ptr(packed), ptr(ones), ptr(zeros), ptr(dx.t) if has_prev else None, ptr(dx.t), st), "dgrad")
     got = unblocked("bf16", dx.t, cin_pad)
     assert dx.intact()
-    R.assert_same_numbers(got, with_zero_channels(r["out"], cin_pad), f"dgrad_s1 {ids(case)}")
+    R.assert_same_numbers(got, want, f"dgrad_s1 {ids(case)}")
+    if not has_prev:
+        return
+    # the same with the residual in a buffer of its own, which comes back unchanged: the in-place form read nothing stale
+    prev = Guarded(shape, "bf16", dev)
+    prev.t.copy_(blocked("bf16", r["prev"], dev, cin_pad))
+    kept = prev.t.clone()
+    dx2 = Guarded(shape, "bf16", dev)
+    check(L.ay_conv_fwd_bf16(C.byref(d), ptr(dzb), ptr(packed), ptr(ones), ptr(zeros), ptr(prev.t), ptr(dx2.t), st), "dgrad, separate residual")
+    got2 = unblocked("bf16", dx2.t, cin_pad)
+    assert dx2.intact() and prev.intact()
+    assert torch.equal(prev.t.view(torch.int16), kept.view(torch.int16)), "the residual operand changed"
+    R.assert_same_numbers(got2, want, f"dgrad_s1, separate residual {ids(case)}")
+    assert torch.equal(dx2.t.view(torch.int16), dx.t.view(torch.int16)), "in-place and separate-buffer forms differ in their bits"
 
 
 @pytest.mark.parametrize("case", [c for c in R.DGRAD_S1_CASES if c[3] == c[4]], ids=ids)
 def test_dgrad_s1_exact(dev, case):
-    """the stride-1 data gradient: ay_pack_dgrad_weights_bf16 + ay_conv_fwd_bf16, accumulation through the residual operand"""
+    """the stride-1 data gradient: ay_pack_dgrad_weights_bf16 + ay_conv_fwd_bf16, accumulation through the residual operand -- in place
+    (residual == out, the engine's form) and from a buffer of its own, bit-identical; the 1x1 cases are the accumulating data gradient
+    of a residual block's first convolution"""
     run_dgrad_s1(dev, case)
 
 
