@@ -12,42 +12,31 @@
 //                       split into four class partitions (class & 3) whose greedy scans are independent; a wave keeps
 //                       its partition's alive words in registers and walks all of them per head in one unrolled pass.
 //                       The heads of all partitions are emitted in global score order by a prefix count over the head
-//                       bitmap.  Larger candidate sets take the one-wavefront scan over the workspace.
+//                       bitmap.  Beyond 4 096 candidates it runs the one-wavefront scan over the workspace.
+//   nms_merge_mid_kernel  1 025 .. 4 096 candidates: the four-wavefront scan with one alive word per lane.
+//   Shared: read_candidate and next_pow2 by all three scans; the cluster step (Cluster) and write_row by the two scans of
+//   nms_merge_kernel.  The mid kernel keeps its cluster step inline (the same statements in the same order).  The scans differ in
+//   the alive-word store.
 //
 // IoU uses the reference's +1-pixel rule and operation order (fp32, no contraction) so `> nms_thres`
 // decisions are bit-identical; only the merged corners (a sum whose order the reference does not fix)
 // differ in the last bits.
 #include <stdlib.h>
 
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
 
-__device__ __forceinline__ float iou_p1(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2,
-                                        float by2) {
-    const float ix1 = fmaxf(ax1, bx1), iy1 = fmaxf(ay1, by1);
-    const float ix2 = fminf(ax2, bx2), iy2 = fminf(ay2, by2);
-    const float inter = fmaxf(ix2 - ix1 + 1.0f, 0.0f) * fmaxf(iy2 - iy1 + 1.0f, 0.0f);
-    const float a1 = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f);
-    const float a2 = (bx2 - bx1 + 1.0f) * (by2 - by1 + 1.0f);
-    return inter / (a1 + a2 - inter + 1e-16f);
-}
-
-static inline int next_pow2(int v) {
+__host__ __device__ static inline int next_pow2(int v) {
     int p = 1;
     while (p < v) p <<= 1;
     return p;
 }
 
 // workspace layout per image (cap = next_pow2(n_rows)):
-//   keys  u64[cap] | cand f32[8][cap] (x1,y1,x2,y2,conf,cls_conf,cls_pred,row-as-int) | alive u64[cap/64] (only used
-//   when an image has more than 65 536 candidates; smaller alive sets live in LDS)
-struct NmsWs {
-    unsigned long long* keys;
-    float* cand;
-    int cap;
-};
-
+//   keys  u64[cap] | cand f32[8][cap] (the fields C_X1 .. C_ROW below) | alive u64[cap/64 + 1]
+//   (cand and alive: images with more candidates than the LDS paths hold)
 // Candidates are appended per WORKGROUP: a workgroup collects its keys in LDS (LDS atomics) and reserves their places in the image's key
 // array with ONE global atomic when its buffer fills up and at the end.  One atomic per candidate put 31 500 returning atomics per
 // batch of 64 tiles on a single 256-byte line (the 64 adjacent counters): ~5 ns each, 160 us for a kernel that moves 200 MB.
@@ -154,9 +143,98 @@ __device__ void bitonic_sort(P d, int n, int tid, int nthreads) {
 constexpr int NMS_FAST = 1024;      // candidates per image whose arrays the fast path keeps in LDS (32 KiB)
 constexpr int NMS_WORDS = NMS_FAST / 64;
 constexpr int NMS_PARTS = 4;        // class partitions (class & 3) = wavefronts of the workgroup
-constexpr int NMS_LDS_KEYS = 1024;  // 8 KiB of keys sorted in LDS (larger candidate sets sort in the workspace): with the 8-KiB alive mask the
-                                    // workgroup stays at 16 KiB of LDS, so it can share a CU with a persistent convolution workgroup of the next
-                                    // batch (117-144 KiB) instead of keeping 64 CUs away from it
+constexpr int NMS_LDS_KEYS = 1024;  // 8 KiB of keys sorted in LDS (larger candidate sets sort in the workspace).  With the fast path's candidate arrays
+                                    // (32 KiB) and head bitmaps nms_merge_kernel holds 41 536 bytes of LDS (the compiler's resource report): of a CU's
+                                    // 160 KiB that leaves 119 KiB, so it shares a CU with a persistent convolution workgroup of the next batch only
+                                    // where that one takes no more (they take 117-144 KiB); beside the larger ones it waits for a CU of its own
+
+// ---- the pieces the merge paths share; the paths differ in where the alive words live ---------------------------------------
+// fields of a gathered candidate, in sorted order: fc[field][j] in LDS, cand[field * cap + j] in the workspace (C_ROW as int)
+enum { C_X1, C_Y1, C_X2, C_Y2, C_CONF, C_CLS, C_CLS_CONF, C_ROW };
+
+struct Candidate {
+    const float* p;   // its row of pred: corners, conf, class scores
+    int row;          // original row
+    float cls, cls_conf;
+};
+
+// sorted key -> original row; class = first maximum of the class scores, like torch.max (:256-257)
+__device__ __forceinline__ Candidate read_candidate(unsigned long long key, const float* pb, int K) {
+    Candidate c;
+    c.row = (int)(unsigned)(key & 0xffffffffu);
+    c.p = pb + (size_t)c.row * K;
+    c.cls_conf = c.p[5];
+    int arg = 0;
+    for (int k = 1; k < K - 5; ++k) {
+        const float v = c.p[5 + k];
+        if (v > c.cls_conf) {
+            c.cls_conf = v;
+            arg = k;
+        }
+    }
+    c.cls = (float)arg;
+    return c;
+}
+
+// One cluster of the greedy scan (:260-269) on one wavefront.  `col(field, j)` reads a field of sorted candidate j.  Lane l visits
+// candidate w * 64 + l of every alive word w the path walks, in ascending w; the members' confidence-weighted corner sums stay per lane
+// until reduce().  That order -- lane = position in the word, words ascending, then the xor butterfly -- is the same on every path, so
+// the merged corners are the same bits whichever path an image takes (tests/nms_exact_reference.py restates it).
+struct Cluster {
+    int head;
+    float hx1, hy1, hx2, hy2, hcls;
+    float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+
+    template <typename Col>
+    __device__ __forceinline__ Cluster(Col col, int head_)
+        : head(head_), hx1(col(C_X1, head_)), hy1(col(C_Y1, head_)), hx2(col(C_X2, head_)), hy2(col(C_Y2, head_)), hcls(col(C_CLS, head_)) {}
+
+    // candidate j = this lane's bit of alive word `a`: does it leave the set with this head?
+    template <typename Col>
+    __device__ __forceinline__ bool visit(Col col, unsigned long long a, int j, int lane, float nms_thres) {
+        bool member = (j == head);  // the head always leaves the set (also when its IoU is NaN)
+        if ((a >> lane) & 1ull) {
+            const float x1 = col(C_X1, j), y1 = col(C_Y1, j), x2 = col(C_X2, j), y2 = col(C_Y2, j);
+            const float iou = iou_p1(hx1, hy1, hx2, hy2, x1, y1, x2, y2);
+            member = member || ((iou > nms_thres) && (col(C_CLS, j) == hcls));
+            if (member) {
+                const float wgt = col(C_CONF, j);
+                sw += wgt;
+                s0 += wgt * x1;
+                s1 += wgt * y1;
+                s2 += wgt * x2;
+                s3 += wgt * y2;
+            }
+        }
+        return member;
+    }
+
+    __device__ __forceinline__ void reduce() {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sw += __shfl_xor(sw, off);
+            s0 += __shfl_xor(s0, off);
+            s1 += __shfl_xor(s1, off);
+            s2 += __shfl_xor(s2, off);
+            s3 += __shfl_xor(s3, off);
+        }
+    }
+
+    __device__ __forceinline__ float4 merged() const { return make_float4(s0 / sw, s1 / sw, s2 / sw, s3 / sw); }   // after reduce()
+};
+
+__device__ __forceinline__ void write_row(float* __restrict__ out_rows, int* __restrict__ keep_idx, size_t slot, float4 box, float conf,
+                                          float cls_conf, float cls, int row) {
+    float* o = out_rows + slot * 7;
+    o[0] = box.x;
+    o[1] = box.y;
+    o[2] = box.z;
+    o[3] = box.w;
+    o[4] = conf;
+    o[5] = cls_conf;
+    o[6] = cls;
+    keep_idx[slot] = row;
+}
 
 __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict__ pred, int N, int C, float nms_thres,
                                                         unsigned long long* keys, float* cand, int cap,
@@ -164,7 +242,7 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
                                                         float* __restrict__ out_rows, int* __restrict__ keep_idx,
                                                         int* __restrict__ count, unsigned long long* alive_ws, int mid_limit) {
     __shared__ unsigned long long skeys[NMS_LDS_KEYS];
-    __shared__ float fc[8][NMS_FAST];  // fast path: x1, y1, x2, y2, conf, class, class conf, original row (as int) in sorted order
+    __shared__ float fc[8][NMS_FAST];  // fast path: the candidates' fields in sorted order
     __shared__ unsigned long long head_s[NMS_PARTS][NMS_WORDS];  // fast path: head bitmap per class partition, then ([0]) their union
     __shared__ int wpre[NMS_WORDS];                              // fast path: heads in the words below
     const int b = blockIdx.x;
@@ -178,8 +256,8 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
     }
     if (n > NMS_FAST && n <= mid_limit) return;   // nms_merge_mid_kernel's image (launched behind this kernel)
     unsigned long long* kb = keys + (size_t)b * cap;
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
+    const float* pb = pred + (size_t)b * N * K;
+    const int np2 = next_pow2(n);
     // ---- sort ------------------------------------------------------------------------------------
     const bool in_lds = np2 <= NMS_LDS_KEYS;
     if (in_lds) {
@@ -191,35 +269,23 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
         __syncthreads();
         bitonic_sort(kb, np2, tid, 256);
     }
-    // ---- fast path: up to 1024 candidates, gathered into LDS, scanned by ONE wavefront -----------------------------
-    // Same scan as below, but the candidate arrays live in LDS instead of the workspace: the greedy loop is a chain of
-    // dependent reads (head box, then one candidate per lane per alive word), an L2 round trip each from the workspace
-    // (1.3-2.3 ms per batch of 64 tiles) against an LDS access here.  Same arithmetic, same order of the
-    // confidence-weighted sums: bit-identical results.
+    // ---- fast path: up to 1024 candidates, gathered into LDS, scanned by four wavefronts --------------------------------------
+    // The greedy loop is a chain of dependent reads (head box, then one candidate per lane per alive word): an LDS access here against
+    // an L2 round trip each from the workspace (1.3-2.3 ms per batch of 64 tiles).
     if (in_lds && n <= NMS_FAST) {
-        const float* pb = pred + (size_t)b * N * K;
         for (int i = tid; i < n; i += 256) {
-            const int r = (int)(unsigned)(skeys[i] & 0xffffffffu);
-            const float* p = pb + (size_t)r * K;
-            float mc = p[5];
-            int arg = 0;
-            for (int k = 1; k < C; ++k) {
-                const float v = p[5 + k];
-                if (v > mc) {  // first maximum wins, like torch.max
-                    mc = v;
-                    arg = k;
-                }
-            }
-            fc[0][i] = p[0];
-            fc[1][i] = p[1];
-            fc[2][i] = p[2];
-            fc[3][i] = p[3];
-            fc[4][i] = p[4];
-            fc[5][i] = (float)arg;
-            fc[6][i] = mc;
-            reinterpret_cast<int*>(fc[7])[i] = r;
+            const Candidate c = read_candidate(skeys[i], pb, K);
+            fc[C_X1][i] = c.p[0];
+            fc[C_Y1][i] = c.p[1];
+            fc[C_X2][i] = c.p[2];
+            fc[C_Y2][i] = c.p[3];
+            fc[C_CONF][i] = c.p[4];
+            fc[C_CLS][i] = c.cls;
+            fc[C_CLS_CONF][i] = c.cls_conf;
+            reinterpret_cast<int*>(fc[C_ROW])[i] = c.row;
         }
         __syncthreads();
+        const auto col = [&](int k, int j) -> float { return fc[k][j]; };
         const int nwords = (n + 63) >> 6;   // <= NMS_WORDS
         const int lane = tid & 63;
         const int part = tid >> 6;          // this wavefront scans the candidates whose class & 3 == part
@@ -228,7 +294,7 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
 #pragma unroll
         for (int w = 0; w < NMS_WORDS; ++w) {
             const int j = w * 64 + lane;
-            const bool mine = w < nwords && j < n && (((int)fc[5][min(j, NMS_FAST - 1)]) & 3) == part;
+            const bool mine = w < nwords && j < n && (((int)fc[C_CLS][min(j, NMS_FAST - 1)]) & 3) == part;
             al[w] = __ballot(mine);
             hm[w] = 0ull;
         }
@@ -238,47 +304,22 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
             for (int w = 0; w < NMS_WORDS; ++w)
                 if (head < 0 && al[w] != 0ull) head = w * 64 + __builtin_ctzll(al[w]);
             if (head < 0) break;   // wave-uniform
-            const float hx1 = fc[0][head], hy1 = fc[1][head], hx2 = fc[2][head], hy2 = fc[3][head], hcls = fc[5][head];
-            float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-            // (the members of a cluster meet the lanes in the order of the one-wavefront scan -- ascending word, lane = position in the
-            // word -- so the partial sums, and with them the merged corners, are the same bits)
+            Cluster cl(col, head);
 #pragma unroll
             for (int w = 0; w < NMS_WORDS; ++w) {
                 const unsigned long long a = al[w];
-                if (a != 0ull && w * 64 + 63 >= head) {   // wave-uniform
-                    const int j = w * 64 + lane;
-                    bool member = (j == head);  // the head always leaves the set (also when its IoU is NaN)
-                    if ((a >> lane) & 1ull) {
-                        const float x1 = fc[0][j], y1 = fc[1][j], x2 = fc[2][j], y2 = fc[3][j];
-                        const float iou = iou_p1(hx1, hy1, hx2, hy2, x1, y1, x2, y2);
-                        member = member || ((iou > nms_thres) && (fc[5][j] == hcls));
-                        if (member) {
-                            const float wgt = fc[4][j];
-                            sw += wgt;
-                            s0 += wgt * x1;
-                            s1 += wgt * y1;
-                            s2 += wgt * x2;
-                            s3 += wgt * y2;
-                        }
-                    }
-                    al[w] = a & ~__ballot(member);
-                }
+                if (a != 0ull && w * 64 + 63 >= head)   // wave-uniform
+                    al[w] = a & ~__ballot(cl.visit(col, a, w * 64 + lane, lane, nms_thres));
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                sw += __shfl_xor(sw, off);
-                s0 += __shfl_xor(s0, off);
-                s1 += __shfl_xor(s1, off);
-                s2 += __shfl_xor(s2, off);
-                s3 += __shfl_xor(s3, off);
-            }
+            cl.reduce();
             // the head's own entry is never read again (it has left every alive set, and other partitions never look at it): it
             // carries the merged corners to the emission pass
             if (lane == 0) {
-                fc[0][head] = s0 / sw;
-                fc[1][head] = s1 / sw;
-                fc[2][head] = s2 / sw;
-                fc[3][head] = s3 / sw;
+                const float4 m = cl.merged();
+                fc[C_X1][head] = m.x;
+                fc[C_Y1][head] = m.y;
+                fc[C_X2][head] = m.z;
+                fc[C_Y2][head] = m.w;
             }
 #pragma unroll
             for (int w = 0; w < NMS_WORDS; ++w)
@@ -311,45 +352,27 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
             if (!((m >> (i & 63)) & 1ull)) continue;
             const int rank = wpre[i >> 6] + __builtin_popcountll(m & ((1ull << (i & 63)) - 1ull));
             if (rank >= max_det) continue;
-            float* o = out_rows + ((size_t)b * max_det + rank) * 7;
-            o[0] = fc[0][i];
-            o[1] = fc[1][i];
-            o[2] = fc[2][i];
-            o[3] = fc[3][i];
-            o[4] = fc[4][i];
-            o[5] = fc[6][i];
-            o[6] = fc[5][i];
-            keep_idx[(size_t)b * max_det + rank] = reinterpret_cast<const int*>(fc[7])[i];
+            write_row(out_rows, keep_idx, (size_t)b * max_det + rank, make_float4(fc[C_X1][i], fc[C_Y1][i], fc[C_X2][i], fc[C_Y2][i]),
+                      fc[C_CONF][i], fc[C_CLS_CONF][i], fc[C_CLS][i], reinterpret_cast<const int*>(fc[C_ROW])[i]);
         }
         return;
     }
-    // ---- gather candidates in sorted order (:255-258) -------------------------------------------
+    // ---- workspace path: gather candidates in sorted order (:255-258) ------------------------------
     float* cb = cand + (size_t)b * 8 * cap;
-    const float* pb = pred + (size_t)b * N * K;
     for (int i = tid; i < n; i += 256) {
-        const unsigned long long key = in_lds ? skeys[i] : kb[i];
-        const int r = (int)(unsigned)(key & 0xffffffffu);
-        const float* p = pb + (size_t)r * K;
-        float mc = p[5];
-        int arg = 0;
-        for (int k = 1; k < C; ++k) {
-            const float v = p[5 + k];
-            if (v > mc) {  // first maximum wins, like torch.max
-                mc = v;
-                arg = k;
-            }
-        }
-        cb[0 * cap + i] = p[0];
-        cb[1 * cap + i] = p[1];
-        cb[2 * cap + i] = p[2];
-        cb[3 * cap + i] = p[3];
-        cb[4 * cap + i] = p[4];
-        cb[5 * cap + i] = mc;
-        cb[6 * cap + i] = (float)arg;
-        reinterpret_cast<int*>(cb)[7 * cap + i] = r;
+        const Candidate c = read_candidate(in_lds ? skeys[i] : kb[i], pb, K);
+        cb[C_X1 * cap + i] = c.p[0];
+        cb[C_Y1 * cap + i] = c.p[1];
+        cb[C_X2 * cap + i] = c.p[2];
+        cb[C_Y2 * cap + i] = c.p[3];
+        cb[C_CONF * cap + i] = c.p[4];
+        cb[C_CLS * cap + i] = c.cls;
+        cb[C_CLS_CONF * cap + i] = c.cls_conf;
+        reinterpret_cast<int*>(cb)[C_ROW * cap + i] = c.row;
     }
+    const auto col = [&](int k, int j) -> float { return cb[k * cap + j]; };
     const int nwords = (n + 63) >> 6;
-    // lane 0 publishes, all lanes re-read: never cache (volatile: LDS, or L2-coherent global accesses of one wave)
+    // the alive words live in global memory: lane 0 publishes, all lanes re-read: never cache (volatile: L2-coherent accesses of one wave)
     volatile unsigned long long* alive = alive_ws + (size_t)b * ((cap >> 6) + 1);
     for (int i = tid; i < nwords; i += 256) {
         const int rem = n - i * 64;
@@ -358,7 +381,7 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
     __threadfence();
     __syncthreads();
     if (tid >= 64) return;
-    // ---- greedy scan by one wavefront ---------------------------------------------------------------
+    // ---- greedy scan by one wavefront, heads emitted as they are met ----------------------------------
     const int lane = tid;
     int kept = 0;
     int cw = 0;
@@ -367,49 +390,17 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
         while (cw < nwords && (aw = alive[cw]) == 0ull) ++cw;  // wave-uniform
         if (cw >= nwords) break;
         const int head = cw * 64 + __builtin_ctzll(aw);
-        const float hx1 = cb[0 * cap + head], hy1 = cb[1 * cap + head], hx2 = cb[2 * cap + head], hy2 = cb[3 * cap + head];
-        const float hcls = cb[6 * cap + head];
-        float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        Cluster cl(col, head);
         for (int w = cw; w < nwords; ++w) {
             const unsigned long long a = alive[w];
             if (a == 0ull) continue;
-            const int j = w * 64 + lane;
-            bool member = (j == head);  // the head always leaves the set (also when its IoU is NaN)
-            if ((a >> lane) & 1ull) {
-                const float x1 = cb[0 * cap + j], y1 = cb[1 * cap + j], x2 = cb[2 * cap + j], y2 = cb[3 * cap + j];
-                const float iou = iou_p1(hx1, hy1, hx2, hy2, x1, y1, x2, y2);
-                member = member || ((iou > nms_thres) && (cb[6 * cap + j] == hcls));
-                if (member) {
-                    const float wgt = cb[4 * cap + j];
-                    sw += wgt;
-                    s0 += wgt * x1;
-                    s1 += wgt * y1;
-                    s2 += wgt * x2;
-                    s3 += wgt * y2;
-                }
-            }
-            const unsigned long long m = __ballot(member);
+            const unsigned long long m = __ballot(cl.visit(col, a, w * 64 + lane, lane, nms_thres));
             if (lane == 0) alive[w] = a & ~m;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sw += __shfl_xor(sw, off);
-            s0 += __shfl_xor(s0, off);
-            s1 += __shfl_xor(s1, off);
-            s2 += __shfl_xor(s2, off);
-            s3 += __shfl_xor(s3, off);
-        }
-        if (lane == 0 && kept < max_det) {
-            float* o = out_rows + ((size_t)b * max_det + kept) * 7;
-            o[0] = s0 / sw;
-            o[1] = s1 / sw;
-            o[2] = s2 / sw;
-            o[3] = s3 / sw;
-            o[4] = cb[4 * cap + head];
-            o[5] = cb[5 * cap + head];
-            o[6] = hcls;
-            keep_idx[(size_t)b * max_det + kept] = reinterpret_cast<const int*>(cb)[7 * cap + head];
-        }
+        cl.reduce();
+        if (lane == 0 && kept < max_det)
+            write_row(out_rows, keep_idx, (size_t)b * max_det + kept, cl.merged(), col(C_CONF, head), col(C_CLS_CONF, head), cl.hcls,
+                      reinterpret_cast<const int*>(cb)[C_ROW * cap + head]);
         ++kept;
         __builtin_amdgcn_wave_barrier();
     }
@@ -417,10 +408,10 @@ __global__ void __launch_bounds__(256) nms_merge_kernel(const float* __restrict_
 }
 
 // ---- 1 025 .. 4 096 candidates per image: the same four-partition scan with everything in LDS (128 KiB: this workgroup has a CU to
-// itself, which the larger candidate sets of 2048^2 crops can afford; the workspace scan below it took 8 / 65 ms per image at 2 000 /
-// 4 000 candidates, an L2 round trip per alive word and head).  A partition's alive words live one per LANE (lane w = word w, 64 words);
+// itself, which the larger candidate sets of 2048^2 crops can afford; the workspace scan took 8 / 65 ms per image at 2 000 / 4 000
+// candidates, an L2 round trip per alive word and head).  A partition's alive words live one per LANE (lane w = word w, 64 words);
 // per head the wave walks the non-empty words only (ballot over the lanes), fetches a word with v_readlane, and the lane that owns the
-// word updates it.  Members meet the lanes in the order of the one-wavefront scan (ascending word, lane = position in the word).
+// word updates it.
 constexpr int NMS_MID = 4096;
 constexpr int NMS_MID_WORDS = NMS_MID / 64;
 
@@ -434,7 +425,7 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
                                                             const int* __restrict__ cand_count, int max_det, float* __restrict__ out_rows,
                                                             int* __restrict__ keep_idx, int* __restrict__ count) {
     __shared__ unsigned long long skeys[NMS_MID];
-    __shared__ float fc[6][NMS_MID];   // x1, y1, x2, y2, conf, class in sorted order (class conf and row come back from pred / the keys)
+    __shared__ float fc[6][NMS_MID];   // C_X1 .. C_CLS in sorted order (class conf and row come back from pred / the keys)
     __shared__ unsigned long long head_s[NMS_PARTS][NMS_MID_WORDS];
     __shared__ int wpre[NMS_MID_WORDS];
     const int b = blockIdx.x;
@@ -443,31 +434,20 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
     const int n = min(cand_count[b], N);
     if (n <= NMS_FAST || n > NMS_MID) return;   // nms_merge_kernel's images (LDS path up to 1 024, workspace scan beyond 4 096)
     const unsigned long long* kb = keys + (size_t)b * cap;
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
+    const int np2 = next_pow2(n);
     for (int i = tid; i < np2; i += 256) skeys[i] = i < n ? kb[i] : ~0ull;
     for (int i = tid; i < NMS_PARTS * NMS_MID_WORDS; i += 256) (&head_s[0][0])[i] = 0ull;
     __syncthreads();
     bitonic_sort(skeys, np2, tid, 256);
     const float* pb = pred + (size_t)b * N * K;
     for (int i = tid; i < n; i += 256) {
-        const int r = (int)(unsigned)(skeys[i] & 0xffffffffu);
-        const float* p = pb + (size_t)r * K;
-        float mc = p[5];
-        int arg = 0;
-        for (int k = 1; k < C; ++k) {
-            const float v = p[5 + k];
-            if (v > mc) {  // first maximum wins, like torch.max
-                mc = v;
-                arg = k;
-            }
-        }
-        fc[0][i] = p[0];
-        fc[1][i] = p[1];
-        fc[2][i] = p[2];
-        fc[3][i] = p[3];
-        fc[4][i] = p[4];
-        fc[5][i] = (float)arg;
+        const Candidate c = read_candidate(skeys[i], pb, K);
+        fc[C_X1][i] = c.p[0];
+        fc[C_Y1][i] = c.p[1];
+        fc[C_X2][i] = c.p[2];
+        fc[C_Y2][i] = c.p[3];
+        fc[C_CONF][i] = c.p[4];
+        fc[C_CLS][i] = c.cls;
     }
     __syncthreads();
     const int nwords = (n + 63) >> 6;
@@ -477,7 +457,7 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
     unsigned long long al = 0ull;
     for (int w = 0; w < nwords; ++w) {
         const int j = w * 64 + lane;
-        const unsigned long long m = __ballot(j < n && (((int)fc[5][min(j, NMS_MID - 1)]) & 3) == part);
+        const unsigned long long m = __ballot(j < n && (((int)fc[C_CLS][min(j, NMS_MID - 1)]) & 3) == part);
         if (lane == w) al = m;
     }
     while (true) {
@@ -485,7 +465,9 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
         if (nz == 0ull) break;
         const int w0 = __builtin_ctzll(nz);
         const int head = w0 * 64 + __builtin_ctzll(readlane64(al, w0));
-        const float hx1 = fc[0][head], hy1 = fc[1][head], hx2 = fc[2][head], hy2 = fc[3][head], hcls = fc[5][head];
+        const float hx1 = fc[C_X1][head], hy1 = fc[C_Y1][head], hx2 = fc[C_X2][head], hy2 = fc[C_Y2][head], hcls = fc[C_CLS][head];
+        // (the cluster step stays inline here, Cluster's statements in Cluster's order: through the struct, and through an emission
+        // shared with the fast path, this kernel measured 1-2 % slower; profiles/nms_refactor_codegen.txt)
         float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
         while (nz != 0ull) {
             const int w = __builtin_ctzll(nz);
@@ -494,11 +476,11 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
             const int j = w * 64 + lane;
             bool member = (j == head);  // the head always leaves the set (also when its IoU is NaN)
             if ((a >> lane) & 1ull) {
-                const float x1 = fc[0][j], y1 = fc[1][j], x2 = fc[2][j], y2 = fc[3][j];
+                const float x1 = fc[C_X1][j], y1 = fc[C_Y1][j], x2 = fc[C_X2][j], y2 = fc[C_Y2][j];
                 const float iou = iou_p1(hx1, hy1, hx2, hy2, x1, y1, x2, y2);
-                member = member || ((iou > nms_thres) && (fc[5][j] == hcls));
+                member = member || ((iou > nms_thres) && (fc[C_CLS][j] == hcls));
                 if (member) {
-                    const float wgt = fc[4][j];
+                    const float wgt = fc[C_CONF][j];
                     sw += wgt;
                     s0 += wgt * x1;
                     s1 += wgt * y1;
@@ -518,10 +500,10 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
             s3 += __shfl_xor(s3, off);
         }
         if (lane == 0) {   // the head's own entry is never read again: it carries the merged corners to the emission pass
-            fc[0][head] = s0 / sw;
-            fc[1][head] = s1 / sw;
-            fc[2][head] = s2 / sw;
-            fc[3][head] = s3 / sw;
+            fc[C_X1][head] = s0 / sw;
+            fc[C_Y1][head] = s1 / sw;
+            fc[C_X2][head] = s2 / sw;
+            fc[C_Y2][head] = s3 / sw;
             head_s[part][head >> 6] |= 1ull << (head & 63);
         }
         __builtin_amdgcn_wave_barrier();
@@ -548,15 +530,15 @@ __global__ void __launch_bounds__(256) nms_merge_mid_kernel(const float* __restr
         const int rank = wpre[i >> 6] + __builtin_popcountll(m & ((1ull << (i & 63)) - 1ull));
         if (rank >= max_det) continue;
         const int r = (int)(unsigned)(skeys[i] & 0xffffffffu);
-        const int cl = (int)fc[5][i];
+        const int cl = (int)fc[C_CLS][i];
         float* o = out_rows + ((size_t)b * max_det + rank) * 7;
-        o[0] = fc[0][i];
-        o[1] = fc[1][i];
-        o[2] = fc[2][i];
-        o[3] = fc[3][i];
-        o[4] = fc[4][i];
+        o[0] = fc[C_X1][i];
+        o[1] = fc[C_Y1][i];
+        o[2] = fc[C_X2][i];
+        o[3] = fc[C_Y2][i];
+        o[4] = fc[C_CONF][i];
         o[5] = pb[(size_t)r * K + 5 + cl];
-        o[6] = fc[5][i];
+        o[6] = fc[C_CLS][i];
         keep_idx[(size_t)b * max_det + rank] = r;
     }
 }

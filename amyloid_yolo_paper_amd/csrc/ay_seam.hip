@@ -32,6 +32,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
@@ -113,8 +114,6 @@ struct SeamGrid {
     int gx, gy;
 };
 
-__device__ __forceinline__ bool seam_finite(float v) { return fabsf(v) <= 3.0e38f; }   // false for NaN and +-inf
-
 // per-block partials: min / max of the box centres (4 floats) and a histogram of the box sides (SEAM_SIDE_BINS ints; bin k counts
 // the rows with 2^(k-1) < max(w, h) + 1 <= 2^k), over the rows whose coordinates are finite.  Integer counts and min / max: the
 // partials are the same bytes in every run.
@@ -128,7 +127,7 @@ __global__ void __launch_bounds__(256) seam_stats_kernel(const float* __restrict
         const float* r = rows + (size_t)i * 7;
         const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
         const float w = x2 - x1 + 1.0f, h = y2 - y1 + 1.0f;
-        if (!(seam_finite(x1) && seam_finite(y1) && seam_finite(x2) && seam_finite(y2) && seam_finite(w) && seam_finite(h))) continue;
+        if (!(finite_f(x1) && finite_f(y1) && finite_f(x2) && finite_f(y2) && finite_f(w) && finite_f(h))) continue;
         const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
         mnx = fminf(mnx, cx), mxx = fmaxf(mxx, cx), mny = fminf(mny, cy), mxy = fmaxf(mxy, cy);
         const int bits = __float_as_int(fmaxf(fmaxf(w, h), 0.0f) + 1.0f);   // >= 1: exponent >= 0
@@ -156,7 +155,7 @@ __global__ void __launch_bounds__(256) seam_stats_kernel(const float* __restrict
 __device__ __forceinline__ int seam_cell(const float* r, const SeamGrid g) {
     const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
     const float w = x2 - x1 + 1.0f, h = y2 - y1 + 1.0f;
-    if (!(w + 1.0f <= g.c) || !(h + 1.0f <= g.c) || !seam_finite(x1) || !seam_finite(y1)) return g.gx * g.gy;
+    if (!(w + 1.0f <= g.c) || !(h + 1.0f <= g.c) || !finite_f(x1) || !finite_f(y1)) return g.gx * g.gy;
     const float fx = floorf(((x1 + x2) * 0.5f - g.x0) / g.c), fy = floorf(((y1 + y2) * 0.5f - g.y0) / g.c);
     const int ix = (int)fminf(fmaxf(fx, 0.0f), (float)(g.gx - 1)), iy = (int)fminf(fmaxf(fy, 0.0f), (float)(g.gy - 1));
     return iy * g.gx + ix;

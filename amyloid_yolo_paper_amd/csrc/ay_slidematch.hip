@@ -27,6 +27,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
@@ -49,8 +50,6 @@ struct SlideThres {
     float v[AY_SLIDE_MAX_THRES];
 };
 
-__device__ __forceinline__ bool slide_finite(float v) { return fabsf(v) <= 3.0e38f; }   // false for NaN and +-inf
-
 // ROI: ignored iff the centre lies outside the closed rectangle (a NaN centre is outside)
 __device__ __forceinline__ bool slide_ignored(const SlideRoi roi, float x1, float y1, float x2, float y2) {
     if (!roi.on) return false;
@@ -58,14 +57,9 @@ __device__ __forceinline__ bool slide_ignored(const SlideRoi roi, float x1, floa
     return !(cx >= roi.x1 && cx <= roi.x2 && cy >= roi.y1 && cy <= roi.y2);
 }
 
-// the operations of iou_p1_s (ay_stats.hip), in its order
+// the IoU of ay_match_detections (ay_stats.hip): the same function
 __device__ __forceinline__ float slide_iou(float ax1, float ay1, float ax2, float ay2, const float4 b) {
-    const float ix1 = fmaxf(ax1, b.x), iy1 = fmaxf(ay1, b.y);
-    const float ix2 = fminf(ax2, b.z), iy2 = fminf(ay2, b.w);
-    const float inter = fmaxf(ix2 - ix1 + 1.0f, 0.0f) * fmaxf(iy2 - iy1 + 1.0f, 0.0f);
-    const float a1 = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f);
-    const float a2 = (b.z - b.x + 1.0f) * (b.w - b.y + 1.0f);
-    return inter / (a1 + a2 - inter + 1e-16f);
+    return iou_p1(ax1, ay1, ax2, ay2, b.x, b.y, b.z, b.w);
 }
 
 // class id of a label: an integer in 0 .. AY_SLIDE_MAX_CLASSES - 1, or -1
@@ -92,7 +86,7 @@ __global__ void __launch_bounds__(256) slide_stats_kernel(const float* __restric
         const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
         const float w = x2 - x1, h = y2 - y1;
         if (slide_ignored(roi, x1, y1, x2, y2)) continue;
-        if (!(slide_finite(x1) && slide_finite(y1) && slide_finite(x2) && slide_finite(y2) && slide_finite(w) && slide_finite(h))) continue;
+        if (!(finite_f(x1) && finite_f(y1) && finite_f(x2) && finite_f(y2) && finite_f(w) && finite_f(h))) continue;
         const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
         mnx = fminf(mnx, cx), mxx = fmaxf(mxx, cx), mny = fminf(mny, cy), mxy = fmaxf(mxy, cy);
         const int bits = __float_as_int(fmaxf(fmaxf(w, h), 0.0f) + 2.0f);     // >= 2: exponent >= 1
@@ -150,7 +144,7 @@ __global__ void __launch_bounds__(256) slide_bin_count_kernel(const float* __res
     if (cls < 0) atomicOr(flags_out, AY_SLIDE_FLAG_CLASS);
     int c = g.gx * g.gy;
     const float w = x2 - x1, h = y2 - y1;
-    if (w <= g.c - 2.0f && h <= g.c - 2.0f && slide_finite(x1) && slide_finite(y1) && slide_finite(x2) && slide_finite(y2)) {
+    if (w <= g.c - 2.0f && h <= g.c - 2.0f && finite_f(x1) && finite_f(y1) && finite_f(x2) && finite_f(y2)) {
         const float fx = floorf(((x1 + x2) * 0.5f - g.x0) / g.c), fy = floorf(((y1 + y2) * 0.5f - g.y0) / g.c);
         c = slide_clamp_cell(fy, g.gy) * g.gx + slide_clamp_cell(fx, g.gx);
     }

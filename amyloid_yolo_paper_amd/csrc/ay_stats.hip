@@ -4,18 +4,10 @@
 // gives the first maximum of the +1-pixel IoU (torch.max semantics), and the detection is a true positive iff that IoU
 // reaches the threshold and that target has not been claimed yet.  The reference's two early-outs are kept: stop once
 // every target is claimed; skip detections whose class is not among the image's target classes.
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
-
-__device__ __forceinline__ float iou_p1_s(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2, float by2) {
-    const float ix1 = fmaxf(ax1, bx1), iy1 = fmaxf(ay1, by1);
-    const float ix2 = fminf(ax2, bx2), iy2 = fminf(ay2, by2);
-    const float inter = fmaxf(ix2 - ix1 + 1.0f, 0.0f) * fmaxf(iy2 - iy1 + 1.0f, 0.0f);
-    const float a1 = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f);
-    const float a2 = (bx2 - bx1 + 1.0f) * (by2 - by1 + 1.0f);
-    return inter / (a1 + a2 - inter + 1e-16f);
-}
 
 constexpr int MAX_T = 2048;  // targets per image held in LDS
 
@@ -63,7 +55,7 @@ __global__ void __launch_bounds__(64) match_detections_kernel(const float* __res
         bool has_label = false;
         for (int t = lane; t < n; t += 64) {
             has_label = has_label || (tb[t][0] == label);
-            const float v = iou_p1_s(x1, y1, x2, y2, tb[t][1], tb[t][2], tb[t][3], tb[t][4]);
+            const float v = iou_p1(x1, y1, x2, y2, tb[t][1], tb[t][2], tb[t][3], tb[t][4]);
             if (v > best) {  // first maximum within the lane's strided subsequence
                 best = v;
                 arg = t;

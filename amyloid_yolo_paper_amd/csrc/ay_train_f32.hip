@@ -5,6 +5,7 @@
 //   Adam on a flat buffer (train.py:81,118).
 // These are the correctness-first versions (plain fp32 FMA, one pass per tensor); the bf16 MFMA forward reuses
 // ay_conv_bf16.hip.  Everything is deterministic except the float atomics of the loss sums (order-dependent last bits).
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
@@ -248,10 +249,7 @@ __device__ __forceinline__ float wh_iou(float w1, float h1, float w2, float h2) 
 __device__ __forceinline__ float iou_cxcywh_p1(float ax, float ay, float aw, float ah, float bx, float by, float bw, float bh) {
     const float ax1 = ax - aw / 2.0f, ax2 = ax + aw / 2.0f, ay1 = ay - ah / 2.0f, ay2 = ay + ah / 2.0f;
     const float bx1 = bx - bw / 2.0f, bx2 = bx + bw / 2.0f, by1 = by - bh / 2.0f, by2 = by + bh / 2.0f;
-    const float ix1 = fmaxf(ax1, bx1), iy1 = fmaxf(ay1, by1), ix2 = fminf(ax2, bx2), iy2 = fminf(ay2, by2);
-    const float inter = fmaxf(ix2 - ix1 + 1.0f, 0.0f) * fmaxf(iy2 - iy1 + 1.0f, 0.0f);
-    const float a1 = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f), a2 = (bx2 - bx1 + 1.0f) * (by2 - by1 + 1.0f);
-    return inter / (a1 + a2 - inter + 1e-16f);
+    return iou_p1(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2);
 }
 
 // GIoU box loss (new feature, no reference counterpart -- SURVEY F3): L = 1 - GIoU(pred, target) on corner boxes without the

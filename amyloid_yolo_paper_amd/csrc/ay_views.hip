@@ -16,6 +16,7 @@
 //   view_select_kernel             stable in-place compaction of the detections with enough votes, one workgroup per image.
 //
 // Every entry point is kernel launches only: no allocation, no host synchronisation, no memset or copy node, no scratch.
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
@@ -121,16 +122,6 @@ __global__ void __launch_bounds__(256) zero_i32_kernel(int32_t* __restrict__ p, 
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0;
 }
 
-// the +1-pixel IoU of ay_box_iou mode 0 on corners, operation for operation (fp32, no contraction)
-__device__ __forceinline__ float iou_p1_v(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2, float by2) {
-    const float ix1 = fmaxf(ax1, bx1), iy1 = fmaxf(ay1, by1);
-    const float ix2 = fminf(ax2, bx2), iy2 = fminf(ay2, by2);
-    const float inter = fmaxf(ix2 - ix1 + 1.0f, 0.0f) * fmaxf(iy2 - iy1 + 1.0f, 0.0f);
-    const float a1 = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f);
-    const float a2 = (bx2 - bx1 + 1.0f) * (by2 - by1 + 1.0f);
-    return inter / (a1 + a2 - inter + 1e-16f);
-}
-
 constexpr int VOTE_CHUNK = 256;   // detections a workgroup holds in LDS at a time
 
 // grid (x, batch): the workgroups of an image share its V * N rows; a workgroup walks the image's detections in chunks
@@ -166,7 +157,7 @@ __global__ void __launch_bounds__(256) view_votes_kernel(const float* __restrict
             const float x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
             const int bit = 1 << (int)(r / N);
             for (int d = 0; d < nd; ++d)
-                if (det[4][d] == (float)cls && iou_p1_v(det[0][d], det[1][d], det[2][d], det[3][d], x1, y1, x2, y2) > vote_thres)
+                if (det[4][d] == (float)cls && iou_p1(det[0][d], det[1][d], det[2][d], det[3][d], x1, y1, x2, y2) > vote_thres)
                     atomicOr(&bits[d], bit);
         }
         __syncthreads();

@@ -1,6 +1,7 @@
 // YOLO head decode (models.py:127-172) and box math (utils/utils.py:53-59,193-232) in fp32.
 // Arithmetic follows the reference's operation order; the library is built with -ffp-contract=off so
 // no multiply-add is fused behind the reference's back (threshold comparisons must land on the same side).
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
@@ -49,16 +50,6 @@ __global__ void xywh2xyxy_kernel(float* boxes, int64_t n, int stride_) {
     }
 }
 
-__device__ __forceinline__ float iou_plus1(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2,
-                                           float by2) {
-    const float ix1 = fmaxf(ax1, bx1), iy1 = fmaxf(ay1, by1);
-    const float ix2 = fminf(ax2, bx2), iy2 = fminf(ay2, by2);
-    const float inter = fmaxf(ix2 - ix1 + 1.0f, 0.0f) * fmaxf(iy2 - iy1 + 1.0f, 0.0f);
-    const float a1 = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f);
-    const float a2 = (bx2 - bx1 + 1.0f) * (by2 - by1 + 1.0f);
-    return inter / (a1 + a2 - inter + 1e-16f);
-}
-
 // GIoU on corner boxes, no +1 rule.  New feature: the reference has none -> parity unpinned.
 __device__ __forceinline__ float giou(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2, float by2) {
     const float iw = fmaxf(fminf(ax2, bx2) - fmaxf(ax1, bx1), 0.0f);
@@ -91,7 +82,7 @@ __global__ void box_iou_kernel(const float* b1, int n1, const float* b2, int n2,
     float ax1, ay1, ax2, ay2, bx1, by1, bx2, by2;
     load_box(b1 + (n1 == 1 ? 0 : (size_t)i * 4), xyxy, ax1, ay1, ax2, ay2);
     load_box(b2 + (size_t)i * 4, xyxy, bx1, by1, bx2, by2);
-    out[i] = mode == 0 ? iou_plus1(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2) : giou(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2);
+    out[i] = mode == 0 ? iou_p1(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2) : giou(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2);
 }
 
 __global__ void box_iou_pairwise_kernel(const float* b1, int n1, const float* b2, int n2, int mode, float* out) {
@@ -101,7 +92,7 @@ __global__ void box_iou_pairwise_kernel(const float* b1, int n1, const float* b2
         const int i = (int)(t / n2);
         const float* p = b1 + (size_t)i * 4;
         const float* q = b2 + (size_t)j * 4;
-        out[t] = mode == 0 ? iou_plus1(p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3])
+        out[t] = mode == 0 ? iou_p1(p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3])
                            : giou(p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3]);
     }
 }

@@ -666,7 +666,7 @@ int ay_view_select(float* rows, int32_t* keep_idx, int32_t* count, const int32_t
  *   Rank (the seam rule's): score_i = conf_i * cls_conf_i, one fp32 multiply; row i comes before j iff score_i > score_j, or the
  *     scores are equal and i < j.  A NaN or negative score is a caller error (the result is then unspecified, but in bounds); so is
  *     a coordinate that is not finite.
- *   IoU: iou_p1_s of csrc/ay_stats.hip exactly: +1 pixel convention, inter / (a1 + a2 - inter + 1e-16f), fp32, no fused multiply-add.
+ *   IoU: iou_p1 of csrc/ay_box.h exactly: +1 pixel convention, inter / (a1 + a2 - inter + 1e-16f), fp32, no fused multiply-add.
  *   Best target: for a non-ignored row, best_target is the lowest-index non-ignored target among those with the largest IoU (torch's
  *     first maximum) and best_iou that value; if no target has a positive IoU, best_target = -1 and best_iou = 0 (thr > 0: this never
  *     changes a flag).  Ignored rows get -1 and 0.

@@ -9,7 +9,11 @@ a ragged last iteration.  `_flush_trace` replays the counter to prove that each 
 
 References: numpy for candidate counts and keys, `oracle/boxes_oracle.py` for the corners (both bit-exact) and for merge-NMS (indices,
 counts exact; rows within 1e-5 relative).  These tests do not make a flush race fire on demand; they pin the boundaries so that a wrong
-flush, a lost or doubled key or a key written outside its image fails deterministically."""
+flush, a lost or doubled key or a key written outside its image fails deterministically.
+
+The merged corners are a sum whose order the reference leaves open, so the oracle pins them to 1e-5 only.  The order the three merge
+paths share is restated in tests/nms_exact_reference.py; `test_nms_rows_equal_the_restatement_bit_for_bit` holds every path to it as
+raw bytes."""
 import ctypes
 import os
 import subprocess
@@ -19,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import nms_exact_reference as R
 from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd import utils as ay
 from amyloid_yolo_paper_amd._lib import check, ptr
@@ -378,7 +383,8 @@ np.savez(sys.argv[3], **out)
 
 def test_nms_mid_kernel_off_equals_default(dev, tmp_path):
     """AY_NMS_MID=0 (read once per process: a fresh child process) sends images with 1 025 .. 4 096 candidates to the workspace scan
-    instead of the mid kernel: the same indices as the default run and the oracle, rows within 1e-5 of the oracle."""
+    instead of the mid kernel: the same indices as the default run and the oracle, rows within 1e-5 of the oracle and, byte for byte,
+    the default run's rows (the mid kernel against the workspace scan on the same images)."""
     specs = FLUSH_SPECS[2:5]
     pred, ncand = _nms_batch(131072 + 37, 3, specs, 64)
     assert ((ncand > 1024) & (ncand <= 4096)).all()
@@ -395,3 +401,26 @@ def test_nms_mid_kernel_off_equals_default(dev, tmp_path):
         np.testing.assert_array_equal(z[f"keep{b}"], res.keep_idx[b])
         np.testing.assert_array_equal(z[f"keep{b}"], o_keep[b])
         close(z[f"rows{b}"], o_rows[b], 1e-5, f"image {b}")
+        np.testing.assert_array_equal(z[f"rows{b}"].view(np.uint32), res[b].cpu().numpy().view(np.uint32), err_msg=f"image {b}")
+
+
+# ----------------------------------------------------------------------------------------- merged rows bit for bit
+@pytest.mark.parametrize("max_det", [max(R.CANDIDATES), 8], ids=lambda m: f"maxdet{m}")
+@pytest.mark.parametrize("C", [3, 6], ids=lambda c: f"C{c}")
+def test_nms_rows_equal_the_restatement_bit_for_bit(dev, C, max_det):
+    """One batch at N = 8 192 with 0, 1, 64, 65, 1 000, 1 024, 1 025, 3 000, 4 096, 4 097 and 6 000 candidates (the word boundary and
+    both sides of each path limit; C = 3 reads 32-byte rows in the filter): count, keep_idx and all seven floats of every valid row
+    equal tests/nms_exact_reference.py, the merge restated in the kernels' order, as raw bytes.  max_det = 6 000 holds every head,
+    max_det = 8 cuts every image that has more."""
+    case = R.exact_case(C)
+    np.testing.assert_array_equal((case.pred[..., 4] >= F32(0.5)).sum(1), R.CANDIDATES)
+    rows, keep, count, cand = ay.nms_device(torch.from_numpy(case.pred.copy()).to(dev), R.CONF_THRES, R.NMS_THRES, max_det, slot=6)
+    rows, keep, count, cand = rows.cpu().numpy(), keep.cpu().numpy(), count.cpu().numpy(), cand.cpu().numpy()
+    np.testing.assert_array_equal(cand, R.CANDIDATES)
+    np.testing.assert_array_equal(count, [len(k) for k in case.keep])
+    for b, n in enumerate(R.CANDIDATES):
+        k = min(len(case.keep[b]), max_det)
+        if k:
+            np.testing.assert_array_equal(keep[b, :k], case.keep[b][:k], err_msg=f"image {b} ({n} candidates)")
+            np.testing.assert_array_equal(rows[b, :k].view(np.uint32), case.rows[b][:k].view(np.uint32),
+                                          err_msg=f"image {b} ({n} candidates)")
