@@ -156,6 +156,9 @@ _SIGS = {
     "ay_view_select": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ay_slide_match_workspace_bytes": (_SZ, [_I, _I, _I]),
     "ay_slide_match": (_I, [_P, _I, _P, _I, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ay_burden_bin": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "ay_field_select_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ay_field_select": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

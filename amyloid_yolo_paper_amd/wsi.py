@@ -24,6 +24,10 @@ Training reads the same rasters: :class:`SlideSampler` draws windows centred on 
 slides and cuts them with the fused augmentation kernel under THE WINDOW RULE (``ay_augment_ingest_window_u8``), for
 ``train(source=...)``.
 
+What a slide carries: :func:`burden_map` bins the rows of a slide into class count maps (``ay_burden_bin``, THE BURDEN RULE),
+:func:`densest_fields` picks the densest microscope-sized fields of every class (``ay_field_select``, THE FIELD RULE), and
+:func:`quantify_region` joins them with :func:`detect_region` and the tissue of every map cell into counts and densities per slide.
+
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
 import math
@@ -477,6 +481,160 @@ def evaluate_region(model, raster, targets, iou_thres=0.5, roi=None, **detect_re
     rows = torch.cat([d for _, _, d in res]) if res else torch.zeros(0, 7)
     out = slide_statistics(rows, targets, iou_thres, roi)
     out["rows"] = rows
+    return out
+
+
+# ---- slide-level burden: class count maps, tissue density, densest fields -----------------------------------------------------------
+BURDEN_MAX_CLASSES, BURDEN_MAX_FIELDS, BURDEN_MAX_FIELD_SIDE = 64, 64, 46340    # include/amyloid_yolo.h, THE BURDEN / FIELD RULE
+BURDEN_FLAG_NONFINITE, BURDEN_FLAG_CLASS = 1, 2
+
+
+def _whole(v, lo, hi, what):
+    """``v`` as an int in ``lo .. hi``, else ``ValueError`` (bools and fractions are no counts)"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what} {v!r} is no integer in {lo} .. {hi}")
+    return int(v)
+
+
+def _burden_device():
+    if not torch.cuda.is_available():
+        raise _lib.AyError("no HIP device: the burden maps have no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _int_planes(a, dev):
+    t = a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32)))
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def burden_map(rows, slide_hw, cell=128, num_classes=2, min_conf=0.0):
+    """Class count maps of a slide's detections (``ay_burden_bin``, THE BURDEN RULE in ``include/amyloid_yolo.h``).
+
+    ``rows`` [M,7] = (x1, y1, x2, y2, conf, cls_conf, cls_pred) in pixels of the (halved) slide, as :func:`detect_region` returns
+    them (concatenated), a tensor or array on the host or the device; ``slide_hw`` = (H, W) of that slide; ``cell`` the side of a
+    map cell in pixels; ``num_classes`` = C in 1 .. 64 (default: the reference's two, Cored and CAA).  A row counts once, in the cell
+    of its centre (a centre outside the slide in the nearest border cell), for its class, if ``conf >= min_conf``; a row with a
+    centre that is not finite or a ``cls_pred`` that is no integer in 0 .. C-1 is flagged and counts nowhere.
+
+    Returns a dict: ``counts`` int32 [C,Gy,Gx] on the device (the grid is ``tile_grid(H, W, cell)``, the one :func:`tissue_counts`
+    counts on with ``tile=cell``), ``counted`` NumPy [C] (``counts[c].sum()``), ``below``, ``flagged`` (``counted.sum() + below +
+    flagged == M``) and ``flags`` (bit 1: a centre not finite, bit 2: a class outside).  Reads the statistics back once."""
+    cell, nc = _whole(cell, 1, 2 ** 31 - 1, "burden_map: cell"), _whole(num_classes, 1, BURDEN_MAX_CLASSES, "burden_map: num_classes")
+    H, W = (_whole(v, 1, 2 ** 31 - 1, "burden_map: slide_hw") for v in slide_hw)
+    if rows is None or len(rows.shape) != 2 or rows.shape[1] != 7:
+        raise ValueError(f"burden_map: rows must be [M,7], got {None if rows is None else tuple(rows.shape)}")
+    min_conf = float(min_conf)
+    gy, gx, _ = tile_grid(H, W, cell)
+    if nc * gy * gx > 1 << 30:
+        raise ValueError(f"burden_map: {nc} classes x {gy} x {gx} cells exceed 2**30 counters; choose a larger cell")
+    from .stats import _slide_array
+    dev = _burden_device()
+    rows = _slide_array(rows, 7, dev)
+    M = int(rows.shape[0])
+    counts = torch.empty(nc, gy, gx, device=dev, dtype=torch.int32)
+    stats = torch.empty(nc + 3, device=dev, dtype=torch.int32)
+    check(_lib.lib().ay_burden_bin(ptr(rows) if M else None, M, nc, H, W, cell, C.c_float(min_conf), ptr(counts), ptr(stats), _lib.stream_ptr()),
+          "ay_burden_bin")
+    st = stats.cpu().numpy()
+    return {"counts": counts, "counted": st[:nc].copy(), "below": int(st[nc]), "flagged": int(st[nc + 1]), "flags": int(st[nc + 2])}
+
+
+def densest_fields(counts, tissue=None, field=8, top_k=5, need_tissue=0):
+    """The densest ``field x field``-cell fields of every class (``ay_field_select``, THE FIELD RULE in ``include/amyloid_yolo.h``).
+
+    ``counts`` int32 [C,Gy,Gx] (:func:`burden_map`), ``tissue`` int32 [Gy,Gx] or None (tissue pixels per cell), on the host or the
+    device.  A field lies entirely inside the grid and is eligible iff ``tissue`` is None or its tissue sum reaches ``need_tissue``;
+    per class, up to ``top_k`` (1 .. 64) rounds pick the eligible field with the largest count that overlaps no earlier pick of the
+    class (ties: the lowest ``fy * (Gx - field + 1) + fx``) and stop at a count of 0.  ``field`` times the cell side the maps were
+    made with must not exceed 46340, so that a field's tissue sum fits int32; this function does not know the cell side and only
+    refuses ``field > 46340``.
+
+    Returns NumPy ``fields`` int32 [C,top_k,4] = (fy, fx, count, tissue) in pick order (rows not filled: -1; tissue 0 without
+    ``tissue``) and ``n_found`` int32 [C]."""
+    if counts is None or len(counts.shape) != 3:
+        raise ValueError(f"densest_fields: counts must be [C,Gy,Gx], got {None if counts is None else tuple(counts.shape)}")
+    Cn, gy, gx = (int(v) for v in counts.shape)
+    if not 1 <= Cn <= BURDEN_MAX_CLASSES or gy < 1 or gx < 1 or gy * gx > 1 << 30:
+        raise ValueError(f"densest_fields: counts {(Cn, gy, gx)}: need 1 .. {BURDEN_MAX_CLASSES} classes and a grid of 1 .. 2**30 cells")
+    if tissue is not None and tuple(tissue.shape) != (gy, gx):
+        raise ValueError(f"densest_fields: tissue {tuple(tissue.shape)} is not the grid {(gy, gx)} of counts")
+    F = _whole(field, 1, BURDEN_MAX_FIELD_SIDE, "densest_fields: field")
+    K = _whole(top_k, 1, BURDEN_MAX_FIELDS, "densest_fields: top_k")
+    need = _whole(need_tissue, 0, 2 ** 31 - 1, "densest_fields: need_tissue")
+    dev = _burden_device()
+    counts = _int_planes(counts, dev)
+    tissue = None if tissue is None else _int_planes(tissue, dev)
+    L = _lib.lib()
+    fields = torch.empty(Cn, K, 4, device=dev, dtype=torch.int32)
+    n_found = torch.empty(Cn, device=dev, dtype=torch.int32)
+    ws = torch.empty(max(int(L.ay_field_select_workspace_bytes(Cn, gy, gx, F)), 16), device=dev, dtype=torch.uint8)
+    check(L.ay_field_select(ptr(counts), Cn, gy, gx, ptr(tissue), F, need, K, ptr(fields), ptr(n_found), ptr(ws), ws.numel(), _lib.stream_ptr()),
+          "ay_field_select")
+    return fields.cpu().numpy(), n_found.cpu().numpy()
+
+
+def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, **detect_region_kwargs):
+    """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
+
+    1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
+       that order into ``rows`` [M,7], as :func:`evaluate_region` does.
+    2. The tissue map on the grid ``tile_grid(H, W, cell)``, in pixels of the (halved) slide, with the ``bg_level``, ``shrink`` and
+       ``probe_stride`` (= d, default 16; it must divide ``cell``) among the keyword arguments.  ``probe_stride=1`` counts on the
+       raster itself and is EXACT (THE TISSUE RULE, at the cost of one more upload of the slide).  Any other stride counts the
+       tissue pixels of :func:`probe_view` (every d-th pixel, single source pixels, no averaging) and multiplies by ``d * d``: an
+       ESTIMATE.  It is a multiple of ``d * d``, a cell on the slide's ragged edge can get up to ``d - 1`` rows and columns more
+       than it holds, and tissue thinner than d pixels is seen by chance; over a field of ``field * cell`` pixels these errors
+       are small against ``field_min_tissue``, per cell they need not be, and densities of single cells inherit them.
+    3. ``burden_map(rows, (H, W), cell, C, min_conf)`` (C = the model's classes) and ``densest_fields(counts, tissue, field, top_k,
+       need_tissue)`` with ``need_tissue = max(1, ceil(field_min_tissue * (field * cell)**2))``, computed once on the host like
+       :func:`wanted_tiles`' bound.  ``field * cell <= 46340``.
+    4. Returns a dict: ``rows``; ``counts`` int32 [C,Gy,Gx] on the device; ``tissue`` NumPy int32 [Gy,Gx]; ``fields`` NumPy int64
+       [C,top_k,5] = (y0, x0, side, count, tissue_px) in pixels of the (halved) slide, in pick order, rows not filled -1;
+       ``n_found`` [C]; ``totals`` [C] (rows counted per class); ``below``, ``flagged``, ``flags`` of :func:`burden_map`.  With
+       ``mpp`` (microns per pixel of the halved slide) also ``density_per_mm2`` float64 [C,Gy,Gx], ``total_density_per_mm2`` [C]
+       (``totals`` over the tissue of the whole map) and ``field_density_per_mm2`` [C,top_k]: ``count / (tissue_px * mpp**2 * 1e-6)``
+       in float64 on the host, NaN where there is no tissue (and for rows not filled).
+
+    The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
+    cell = _whole(cell, 1, BURDEN_MAX_FIELD_SIDE, "quantify_region: cell")
+    F = _whole(field, 1, BURDEN_MAX_FIELD_SIDE, "quantify_region: field")
+    K = _whole(top_k, 1, BURDEN_MAX_FIELDS, "quantify_region: top_k")
+    if F * cell > BURDEN_MAX_FIELD_SIDE:
+        raise ValueError(f"quantify_region: field * cell = {F * cell} exceeds {BURDEN_MAX_FIELD_SIDE} (a field's tissue must fit int32)")
+    if not 0.0 <= float(field_min_tissue) <= 1.0:       # a NaN fails both comparisons
+        raise ValueError(f"quantify_region: field_min_tissue {field_min_tissue!r} is no fraction of a field")
+    if mpp is not None and not 0.0 < float(mpp) < math.inf:
+        raise ValueError(f"quantify_region: mpp {mpp!r} is no positive number of microns per pixel")
+    d = int(detect_region_kwargs.get("probe_stride", 16))
+    if d < 1 or cell % d:
+        raise ValueError(f"quantify_region: probe_stride {d} must divide cell {cell}")
+    shrink, bg_level = int(detect_region_kwargs.get("shrink", 1)), detect_region_kwargs.get("bg_level", 220)
+    if getattr(raster, "ndim", 0) != 3 or raster.shape[0] // shrink < 1 or raster.shape[1] // shrink < 1:
+        raise ValueError("quantify_region: raster must be a uint8 [H,W,3] array with at least one (halved) pixel")
+    min_conf = float(min_conf)
+    need = max(1, math.ceil(float(field_min_tissue) * (F * cell) ** 2))
+    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
+    num_classes = int(model.yolo_layers[0].num_classes)
+    res = detect_region(model, raster, **detect_region_kwargs)
+    rows = torch.cat([r for _, _, r in res]) if res else torch.zeros(0, 7)
+    if d == 1:
+        tissue = tissue_counts(raster, cell, shrink, 0, bg_level)
+    else:
+        view, t, _ = probe_view(raster, cell, shrink, 0, d)
+        tissue = tissue_counts(view, t, 1, 0, bg_level) * np.int32(d * d)
+    bm = burden_map(rows, (H, W), cell, num_classes, min_conf)
+    picked, n_found = densest_fields(bm["counts"], tissue, F, K, need)
+    fields = np.full((num_classes, K, 5), -1, np.int64)
+    filled = picked[:, :, 0] >= 0
+    fields[filled] = np.stack([picked[:, :, 0].astype(np.int64) * cell, picked[:, :, 1].astype(np.int64) * cell,
+                               np.full(picked.shape[:2], F * cell, np.int64), picked[:, :, 2], picked[:, :, 3]], 2)[filled]
+    out = {"rows": rows, "counts": bm["counts"], "tissue": tissue, "fields": fields, "n_found": n_found, "totals": bm["counted"],
+           "below": bm["below"], "flagged": bm["flagged"], "flags": bm["flags"]}
+    if mpp is not None:
+        mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue
+        out["density_per_mm2"] = bm["counts"].cpu().numpy().astype(np.float64) / mm2(tissue)[None]
+        out["total_density_per_mm2"] = bm["counted"].astype(np.float64) / mm2(np.int64(tissue.sum(dtype=np.int64)))
+        out["field_density_per_mm2"] = np.where(filled, fields[:, :, 3], 0).astype(np.float64) / mm2(np.where(filled, fields[:, :, 4], 0))
     return out
 
 

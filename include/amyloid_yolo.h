@@ -699,9 +699,59 @@ int ay_slide_match(const float* rows, int n_rows, const float* targets, int n_ta
                    uint8_t* row_ignored, uint8_t* target_ignored, int32_t* stats, void* workspace, size_t workspace_bytes,
                    ay_stream_t stream);
 
+/* ---- slide-level burden: class count maps and the densest fields (wsi.burden_map, wsi.densest_fields, wsi.quantify_region;
+ *      csrc/ay_burden.hip) ------------------------------------------------------------------------------------------------------------
+ * What a slide's detections are for: how many objects of every class it carries per area of tissue, and how dense the densest
+ * microscope-sized field is.  Both rules are exact (two fp32 operations, integers after them) and tests/burden_reference.py restates
+ * them in NumPy.
+ *
+ * THE BURDEN RULE.  Input: rows [M][7] fp32 (x1, y1, x2, y2, conf, cls_conf, cls_pred) in pixels of the (halved) slide, the slide's
+ *   H, W >= 1, an integer cell >= 1 (pixels), C classes with 1 <= C <= AY_BURDEN_MAX_CLASSES, and min_conf.
+ *   Grid: Gy = ceil(H / cell), Gx = ceil(W / cell): wsi.tile_grid(H, W, cell, 0), the grid ay_tile_tissue_u8 counts on with tile = step
+ *     = cell.
+ *   For each row, in this order:
+ *   Centre: cx = fl32((x1 + x2) * 0.5f), cy = fl32((y1 + y2) * 0.5f): the slide-match rule's two fp32 operations, no fused multiply-add.
+ *   Flagged: a row whose cx or cy is not finite sets AY_BURDEN_FLAG_NONFINITE; a row whose cls_pred is not an integer value in
+ *     0 .. C - 1 (a NaN included) sets AY_BURDEN_FLAG_CLASS.  A row that sets a bit is FLAGGED and counts nowhere.
+ *   Below: any other row with !(conf >= min_conf) is BELOW and counts nowhere; a NaN confidence is therefore below.
+ *   Counted: any other row counts once: px = (int)floorf(min(max(cx, 0), W - 1)) (W - 1 as fp32; and at most W - 1 on integers,
+ *     which only matters above 2^24), py alike -- a centre outside the slide goes to the nearest border cell, nothing is lost --
+ *     ix = px / cell, iy = py / cell (integer division), counts[c][iy][ix] += 1.
+ *   Output: counts int32 [C][Gy][Gx] and stats int32 [C + 3] = rows counted per class, rows below, rows flagged, AY_BURDEN_FLAG_* bits.
+ *     counts[c].sum() == stats[c], and sum(stats[:C]) + below + flagged == M.
+ *
+ * THE FIELD RULE.  Input: counts [C][Gy][Gx] (non-negative); optionally tissue int32 [Gy][Gx], the tissue pixels of every cell;
+ *   field = F >= 1 cells per side with F * cell <= 46340, so that a field's tissue sum fits int32 (THE TISSUE RULE's bound);
+ *   need_tissue >= 0; top_k = K, 1 <= K <= AY_BURDEN_MAX_FIELDS.
+ *   Fields: the F x F blocks of cells that lie entirely inside the grid: field (fy, fx), 0 <= fy <= Gy - F, 0 <= fx <= Gx - F, has the
+ *     linear index fy * (Gx - F + 1) + fx; there is none if Gy < F or Gx < F.  n_c(f) is the sum of counts[c] over the field's
+ *     cells, t(f) the sum of tissue.  A field is ELIGIBLE iff tissue is NULL or t(f) >= need_tissue.
+ *   Selection, for every class on its own, for up to K rounds: among the eligible fields that overlap no field already picked for
+ *     this class (|fy - py| < F and |fx - px| < F is an overlap) take the largest n_c, ties to the lowest linear index; stop if there
+ *     is no such field or that largest count is 0.
+ *   Output: fields int32 [C][K][4] = (fy, fx, n, t) in pick order, rows not filled hold -1, -1, -1, -1, t is 0 when tissue is NULL;
+ *     n_found int32 [C].  Integers, max and min only: a function of the inputs alone, the same bytes on every run.
+ *
+ * ay_burden_bin, ay_field_select: everything on the device.  Both are kernel launches only -- no memset node, no allocation, no host
+ *   read -- and can sit in a captured step.  A kernel of the call zeroes counts and stats and fills fields with -1.  n_rows == 0 is
+ *   legal (rows may then be NULL).  ay_field_select does not know the cell side: it refuses field > 46340, and the caller who knows
+ *   both keeps field * cell <= 46340 (wsi.quantify_region does).  The field sums are separable (a row pass of F, a column pass of F,
+ *   over the C count planes and the tissue plane, into the workspace); one workgroup per class runs the rounds.  workspace: 16-byte
+ *   aligned, ay_field_select_workspace_bytes(num_classes, gy, gx, field) bytes (0 for arguments the call refuses).  No scratch. */
+#define AY_BURDEN_MAX_CLASSES 64
+#define AY_BURDEN_MAX_FIELDS 64
+#define AY_BURDEN_FLAG_NONFINITE 1
+#define AY_BURDEN_FLAG_CLASS 2
+int ay_burden_bin(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, int cell, float min_conf, int32_t* counts,
+                  int32_t* stats, ay_stream_t stream);
+size_t ay_field_select_workspace_bytes(int num_classes, int gy, int gx, int field);
+int ay_field_select(const int32_t* counts, int num_classes, int gy, int gx, const int32_t* tissue, int field, int need_tissue, int top_k,
+                    int32_t* fields, int32_t* n_found, void* workspace, size_t workspace_bytes, ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call (the once-per-slide calls ay_seam_merge and ay_slide_match excepted:
- * they memset, read a few words back and synchronise the stream, and are not for capture) -- so a stream capture of a step
+ * they memset, read a few words back and synchronise the stream, and are not for capture; ay_burden_bin and ay_field_select, also
+ * once per slide, are kernel launches only and capturable) -- so a stream capture of a step
  * (ay_plan_forward + ay_nms_merge ...) replays like any other graph (scripts/micro/graph_sync.hip, graph_coherence.hip,
  * graph_input_coherence.hip: every wait covers a replayed graph, a kernel behind a replay sees its writes, a replay sees eager writes to its inputs).  The persistent kernels rely on
  * stream order between launches (a launch hands its work-counter set back zeroed for a later launch on that stream, the plan's
