@@ -88,6 +88,10 @@ _SIGS = {
     "ay_resblock_supported": (_I, [_I]),
     "ay_plan_create": (_I, [C.POINTER(PlanOp), _I, C.POINTER(C.c_size_t), _I, _I, _I, _I, C.POINTER(C.c_void_p)]),
     "ay_plan_destroy": (None, [_P]),
+    "ay_plan_set_alternation": (_I, [_P, _I]),
+    "ay_plan_op_reversed": (_I, [_P, _I]),
+    "ay_conv_set_traversal": (None, [_I]),
+    "ay_conv_get_traversal": (_I, []),
     "ay_plan_workspace_bytes": (_SZ, [_P]),
     "ay_plan_value_offset": (_SZ, [_P, _I]),
     "ay_plan_forward": (_I, [_P, _P, _P, _P, _P]),

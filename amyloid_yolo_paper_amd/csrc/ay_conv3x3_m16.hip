@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
     const int wm = wave & 1, wn = wave >> 1;
     const int r = lane & 15, g = lane >> 4, h = g & 1, hi = g >> 1;
 
-    const ItemRange rg(n_items);
+    const ItemRange rg(n_items, a.reverse);
     const int last = rg.last;
     int item = rg.first_item();
     // item dealing (ItemDealer): dynamic with a counter set in a.deal, static without; fetch-ahead distance 3 items
@@ -104,7 +104,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
     int ld_cg = 0;
     int ld_item = item, ld_s = 0, ld_par = 0;
     bool ld_done = false;
-    auto setup_loader = [&](int it) __attribute__((always_inline)) {
+    auto setup_loader = [&](int id) __attribute__((always_inline)) {
+        const int it = rg.item_of(id);
         ld_cg = it % a.n_cgroups;
         const int pt = it / a.n_cgroups;
         const int b = pt / tiles_per_img;
@@ -178,8 +179,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
            const unsigned long long tk_begin = wall_clock64();)
     while (true) {
         AY_CLK(if (clk) tk0 = wall_clock64();)
-        const int cg = item % a.n_cgroups;
-        const int pt = item / a.n_cgroups;
+        const int it = rg.item_of(item);
+        const int cg = it % a.n_cgroups;
+        const int pt = it / a.n_cgroups;
         const int b = pt / tiles_per_img;
         const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
         const int next_item = dealer.id_at(seq_c + 1);

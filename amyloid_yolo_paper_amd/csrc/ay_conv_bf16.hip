@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(ConvArgs a, DecodeArg
 
     // workgroup -> (image, pixel tile, channel group); channel groups of one pixel tile are adjacent
     // so they hit the same staged input in L2.
-    const int bid = blockIdx.x;
+    const int bid = a.reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;  // ConvArgs::reverse: the grid taken from its far end
     const int cg = bid % a.n_cgroups;
     const int pt = bid / a.n_cgroups;
     const int tile_x = pt % a.tiles_x;
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     const int wm = wave % WM, wn = wave / WM;
     const int c = lane & 31, hh = lane >> 5;
 
-    const ItemRange rg(n_items);
+    const ItemRange rg(n_items, a.reverse);
     const int last = rg.last;
     int item = rg.first_item();
     // item dealing (ItemDealer): dynamic with a counter set in a.deal, static without; fetch-ahead distance in items
@@ -342,7 +342,8 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
         }
         w_off[i] = off;
     }
-    auto setup_loader = [&](int it) __attribute__((always_inline)) {
+    auto setup_loader = [&](int id) __attribute__((always_inline)) {
+        const int it = rg.item_of(id);
         int cg = it % a.n_cgroups;
         const int pt = it / a.n_cgroups;
         const int b = pt / tiles_per_img;
@@ -473,13 +474,14 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
     if (clk) tk_begin = wall_clock64();
     while (true) {
         if (clk) tk0 = wall_clock64();
-        int cg = item % a.n_cgroups;
+        const int it = rg.item_of(item);
+        int cg = it % a.n_cgroups;
         const int cls = PAIR ? (cg & 1) * 2 : UP2 ? (cg & 3) : 0;
         if constexpr (PAIR)
             cg >>= 1;
         else if constexpr (UP2)
             cg >>= 2;
-        const int pt = item / a.n_cgroups;
+        const int pt = it / a.n_cgroups;
         const int b = pt / tiles_per_img;
         const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
         const int next_item = dealer.id_at(seq_c + 1);
@@ -714,7 +716,16 @@ void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* 
     a.deal = nullptr;
     a.canvas_gx = 0;
     a.w_class_stride = 0;
+    a.reverse = conv_traversal_reverse();
 }
+
+// Per host thread: a launch takes the direction in force on the thread that issues it (a captured launch keeps it in its node)
+static thread_local int t_traversal_reverse = 0;
+int conv_traversal_reverse() { return t_traversal_reverse; }
+}  // namespace ay
+extern "C" void ay_conv_set_traversal(int reverse) { ay::t_traversal_reverse = reverse != 0; }
+extern "C" int ay_conv_get_traversal(void) { return ay::t_traversal_reverse; }
+namespace ay {
 
 int conv_dbg() {
     static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;

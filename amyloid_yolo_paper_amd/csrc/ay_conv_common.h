@@ -37,6 +37,11 @@ struct ConvArgs {
     // lies w_class_stride bytes after the previous one, and output pixel (oy, ox) of the class grid is pixel (2 oy + py, 2 ox + px)
     // of the [2 hout][2 wout] output planes
     unsigned w_class_stride;
+    // persistent kernels: 1 = every XCD walks its item range from the top down (ItemRange::item_of).  A launch that walks opposite
+    // to the launch that wrote its input starts on the lines that launch wrote last, which are still in the Infinity Cache; results
+    // do not depend on the order.  fill_args takes it from ay_conv_set_traversal (0 unless a caller asked: training, the
+    // per-layer path and every single call walk forward)
+    int reverse;
 };
 
 // Fused YOLO decode of a detection head (ay_head_decode_fwd_*: models.py:127-172 applied in the epilogue of the head's 1x1
@@ -55,15 +60,23 @@ struct DecodeArgs {
 // XCD's workgroup number `slot`.  The n_items items are cut into 8 consecutive ranges, one per XCD (neighbouring items share
 // input lines, and an XCD has its own L2); the XCD's workgroups share [first, last).  Static dealing: first_item(), then every
 // slots-th item below `last`.  A workgroup with first_item() >= last has nothing to do.
+// Direction (ConvArgs::reverse): the ids dealt -- statically or by ItemDealer -- always run upward through [first, last); a reversed
+// launch works on item last - 1 - (id - first) where a forward one works on item id.  item_of() is that map, applied in the one
+// place where a kernel turns an id below `last` into tile coordinates (its loader and its MFMA side alike, so a look-ahead fetches
+// the tile that will be computed).  The cut into XCD ranges is the same in both directions, and the channel groups of one pixel
+// tile stay neighbours in the walk.
 struct ItemRange {
     int xcd, slot, slots, first, last;
-    __device__ __forceinline__ explicit ItemRange(int n_items) {
+    int flip;  // reversed: first + last - 1 (>= 0 for a non-empty range); forward: -1
+    __device__ __forceinline__ explicit ItemRange(int n_items, int reverse = 0) {
         xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
         const int per_xcd = (n_items + 7) >> 3;
         first = xcd * per_xcd;
         last = min(first + per_xcd, n_items);
+        flip = reverse ? first + last - 1 : -1;
     }
     __device__ __forceinline__ int first_item() const { return first + slot; }
+    __device__ __forceinline__ int item_of(int id) const { return flip >= 0 ? flip - id : id; }
 };
 
 // Item dealing of the ring kernels.  A workgroup's first D items are static (no atomics, no wait in the prologue); the following
@@ -72,7 +85,8 @@ struct ItemRange {
 // mailbox indexed by sequence number: thread 0 fetches id[c+D] at the start of the epilogue of item c (the atomic's latency hides
 // under it) and posts it at its end; the stage barriers publish it long before the loader (at most 2 item boundaries ahead) or the
 // MFMA side need it.  Without a counter set (deal == nullptr: static dealing) the same mailbox carries the static ids.  An id
-// >= rg.last reads as "no more items".
+// >= rg.last reads as "no more items".  The mailbox carries ids of the dealing sequence in both directions (ItemRange::item_of
+// maps them at the use), so the bound below is the same for a reversed launch.
 struct ItemDealer {
     // explicit LDS address space: through a generic pointer these volatile accesses become flat_load/flat_store, which count on
     // vmcnt as well, and hipcc then waits vmcnt(0) -- draining the DMA ring -- at every mailbox access
@@ -447,10 +461,12 @@ __device__ __forceinline__ void head_decode_epilogue(const ConvArgs& a, const De
 int conv_num_cus();
 // AY_DBG, read once (timing experiments: only the instrumented build's kernels look at ConvArgs::dbg)
 int conv_dbg();
+// direction of the persistent conv launches this host thread issues next (ay_conv_set_traversal)
+int conv_traversal_reverse();
 // counter set for the dynamic item dealing of the next ring-kernel launch on `st` (nullptr: static dealing)
 unsigned* next_deal_set(hipStream_t st);
 // THE initialiser of ConvArgs: every field, for the convolution `d` tiled TH x TW pixels by BN channels image by image; static
-// dealing, no debug bits.  A launcher overrides only what differs.
+// dealing, no debug bits, the calling thread's traversal direction.  A launcher overrides only what differs.
 void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* w, const float* scale, const float* shift,
                const void* residual, void* out, int TH, int TW, int BN);
 // workgroups of a persistent launch over n_items items: 8 XCDs x min(items per XCD, wgs_per_cu x CUs per XCD); 0: n_items is

@@ -27,6 +27,9 @@ struct ay_plan {
     // fused[i] = j > 0: op i is a detection head (linear 1x1 convolution into an fp32 value) whose only reader is the decode op j:
     // issued as ONE ay_head_decode_fwd_* launch, the head value is never written; fused[j] = -1: issued with op i, skip
     std::vector<int> fused;
+    // reverse[i] = 1: op i walks its items opposite to the op that last touched the largest value it reads (ay_plan_set_alternation)
+    std::vector<unsigned char> reverse;
+    bool alternate = false;
     // profiling (ay_plan_profile_begin/end): one event list per recorded forward, a pair per selected op
     mutable bool profiling = false;
     mutable int prof_every = 1, prof_seen = 0;   // event pairs on every prof_every-th forward since ay_plan_profile_begin*
@@ -61,7 +64,7 @@ constexpr Entries ENTRIES_BF16 = {ay_head_decode_fwd_bf16, ay_stem_s2_fused_fwd,
 constexpr Entries ENTRIES_F16 = {ay_head_decode_fwd_f16, ay_stem_s2_fused_fwd_f16, ay_stem_conv_fwd_f16,
                                  ay_conv_fwd_f16,        ay_resblock_fwd_f16,      ay_conv1x1_cat_fwd_f16};
 
-int issue(const ay_plan* p, size_t idx, const float* x, uint8_t* ws, float* out, ay_stream_t st) {
+int issue_op(const ay_plan* p, size_t idx, const float* x, uint8_t* ws, float* out, ay_stream_t st) {
     const ay_plan_op& o = p->ops[idx];
     const Entries& fn = p->dtype == AY_DT_F16 ? ENTRIES_F16 : ENTRIES_BF16;
     auto at = [&](int v) -> void* { return v >= 0 ? ws + p->offset[v] : nullptr; };
@@ -95,6 +98,42 @@ int issue(const ay_plan* p, size_t idx, const float* x, uint8_t* ws, float* out,
     return AY_ERR_ARG;
 }
 
+// op idx in the direction the plan chose for it (alternation on); the calling thread's own direction is put back afterwards,
+// whatever the op returned.  Alternation off: the plan does not touch the direction.
+int issue(const ay_plan* p, size_t idx, const float* x, uint8_t* ws, float* out, ay_stream_t st) {
+    if (!p->alternate) return issue_op(p, idx, x, ws, out, st);
+    const int before = ay_conv_get_traversal();
+    ay_conv_set_traversal(p->reverse[idx]);
+    const int rc = issue_op(p, idx, x, ws, out, st);
+    ay_conv_set_traversal(before);
+    return rc;
+}
+
+// Directions: a launch walks opposite to the launch that last TOUCHED -- wrote or read -- the largest value it reads (by bytes: a
+// route reads two values, a shortcut convolution its source and the residual), so that it starts on the lines that launch
+// touched last -- what is left of them in the Infinity Cache -- instead of on its oldest ones.  The last touch, not the producer:
+// the shortcut operand of a residual 3x3 was written two launches back, but the 1x1 in between has just read it, in the
+// opposite direction.  The network input counts as touched forward, so the first launch walks forward; for a chain of layers
+// this is plain alternation.  Ops that are not persistent convolution launches (route copy, stand-alone decode, the unfused
+// stem) walk their grid forward whatever is asked.
+void choose_directions(ay_plan* p) {
+    const size_t n = p->ops.size();
+    p->reverse.assign(n, 0);
+    std::vector<unsigned char> touched_rev(p->bytes.size(), 0);   // per value: direction of the last launch that touched it
+    for (size_t i = 0; i < n; ++i) {
+        const ay_plan_op& o = p->ops[i];
+        const bool persistent = o.kind == AY_OP_STEM_S2_FUSED || o.kind == AY_OP_CONV || o.kind == AY_OP_RESBLOCK || o.kind == AY_OP_CONV1X1_CAT;
+        int r[3];
+        op_reads(o, r);
+        int big = AY_PLAN_NONE;
+        for (int v : r)
+            if (v >= 0 && (big < 0 || p->bytes[v] > p->bytes[big])) big = v;
+        p->reverse[i] = persistent && big >= 0 && !touched_rev[big];
+        for (int v : r)
+            if (v >= 0) touched_rev[v] = p->reverse[i];
+        if (o.kind != AY_OP_DECODE) touched_rev[o.dst] = p->reverse[i];
+    }
+}
 }  // namespace
 
 extern "C" int ay_plan_create(const ay_plan_op* ops, int n_ops, const size_t* value_bytes, int n_values, int img_dim,
@@ -176,8 +215,19 @@ extern "C" int ay_plan_create(const ay_plan_op* ops, int n_ops, const size_t* va
         live.push_back({off, need, p->last_use[v]});
         p->arena = std::max(p->arena, off + need);
     }
+    choose_directions(p);
     *out_plan = p;
     return AY_OK;
+}
+
+extern "C" int ay_plan_set_alternation(ay_plan* plan, int on) {
+    AY_CHECK_ARG(plan, "ay_plan_set_alternation: null plan");
+    plan->alternate = on != 0;
+    return AY_OK;
+}
+
+extern "C" int ay_plan_op_reversed(const ay_plan* plan, int op) {
+    return (plan && plan->alternate && op >= 0 && op < (int)plan->reverse.size()) ? plan->reverse[op] : 0;
 }
 
 extern "C" void ay_plan_destroy(ay_plan* plan) { delete plan; }

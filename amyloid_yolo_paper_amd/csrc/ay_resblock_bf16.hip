@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
     const int wma = wave % WMA, wna = wave / WMA;
     const int wm = wave % WM, wn = wave / WM;
 
-    const ItemRange rg(n_items);  // static dealing
+    const ItemRange rg(n_items, a.reverse);  // static dealing
     const int slots = rg.slots, last = rg.last;
     int item = rg.first_item();
     if (item >= last) return;
@@ -108,7 +108,8 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
     const uint8_t* ld_xbase = nullptr;
     int ld_item = item, ld_ls = 0;   // stage within the item: 0..SA-1 phase A, SA..SA+SB-1 phase B
     bool ld_done = false;
-    auto setup_loader = [&](int it) __attribute__((always_inline)) {
+    auto setup_loader = [&](int id) __attribute__((always_inline)) {
+        const int it = rg.item_of(id);
         const int b = it / tiles_per_img;
         const int y0 = ((it / a.tiles_x) % a.tiles_y) * TH, x0 = (it % a.tiles_x) * TW;
         ld_xbase = s.x + (size_t)b * (C / 16) * plane_bytes;
@@ -206,8 +207,9 @@ __global__ void __launch_bounds__(512, 2) resblock_bf16_kernel(ResBlockArgs s, i
 
     int cur = 0;
     while (true) {
-        const int b = item / tiles_per_img;
-        const int y0 = ((item / a.tiles_x) % a.tiles_y) * TH, x0 = (item % a.tiles_x) * TW;
+        const int it = rg.item_of(item);
+        const int b = it / tiles_per_img;
+        const int y0 = ((it / a.tiles_x) % a.tiles_y) * TH, x0 = (it % a.tiles_x) * TW;
         const int next_item = item + slots;
         const bool has_next = next_item < last;
 

@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
     const int c = lane & 31, hh = lane >> 5;
     const ConvArgs& a = s.c1;
 
-    const ItemRange rg(n_items);  // static dealing
+    const ItemRange rg(n_items, a.reverse);  // static dealing
     const int slots = rg.slots, last = rg.last;
     int item = rg.first_item();
     if (item >= last) return;
@@ -110,7 +110,8 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
     // page of zeros; every wave issues NDMA instructions per tile so the waits below are counted.
     const uint8_t* zero_page = reinterpret_cast<const uint8_t*>(g_zero_page_st);
     const unsigned lds_base = lds_addr_of(lds);
-    auto issue_image = [&](int it, int slot_i) __attribute__((always_inline)) {
+    auto issue_image = [&](int id, int slot_i) __attribute__((always_inline)) {
+        const int it = rg.item_of(id);
         const int b = it / tiles_per_img;
         const int y0 = ((it / a.tiles_x) % a.tiles_y) * TH, x0 = (it % a.tiles_x) * TW;
         const float* xb = s.x + (size_t)b * 3 * s.H * s.W;
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
     unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tk_last = wall_clock64();
 #endif
     while (true) {
-        const int pt = item;
+        const int pt = rg.item_of(item);
         const int b = pt / tiles_per_img;
         const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
         const int next_item = item + slots;
@@ -334,13 +335,13 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
     const int c = lane & 31, hh = lane >> 5;
     const ConvArgs& a = s.c1;
 
-    const ItemRange rg(n_items);  // static dealing
+    const ItemRange rg(n_items, a.reverse);  // static dealing
     if (rg.first_item() >= rg.last) return;
     const int nk = (rg.last - rg.first_item() + rg.slots - 1) / rg.slots;   // items of this workgroup: first_item() + k * slots, k < nk
     const unsigned tiles_per_img = (unsigned)(a.tiles_x * a.tiles_y);
     struct Coord { int b, y0, x0; };
     auto coord_of = [&](int k) __attribute__((always_inline)) {   // item k of this workgroup -> image, tile origin
-        const unsigned it = (unsigned)(rg.first_item() + k * rg.slots);
+        const unsigned it = (unsigned)rg.item_of(rg.first_item() + k * rg.slots);
         unsigned b = __umulhi(it, s.m_tpi), r = it - b * tiles_per_img;
         if (r >= tiles_per_img) ++b, r -= tiles_per_img;
         unsigned ty = __umulhi(r, s.m_tx), tx = r - ty * (unsigned)a.tiles_x;

@@ -151,6 +151,9 @@ class Darknet(nn.Module):
         self.fold_routes = True         # route [upsampled | direct] -> 1x1 conv without materialising the concatenation
         self.fuse_blocks = True         # fused residual-block kernel for the C=64/128 blocks (False: two conv launches)
         self.use_plan = os.environ.get("AY_USE_PLAN", "1") != "0"  # bf16 inference: the whole network issued by the native plan (ay_plan_forward)
+        # plan only: each conv launch walks its items opposite to the launch that last touched its largest input (ay_plan_set_alternation;
+        # same bits either way).  AY_PLAN_ALTERNATE=0 keeps every launch walking forward, as the per-layer path always does
+        self.alternate_traversal = os.environ.get("AY_PLAN_ALTERNATE", "1") != "0"
         self.box_loss = "mse"           # "giou": 1 - GIoU replaces the four squared-error box terms (new feature; the
                                         # reference has only the MSE form, models.py:183-186)
 
@@ -667,7 +670,7 @@ class Darknet(nn.Module):
     def _plan(self, B, S, prep, dev):
         """native executor (``_Plan``) of the lowering for this batch shape; plans live in ``prep`` and die with it (new weights)"""
         plans = prep.setdefault("plans", {})
-        key = self._lower_key(B, S)
+        key = self._lower_key(B, S) + (bool(self.alternate_traversal),)
         if key not in plans:
             assert self._mfma
             L = _lib.lib()
@@ -677,6 +680,7 @@ class Darknet(nn.Module):
             handle = C.c_void_p()
             check(L.ay_plan_create(arr, len(low.ops), vb, len(vb), S, self.num_boxes(S), int(self.precision == "fp16"), C.byref(handle)),
                   "ay_plan_create")
+            check(L.ay_plan_set_alternation(handle, int(bool(self.alternate_traversal))), "ay_plan_set_alternation")
             ws = torch.empty(L.ay_plan_workspace_bytes(handle), device=dev, dtype=torch.uint8)
             plans[key] = _Plan(handle, ws, low)
         return plans[key]

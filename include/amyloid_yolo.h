@@ -89,6 +89,13 @@ int ay_stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const flo
                          const void* w1_packed, const float* scale1, const float* shift1, int leaky1, void* out_blocked,
                          int batch, int h, int w, ay_stream_t stream);
 
+/* Direction in which the persistent convolution launches (stem, ay_conv_fwd_*, ay_conv3x3_m16_fwd_*, ay_conv1x1_cat_fwd_*,
+ * ay_resblock_fwd_*, ay_head_decode_fwd_*) that THIS host thread issues from now on walk their work items: 0 (the default) upward,
+ * 1 downward inside each XCD's range.  Same results bit for bit; a plan with alternation sets it per op (ay_plan_set_alternation)
+ * and puts back what it found.  Training never sets it. */
+void ay_conv_set_traversal(int reverse);
+int ay_conv_get_traversal(void);
+
 /* 3x3 (stride 1|2) and 1x1 convolution, blocked bf16 in, MFMA 32x32x16 bf16, fp32 accumulate,
  * fused scale/shift + leaky + residual epilogue; `residual` (blocked bf16, output shape) may be NULL. */
 int ay_conv_fwd_bf16(const ay_conv_desc* d, const void* src, const void* w_packed, const float* scale,
@@ -550,6 +557,13 @@ int ay_plan_create(const ay_plan_op* ops, int n_ops, const size_t* value_bytes, 
 void ay_plan_destroy(ay_plan* plan);
 size_t ay_plan_workspace_bytes(const ay_plan* plan);       /* 256-byte aligned arena the caller allocates */
 size_t ay_plan_value_offset(const ay_plan* plan, int value); /* where a value lives in the arena (tests) */
+/* Traversal directions.  Off (as created): every launch walks its items upward.  On: each persistent convolution launch walks
+ * opposite to the launch that last touched (wrote or read) the largest value it reads (the first one, which reads the image, forward), so that it starts
+ * on the lines its producer wrote last, while they are still in the Infinity Cache.  The results do not depend on it, bit for bit.
+ * Takes effect with the next ay_plan_forward (a captured forward keeps the directions it was captured with).
+ * ay_plan_op_reversed: 1 if op `op` of the plan is issued reversed (0 with alternation off). */
+int ay_plan_set_alternation(ay_plan* plan, int on);
+int ay_plan_op_reversed(const ay_plan* plan, int op);
 /* x: [B][3][S][S] fp32 NCHW; out_rows: [B][n_total_rows][5+C] fp32.  Stream-ordered, no host synchronisation. */
 int ay_plan_forward(const ay_plan* plan, const float* x_nchw, void* workspace, float* out_rows, ay_stream_t stream);
 /* Profiling without a host synchronisation inside the measured region: between begin and end every ay_plan_forward records
