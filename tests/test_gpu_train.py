@@ -276,6 +276,67 @@ def test_adam_flat_matches_torch():
     assert (p.cpu() - p_ref.detach()).abs().max() <= 1e-6
 
 
+ADAM_STEPS = [(1, 1.0), (2, 0.5), (1000, 0.5)]       # (step argument, grad_scale)
+
+
+def _adam_numpy(grads, f):
+    """torch.optim.Adam's update in NumPy type `f`, with the hyper-parameters as the float32 values ay_adam_flat receives and, for
+    float32, its operation order.  Per step: (update, m, v, scale of m), the update as a difference of the parameter, which needs no
+    parameter: p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)"""
+    lr, b1, b2, eps = (f(np.float32(v)) for v in (1e-3, 0.9, 0.999, 1e-8))
+    m, v, m_scale = np.zeros(grads[0].size, f), np.zeros(grads[0].size, f), np.zeros(grads[0].size, f)
+    for (step, gs), g in zip(ADAM_STEPS, grads):
+        bc1, bc2 = f(1) - f(np.power(b1, f(step))), f(1) - f(np.power(b2, f(step)))
+        g = g.astype(f) * f(gs)
+        m_scale = b1 * m_scale + (f(1) - b1) * np.abs(g)      # the same recurrence on magnitudes: what m's rounding is relative to
+        m = b1 * m + (f(1) - b1) * g
+        v = b2 * v + (f(1) - b2) * g * g
+        yield (lr / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + eps), m, v, m_scale
+
+
+def adam_grid_stride_figures():
+    """ay_adam_flat on 32 768 x 256 + 1 000 elements, the first size past the grid cap (the tail is a few threads' second
+    iteration): per step E (float32 NumPy twin vs float64 NumPy Adam, relative to the scale: lr for the update, m's recurrence on
+    the magnitudes of the gradients for m, v itself for v), the bar max(4 E, 2^-22) and the device's
+    error.  |p| <= 2^-6 at the start, so the rounding of a stored parameter (<= 2^-30) is part of E and small against an update of 1e-3."""
+    L = _lib.lib()
+    dev = torch.device("cuda", 0)
+    n = 32768 * 256 + 1000
+    rng = np.random.Generator(np.random.PCG64(21))
+    p0 = rng.uniform(-2.0 ** -6, 2.0 ** -6, n).astype(np.float32)
+    grads = [rng.normal(0, 1, n).astype(np.float32) for _ in ADAM_STEPS]
+    r64, r32 = _adam_numpy(grads, np.float64), _adam_numpy(grads, np.float32)
+    p, m, v = torch.from_numpy(p0).to(dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    p_twin, rows = p0.copy(), []
+    for (step, gs), g, (u64, m64, v64, ms), (u32, m32, v32, _) in zip(ADAM_STEPS, grads, r64, r32):
+        before = p.cpu().numpy().astype(np.float64)
+        gd = torch.from_numpy(g).to(dev)
+        check(L.ay_adam_flat(ptr(p), ptr(gd), ptr(m), ptr(v), n, C.c_float(1e-3), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-8), step,
+                             C.c_float(gs), _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        p_next = (p_twin - u32).astype(np.float32)            # the twin stores its parameter in float32 too
+        lr = float(np.float32(1e-3))
+        for what, got, twin, want, scale in (("update", before - p.cpu().numpy(), p_twin.astype(np.float64) - p_next, u64, lr),
+                                             ("m", m.cpu().numpy(), m32, m64, ms), ("v", v.cpu().numpy(), v32, v64, v64)):
+            E = float((np.abs(twin - want) / scale).max())
+            rows.append(dict(step=step, grad_scale=gs, what=what, E=E, bar=max(4 * E, 2.0 ** -22),
+                             device=float((np.abs(got - want) / scale).max())))
+        p_twin = p_next
+    return rows
+
+
+def test_adam_flat_grid_stride_and_update_scale():
+    """the update p_new - p_old, m and v against a float64 NumPy Adam past the grid cap of 32 768 workgroups, bias corrections of
+    step 1, 2 and 1000, grad_scale 1 and 0.5; bars from the float32 twin (1e-6 to 2e-5 of the update -- a sum of gradients that
+    cancel in m is divided by a small sqrt(v) -- where test_adam_flat_matches_torch holds 1e-3 of it)"""
+    rows = adam_grid_stride_figures()
+    for r in rows:
+        print("adam_flat  step {step:4d} grad_scale {grad_scale:4.2f} {what:7s} E {E:9.2e}  bar {bar:9.2e}  device {device:9.2e}".format(**r))
+    assert len(rows) == 9
+    for r in rows:
+        assert r["bar"] < 1e-4 and r["device"] <= r["bar"], r
+
+
 @pytest.mark.parametrize("precision,box_loss", [("fp32", "mse"), ("bf16", "giou")])
 def test_train_loop_checkpoint_and_eval(tmp_path, tmp_cfg_dir, precision, box_loss):
     """train() end to end on a tiny on-disk dataset: label txt format, collate, 3 optimiser steps with the reference's
