@@ -20,7 +20,8 @@ def detect(image_folder="data/samples", model_def="config/yolov3.cfg", weights_p
            class_path=None, conf_thres=0.8, nms_thres=0.4, batch_size=1, n_cpu=0, img_size=416, precision="bf16",
            rescale=True, verbose=True, device_ingest=True, merge_boxes=False, merge_on_device=False, write_CAA_detections_to_pickle=False,
            filter_CAA_detections_by_model=False):
-    """``precision``: "bf16" | "fp16" (the two 16-bit MFMA storage types) | "fp32" (reference-precision parity path).
+    """``precision``: "bf16" | "fp16" (the two 16-bit MFMA storage types) | "fp32" (reference-precision parity path) | "bf16x6" / "bf16x3" (the
+    fp32 path's layout with split-bf16 products on the bf16 matrix cores; inference only).
     ``device_ingest``: upload the decoded uint8 tiles and do /255 + pad-to-square + nearest resize on the GPU
     (``ay_ingest_tiles_u8``, bit-identical to the host transforms); batches of mixed image sizes are ingested one size at a time.
     ``merge_boxes``: the reference's ``--merge_boxes True`` (``detect.py:131-133``): union-merge overlapping same-class boxes
@@ -95,7 +96,7 @@ def main(argv=None):
     ap.add_argument("--n_cpu", type=int, default=0)
     ap.add_argument("--img_size", type=int, default=416)
     ap.add_argument("--checkpoint_model", type=str)
-    ap.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp16", "fp32", "bf16x3", "bf16x6"])
     ap.add_argument("--merge_boxes", type=str, default="False", help="merge overlapping boxes of the same class (reference detect.py:42)")
     ap.add_argument("--write_CAA_detections_to_pickle", type=str, default="False", help="reference detect.py:43 -- out of scope: errors when True")
     ap.add_argument("--filter_CAA_detections_by_model", type=str, default="False", help="reference detect.py:44 -- out of scope: errors when True")

@@ -13,6 +13,9 @@ forward itself is a planned sequence of calls into ``libamyloid_yolo_hip.so``: t
   configs[4]'s "fp16 MFMA path"): identical bytes and MFMA rate, an 8x smaller rounding step per stored activation.
 * ``precision="fp32"``: every block through the fp32 nchw kernel (reference layout, reference
   precision) -- the mode the 1e-4 parity tests run.
+* ``precision="bf16x6"`` / ``"bf16x3"`` (inference only): the fp32 mode's layout, lowering and host executor with
+  ``ay_conv_fwd_split`` for every block: both fp32 operands split into three / two bf16 planes in the loader, six / three plane
+  products per multiply on the bf16 matrix cores, fp32 accumulation (THE SPLIT RULE, ``include/amyloid_yolo.h``).
 
 The ``nn.Conv2d`` / ``nn.BatchNorm2d`` objects in ``module_list`` are parameter containers only (they give
 the reference's ``state_dict`` schema, optimiser hooks and ``.to(device)``); they are never called.
@@ -28,6 +31,9 @@ import torch.nn as nn
 from . import _lib
 from ._lib import ConvDesc, check, ptr
 from .parse_config import parse_model_config
+
+# split-bf16 modes -> bf16 planes per fp32 operand (the ``nsplit`` of ``ay_conv_fwd_split``)
+SPLIT_PRECISIONS = {"bf16x3": 2, "bf16x6": 3}
 
 
 class Upsample(nn.Module):
@@ -137,7 +143,7 @@ class Darknet(nn.Module):
         self.img_size = img_size
         self.seen = 0
         self.header_info = np.array([0, 0, 0, self.seen, 0], dtype=np.int32)
-        assert precision in ("bf16", "fp16", "fp32")
+        assert precision in ("bf16", "fp16", "fp32") + tuple(SPLIT_PRECISIONS)
         self.precision = precision
         # residual blocks run through the fused kernel: C=64 (measured 1.74 ms vs 2.37 for the two launches at B=64, 512^2);
         # the C=128 kernel exists (ay_resblock_supported) but measures 1.15 vs 1.04 ms, so it is not used by default
@@ -297,7 +303,7 @@ class Darknet(nn.Module):
             w = conv.weight.detach().to(device=device, dtype=torch.float32).contiguous()
             cout = e["cout"]
             first = (i == 0 and e["cin"] == 3 and e["k"] == 3 and e["stride"] == 1 and cout == 32)
-            cpad = cout if self.precision == "fp32" else _pad_to(cout, 32)
+            cpad = _pad_to(cout, 32) if self._mfma else cout
             scale = torch.empty(cpad, device=device, dtype=torch.float32)
             shift = torch.empty(cpad, device=device, dtype=torch.float32)
             if e["bn"]:
@@ -333,6 +339,13 @@ class Darknet(nn.Module):
     @property
     def _mfma(self):
         return self.precision in ("bf16", "fp16")
+
+    @property
+    def _nsplit(self):
+        """bf16 planes per fp32 operand of the split modes (``ay_conv_fwd_split``); 0: not a split mode.  Together with ``_mfma``
+        this is the one place that sorts the precisions: ``not _mfma`` = the NCHW fp32 layout, lowering and host executor of
+        ``precision="fp32"``, which the split modes share; ``_nsplit`` only picks the convolution's arithmetic."""
+        return SPLIT_PRECISIONS.get(self.precision, 0)
 
     @property
     def _act_dtype(self):
@@ -389,6 +402,9 @@ class Darknet(nn.Module):
         return out
 
     def _no_fp16_training(self):
+        if self._nsplit:
+            raise _lib.AyError(f"precision={self.precision!r} is an inference arithmetic (split-bf16 products of the fp32 path): "
+                               "train with precision='bf16' or 'fp32' -- the weights are fp32 either way")
         if self.precision == "fp16":
             raise _lib.AyError("precision='fp16' is an inference storage type (no loss scaling, 5-bit exponent): train with "
                                "precision='bf16' (or 'fp32') and switch to fp16 for detection -- the weights are fp32 either way")
@@ -458,6 +474,9 @@ class Darknet(nn.Module):
                     ev0.record()
                 if mfma:
                     check(fn("ay_conv_fwd")(C.byref(d), at(o.src), o.w, o.scale, o.shift, at(o.res), at(o.dst), st), "ay_conv_fwd_bf16")
+                elif self._nsplit:
+                    check(L.ay_conv_fwd_split(C.byref(d), at(o.src), o.c1, o.up1, at(o.src2), o.w, o.scale, o.shift, at(o.res),
+                                              at(o.dst), self._nsplit, st), "ay_conv_fwd_split")
                 else:
                     check(L.ay_conv_fwd_f32(C.byref(d), at(o.src), o.c1, o.up1, at(o.src2), o.w, o.scale, o.shift, at(o.res),
                                             at(o.dst), st), "ay_conv_fwd_f32")
@@ -493,8 +512,8 @@ class Darknet(nn.Module):
         shortcut in the conv epilogue, lazy x2 upsample, route folded into a convolution's loader): -> ``_Lowered``, the flat
         op list (``_lib.PlanOp``) with symbolic values, run by ``ay_plan_create`` / ``ay_plan_forward`` or by ``_run_ops``.
 
-        bf16 / fp16: the op list ``ay_plan_create`` takes.  fp32 (host executor only, ``ay_plan_create`` never sees it): every
-        convolution is an ``OP_CONV`` for ``ay_conv_fwd_f32``, whose loader reads ``src`` (``PLAN_INPUT`` = the image) with
+        bf16 / fp16: the op list ``ay_plan_create`` takes.  fp32 and the split modes (host executor only, ``ay_plan_create`` never sees it): every
+        convolution is an ``OP_CONV`` for ``ay_conv_fwd_f32`` / ``ay_conv_fwd_split``, whose loader reads ``src`` (``PLAN_INPUT`` = the image) with
         ``c1`` channels, x2 nearest-upsampled when ``up1``, followed by the channels of ``src2`` when set; a lazy upsample
         that anything else reads is an ``OP_CONCAT_UPSAMPLE`` with ``c2 = 0`` (a tensor copy)."""
         mfma, graph = self._mfma, self._graph

@@ -174,6 +174,30 @@ int ay_conv_fwd_f32_valu(const ay_conv_desc* d, const float* src1, int cin1, int
                     const float* w_oihw, const float* scale, const float* shift, const float* residual,
                     float* out, ay_stream_t stream);
 
+/* ---- split-bf16 parity path: fp32-grade products on the bf16 matrix cores ------------------------ */
+
+/* The block of ay_conv_fwd_f32 -- same operands, layouts, route / upsample loader and epilogue -- with both fp32 operands split
+ * into bf16 planes in the loader and the plane products run on v_mfma_f32_32x32x16_bf16 into fp32 accumulators.
+ *
+ * THE SPLIT RULE.  For an fp32 value x:
+ *     p0 = bf16_rne(x),   p1 = bf16_rne(x - p0),   p2 = bf16_rne(x - p0 - p1)
+ * (bf16_rne: round to nearest even to 8 significand bits; every subtraction is in fp32 and exact).  p0 + p1 + p2 == x exactly;
+ * |x - p0 - p1| <= 2^-16 |x|.  With q the planes of the other operand,
+ *     nsplit = 2 ("bf16x3"):  x*y ~ p0q0 + p0q1 + p1q0                        dropped terms <= 3 * 2^-16 |x||y|
+ *     nsplit = 3 ("bf16x6"):  x*y ~ p0q0 + p0q1 + p1q0 + p0q2 + p2q0 + p1q1   dropped terms <= 2^-22 |x||y|
+ * Every included product is exact in fp32 (8 x 8 significand bits) and is accumulated in fp32 by the MFMA (nsplit = 3: p0q0 in one
+ * accumulator, the five correction products in a second one, the two added in fp32 before the epilogue).  The epilogue is
+ * ay_conv_fwd_f32's, operation for operation and unfused: acc * scale + shift, LeakyReLU(0.1), + residual, fp32 store.
+ * Outside the rule: non-finite inputs (inf - inf in the split gives NaN planes) and fp32 subnormals (inputs, and residuals
+ * x - p0 that fall below 2^-126, which the matrix cores may flush).
+ *
+ * Covered: 3x3 stride 1 / 2 and 1x1 stride 1 (the cfg format's shapes).  Anything else is refused with AY_ERR_ARG and a message
+ * (ay_last_error) and `out` is not touched -- there is no fallback to another arithmetic: other kernel sizes, a route whose
+ * cin1 is not a multiple of 16, an image or filter tensor beyond the 32-bit descriptor range (2 GiB), nsplit outside {2, 3}. */
+int ay_conv_fwd_split(const ay_conv_desc* d, const float* src1, int cin1, int up1, const float* src2,
+                      const float* w_oihw, const float* scale, const float* shift, const float* residual,
+                      float* out, int nsplit, ay_stream_t stream);
+
 /* ---- YOLO head decode: models.py:127-172 ------------------------------------------------------- */
 /* head: blocked f32 [B][cpad/16][G][G][16], cpad = A*(5+C) rounded up to 32 (layout=1) or nchw f32 [B][A*(5+C)][G][G] (layout=0).
  * Writes rows [row_offset, row_offset + A*G*G) of out [B][n_total][5+C]:
