@@ -42,6 +42,11 @@ PLAN_INPUT, PLAN_NONE = -1, -2
 OP_STEM_S2_FUSED, OP_STEM, OP_CONV, OP_RESBLOCK, OP_CONV1X1_CAT, OP_CONCAT_UPSAMPLE, OP_DECODE = 1, 2, 3, 4, 5, 6, 7
 
 
+class StainParams(C.Structure):
+    """ay_stain_params (include/amyloid_yolo.h, THE STAIN RULE): the tables of one stain map, uploaded once per slide"""
+    _fields_ = [("od", C.c_float * 256), ("D", C.c_float * 9), ("A", C.c_float * 9), ("T", C.c_float * 257)]
+
+
 class AyError(RuntimeError):
     pass
 
@@ -164,6 +169,9 @@ _SIGS = {
     "ay_burden_bin": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "ay_field_select_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "ay_field_select": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "ay_stain_hist_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _P, _P]),
+    "ay_ingest_region_tiles_stain_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, C.POINTER(C.c_int), _I, _P, _I, _P, _P]),
+    "ay_stain_apply_u8": (_I, [_P, _I, _I, _SZ, _I, _P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -135,27 +135,84 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
 
-// The tap of the whole-slide cut (ay_ingest.hip, ay_views.hip): pixel (X, Y) of the (halved, for shrink == 2) H x W slide that the
+// The tap of the whole-slide cut (ay_cut.h: ay_ingest.hip, ay_views.hip, ay_stain.hip): pixel (X, Y) of the (halved, for shrink == 2) H x W slide that the
 // region `reg` (rows `stride` bytes apart) holds -> px[3] in 0 .. 1; the background 255 = 1.0 outside.  shrink == 2 is the 2x2 mean
 // with round-half-up in uint8.  X and Y are origin + offset added in `unsigned` (int32 origin, 0 <= offset < 2^24): a sum below 0
 // or beyond 2^31 - 1 wraps to a value >= 2^31 > W, H, so the one unsigned comparison per axis gates every read for any origin, and
 // no signed sum can overflow.
-__device__ __forceinline__ void region_tap(const uint8_t* __restrict__ reg, size_t stride, int shrink, int H, int W, unsigned X,
-                                           unsigned Y, float px[3]) {
-    px[0] = px[1] = px[2] = 1.0f;
-    if (Y < (unsigned)H && X < (unsigned)W) {
-        if (shrink == 1) {
-            const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
+//
+// region_tap_u8 hands out the (halved) bytes b[3] and whether the pixel lies inside (b is untouched outside); the COLOUR STAGE of
+// the cut turns them into px[3].  PlainColour is byte / 255; StainColour is THE STAIN RULE's mapped value (include/amyloid_yolo.h),
+// with od, A and T in LDS.  A cut kernel declares `__shared__ typename Colour::Tables tab`, calls colour.load(tab) once (every thread
+// of the workgroup: it holds a barrier) and region_tap(colour, tab, ...) per pixel.
+__device__ __forceinline__ bool region_tap_u8(const uint8_t* __restrict__ reg, size_t stride, int shrink, int H, int W, unsigned X,
+                                              unsigned Y, int b[3]) {
+    if (!(Y < (unsigned)H && X < (unsigned)W)) return false;
+    if (shrink == 1) {
+        const uint8_t* p = reg + (size_t)Y * stride + (size_t)X * 3;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) px[c] = (float)p[c] / 255.0f;
-        } else {
-            const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
-            const uint8_t* p1 = p0 + stride;
+        for (int c = 0; c < 3; ++c) b[c] = p[c];
+    } else {
+        const uint8_t* p0 = reg + (size_t)(2 * Y) * stride + (size_t)(2 * X) * 3;
+        const uint8_t* p1 = p0 + stride;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) px[c] = (float)((p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2) / 255.0f;
-        }
+        for (int c = 0; c < 3; ++c) b[c] = (p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2;
     }
+    return true;
 }
+
+struct PlainColour {
+    struct Tables {};
+    __device__ __forceinline__ void load(Tables&) const {}
+    __device__ __forceinline__ void map(const Tables&, const int b[3], float px[3]) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = (float)b[c] / 255.0f;
+    }
+};
+
+// THE STAIN RULE's mapped value of one channel from its mapped optical density
+__device__ __forceinline__ float stain_value(float o, const float* T) {
+    o = o > 0.0f ? o : 0.0f;
+    o = o < 4.0f ? o : 4.0f;
+    const float u = o * 64.0f;
+    const int k = min((int)u, 255);
+    const float f = u - (float)k;
+    const float t0 = T[k];
+    float x = t0 + f * (T[k + 1] - t0);
+    x = x > 0.0f ? x : 0.0f;
+    return x < 1.0f ? x : 1.0f;
+}
+
+struct StainColour {
+    const ay_stain_params* __restrict__ params;
+    struct Tables {
+        float od[256], A[9], T[257];
+    };
+    __device__ __forceinline__ void load(Tables& t) const {
+        for (int i = threadIdx.x; i < 257; i += blockDim.x) {
+            if (i < 256) t.od[i] = params->od[i];
+            if (i < 9) t.A[i] = params->A[i];
+            t.T[i] = params->T[i];
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void map(const Tables& t, const int b[3], float px[3]) const {
+        const float o0 = t.od[b[0]], o1 = t.od[b[1]], o2 = t.od[b[2]];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = stain_value((o0 * t.A[c] + o1 * t.A[3 + c]) + o2 * t.A[6 + c], t.T);
+    }
+};
+
+template <typename Colour>
+__device__ __forceinline__ void region_tap(const Colour& colour, const typename Colour::Tables& tab, const uint8_t* __restrict__ reg,
+                                           size_t stride, int shrink, int H, int W, unsigned X, unsigned Y, float px[3]) {
+    int b[3];
+    px[0] = px[1] = px[2] = 1.0f;
+    if (region_tap_u8(reg, stride, shrink, H, W, X, Y, b)) colour.map(tab, b, px);
+}
+
+// byte j of a row segment held in dwords (the read streams over a region: ay_tissue.hip, ay_stain.hip)
+__device__ __forceinline__ int byte_of(const uint32_t* w, int j) { return (int)((w[j >> 2] >> (8 * (j & 3))) & 0xffu); }
 
 static inline hipStream_t S(ay_stream_t s) { return (hipStream_t)s; }
 

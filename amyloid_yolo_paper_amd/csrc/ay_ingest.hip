@@ -4,7 +4,7 @@
 //   pad_to_square       centre zero padding, short side             (utils/datasets.py:22-32; PadSquare transforms.py:83-90)
 //   resize              F.interpolate(mode="nearest"): src = min(floor(dst * (float)in / out), in - 1)   (utils/datasets.py:35-37)
 // so the host uploads 3 bytes per pixel instead of 12 and never touches the pixels again.
-#include "ay_common.h"
+#include "ay_cut.h"
 
 namespace ay {
 
@@ -35,77 +35,7 @@ __global__ void __launch_bounds__(256) ingest_u8_kernel(const uint8_t* __restric
     }
 }
 
-// WSI -> tile streaming (crop.py:13-25,44-47): the tiles dzsave(layout='google', tile_size=1536) cuts out of a
-// slide -- edge tiles padded to the full size with the background 255 -- taken straight out of a resident uint8 HWC region
-// (a full-width strip of the slide: one contiguous upload), optionally after the 40x -> 20x halving, then the N1 chain
-// (/255, nearest resize to the network size).  The halving is a 2x2 mean with round-half-up in uint8: pyvips' resize(0.5) is a
-// lanczos3 reduce and the reference then goes through JPEG Q=90, neither is restated (parity unpinned).
-//
-// ONE cut for every region entry point.  Tile t has its origin at Origins::at(t) on the (halved) slide and a side of `tile`; a thread
-// produces V consecutive output pixels of one row (region_tap of ay_common.h per pixel) and stores them as one V-float vector per
-// channel plane: the kernel is bound by its 12 B of stores per output pixel, and a 16-byte store per lane moves them in a quarter of
-// the store instructions of the scalar form.
-struct GridOrigins {   // tile (ty, tx) of a tiles_x-wide grid starts at (tx * step, ty * step); step == tile: dzsave's abutting grid
-    int tiles_x, step;
-    __device__ __forceinline__ void at(size_t t, unsigned& x, unsigned& y) const {
-        x = (unsigned)(t % tiles_x) * (unsigned)step;
-        y = (unsigned)(t / tiles_x) * (unsigned)step;
-    }
-};
-struct ListOrigins {   // tile t starts at xy[t] = (x, y), any int32 pair (wsi.RegionTileStream(tile_mask=...): only the wanted tiles)
-    const int32_t* __restrict__ xy;
-    __device__ __forceinline__ void at(size_t t, unsigned& x, unsigned& y) const {
-        x = (unsigned)xy[2 * t];
-        y = (unsigned)xy[2 * t + 1];
-    }
-};
-
-template <int V, typename Origins>
-__global__ void __launch_bounds__(256) region_tiles_cut_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
-                                                                   int tile, Origins origins, size_t n, int S, float* __restrict__ out) {
-    typedef float vec __attribute__((ext_vector_type(V)));
-    const int H = RH / shrink, W = RW / shrink;  // the (halved) image the tiles lie on
-    const float scale = (float)tile / (float)S;
-    const size_t plane = (size_t)S * S;
-    const int SV = S / V;   // S % V == 0 (launch_cut)
-    const size_t total = n * S * SV;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x0 = (int)(i % SV) * V, y = (int)((i / SV) % S);
-        const size_t t = i / ((size_t)SV * S);
-        unsigned ox, oy;
-        origins.at(t, ox, oy);
-        const unsigned Y = oy + (unsigned)min((int)floorf(y * scale), tile - 1);
-        vec v[3];
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            float px[3];
-            region_tap(reg, stride, shrink, H, W, ox + (unsigned)min((int)floorf((x0 + k) * scale), tile - 1), Y, px);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c][k] = px[c];
-        }
-        float* o = out + t * 3 * plane + (size_t)y * S + x0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(vec*)(o + c * plane) = v[c];
-    }
-}
-
-// the launch of the three region entry points: 16-byte stores where every row of every plane starts on 16 bytes, scalar ones otherwise
-template <typename Origins>
-static int launch_cut(const void* reg, int RH, int RW, size_t stride, int shrink, int tile, Origins origins, size_t n, int out_size,
-                      float* out, ay_stream_t stream) {
-    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out & 15) == 0;
-    const size_t total = n * out_size * (out_size / (vec4 ? 4 : 1));
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (vec4)
-        hipLaunchKernelGGL((region_tiles_cut_u8_kernel<4, Origins>), dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)reg, RH,
-                           RW, stride, shrink, tile, origins, n, out_size, out);
-    else
-        hipLaunchKernelGGL((region_tiles_cut_u8_kernel<1, Origins>), dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)reg, RH,
-                           RW, stride, shrink, tile, origins, n, out_size, out);
-    AY_CHECK_LAUNCH("region_tiles_cut_u8_kernel");
-    return AY_OK;
-}
+// The WSI cut itself (region_tiles_cut_u8_kernel, launch_cut, the origins) lives in ay_cut.h, which ay_stain.hip shares.
 
 }  // namespace ay
 

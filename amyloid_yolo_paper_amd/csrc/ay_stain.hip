@@ -1,0 +1,203 @@
+// Stain normalisation for whole-slide detection (wsi.stain_stats, wsi.StainMap, wsi.detect_region(stain=...), wsi.normalize_region;
+// THE STAIN RULE is stated in include/amyloid_yolo.h and restated in NumPy fp32 by tests/stain_reference.py).
+//
+//   stain_hist_u8_kernel    histograms of the two stain concentrations over the tissue pixels of a resident region: a read stream with
+//                           ay_tissue.hip's choice of loads (16-byte loads when base and stride allow, byte loads otherwise) that
+//                           walks the IMAGE.  A work unit is 16 rows x up to 2048 items; an item is 48 consecutive bytes of a row, 16
+//                           whole pixels (8 of the halved image, with the same bytes of the next row), so that pixel p of the item
+//                           sits at the same bytes in every lane: the unrolled pixel loop extracts at constant positions and its
+//                           branches diverge only on the tissue test.  A lane unmixes the TISSUE pixels of its item (od in LDS, D
+//                           in scalar registers; most of a slide is glass and costs a minimum and a compare) and counts them in the
+//                           workgroup's int32 LDS histograms, which go to the uint64 histogram in memory with integer atomics when
+//                           the workgroup is done, and every HIST_FLUSH units before that: HIST_FLUSH * 16 * 2048 * 16 < 2^31.
+//   stain_apply_u8_kernel   the mapped (halved) image in the uint8 form, one pixel per thread.
+//   The stain CUT is the cut kernel / the views kernel of ay_cut.h instantiated here with StainColour (ay_common.h) as colour stage.
+//
+// Every entry point is kernel launches only: no allocation, no host synchronisation, no memset or copy node, no scratch.
+#include "ay_cut.h"
+
+namespace ay {
+
+constexpr int HIST_BAND = 16;      // rows of a work unit
+constexpr int HIST_ITEM = 48;      // bytes of a row a lane takes at a time: 16 pixels, 8 of the halved image
+constexpr int HIST_XQ = 2048;      // items of a row in a work unit
+constexpr int HIST_FLUSH = 2048;   // units between two flushes of a workgroup: 2048 * 16 * 2048 * 16 pixels = 1.07e9 < 2^31
+constexpr int HIST_WORDS = 2 * AY_STAIN_BINS + 1;
+
+// bytes [o, o + 48) of one row into w[0..11]; bytes at or behind row_bytes read as 0 (they are never part of a counted pixel)
+template <bool WIDE>
+__device__ __forceinline__ void load48(const uint8_t* __restrict__ row, unsigned o, unsigned row_bytes, uint32_t w[12]) {
+    if (WIDE && o + 48 <= row_bytes) {   // row and o are multiples of 16
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const u32x4 a = *(const u32x4*)(row + o + 16 * k);
+            w[4 * k] = a[0], w[4 * k + 1] = a[1], w[4 * k + 2] = a[2], w[4 * k + 3] = a[3];
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < 12; ++d) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const unsigned at = o + 4 * d + b;
+                if (at < row_bytes) v |= (uint32_t)row[at] << (8 * b);
+            }
+            w[d] = v;
+        }
+    }
+}
+
+template <bool WIDE, int SHRINK>
+__global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __restrict__ reg, int H, int W, int RW, size_t stride, int bg,
+                                                             int n_xc, long long units, const ay_stain_params* __restrict__ params,
+                                                             unsigned long long* __restrict__ hist) {
+    __shared__ float od[256];
+    __shared__ int lh[HIST_WORDS];
+    constexpr int BPP = 3 * SHRINK;                          // source bytes of one row per image pixel
+    const int tid = threadIdx.x;
+    od[tid] = params->od[tid];
+    float D[9];                                              // uniform: scalar registers
+#pragma unroll
+    for (int i = 0; i < 9; ++i) D[i] = params->D[i];
+    for (int i = tid; i < HIST_WORDS; i += 256) lh[i] = 0;
+    __syncthreads();
+    const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * BPP;   // bytes of a source row; those that belong to a pixel
+    const unsigned nq = (used + HIST_ITEM - 1) / HIST_ITEM;
+    int cnt = 0, pending = 0;
+    auto flush = [&]() {
+        if (cnt) atomicAdd(&lh[2 * AY_STAIN_BINS], cnt);
+        cnt = 0;
+        __syncthreads();
+        for (int i = tid; i < HIST_WORDS; i += 256) {
+            const int v = lh[i];
+            if (v) {
+                atomicAdd(hist + i, (unsigned long long)v);
+                lh[i] = 0;
+            }
+        }
+        __syncthreads();
+    };
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of flush
+        const unsigned q0 = (unsigned)(u % n_xc) * HIST_XQ, wq = min((unsigned)HIST_XQ, nq - q0);
+        const int y_lo = (int)(u / n_xc) * HIST_BAND, y_hi = min(y_lo + HIST_BAND, H);
+        const unsigned items = (unsigned)(y_hi - y_lo) * wq;
+        for (unsigned i = tid; i < items; i += 256) {
+            const unsigned o = (q0 + i % wq) * HIST_ITEM;
+            const int Y = y_lo + (int)(i / wq);
+            uint32_t w0[12], w1[12];
+            if (SHRINK == 1) {
+                load48<WIDE>(reg + (size_t)Y * stride, o, row_bytes, w0);
+            } else {
+                load48<WIDE>(reg + (size_t)(2 * Y) * stride, o, row_bytes, w0);
+                load48<WIDE>(reg + (size_t)(2 * Y + 1) * stride, o, row_bytes, w1);
+            }
+#pragma unroll
+            for (int p = 0; p < 48 / BPP; ++p) {                 // the pixels of the item lie at the same bytes in every lane
+                const int j = p * BPP;
+                if (o + j >= used) continue;                     // behind the last pixel of the row
+                int b[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    b[c] = SHRINK == 1 ? byte_of(w0, j + c)
+                                       : (byte_of(w0, j + c) + byte_of(w0, j + 3 + c) + byte_of(w1, j + c) + byte_of(w1, j + 3 + c) + 2) >> 2;
+                if (min(min(b[0], b[1]), b[2]) >= bg) continue;  // THE TISSUE RULE: most of a slide is glass
+                ++cnt;
+                const float o0 = od[b[0]], o1 = od[b[1]], o2 = od[b[2]];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const float c = (o0 * D[s] + o1 * D[3 + s]) + o2 * D[6 + s];
+                    // c < 0 ? 0 : min((int)(c * 64), 511), without converting a float beyond the int range
+                    const int bin = c < 0.0f ? 0 : (c < 8.0f ? (int)(c * 64.0f) : AY_STAIN_BINS - 1);
+                    atomicAdd(&lh[s * AY_STAIN_BINS + bin], 1);
+                }
+            }
+        }
+        if (++pending == HIST_FLUSH) {
+            flush();
+            pending = 0;
+        }
+    }
+    flush();
+}
+
+__global__ void __launch_bounds__(256) stain_apply_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
+                                                              StainColour colour, uint8_t* __restrict__ out, size_t out_stride) {
+    __shared__ StainColour::Tables tab;
+    colour.load(tab);
+    const int H = RH / shrink, W = RW / shrink;
+    const size_t total = (size_t)H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const unsigned X = (unsigned)(i % W), Y = (unsigned)(i / W);
+        int b[3];
+        float px[3];
+        if (!region_tap_u8(reg, stride, shrink, H, W, X, Y, b)) continue;   // never: X < W and Y < H
+        colour.map(tab, b, px);
+        uint8_t* o = out + (size_t)Y * out_stride + (size_t)X * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = (uint8_t)(px[c] * 255.0f + 0.5f);
+    }
+}
+
+}  // namespace ay
+
+extern "C" int ay_stain_hist_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int bg_level,
+                                const ay_stain_params* params_device, uint64_t* hist, ay_stream_t stream) {
+    using namespace ay;
+    AY_CHECK_ARG(region_hwc_u8 && params_device && hist, "ay_stain_hist_u8: null");
+    AY_CHECK_ARG(region_h > 0 && region_w > 0 && region_w <= (1 << 30) / 3 && row_stride_bytes >= (size_t)region_w * 3 &&
+                     (shrink == 1 || shrink == 2),
+                 "ay_stain_hist_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && ((uintptr_t)hist & 7) == 0, "ay_stain_hist_u8: bg_level %d, hist %p", bg_level,
+                 (void*)hist);
+    const int H = region_h / shrink, W = region_w / shrink;
+    if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
+    const unsigned nq = ((unsigned)W * 3 * shrink + HIST_ITEM - 1) / HIST_ITEM;
+    const int n_xc = (int)((nq + HIST_XQ - 1) / HIST_XQ);
+    const long long units = (long long)((H + HIST_BAND - 1) / HIST_BAND) * n_xc;
+    const unsigned blocks = (unsigned)(units > 256 * 8 ? 256 * 8 : units);
+    const bool wide = ((uintptr_t)region_hwc_u8 & 15) == 0 && row_stride_bytes % 16 == 0;
+#define AY_STAIN_HIST_LAUNCH(WIDE, SHRINK)                                                                                          \
+    hipLaunchKernelGGL((stain_hist_u8_kernel<WIDE, SHRINK>), dim3(blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, H, W, \
+                       region_w, row_stride_bytes, bg_level, n_xc, units, params_device, (unsigned long long*)hist)
+    if (wide && shrink == 1) AY_STAIN_HIST_LAUNCH(true, 1);
+    else if (wide) AY_STAIN_HIST_LAUNCH(true, 2);
+    else if (shrink == 1) AY_STAIN_HIST_LAUNCH(false, 1);
+    else AY_STAIN_HIST_LAUNCH(false, 2);
+#undef AY_STAIN_HIST_LAUNCH
+    AY_CHECK_LAUNCH("stain_hist_u8_kernel");
+    return AY_OK;
+}
+
+extern "C" int ay_ingest_region_tiles_stain_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                               int tile, const int32_t* origins_xy, int n, const int* views, int n_views,
+                                               const ay_stain_params* params_device, int out_size, float* out_nchw, ay_stream_t stream) {
+    using namespace ay;
+    AY_CHECK_ARG(region_hwc_u8 && out_nchw && origins_xy && views && params_device, "ay_ingest_region_tiles_stain_u8: null");
+    AY_CHECK_ARG(region_h > 0 && region_w > 0 && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2),
+                 "ay_ingest_region_tiles_stain_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    AY_CHECK_ARG(tile > 0 && tile <= (1 << 24) && n > 0 && out_size > 0, "ay_ingest_region_tiles_stain_u8: %d tiles of %d -> %d", n, tile,
+                 out_size);
+    if (n_views == 1 && views[0] == 0)   // the list cut's geometry and kernel
+        return launch_cut(region_hwc_u8, region_h, region_w, row_stride_bytes, shrink, tile, ListOrigins{origins_xy}, (size_t)n, out_size,
+                          out_nchw, stream, StainColour{params_device});
+    return launch_views(region_hwc_u8, region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, views, n_views, out_size, out_nchw,
+                        stream, StainColour{params_device}, "ay_ingest_region_tiles_stain_u8");
+}
+
+extern "C" int ay_stain_apply_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                 const ay_stain_params* params_device, uint8_t* out_hwc_u8, size_t out_stride_bytes, ay_stream_t stream) {
+    using namespace ay;
+    AY_CHECK_ARG(region_hwc_u8 && params_device && out_hwc_u8, "ay_stain_apply_u8: null");
+    AY_CHECK_ARG(region_h > 0 && region_w > 0 && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2),
+                 "ay_stain_apply_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    const int H = region_h / shrink, W = region_w / shrink;
+    AY_CHECK_ARG(out_stride_bytes >= (size_t)W * 3, "ay_stain_apply_u8: out rows of %d pixels %zu bytes apart", W, out_stride_bytes);
+    if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
+    const size_t total = (size_t)H * W;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipLaunchKernelGGL(stain_apply_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, region_h, region_w,
+                       row_stride_bytes, shrink, StainColour{params_device}, out_hwc_u8, out_stride_bytes);
+    AY_CHECK_LAUNCH("stain_apply_u8_kernel");
+    return AY_OK;
+}

@@ -42,7 +42,7 @@ __device__ __forceinline__ void load24(const uint8_t* __restrict__ row, unsigned
     }
 }
 
-__device__ __forceinline__ int byte_of(const uint32_t w[6], int j) { return (int)((w[j >> 2] >> (8 * (j & 3))) & 0xffu); }
+// byte_of (ay_common.h): byte j of such a segment, shared with the stain histogram
 
 // tiles (per axis) that contain the interval [lo, hi), which no tile boundary cuts: t * step <= lo and hi <= t * step + tile
 __device__ __forceinline__ void tile_range(int lo, int hi, int tile, int step, int tiles, int& t_lo, int& t_hi) {

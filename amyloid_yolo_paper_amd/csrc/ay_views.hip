@@ -17,91 +17,11 @@
 //
 // Every entry point is kernel launches only: no allocation, no host synchronisation, no memset or copy node, no scratch.
 #include "ay_box.h"
-#include "ay_common.h"
+#include "ay_cut.h"
 
 namespace ay {
 
-constexpr int VIEW_BLOCK = 32;   // side of the block of I0 a workgroup holds
-constexpr int VIEW_PITCH = 33;   // floats between its rows in LDS
-
-struct ViewList {
-    int n;
-    int v[8];
-};
-
-// 1 <= n_views <= 8, distinct ids in 0 .. 7
-static bool take_views(const int* views, int n_views, ViewList* out) {
-    if (!views || n_views < 1 || n_views > 8) return false;
-    unsigned seen = 0;
-    out->n = n_views;
-    for (int i = 0; i < 8; ++i) out->v[i] = 0;
-    for (int i = 0; i < n_views; ++i) {
-        const int v = views[i];
-        if (v < 0 || v > 7 || (seen >> v & 1u)) return false;
-        seen |= 1u << v;
-        out->v[i] = v;
-    }
-    return true;
-}
-
-template <int V>
-__global__ void __launch_bounds__(256) region_tiles_views_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
-                                                                     int tile, const int32_t* __restrict__ origins, int n, ViewList views,
-                                                                     int S, float* __restrict__ out) {
-    typedef float vec __attribute__((ext_vector_type(V)));
-    __shared__ float blk[3][VIEW_BLOCK][VIEW_PITCH];
-    const int H = RH / shrink, W = RW / shrink;
-    const float scale = (float)tile / (float)S;
-    const size_t plane = (size_t)S * S;
-    const int nb = (S + VIEW_BLOCK - 1) / VIEW_BLOCK;
-    const size_t per_tile = (size_t)nb * nb;
-    const size_t total = (size_t)n * per_tile;
-    const int tid = threadIdx.x;
-    for (size_t b = blockIdx.x; b < total; b += gridDim.x) {   // the same trip count for the whole workgroup: the barriers are safe
-        const size_t t = b / per_tile;
-        const int rem = (int)(b % per_tile);
-        const int r0 = (rem / nb) * VIEW_BLOCK, c0 = (rem % nb) * VIEW_BLOCK;      // the block of I0: rows r0 .., columns c0 ..
-        const int h = min(VIEW_BLOCK, S - r0), w = min(VIEW_BLOCK, S - c0);
-        const unsigned ox = (unsigned)origins[2 * t], oy = (unsigned)origins[2 * t + 1];
-        // ---- I0: the tap of the cut kernel (region_tap, ay_common.h) ----
-        for (int i = tid; i < VIEW_BLOCK * VIEW_BLOCK; i += 256) {
-            const int ly = i >> 5, lx = i & 31;
-            if (ly >= h || lx >= w) continue;
-            float px[3];
-            region_tap(reg, stride, shrink, H, W, ox + (unsigned)min((int)floorf((c0 + lx) * scale), tile - 1),
-                       oy + (unsigned)min((int)floorf((r0 + ly) * scale), tile - 1), px);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) blk[c][ly][lx] = px[c];
-        }
-        __syncthreads();
-        // ---- the block in every view: a rows x cols rectangle at (Y0, X0), lanes along its rows ----
-        for (int vi = 0; vi < views.n; ++vi) {
-            const int v = views.v[vi];
-            const bool FX = v & 1, FY = (v >> 1) & 1, T = (v >> 2) & 1;
-            const int xs = FX ? S - (c0 + w) : c0;      // where the block's columns / rows land along the axis they map to
-            const int ys = FY ? S - (r0 + h) : r0;
-            const int rows = T ? w : h, cols = T ? h : w;
-            const int Y0 = T ? xs : ys, X0 = T ? ys : xs;
-            float* o = out + ((t * views.n + vi) * 3) * plane + (size_t)Y0 * S + X0;
-            constexpr int QPR = VIEW_BLOCK / V;                      // lane groups per row
-            constexpr int ITEMS = 3 * VIEW_BLOCK * QPR;
-#pragma unroll 1
-            for (int item = tid; item < ITEMS; item += 256) {
-                const int xo = (item % QPR) * V, ro = (item / QPR) % VIEW_BLOCK, c = item / (QPR * VIEW_BLOCK);
-                if (ro >= rows || xo >= cols) continue;              // cols % V == 0 (V == 4 only when S % 4 == 0)
-                vec val;
-#pragma unroll
-                for (int k = 0; k < V; ++k) {
-                    const int a = T ? ro : xo + k, bb = T ? xo + k : ro;   // (a, b) of the rule, relative to the rectangle
-                    const int lx = FX ? w - 1 - a : a, ly = FY ? h - 1 - bb : bb;
-                    val[k] = blk[c][ly][lx];
-                }
-                *(vec*)(o + c * plane + (size_t)ro * S + xo) = val;
-            }
-        }
-        __syncthreads();
-    }
-}
+// VIEW_BLOCK, ViewList, take_views, region_tiles_views_u8_kernel and launch_views live in ay_cut.h, which ay_stain.hip shares.
 
 __global__ void __launch_bounds__(256) unview_rows_kernel(float* __restrict__ pred, size_t total, int N, int K, ViewList views, float Sf) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -217,21 +137,8 @@ extern "C" int ay_ingest_region_tiles_views_u8(const void* region_hwc_u8, int re
                  "ay_ingest_region_tiles_views_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
     AY_CHECK_ARG(tile > 0 && tile <= (1 << 24) && n > 0 && out_size > 0, "ay_ingest_region_tiles_views_u8: %d tiles of %d -> %d", n, tile,
                  out_size);
-    ViewList vl;
-    AY_CHECK_ARG(take_views(views, n_views, &vl), "ay_ingest_region_tiles_views_u8: need 1 .. 8 distinct view ids in 0 .. 7 (n_views %d)",
-                 n_views);
-    const bool vec4 = out_size % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;   // every row of every plane of every view then starts on 16 bytes
-    const size_t nb = (size_t)(out_size + VIEW_BLOCK - 1) / VIEW_BLOCK;
-    size_t blocks = (size_t)n * nb * nb;
-    if (blocks > (1u << 20)) blocks = 1u << 20;
-    if (vec4)
-        hipLaunchKernelGGL(region_tiles_views_u8_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
-                           region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, vl, out_size, out_nchw);
-    else
-        hipLaunchKernelGGL(region_tiles_views_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
-                           region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, vl, out_size, out_nchw);
-    AY_CHECK_LAUNCH("region_tiles_views_u8_kernel");
-    return AY_OK;
+    return launch_views(region_hwc_u8, region_h, region_w, row_stride_bytes, shrink, tile, origins_xy, n, views, n_views, out_size, out_nchw,
+                        stream, PlainColour{}, "ay_ingest_region_tiles_views_u8");
 }
 
 extern "C" int ay_unview_rows(float* pred, int n_images, const int* views, int n_views, int n_rows, int num_classes, int img_dim,

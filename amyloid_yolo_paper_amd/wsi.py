@@ -28,6 +28,10 @@ What a slide carries: :func:`burden_map` bins the rows of a slide into class cou
 :func:`densest_fields` picks the densest microscope-sized fields of every class (``ay_field_select``, THE FIELD RULE), and
 :func:`quantify_region` joins them with :func:`detect_region` and the tissue of every map cell into counts and densities per slide.
 
+Stain: :func:`stain_stats` unmixes the tissue pixels of a slide into hematoxylin and DAB (``ay_stain_hist_u8``, THE STAIN RULE),
+:class:`StainMap` turns its strengths and a target's into gains, and ``detect_region(stain=...)`` cuts every tile through the colour
+map (``ay_ingest_region_tiles_stain_u8``); :func:`normalize_region` gives the mapped raster itself.
+
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
 import math
@@ -105,10 +109,16 @@ class RegionTileStream:
     ``views`` (default ``(0,)``: the tile as it lies on the slide): a list of distinct dihedral view ids 0..7 (``views.py``, THE VIEW
     RULE in ``include/amyloid_yolo.h``).  With any other list every tile is cut in each of the ``V`` views by
     ``ay_ingest_region_tiles_views_u8`` -- the strip is read once for all of them -- and a strip yields ``[n * V, 3, S, S]``,
-    tile-major (tile ``i`` in view ``views[j]`` is image ``i * V + j``), with the coordinates of the ``n`` tiles."""
+    tile-major (tile ``i`` in view ``views[j]`` is image ``i * V + j``), with the coordinates of the ``n`` tiles.
 
-    def __init__(self, raster, tile=1536, img_size=1024, shrink=1, overlap=0, tile_mask=None, views=(0,)):
+    ``stain`` (default ``None``: ``byte / 255``, the present cut): a :class:`StainMap`.  Every tile, masked or not, in any list of
+    views, is then cut by ``ay_ingest_region_tiles_stain_u8``, which stores THE STAIN RULE's mapped value instead."""
+
+    def __init__(self, raster, tile=1536, img_size=1024, shrink=1, overlap=0, tile_mask=None, views=(0,), stain=None):
         self.views = check_views(views)
+        if stain is not None and not isinstance(stain, StainMap):
+            raise ValueError(f"stain: need a wsi.StainMap or None, got {type(stain).__name__}")
+        self.stain = stain
         if not torch.cuda.is_available():
             raise _lib.AyError("no HIP device: RegionTileStream has no CPU fallback")
         assert raster.ndim == 3 and raster.shape[2] == 3 and raster.dtype == np.uint8, "uint8 [H,W,3] raster"
@@ -222,6 +232,12 @@ class RegionTileStream:
 
     def _ingest_list(self, L, k, n, w, origins, m, out):
         """tiles ``origins[:m]`` of the block in ``_strips[k]`` -> ``out[:m * V]``, every tile in the stream's views"""
+        if self.stain is not None:
+            ids = (C.c_int * len(self.views))(*self.views)
+            check(L.ay_ingest_region_tiles_stain_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, ids,
+                                                    len(ids), ptr(self.stain.params), self.S, ptr(out), _lib.stream_ptr()),
+                  "ay_ingest_region_tiles_stain_u8")
+            return
         if self.views != (0,):
             ids = (C.c_int * len(self.views))(*self.views)
             check(L.ay_ingest_region_tiles_views_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, ids,
@@ -236,12 +252,12 @@ class RegionTileStream:
         if self.tile_mask is not None:
             table, starts = self._wanted_table()
             coords = self._wanted()
-        elif self.views != (0,):     # the views entry takes a list of origins: those of a full tile row
+        elif self.views != (0,) or self.stain is not None:     # the views and stain entries take a list of origins: those of a full tile row
             row = torch.tensor([(i * self.step, 0) for i in range(self.tiles_x)], dtype=torch.int32, device=self.dev)
         for j, k, valid, width in self._strip_loop():
             if self.tile_mask is None:
                 out = torch.empty(self.tiles_x * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
-                if self.views != (0,):
+                if self.views != (0,) or self.stain is not None:
                     self._ingest_list(L, k, valid, width, row, self.tiles_x, out)
                 else:    # the grid origins are computed, not read: faster than the list entry; overlap == 0 is step == tile
                     check(L.ay_ingest_region_tiles_step_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile,
@@ -333,7 +349,7 @@ def tissue_mask(raster, tile, shrink=1, overlap=0, min_tissue=0.01, bg_level=220
 
 def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=0.8, nms_thres=0.4, batch_size=64, overlap=0,
                   seam_thres=0.5, max_det=1024, seam_capacity=None, tile_mask=None, min_tissue=0.0, bg_level=220, probe_stride=16,
-                  views=(0,), min_views=1, vote_thres=None):
+                  views=(0,), min_views=1, vote_thres=None, stain=None):
     """Detection over a whole raster: the loop of ``detect.py:88-105`` fed by :class:`RegionTileStream`.
 
     Returns a list of ``(ty, tx, boxes)`` with ``boxes [n,7]`` = (x1, y1, x2, y2, conf, cls_conf, cls_pred) in pixels of the
@@ -374,7 +390,14 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
     a box, and an error the network makes in every orientation gets every vote.  The views only agree as far as the model is
     equivariant: for a model that is not (one trained without ``augment=True``), the merged boxes and the votes depend on which
     views are listed and on their order only through the rows the network returns -- the same list always gives the same bytes,
-    another list may give another result.  With the defaults nothing of this is called and the result is unchanged, bit for bit."""
+    another list may give another result.  With the defaults nothing of this is called and the result is unchanged, bit for bit.
+
+    ``stain`` (default ``None``; a :class:`StainMap`, e.g. ``StainMap(stain_stats(raster), stain_stats(training_slide).strength())``)
+    brings the slide's stain strengths to those the model was trained on: every tile is cut through THE STAIN RULE's colour map
+    (``include/amyloid_yolo.h``) instead of ``byte / 255``, on the masked, unmasked, overlap and views paths alike; the tissue probe
+    of ``min_tissue`` still looks at the raster's own colours.  With ``None`` nothing of it is called."""
+    if stain is not None and not isinstance(stain, StainMap):
+        raise ValueError(f"detect_region: stain must be a wsi.StainMap or None, got {type(stain).__name__}")
     views = check_views(views)
     if isinstance(min_views, bool) or int(min_views) != min_views or not 1 <= int(min_views) <= len(views):
         raise ValueError(f"detect_region: min_views {min_views!r} outside 1 .. {len(views)} (the number of views)")
@@ -387,7 +410,7 @@ def detect_region(model, raster, tile=1536, img_size=1024, shrink=1, conf_thres=
     if tile_mask is not None and not check_tile_mask(tile_mask, H, W, tile, overlap).any():
         return []
     per_call = int(batch_size) if tta is None else max(1, int(batch_size) // len(views))   # tiles per model call: at most batch_size images
-    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask, views)
+    stream = RegionTileStream(raster, tile, img_size, shrink, overlap, tile_mask, views, stain)
     model.eval()
     if overlap:
         return _detect_region_overlap(model, stream, per_call, conf_thres, nms_thres, seam_thres, int(max_det), seam_capacity, tta)
@@ -573,7 +596,8 @@ def densest_fields(counts, tissue=None, field=8, top_k=5, need_tissue=0):
     return fields.cpu().numpy(), n_found.cpu().numpy()
 
 
-def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, **detect_region_kwargs):
+def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
+                    dab_thres=None, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
 
     1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
@@ -595,7 +619,22 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
        (``totals`` over the tissue of the whole map) and ``field_density_per_mm2`` [C,top_k]: ``count / (tissue_px * mpp**2 * 1e-6)``
        in float64 on the host, NaN where there is no tissue (and for rows not filled).
 
+    5. With ``stain_stats`` (a :class:`StainStats` of this slide, :func:`stain_stats`) and ``dab_thres`` (an optical density) both
+       given, also ``dab_positive_fraction`` = ``stain_stats.positive_fraction(1, dab_thres)[0]``, the share of tissue pixels whose
+       stain-1 (DAB) concentration reaches the threshold (the classical "amyloid load"), and ``dab_thres`` as it took effect (a
+       multiple of 1/64).  Host arithmetic on the histogram; nothing else changes, and without the two arguments the result has
+       the keys it had.  A ``stain=`` among the keyword arguments reaches :func:`detect_region`; its basis must be the statistics'.
+
     The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
+    if (stain_stats is None) != (dab_thres is None):
+        raise ValueError("quantify_region: stain_stats and dab_thres go together")
+    if stain_stats is not None:
+        if not isinstance(stain_stats, StainStats):
+            raise ValueError(f"quantify_region: stain_stats must be a wsi.StainStats, got {type(stain_stats).__name__}")
+        stain_stats.positive_fraction(1, dab_thres)       # a bad threshold is refused before any launch
+        st = detect_region_kwargs.get("stain")
+        if isinstance(st, StainMap) and st.basis != stain_stats.basis:
+            raise ValueError("quantify_region: stain and stain_stats were made on different bases")
     cell = _whole(cell, 1, BURDEN_MAX_FIELD_SIDE, "quantify_region: cell")
     F = _whole(field, 1, BURDEN_MAX_FIELD_SIDE, "quantify_region: field")
     K = _whole(top_k, 1, BURDEN_MAX_FIELDS, "quantify_region: top_k")
@@ -630,12 +669,212 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
                                np.full(picked.shape[:2], F * cell, np.int64), picked[:, :, 2], picked[:, :, 3]], 2)[filled]
     out = {"rows": rows, "counts": bm["counts"], "tissue": tissue, "fields": fields, "n_found": n_found, "totals": bm["counted"],
            "below": bm["below"], "flagged": bm["flagged"], "flags": bm["flags"]}
+    if stain_stats is not None:
+        out["dab_positive_fraction"], out["dab_thres"] = stain_stats.positive_fraction(1, dab_thres)
     if mpp is not None:
         mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue
         out["density_per_mm2"] = bm["counts"].cpu().numpy().astype(np.float64) / mm2(tissue)[None]
         out["total_density_per_mm2"] = bm["counted"].astype(np.float64) / mm2(np.int64(tissue.sum(dtype=np.int64)))
         out["field_density_per_mm2"] = np.where(filled, fields[:, :, 3], 0).astype(np.float64) / mm2(np.where(filled, fields[:, :, 4], 0))
     return out
+
+
+# ---- stain normalisation: H/DAB statistics, gains, the colour map of the cut ------------------------------------------------------
+STAIN_BINS = 512        # include/amyloid_yolo.h, THE STAIN RULE: bins of 1/64 OD
+
+
+class StainBasis:
+    """Two stain OD vectors (R, G, B), each normalised to unit length; ``M`` (float64 3x3) has them as rows 0 and 1 and their
+    normalised cross product as row 2 (THE STAIN RULE, ``include/amyloid_yolo.h``).  ``ValueError`` for vectors that are not three
+    finite numbers, of length 0, or (nearly) parallel: the basis would be singular."""
+
+    def __init__(self, stain0, stain1):
+        rows = []
+        for v in (stain0, stain1):
+            v = np.asarray(v, np.float64).reshape(-1)
+            if v.shape != (3,) or not np.isfinite(v).all() or not np.linalg.norm(v) > 0:
+                raise ValueError(f"StainBasis: a stain vector is three finite numbers, not all 0 (got {v!r})")
+            rows.append(v / np.linalg.norm(v))
+        cross = np.cross(rows[0], rows[1])
+        if not np.linalg.norm(cross) > 1e-6:
+            raise ValueError("StainBasis: the two stain vectors are parallel: the basis is singular")
+        self.M = np.stack([rows[0], rows[1], cross / np.linalg.norm(cross)])
+        self.M.setflags(write=False)
+
+    def __eq__(self, other):
+        return isinstance(other, StainBasis) and np.array_equal(self.M, other.M)
+
+    def __hash__(self):
+        return hash(self.M.tobytes())
+
+    def __repr__(self):
+        return f"StainBasis({tuple(self.M[0])}, {tuple(self.M[1])})"
+
+
+H_DAB = StainBasis((0.650, 0.704, 0.286), (0.268, 0.570, 0.776))     # Ruifrok & Johnston: hematoxylin, DAB
+
+
+def stain_tables(basis, gains=(1.0, 1.0)):
+    """The tables of THE STAIN RULE, built in float64 and rounded to fp32 once -> ``_lib.StainParams`` (host)"""
+    v = np.arange(256, dtype=np.float64)
+    Minv = np.linalg.inv(basis.M)
+    A = Minv @ np.diag([float(gains[0]), float(gains[1]), 1.0]) @ basis.M
+    k = np.arange(257, dtype=np.float64)
+    T = (256.0 * 10.0 ** (-k / 64.0) - 1.0) / 255.0
+    tabs = [(-np.log10((v + 1.0) / 256.0)), Minv.reshape(-1), A.reshape(-1), T]
+    if not all(np.isfinite(t).all() and np.isfinite(t.astype(np.float32)).all() for t in tabs):
+        raise ValueError("stain_tables: the basis and gains give tables that are not finite in fp32")
+    p = _lib.StainParams()
+    for name, t in zip(("od", "D", "A", "T"), tabs):
+        getattr(p, name)[:] = t.astype(np.float32).tolist()
+    return p
+
+
+def _params_to_device(p, dev):
+    host = torch.from_numpy(np.frombuffer(bytes(p), dtype=np.uint8).copy())
+    return host.to(dev)
+
+
+class StainStats:
+    """Histograms of the two stain concentrations over the tissue pixels of a slide (:func:`stain_stats`): ``hist`` int64 ``[2,
+    512]`` in bins of 1/64 OD (``hist[s, b]``: pixels with ``b / 64 <= c_s < (b + 1) / 64``, negative concentrations in bin 0, those
+    from 8 OD on in bin 511), ``n_tissue`` (every row of ``hist`` sums to it) and the ``basis`` they were unmixed on."""
+
+    def __init__(self, hist, n_tissue, basis=H_DAB):
+        hist = np.asarray(hist)
+        if hist.shape != (2, STAIN_BINS) or hist.dtype.kind not in "iu" or (hist < 0).any():
+            raise ValueError(f"StainStats: hist must be [2, {STAIN_BINS}] non-negative integers")
+        if not isinstance(basis, StainBasis):
+            raise ValueError("StainStats: basis must be a wsi.StainBasis")
+        self.hist, self.n_tissue, self.basis = hist.astype(np.int64), int(n_tissue), basis
+        if (self.hist.sum(1) != self.n_tissue).any():
+            raise ValueError(f"StainStats: every row of hist must sum to n_tissue = {self.n_tissue}")
+
+    def strength(self, p=99.0):
+        """``(q0, q1)``: per stain the upper edge ``(b* + 1) / 64`` of the first bin whose cumulative count reaches ``K = max(1,
+        ceil(p * n / 100))``, the ``p``-th percentile of its concentration over the tissue.  ``ValueError`` without tissue or for
+        ``p`` outside (0, 100]."""
+        p = float(p)
+        if not 0.0 < p <= 100.0:       # a NaN fails both comparisons
+            raise ValueError(f"StainStats.strength: p {p!r} outside (0, 100]")
+        if self.n_tissue == 0:
+            raise ValueError("StainStats.strength: no tissue pixel: a slide without tissue has no stain strength")
+        K = max(1, math.ceil(p * self.n_tissue / 100.0))
+        return tuple((int(np.searchsorted(np.cumsum(self.hist[s]), K, side="left")) + 1) / 64.0 for s in (0, 1))
+
+    def positive_fraction(self, stain=1, thres=0.15):
+        """``(share, j / 64)``: the share of tissue pixels whose concentration of ``stain`` (0 or 1) is at least ``j / 64``, ``j =
+        round(thres * 64)``: the threshold moves to a bin edge and comes back as it took effect.  NaN without tissue."""
+        if stain not in (0, 1):
+            raise ValueError(f"StainStats.positive_fraction: stain {stain!r} is neither 0 nor 1")
+        thres = float(thres)
+        if not 0.0 <= thres < math.inf:
+            raise ValueError(f"StainStats.positive_fraction: thres {thres!r} is no optical density >= 0")
+        j = min(int(round(thres * 64.0)), STAIN_BINS)
+        share = float(self.hist[stain, j:].sum()) / self.n_tissue if self.n_tissue else math.nan
+        return share, j / 64.0
+
+
+class StainMap:
+    """The colour map that brings a slide's stain strengths to a target's (THE STAIN RULE): per stain the gain ``g_s = clip(t_s / q_s,
+    1 / max_gain, max_gain)`` with ``(q0, q1) = source.strength(p)`` and ``(t0, t1)`` the target: a :class:`StainStats` (its
+    ``strength(p)``; it must share the source's basis) or a pair of positive finite strengths, e.g.
+    ``stain_stats(training_slide).strength()``.  There is no built-in target.  ``basis``, if given, must be the source's.
+    ``gains`` is the pair; ``tables`` the host struct; ``params`` the struct on the current device, uploaded on first use."""
+
+    def __init__(self, source, target, p=99.0, max_gain=4.0, basis=None):
+        if not isinstance(source, StainStats):
+            raise ValueError(f"StainMap: source must be a wsi.StainStats, got {type(source).__name__}")
+        if basis is not None and basis != source.basis:
+            raise ValueError("StainMap: basis differs from the basis of the source statistics")
+        max_gain = float(max_gain)
+        if not 1.0 <= max_gain < math.inf:
+            raise ValueError(f"StainMap: max_gain {max_gain!r} must be a finite number >= 1")
+        q = source.strength(p)
+        if isinstance(target, StainStats):
+            if target.basis != source.basis:
+                raise ValueError("StainMap: source and target statistics were made on different bases")
+            t = target.strength(p)
+        else:
+            try:
+                t = tuple(float(v) for v in target)
+            except TypeError:
+                raise ValueError(f"StainMap: target must be a wsi.StainStats or a pair of strengths, got {target!r}") from None
+            if len(t) != 2 or not all(0.0 < v < math.inf for v in t):
+                raise ValueError(f"StainMap: target strengths must be two positive finite numbers, got {target!r}")
+        self._set(source.basis, tuple(min(max(ts / qs, 1.0 / max_gain), max_gain) for ts, qs in zip(t, q)))
+        self.source, self.target, self.p, self.max_gain = source, t, float(p), max_gain
+
+    def _set(self, basis, gains):
+        self.basis, self.gains = basis, gains
+        self.tables = stain_tables(basis, gains)
+        self._params = {}
+
+    @classmethod
+    def identity(cls, basis=H_DAB):
+        """gains (1, 1) on ``basis``: the map that returns every uint8 value (for tests, and for the statistics' unmixing tables)"""
+        if not isinstance(basis, StainBasis):
+            raise ValueError("StainMap.identity: basis must be a wsi.StainBasis")
+        self = cls.__new__(cls)
+        self._set(basis, (1.0, 1.0))
+        self.source, self.target, self.p, self.max_gain = None, None, None, None
+        return self
+
+    @property
+    def params(self):
+        if not torch.cuda.is_available():
+            raise _lib.AyError("no HIP device: the stain map has no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if dev not in self._params:
+            self._params[dev] = _params_to_device(self.tables, dev)
+        return self._params[dev]
+
+
+def stain_stats(raster, shrink=1, bg_level=220, probe_stride=16, basis=H_DAB):
+    """Stain statistics of a slide -> :class:`StainStats`: the two concentration histograms over its TISSUE pixels (THE TISSUE RULE
+    with ``bg_level``), by ``ay_stain_hist_u8``.  The probe is :func:`tissue_mask`'s: every ``probe_stride``-th pixel of the (halved)
+    slide, single source pixels (:func:`probe_view`); ``probe_stride=1`` is the exact rule, the 2x2 means of ``shrink=2`` included,
+    at the cost of a full upload.  The strips of :class:`RegionTileStream` accumulate on the device; one read-back at the end."""
+    bg_level, d = int(bg_level), int(probe_stride)
+    if not 0 <= bg_level <= 256:
+        raise ValueError(f"stain_stats: bg_level {bg_level} outside 0 .. 256")
+    if d < 1:
+        raise ValueError(f"stain_stats: probe_stride {d} must be at least 1")
+    if not isinstance(basis, StainBasis):
+        raise ValueError("stain_stats: basis must be a wsi.StainBasis")
+    if d > 1:
+        raster, shrink = probe_view(raster, d, shrink, 0, d)[0], 1
+    params = StainMap.identity(basis).params
+    stream = RegionTileStream(raster, min(1536, max(1, raster.shape[0] // shrink)), 1, shrink)
+    L = _lib.lib()
+    hist = torch.zeros(2 * STAIN_BINS + 1, device=stream.dev, dtype=torch.int64)
+    for j, k, valid, width in stream._strip_loop():
+        check(L.ay_stain_hist_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, bg_level, ptr(params), ptr(hist),
+                                 _lib.stream_ptr()), "ay_stain_hist_u8")
+        stream._release(k)
+    h = hist.cpu().numpy()
+    return StainStats(h[:2 * STAIN_BINS].reshape(2, STAIN_BINS), h[2 * STAIN_BINS], basis)
+
+
+def normalize_region(raster, stain, shrink=1, device=False):
+    """The (halved) raster through the stain map, in THE STAIN RULE's uint8 form -> uint8 ``[H // shrink, W // shrink, 3]``: a NumPy
+    array, or with ``device=True`` a tensor on the device (:class:`SlideSampler` reads device rasters in place: the way to train on
+    normalised slides; also for a look at the result).  Strip by strip through ``ay_stain_apply_u8``."""
+    if not isinstance(stain, StainMap):
+        raise ValueError(f"normalize_region: stain must be a wsi.StainMap, got {type(stain).__name__}")
+    if getattr(raster, "ndim", 0) != 3 or raster.shape[0] // shrink < 1 or raster.shape[1] // shrink < 1:
+        raise ValueError("normalize_region: raster must be a uint8 [H,W,3] array with at least one (halved) pixel")
+    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
+    stream = RegionTileStream(raster, min(1536, H), 1, shrink)
+    L = _lib.lib()
+    params = stain.params
+    out = torch.empty(H, W, 3, device=stream.dev, dtype=torch.uint8)
+    for j, k, valid, width in stream._strip_loop():
+        if valid // shrink:
+            check(L.ay_stain_apply_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, ptr(params),
+                                      ptr(out[j * stream.tile:]), W * 3, _lib.stream_ptr()), "ay_stain_apply_u8")
+        stream._release(k)
+    return out if device else out.cpu().numpy()
 
 
 # ---- training windows out of annotated slides ------------------------------------------------------------------------------------

@@ -786,6 +786,66 @@ size_t ay_field_select_workspace_bytes(int num_classes, int gy, int gx, int fiel
 int ay_field_select(const int32_t* counts, int num_classes, int gy, int gx, const int32_t* tissue, int field, int need_tissue, int top_k,
                     int32_t* fields, int32_t* n_found, void* workspace, size_t workspace_bytes, ay_stream_t stream);
 
+/* ---- stain normalisation for whole-slide detection (wsi.stain_stats, wsi.StainMap, wsi.detect_region(stain=...); csrc/ay_stain.hip) --
+ * Amyloid IHC slides are hematoxylin + DAB and differ in stain strength from batch to batch and from scanner to scanner.  The slide's
+ * optical densities are unmixed on a fixed two-stain basis, each stain is scaled by a gain that brings its strength to a target's,
+ * and the result is mixed again: a per-pixel colour map, fused into the region cut.  PARITY WITH ANY OUTSIDE STAIN-NORMALISATION
+ * PACKAGE IS UNPINNED: the behaviour is defined by the rule below and restated in NumPy fp32 by tests/stain_reference.py.
+ *
+ * THE STAIN RULE (every device operation IEEE fp32, in the order written, nothing fused; no transcendental on the device).
+ *   The pixel is (b0, b1, b2), the uint8 values of the (halved) image; for shrink == 2 the ingest's 2x2 round-half-up means.
+ *   Tables (ay_stain_params, built on the host in float64, rounded to fp32 once, uploaded once per slide):
+ *     od[256]   od[v] = fp32(-log10((v + 1) / 256));  od[255] == 0.
+ *     M         3 x 3: rows 0 and 1 the unit OD vectors of stain 0 and stain 1, row 2 their normalised cross product.  The default
+ *               basis H_DAB is Ruifrok's hematoxylin (0.650, 0.704, 0.286) and DAB (0.268, 0.570, 0.776), each normalised.
+ *     D[9]      fp32(inv(M)), row-major.
+ *     A[9]      fp32(inv(M) . diag(g0, g1, 1) . M), row-major, from the float64 factors; g0, g1 the gains.
+ *     T[257]    T[k] = fp32((256 * 10^(-k / 64) - 1) / 255);  T[0] == 1.
+ *   On the device, with o_c = od[b_c]:
+ *     Concentration of stain s in {0, 1}:  c_s = (o_0 * D[0*3+s] + o_1 * D[1*3+s]) + o_2 * D[2*3+s].
+ *     Bin of c_s (512 bins of 1/64 OD):    c_s < 0 ? 0 : min((int)(c_s * 64), 511).  With H_DAB no uint8 pixel exceeds 4.55; the
+ *                                          clamp is for user bases.
+ *     Mapped value of channel c:
+ *       o'_c = (o_0 * A[0*3+c] + o_1 * A[1*3+c]) + o_2 * A[2*3+c]
+ *       u    = min(max(o'_c, 0), 4) * 64   (evaluated as o > 0 ? o : 0, then o < 4 ? o : 4),  k = min((int)u, 255),  f = u - (float)k
+ *       x_c  = T[k] + f * (T[k+1] - T[k])
+ *       x_c  = min(max(x_c, 0), 1)         (x > 0 ? x : 0, then x < 1 ? x : 1)
+ *     What lies outside the region stays exactly 1.0f (it is not mapped; the rule gives 1.0f for 255 as well).
+ *     uint8 form: (uint8)(x_c * 255.0f + 0.5f).
+ *   On the host (float64):
+ *     Strength of stain s at percentile p (0 < p <= 100) over the n tissue pixels of a histogram: K = max(1, ceil(p * n / 100)),
+ *       b* the first bin whose cumulative count reaches K, q_s = (b* + 1) / 64.  n == 0 is an error.
+ *     Gain: g_s = clip(t_s / q_s, 1 / max_gain, max_gain), t_s the target's strength.
+ *   The table is piecewise linear in 1/64-OD steps: against the exact exponential its error is at most (ln 10 / 64)^2 / 8 * 256 / 255
+ *   = 1.63e-4 of full scale (0.04 grey levels); the identity map (gains 1, 1) returns every uint8 value unchanged in the uint8 form.
+ *
+ * ay_stain_hist_u8: for every TISSUE pixel (THE TISSUE RULE with bg_level) of the (halved) image of a resident region, hist[s * 512 +
+ *   bin_s] += 1 for s = 0 and 1 and hist[1024] += 1; hist is uint64 [1025] on the device and is ADDED to: the caller zeroes it, and
+ *   the strips of a slide accumulate with no host synchronisation.  Only od and D of the params are read.  A read stream with
+ *   ay_tile_tissue_u8's choice of loads (16-byte loads when the base and row_stride_bytes are multiples of 16, byte loads otherwise,
+ *   the same counts); od in LDS; per-workgroup int32 histograms in LDS, flushed with 64-bit integer atomics at the latest every 2048
+ *   work units of at most 524288 pixels, so that no LDS counter can overflow; integers only: the same bits every run.
+ * ay_ingest_region_tiles_stain_u8: ay_ingest_region_tiles_views_u8 (views = {0}: ay_ingest_region_tiles_list_u8) with the mapped
+ *   value x_c in place of byte / 255: the same kernels instantiated with another colour stage (od, A and T in LDS), the same
+ *   geometry, argument checks and choice of 16-byte or scalar stores, and nothing outside the region is read.
+ * ay_stain_apply_u8: the (halved) image, mapped, in the uint8 form: out [region_h / shrink][region_w / shrink][3] uint8, rows
+ *   out_stride_bytes apart.
+ * All three: kernel launches only (capturable), no scratch. */
+#define AY_STAIN_BINS 512
+typedef struct ay_stain_params {
+    float od[256];
+    float D[9];
+    float A[9];
+    float T[257];
+} ay_stain_params;
+int ay_stain_hist_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int bg_level,
+                     const ay_stain_params* params_device, uint64_t* hist, ay_stream_t stream);
+int ay_ingest_region_tiles_stain_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                                    int tile, const int32_t* origins_xy, int n, const int* views, int n_views,
+                                    const ay_stain_params* params_device, int out_size, float* out_nchw, ay_stream_t stream);
+int ay_stain_apply_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
+                      const ay_stain_params* params_device, uint8_t* out_hwc_u8, size_t out_stride_bytes, ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call (the once-per-slide calls ay_seam_merge and ay_slide_match excepted:
  * they memset, read a few words back and synchronise the stream, and are not for capture; ay_burden_bin and ay_field_select, also
