@@ -24,28 +24,7 @@ constexpr int HIST_XQ = 2048;      // items of a row in a work unit
 constexpr int HIST_FLUSH = 2048;   // units between two flushes of a workgroup: 2048 * 16 * 2048 * 16 pixels = 1.07e9 < 2^31
 constexpr int HIST_WORDS = 2 * AY_STAIN_BINS + 1;
 
-// bytes [o, o + 48) of one row into w[0..11]; bytes at or behind row_bytes read as 0 (they are never part of a counted pixel)
-template <bool WIDE>
-__device__ __forceinline__ void load48(const uint8_t* __restrict__ row, unsigned o, unsigned row_bytes, uint32_t w[12]) {
-    if (WIDE && o + 48 <= row_bytes) {   // row and o are multiples of 16
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const u32x4 a = *(const u32x4*)(row + o + 16 * k);
-            w[4 * k] = a[0], w[4 * k + 1] = a[1], w[4 * k + 2] = a[2], w[4 * k + 3] = a[3];
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < 12; ++d) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const unsigned at = o + 4 * d + b;
-                if (at < row_bytes) v |= (uint32_t)row[at] << (8 * b);
-            }
-            w[d] = v;
-        }
-    }
-}
+// load48 (ay_common.h): the item's bytes, shared with the load pass
 
 template <bool WIDE, int SHRINK>
 __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __restrict__ reg, int H, int W, int RW, size_t stride, int bg,

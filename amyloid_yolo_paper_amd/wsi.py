@@ -32,6 +32,10 @@ Stain: :func:`stain_stats` unmixes the tissue pixels of a slide into hematoxylin
 :class:`StainMap` turns its strengths and a target's into gains, and ``detect_region(stain=...)`` cuts every tile through the colour
 map (``ay_ingest_region_tiles_stain_u8``); :func:`normalize_region` gives the mapped raster itself.
 
+Amyloid load: :func:`stain_load` classifies every pixel of a slide (tissue, DAB-positive) and sums it per map cell and per detection
+box (``ay_stain_load_u8``, THE LOAD RULE); :func:`box_morphometry` turns the box sums into areas, fill and mean optical density,
+and ``quantify_region(load=True)`` puts the load map next to the count maps.
+
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
 import math
@@ -597,7 +601,7 @@ def densest_fields(counts, tissue=None, field=8, top_k=5, need_tissue=0):
 
 
 def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
-                    dab_thres=None, **detect_region_kwargs):
+                    dab_thres=None, load=False, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
 
     1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
@@ -625,8 +629,20 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
        multiple of 1/64).  Host arithmetic on the histogram; nothing else changes, and without the two arguments the result has
        the keys it had.  A ``stain=`` among the keyword arguments reaches :func:`detect_region`; its basis must be the statistics'.
 
+    6. With ``load=True`` (``dab_thres`` is then required, ``stain_stats`` stays optional; ``cell >= 16``) one more pass over the
+       raster, ``stain_load(raster, rows, cell, shrink, bg_level, dab_thres, 1, basis)`` -- exact and at full resolution whatever
+       ``probe_stride`` is; the basis is the statistics', else the ``stain=`` map's, else ``H_DAB`` -- adds ``load_tissue`` and
+       ``load_positive`` int64 [Gy,Gx], ``load_map`` (their ratio, NaN without tissue), ``total_load``, ``box_load`` int64 [M,4] =
+       (pixels, tissue, positive, bin_sum) for ``rows`` (:func:`box_morphometry` makes areas of it) and ``field_load`` float64
+       [C,top_k]: positive over tissue, summed on the host over the cells of every picked field, NaN for rows not filled and for a
+       field without tissue.  The threshold applies to the slide's own concentrations, with or without a ``stain=`` map.
+
     The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
-    if (stain_stats is None) != (dab_thres is None):
+    if load:
+        if dab_thres is None:
+            raise ValueError("quantify_region: load=True needs dab_thres")
+        _thres_bin(dab_thres, "quantify_region")
+    elif (stain_stats is None) != (dab_thres is None):
         raise ValueError("quantify_region: stain_stats and dab_thres go together")
     if stain_stats is not None:
         if not isinstance(stain_stats, StainStats):
@@ -650,6 +666,10 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
     shrink, bg_level = int(detect_region_kwargs.get("shrink", 1)), detect_region_kwargs.get("bg_level", 220)
     if getattr(raster, "ndim", 0) != 3 or raster.shape[0] // shrink < 1 or raster.shape[1] // shrink < 1:
         raise ValueError("quantify_region: raster must be a uint8 [H,W,3] array with at least one (halved) pixel")
+    if load:        # refused before any launch, like everything above
+        st = detect_region_kwargs.get("stain")
+        load_basis = stain_stats.basis if stain_stats is not None else st.basis if isinstance(st, StainMap) else H_DAB
+        _check_load("quantify_region", raster, shrink, cell, bg_level, 1, load_basis)
     min_conf = float(min_conf)
     need = max(1, math.ceil(float(field_min_tissue) * (F * cell) ** 2))
     H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
@@ -671,6 +691,16 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
            "below": bm["below"], "flagged": bm["flagged"], "flags": bm["flags"]}
     if stain_stats is not None:
         out["dab_positive_fraction"], out["dab_thres"] = stain_stats.positive_fraction(1, dab_thres)
+    if load:
+        ld = stain_load(raster, rows, cell, shrink, bg_level, dab_thres, 1, load_basis)
+        out["load_tissue"], out["load_positive"], out["load_map"] = ld["tissue"], ld["positive"], ld["load"]
+        out["total_load"], out["box_load"] = ld["total_load"], ld["boxes"]
+        out["field_load"] = np.full((num_classes, K), np.nan)
+        for c, k in zip(*np.nonzero(filled)):
+            fy, fx = int(picked[c, k, 0]), int(picked[c, k, 1])
+            t = int(ld["tissue"][fy:fy + F, fx:fx + F].sum())
+            if t:
+                out["field_load"][c, k] = float(int(ld["positive"][fy:fy + F, fx:fx + F].sum())) / t
     if mpp is not None:
         mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue
         out["density_per_mm2"] = bm["counts"].cpu().numpy().astype(np.float64) / mm2(tissue)[None]
@@ -875,6 +905,122 @@ def normalize_region(raster, stain, shrink=1, device=False):
                                       ptr(out[j * stream.tile:]), W * 3, _lib.stream_ptr()), "ay_stain_apply_u8")
         stream._release(k)
     return out if device else out.cpu().numpy()
+
+
+# ---- amyloid load: stain-positive area per map cell and per detection ---------------------------------------------------------------
+LOAD_MIN_CELL, LOAD_MAX_SIDE, LOAD_FLAG_NONFINITE = 16, 1 << 24, 1       # include/amyloid_yolo.h, THE LOAD RULE
+LOAD_MAX_CELLS = 1 << 26                                                 # 24 bytes per cell on the device
+
+
+def _thres_bin(thres, what):
+    """an optical density -> THE LOAD RULE's ``thres_bin``, as :meth:`StainStats.positive_fraction` moves it to a bin edge"""
+    try:
+        thres = float(thres)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: thres {thres!r} is no optical density >= 0") from None
+    if not 0.0 <= thres < math.inf:       # a NaN fails both comparisons
+        raise ValueError(f"{what}: thres {thres!r} is no optical density >= 0")
+    return min(int(round(thres * 64.0)), STAIN_BINS)
+
+
+def _check_load(what, raster, shrink, cell, bg_level, stain, basis):
+    """the host checks :func:`stain_load` and ``quantify_region(load=True)`` share -> (H, W, cell, bg_level)"""
+    if shrink not in (1, 2):
+        raise ValueError(f"{what}: shrink {shrink!r} is neither 1 nor 2")
+    if getattr(raster, "ndim", 0) != 3 or raster.shape[2] != 3 or raster.dtype != np.uint8:
+        raise ValueError(f"{what}: raster must be a uint8 [H,W,3] array")
+    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: raster {tuple(raster.shape)} has no (halved) pixel")
+    if max(H, W) > LOAD_MAX_SIDE:
+        raise ValueError(f"{what}: a (halved) slide of {H} x {W} exceeds {LOAD_MAX_SIDE} pixels per side")
+    cell = _whole(cell, LOAD_MIN_CELL, 2 ** 31 - 1, f"{what}: cell")
+    gy, gx, _ = tile_grid(H, W, cell)
+    if gy * gx > LOAD_MAX_CELLS:
+        raise ValueError(f"{what}: {gy} x {gx} cells exceed {LOAD_MAX_CELLS}; choose a larger cell")
+    bg_level = _whole(bg_level, 0, 256, f"{what}: bg_level")
+    if isinstance(stain, bool) or stain not in (0, 1):
+        raise ValueError(f"{what}: stain {stain!r} is neither 0 nor 1")
+    if not isinstance(basis, StainBasis):
+        raise ValueError(f"{what}: basis must be a wsi.StainBasis")
+    return H, W, cell, bg_level
+
+
+def stain_load(raster, rows=None, cell=128, shrink=1, bg_level=220, thres=0.15, stain=1, basis=H_DAB):
+    """Amyloid load of a slide (``ay_stain_load_u8``, THE LOAD RULE in ``include/amyloid_yolo.h``): per cell of the grid
+    ``tile_grid(H, W, cell)`` -- :func:`burden_map`'s -- the tissue pixels, the pixels whose concentration of ``stain`` (0 or 1;
+    default 1, DAB on ``H_DAB``) reaches the threshold, and the sum of their bins; with ``rows`` the same inside every box.
+
+    The raster goes ONCE through the strips of :class:`RegionTileStream`, at full resolution, without a probe: the exact rule, the
+    2x2 means of ``shrink=2`` included.  The tables are ``StainMap.identity(basis)``'s (only ``od`` and ``D`` are read); the outputs
+    are zeroed once, every strip adds to them on the device and they are read back once.  ``cell >= 16``; (halved) sides up to 2^24.
+
+    ``thres`` is an optical density; it moves to a bin edge as in :meth:`StainStats.positive_fraction`, ``j = min(round(thres * 64),
+    512)``, and a pixel is positive iff it is tissue and its bin is ``>= j`` (``j == 512``: none).  The threshold applies to the
+    slide's OWN concentrations: for a threshold on the scale a :class:`StainMap` normalises to, pass ``thres / stain_map.gains[s]``.
+
+    ``rows``: None, or ``[M, 7]`` as :func:`detect_region` returns them (concatenated; pixels of the (halved) slide; a tensor or
+    array on the host or the device).  Only the four coordinates are read.  A box owns the pixels whose centre lies in ``[x1, x2) x
+    [y1, y2)``, clamped to the slide; overlapping boxes each count their own pixels; a row with a coordinate that is not finite is
+    flagged and gets zeros.  One box runs on one wavefront: made for detections, correct for any rectangle.
+
+    Returns a dict: ``tissue``, ``positive``, ``bin_sum`` NumPy int64 ``[Gy, Gx]``; ``load`` float64 ``positive / tissue``, NaN where
+    a cell has no tissue; ``total_load`` (``positive.sum() / tissue.sum()``, NaN without tissue: on the same ``bg_level``, ``stain``
+    and ``thres`` exactly ``stain_stats(raster, probe_stride=1).positive_fraction(stain, thres)[0]``); ``thres`` as it took effect
+    (``j / 64``); with ``rows`` also ``boxes`` int64 ``[M, 4]`` = (pixels, tissue, positive, bin_sum) -- :func:`box_morphometry` turns
+    them into areas -- and ``flags`` (bit 1: a coordinate not finite)."""
+    H, W, cell, bg_level = _check_load("stain_load", raster, shrink, cell, bg_level, stain, basis)
+    j = _thres_bin(thres, "stain_load")
+    if rows is not None and (len(getattr(rows, "shape", ())) != 2 or rows.shape[1] != 7):
+        raise ValueError(f"stain_load: rows must be [M,7] or None, got {tuple(getattr(rows, 'shape', ())) or type(rows).__name__}")
+    from .stats import _slide_array
+    stream = RegionTileStream(raster, min(1536, H), 1, shrink)
+    dev = stream.dev
+    params = StainMap.identity(basis).params
+    gy, gx, _ = tile_grid(H, W, cell)
+    cells = torch.zeros(gy, gx, 3, device=dev, dtype=torch.int64)
+    M = 0
+    if rows is not None:
+        rows = _slide_array(rows, 7, dev)
+        M = int(rows.shape[0])
+        boxes = torch.zeros(M, 4, device=dev, dtype=torch.int64)
+        flags = torch.zeros(1, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    for jy, k, valid, width in stream._strip_loop():
+        check(L.ay_stain_load_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, jy * stream.tile, 0, H, W, bg_level,
+                                 ptr(params), int(stain), j, cell, ptr(cells), ptr(rows) if M else None, M, ptr(boxes) if M else None,
+                                 ptr(flags) if M else None, _lib.stream_ptr()), "ay_stain_load_u8")
+        stream._release(k)
+    c = cells.cpu().numpy()
+    tissue, positive, bin_sum = (np.ascontiguousarray(c[:, :, i]) for i in range(3))
+    n_t, n_p = int(tissue.sum()), int(positive.sum())
+    out = {"tissue": tissue, "positive": positive, "bin_sum": bin_sum,
+           "load": positive.astype(np.float64) / np.where(tissue > 0, tissue, np.nan),
+           "total_load": float(n_p) / n_t if n_t else math.nan, "thres": j / 64.0}
+    if rows is not None:
+        out["boxes"], out["flags"] = boxes.cpu().numpy(), int(flags.item())
+    return out
+
+
+def box_morphometry(boxes, mpp=None):
+    """Per-detection morphometry from :func:`stain_load`'s ``boxes`` ``[M, 4]`` = (pixels, tissue, positive, bin_sum); host
+    arithmetic in float64 -> a dict of ``[M]`` arrays:
+    ``area_px`` the positive pixels; ``fill = positive / pixels``; ``mean_od = (bin_sum / positive + 0.5) / 64``, the mean optical
+    density of the positive pixels at the centres of their 1/64-OD bins (bin 511 holds everything from 8 OD on: it saturates); with
+    ``mpp`` (microns per pixel of the (halved) slide) ``area_um2 = area_px * mpp**2`` and ``equiv_diameter_um = 2 * sqrt(area_um2 /
+    pi)``, the diameter of the disc of that area.  NaN where a box has no positive pixel (``fill``: where it owns no pixel)."""
+    b = np.asarray(boxes)
+    if b.ndim != 2 or b.shape[1] != 4 or b.dtype.kind not in "iu" or (b < 0).any():
+        raise ValueError(f"box_morphometry: boxes must be [M, 4] non-negative integers, got {b.dtype} {b.shape}")
+    if mpp is not None and not 0.0 < float(mpp) < math.inf:
+        raise ValueError(f"box_morphometry: mpp {mpp!r} is no positive number of microns per pixel")
+    pixels, positive, bin_sum = (b[:, i].astype(np.float64) for i in (0, 2, 3))
+    some = np.where(positive > 0, positive, np.nan)
+    out = {"area_px": some, "fill": positive / np.where(pixels > 0, pixels, np.nan), "mean_od": (bin_sum / some + 0.5) / 64.0}
+    if mpp is not None:
+        out["area_um2"] = some * float(mpp) ** 2
+        out["equiv_diameter_um"] = 2.0 * np.sqrt(out["area_um2"] / math.pi)
+    return out
 
 
 # ---- training windows out of annotated slides ------------------------------------------------------------------------------------

@@ -846,6 +846,56 @@ int ay_ingest_region_tiles_stain_u8(const void* region_hwc_u8, int region_h, int
 int ay_stain_apply_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                       const ay_stain_params* params_device, uint8_t* out_hwc_u8, size_t out_stride_bytes, ay_stream_t stream);
 
+/* ---- amyloid load: stain-positive area per map cell and per detection (wsi.stain_load, wsi.box_morphometry,
+ *      wsi.quantify_region(load=True); csrc/ay_load.hip) ----------------------------------------------------------------------------------
+ * The field's second read-out next to object counts: the share of tissue area that is DAB-positive, on THE BURDEN RULE's grid, and the
+ * positive pixels inside every detection's box (plaque area, fill, mean optical density).  tests/load_reference.py restates the rule
+ * in NumPy.
+ *
+ * THE LOAD RULE (integers, and the fp32 operations written below, in that order; a function of the inputs alone, the same bytes on
+ *   every run).
+ *   Pixel classes.  A pixel (X, Y) of the (halved) H x W slide is TISSUE by THE TISSUE RULE: min(b0, b1, b2) < bg_level; for shrink ==
+ *     2 the bytes are the ingest's 2x2 round-half-up means.  Its bin q is THE STAIN RULE's bin of c_s for the chosen stain s in {0,
+ *     1}: od, D, the same expression, the same clamp.  It is POSITIVE iff it is tissue and q >= thres_bin; thres_bin is an integer in
+ *     0 .. 512, and 512 makes nothing positive.  The host turns an optical density into thres_bin as StainStats.positive_fraction
+ *     does: min(round(thres * 64), 512).  The threshold applies to the slide's OWN concentrations (a caller who wants it on a
+ *     normalised scale divides it by the stain map's gain); A and T of the params are never read.
+ *   Three sums per entity (a cell or a box): tissue = its tissue pixels, positive = its positive pixels, bin_sum = the sum of q over
+ *     its positive pixels.
+ *   Cells.  The grid is wsi.tile_grid(H, W, cell, 0) over the whole (halved) slide: Gy = ceil(H / cell), Gx = ceil(W / cell); pixel
+ *     (X, Y) belongs to cell (Y / cell, X / cell).  cell >= AY_LOAD_MIN_CELL = 16: the cell pass takes 16 pixels of a row per lane and
+ *     16 rows per work unit, and its on-chip table holds the two cells and two cell rows those can touch.  Output: uint64 [Gy][Gx][3] =
+ *     (tissue, positive, bin_sum).
+ *   Boxes.  Input: rows [M][7] fp32, detect_region's rows in pixels of the (halved) slide; only columns 0 .. 3 = (x1, y1, x2, y2) are
+ *     read.  A row with a coordinate that is not finite sets AY_LOAD_FLAG_NONFINITE in the flags word and gets nothing.  Otherwise, in
+ *     fp32: lo_x = min(max(ceilf(x1 - 0.5f), 0.0f), (float)W), hi_x the same of x2, lo_y and hi_y the same of y1 and y2 with H, then
+ *     each converted to int.  The box OWNS the pixels lo_x <= X < hi_x, lo_y <= Y < hi_y: those whose centre (X + 0.5, Y + 0.5) lies
+ *     in [x1, x2) x [y1, y2).  An inverted or empty box owns none.  H, W <= 2^24, so that (float)W is exact.  Output: uint64 [M][4] =
+ *     (pixels, tissue, positive, bin_sum), pixels the owned pixels that were visited: (hi_x - lo_x) * (hi_y - lo_y) once every strip
+ *     has been seen.  Overlapping boxes are independent: each counts its own pixels.
+ *   Accumulation.  A call sees one resident region (a strip) whose (halved) image has its top-left pixel at (origin_y, origin_x) of
+ *     the slide, both >= 0 and the image inside H x W; the origin need not be a multiple of cell.  The call ADDS to cells and boxes
+ *     and ORs into flags: the caller zeroes them once, visits every pixel of the slide once over the strips and reads back once.
+ *
+ * ay_stain_load_u8: kernel launches only -- no allocation, no memset node, no host read, no scratch -- so it can sit in a captured
+ *   step.  cells == NULL skips the cell pass; n_rows == 0 skips the box pass (rows, boxes and flags may then be NULL).  A region
+ *   without a halved image returns AY_OK.  Refused (-1, nothing launched): a bad shape or stride, shrink outside {1, 2}, bg_level
+ *   outside 0 .. 256, stain outside {0, 1}, thres_bin outside 0 .. 512, cell < AY_LOAD_MIN_CELL (with or without cells), slide_h or
+ *   slide_w outside 1 .. 2^24, a region that does not lie inside the slide, cells or boxes not 8-byte aligned.
+ *   The cell pass is a read stream over the image with ay_stain_hist_u8's items and choice of loads (16-byte loads when the base and
+ *   row_stride_bytes are multiples of 16, byte loads otherwise, the same counts), od in LDS, the chosen stain's three D in scalar
+ *   registers, the tissue test before the unmixing; a lane sums its 16 pixels in registers, a workgroup its unit of 16 rows x 4096
+ *   pixels in an int32 LDS table (at most 65536 * 511 < 2^31 per word), and memory sees one 64-bit integer atomic per (workgroup,
+ *   unit, cell, sum) that is not 0.  The box pass is a gather for detection boxes: one wavefront per box, an integer intersection
+ *   with the region first, at most four 64-bit atomics per box and call.  It is correct for any box, a whole-slide rectangle
+ *   included, but ONE HUGE BOX RUNS ON ONE WAVEFRONT. */
+#define AY_LOAD_MIN_CELL 16
+#define AY_LOAD_FLAG_NONFINITE 1
+int ay_stain_load_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int origin_y,
+                     int origin_x, int slide_h, int slide_w, int bg_level, const ay_stain_params* params_device, int stain, int thres_bin,
+                     int cell, uint64_t* cells /* or NULL */, const float* rows, int n_rows, uint64_t* boxes,
+                     int32_t* flags /* NULL iff n_rows == 0 */, ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call (the once-per-slide calls ay_seam_merge and ay_slide_match excepted:
  * they memset, read a few words back and synchronise the stream, and are not for capture; ay_burden_bin and ay_field_select, also

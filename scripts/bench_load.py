@@ -1,0 +1,137 @@
+"""Cost of the amyloid load pass (THE LOAD RULE, include/amyloid_yolo.h) on the synthetic strip of scripts/bench_stain.py: one
+resident strip of TX 1536-px tiles, one process, five calls taken in turn inside one timed loop:
+  ay_tile_tissue_u8      one tile row (the floor: a minimum and a compare per pixel)
+  ay_stain_hist_u8       the yardstick: the same bytes, both stains unmixed, two LDS adds per tissue pixel
+  ay_stain_load_u8       cells only (cell 128) | boxes only | both
+The strip lies at rows STRIP_ROW .. of a 70 000-px square slide, and the rows are those of scripts/bench_slide_match.py's synthetic
+slide (250 000 boxes of 8..47 px all over the slide: most miss the strip, as most miss any strip of a real slide).
+CALL time: after WARM warm rounds, REPS rounds, two device events around each call; median (min .. max).  Calls are kernel launches
+only, so this is launch overhead plus kernels.  GB/s of READS: 3 B per source pixel of the strip over the median (the box pass
+reads only the pixels of its boxes: for it the figure is not a bandwidth and is not printed).  bg_level 170 as in bench_stain.py.
+WHERE THE BYTES COME FROM: the strip (226 MB at TX = 32) is smaller than the MI355X's 256 MiB last-level cache, and a loop that reads
+one buffer again and again may be served from it, which no strip of wsi.stain_load is (each is uploaded and read once).  So the calls
+rotate over COPIES copies of the strip at different addresses (default 4: between two reads of a copy lie three other calls, of
+which at most one is the box pass: at least 0.45 GB of other copies);
+--copies 1 is the re-read buffer, for comparison.  The ratios between the calls of one run are the yardstick either way.
+usage: timeout 300 python scripts/bench_load.py [TX] [--reps 20] [--warm 3] [--copies 4] [--out profiles/load.txt]
+       (the whole run takes a few seconds; the time limit keeps a hung device from holding a shared machine)"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from amyloid_yolo_paper_amd import _lib, synth
+from amyloid_yolo_paper_amd._lib import check, ptr
+from amyloid_yolo_paper_amd.wsi import StainMap, tile_grid
+
+ap = argparse.ArgumentParser()
+ap.add_argument("tx", nargs="?", type=int, default=32)
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--warm", type=int, default=3)
+ap.add_argument("--copies", type=int, default=4, help="copies of the strip the calls rotate over (1: one buffer, re-read)")
+ap.add_argument("--out", default=None)
+a = ap.parse_args()
+TX, tile, BG, CELL, THRES_BIN, SIDE, STRIP_ROW = a.tx, 1536, 170, 128, 10, 70000, 20 * 1536
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def fmt(ms):
+    return "%.3f ms (%.3f .. %.3f)" % (statistics.median(ms), min(ms), max(ms))
+
+
+def slide_rows(M=250000, T=50000, side=float(SIDE), seed=0):
+    """the rows of scripts/bench_slide_match.py's synthetic_slide (the same draws in the same order)"""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(0, side, (T, 2))
+    tb = np.concatenate([xy, xy + rng.uniform(8, 47, (T, 2))], 1)
+    cls = rng.integers(0, 3, T)
+    g = rng.integers(0, T, M)
+    box = tb[g] + rng.normal(0, 3.0, (M, 4))
+    anywhere = rng.uniform(size=M) < 0.2
+    p = rng.uniform(0, side, (M, 2))
+    box[anywhere] = np.concatenate([p, p + rng.uniform(8, 47, (M, 2))], 1)[anywhere]
+    return np.concatenate([box, rng.uniform(0.5, 1, (M, 2)), cls[g][:, None]], 1).astype(np.float32)
+
+
+dev = torch.device("cuda:0")
+base = (synth.synth_tiles(4, tile, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)     # bench_stain.py's strip
+strip = torch.from_numpy(np.concatenate([base[i % 4] for i in range(TX)], 1)).to(dev)
+strips = [strip] + [strip.clone() for _ in range(a.copies - 1)]
+turn = [0]
+
+
+def next_strip():
+    """the copy this call reads: the one read longest ago"""
+    turn[0] += 1
+    return ptr(strips[turn[0] % len(strips)])
+
+
+H, W = strip.shape[:2]
+assert W <= SIDE and STRIP_ROW + H <= SIDE
+rows_h = slide_rows()
+rows = torch.from_numpy(rows_h).to(dev)
+M = len(rows_h)
+on_strip = int(((rows_h[:, 3] > STRIP_ROW) & (rows_h[:, 1] < STRIP_ROW + H) & (rows_h[:, 2] > 0) & (rows_h[:, 0] < W)).sum())
+say("%s: strip %d x %d, %.3f GB, at row %d of a %d-px square slide; %d rows, about %d of them on the strip; cell %d, thres_bin %d, "
+    "bg_level %d; %d warm + %d timed rounds; the calls rotate over %d cop%s of the strip"
+    % (torch.cuda.get_device_name(0), H, W, strip.numel() / 1e9, STRIP_ROW, SIDE, M, on_strip, CELL, THRES_BIN, BG, a.warm, a.reps, a.copies,
+       "y (one buffer, re-read: it fits the last-level cache)" if a.copies == 1 else "ies"))
+L, sp = _lib.lib(), _lib.stream_ptr()
+params = StainMap.identity().params
+gy, gx, _ = tile_grid(SIDE, SIDE, CELL)
+counts = torch.empty(TX, device=dev, dtype=torch.int32)
+hist = torch.zeros(1025, device=dev, dtype=torch.int64)
+cells = [torch.zeros(gy, gx, 3, device=dev, dtype=torch.int64) for _ in range(2)]            # cells only; both
+boxes = [torch.zeros(M, 4, device=dev, dtype=torch.int64) for _ in range(2)]                 # boxes only; both
+flags = torch.zeros(1, device=dev, dtype=torch.int32)
+
+
+def load(c, b):
+    check(L.ay_stain_load_u8(next_strip(), H, W, W * 3, 1, STRIP_ROW, 0, SIDE, SIDE, BG, ptr(params), 1, THRES_BIN, CELL, ptr(c),
+                             ptr(rows) if b is not None else None, M if b is not None else 0, ptr(b), ptr(flags) if b is not None else None, sp),
+          "ay_stain_load_u8")
+
+
+calls = [("ay_tile_tissue_u8           ", lambda: check(L.ay_tile_tissue_u8(next_strip(), H, W, W * 3, 1, tile, tile, 1, TX, BG, ptr(counts), sp), "tissue")),
+         ("ay_stain_hist_u8            ", lambda: check(L.ay_stain_hist_u8(next_strip(), H, W, W * 3, 1, BG, ptr(params), ptr(hist), sp), "hist")),
+         ("ay_stain_load_u8 cells only ", lambda: load(cells[0], None)),
+         ("ay_stain_load_u8 boxes only ", lambda: load(None, boxes[0])),
+         ("ay_stain_load_u8 cells+boxes", lambda: load(cells[1], boxes[1]))]
+ms = [[] for _ in calls]
+for i in range(a.warm + a.reps):
+    for k, (_, call) in enumerate(calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        if i >= a.warm:
+            ms[k].append(e0.elapsed_time(e1))
+reads = strip.numel()
+for k, (name, _) in enumerate(calls):
+    rate = "" if "boxes only" in name else ", %.0f GB/s of reads" % (reads / statistics.median(ms[k]) / 1e6)
+    say("%s: %s per strip%s" % (name, fmt(ms[k]), rate))
+med = [statistics.median(m) for m in ms]
+say("cells only / ay_stain_hist_u8 = %.2f, cells only / ay_tile_tissue_u8 = %.2f, cells+boxes / cells only = %.2f (medians)"
+    % (med[2] / med[1], med[2] / med[0], med[4] / med[2]))
+spread = lambda m: (max(m) - min(m)) / statistics.median(m)
+say("repeat spread (max - min) / median: hist %.1f %%, cells only %.1f %%" % (100 * spread(ms[1]), 100 * spread(ms[2])))
+# the passes counted the same pixels: tissue three ways, positives against the histogram's tail, the boxes two ways
+n = a.warm + a.reps
+tissue = int(counts.sum())
+assert int(hist[1024]) == tissue * n and int(cells[0][:, :, 0].sum()) == tissue * n and torch.equal(cells[0], cells[1])
+assert int(cells[0][:, :, 1].sum()) == int(hist[512 + THRES_BIN:1024].sum()) and torch.equal(boxes[0], boxes[1]) and int(flags.item()) == 0
+say("tissue pixels of the strip: %d of %d; positive: %d; boxes with a pixel on the strip: %d; the three passes agree" %
+    (tissue, H * W, int(cells[0][:, :, 1].sum()) // n, int((boxes[0][:, 0] > 0).sum())))
+if a.out:
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
