@@ -20,4 +20,10 @@ __device__ __forceinline__ float iou_p1(float ax1, float ay1, float ax2, float a
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.0e38f; }   // false for NaN and +-inf
 
+// THE LOAD RULE's box ownership (ay_load.hip, ay_focus.hip): a coordinate counts iff it is finite, up to FLT_MAX
+__device__ __forceinline__ bool load_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN and +-inf
+
+// THE LOAD RULE's edge of a box: the first pixel whose centre is not left of (above) v, clamped into 0 .. n
+__device__ __forceinline__ int load_edge(float v, int n) { return (int)fminf(fmaxf(ceilf(v - 0.5f), 0.0f), (float)n); }
+
 }  // namespace ay

@@ -18,6 +18,7 @@
 //
 // Integers and order-free integer atomics only: the same bytes every run.  Kernel launches only: no allocation, no memset node, no
 // host read, no scratch.
+#include "ay_box.h"
 #include "ay_common.h"
 
 namespace ay {
@@ -125,10 +126,7 @@ __global__ void __launch_bounds__(256) stain_load_cells_kernel(const uint8_t* __
     }
 }
 
-__device__ __forceinline__ bool load_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN and +-inf
-
-// THE LOAD RULE's edge of a box: the first pixel whose centre is not left of (above) v, clamped into 0 .. n
-__device__ __forceinline__ int load_edge(float v, int n) { return (int)fminf(fmaxf(ceilf(v - 0.5f), 0.0f), (float)n); }
+// load_finite and load_edge, THE LOAD RULE's box ownership: ay_box.h (the focus pass owns the same pixels)
 
 __global__ void __launch_bounds__(256) stain_load_boxes_kernel(const uint8_t* __restrict__ reg, int H, int W, size_t stride, int shrink, int bg,
                                                                 int oy, int ox, int slide_h, int slide_w,

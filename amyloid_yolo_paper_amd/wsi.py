@@ -36,6 +36,9 @@ Amyloid load: :func:`stain_load` classifies every pixel of a slide (tissue, DAB-
 box (``ay_stain_load_u8``, THE LOAD RULE); :func:`box_morphometry` turns the box sums into areas, fill and mean optical density,
 and ``quantify_region(load=True)`` puts the load map next to the count maps.
 
+Focus: :func:`focus_map` sums the Laplacian of the luma over the tissue of every map cell and detection box (``ay_focus_u8``, THE
+FOCUS RULE) into a sharpness map, :func:`focus_summary` reads it, and ``quantify_region(focus=True)`` reports it next to the counts.
+
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
 import math
@@ -601,7 +604,7 @@ def densest_fields(counts, tissue=None, field=8, top_k=5, need_tissue=0):
 
 
 def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
-                    dab_thres=None, load=False, **detect_region_kwargs):
+                    dab_thres=None, load=False, focus=False, min_sharpness=None, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
 
     1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
@@ -637,7 +640,21 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
        [C,top_k]: positive over tissue, summed on the host over the cells of every picked field, NaN for rows not filled and for a
        field without tissue.  The threshold applies to the slide's own concentrations, with or without a ``stain=`` map.
 
+    7. With ``focus=True`` (``cell >= 16``) one more pass over the raster, ``focus_map(raster, rows, cell, shrink, bg_level)`` -- THE
+       FOCUS RULE, exact and at full resolution -- adds ``focus_n`` int64 and ``focus_sharpness`` float64 [Gy,Gx], ``box_sharpness``
+       float64 [M] for ``rows`` and ``field_sharpness`` float64 [C,top_k]: the pooled variance of the Laplacian from the summed ``n``,
+       ``s1``, ``s2`` of the cells of every picked field, NaN for rows not filled and for a field without an evaluated pixel.  Every
+       count and load above assumes the scanner was in focus where it counted; these say where it was.  With ``min_sharpness`` (only
+       with ``focus=True``; no default is offered, see :func:`focus_summary`) also ``in_focus`` bool [Gy,Gx] and
+       ``in_focus_fraction``.  The fields are picked as before: sharpness is reported, never used.  Without ``focus`` the result has
+       the keys it had.
+
     The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
+    if min_sharpness is not None:
+        if not focus:
+            raise ValueError("quantify_region: min_sharpness needs focus=True")
+        if isinstance(min_sharpness, bool) or not 0.0 <= float(min_sharpness) < math.inf:
+            raise ValueError(f"quantify_region: min_sharpness {min_sharpness!r} is no variance >= 0")
     if load:
         if dab_thres is None:
             raise ValueError("quantify_region: load=True needs dab_thres")
@@ -670,6 +687,8 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         st = detect_region_kwargs.get("stain")
         load_basis = stain_stats.basis if stain_stats is not None else st.basis if isinstance(st, StainMap) else H_DAB
         _check_load("quantify_region", raster, shrink, cell, bg_level, 1, load_basis)
+    if focus:
+        _check_focus("quantify_region", raster, shrink, cell, bg_level)
     min_conf = float(min_conf)
     need = max(1, math.ceil(float(field_min_tissue) * (F * cell) ** 2))
     H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
@@ -701,6 +720,18 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
             t = int(ld["tissue"][fy:fy + F, fx:fx + F].sum())
             if t:
                 out["field_load"][c, k] = float(int(ld["positive"][fy:fy + F, fx:fx + F].sum())) / t
+    if focus:
+        fm = focus_map(raster, rows, cell, shrink, bg_level)
+        out["focus_n"], out["focus_sharpness"], out["box_sharpness"] = fm["n"], fm["sharpness"], fm["box_sharpness"]
+        out["field_sharpness"] = np.full((num_classes, K), np.nan)
+        for c, k in zip(*np.nonzero(filled)):
+            fy, fx = int(picked[c, k, 0]), int(picked[c, k, 1])
+            n, s1, s2 = (int(fm[key][fy:fy + F, fx:fx + F].sum()) for key in ("n", "s1", "s2"))
+            if n:
+                out["field_sharpness"][c, k] = s2 / n - (s1 / n) ** 2
+        if min_sharpness is not None:
+            fs = focus_summary(fm, None, min_sharpness)
+            out["in_focus"], out["in_focus_fraction"] = fs["in_focus"], fs["in_focus_fraction"]
     if mpp is not None:
         mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue
         out["density_per_mm2"] = bm["counts"].cpu().numpy().astype(np.float64) / mm2(tissue)[None]
@@ -1020,6 +1051,124 @@ def box_morphometry(boxes, mpp=None):
     if mpp is not None:
         out["area_um2"] = some * float(mpp) ** 2
         out["equiv_diameter_um"] = 2.0 * np.sqrt(out["area_um2"] / math.pi)
+    return out
+
+
+# ---- focus map: sharpness per map cell and per detection ------------------------------------------------------------------------------
+FOCUS_MIN_CELL, FOCUS_MAX_SIDE, FOCUS_FLAG_NONFINITE = 16, 1 << 24, 1    # include/amyloid_yolo.h, THE FOCUS RULE
+FOCUS_MAX_PIXELS = 1 << 43                                               # H * W below it: s2 fits int64
+
+
+def _check_focus(what, raster, shrink, cell, bg_level):
+    """the host checks :func:`focus_map` and ``quantify_region(focus=True)`` share (:func:`_check_load`'s) -> (H, W, cell, bg_level)"""
+    if shrink not in (1, 2):
+        raise ValueError(f"{what}: shrink {shrink!r} is neither 1 nor 2")
+    if getattr(raster, "ndim", 0) != 3 or raster.shape[2] != 3 or raster.dtype != np.uint8:
+        raise ValueError(f"{what}: raster must be a uint8 [H,W,3] array")
+    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: raster {tuple(raster.shape)} has no (halved) pixel")
+    if max(H, W) > FOCUS_MAX_SIDE or H * W >= FOCUS_MAX_PIXELS:
+        raise ValueError(f"{what}: a (halved) slide of {H} x {W} exceeds {FOCUS_MAX_SIDE} pixels per side or 2**43 pixels")
+    cell = _whole(cell, FOCUS_MIN_CELL, 2 ** 31 - 1, f"{what}: cell")
+    gy, gx, _ = tile_grid(H, W, cell)
+    if gy * gx > LOAD_MAX_CELLS:
+        raise ValueError(f"{what}: {gy} x {gx} cells exceed {LOAD_MAX_CELLS}; choose a larger cell")
+    return H, W, cell, _whole(bg_level, 0, 256, f"{what}: bg_level")
+
+
+def _sharpness(n, s1, s2):
+    """THE FOCUS RULE's host step: the variance of the Laplacian ``s2 / n - (s1 / n)**2`` in float64, NaN where ``n == 0``"""
+    n = np.where(np.asarray(n) > 0, n, np.nan).astype(np.float64)
+    return np.asarray(s2, np.float64) / n - (np.asarray(s1, np.float64) / n) ** 2
+
+
+def focus_map(raster, rows=None, cell=128, shrink=1, bg_level=220, strip=1536):
+    """Image sharpness of a slide (``ay_focus_u8``, THE FOCUS RULE in ``include/amyloid_yolo.h``): per cell of the grid
+    ``tile_grid(H, W, cell)`` -- :func:`burden_map`'s -- the variance of the 4-neighbour Laplacian of the luma over the EVALUATED
+    pixels: those that are tissue at ``bg_level`` with all four edge neighbours, so that a tissue / glass edge never counts as
+    sharpness; with ``rows`` the same inside every box (the pixels :func:`stain_load` gives it).
+
+    The raster goes ONCE through the strips of :class:`RegionTileStream` at full resolution; a pixel needs the rows above and below
+    it, so consecutive strips share two rows: with ``T = min(strip, H)`` strip ``j`` starts at row ``j * (T - 2)`` and owns the centre
+    rows ``[j * (T - 2) + 1, j * (T - 2) + T - 1)``, clipped to what it holds, and every row ``1 .. H - 2`` is owned exactly once:
+    the result does not depend on ``strip`` (an integer ``>= 3``).  The outputs are zeroed once, every strip adds to them on the
+    device and they are read back once.  ``cell >= 16``; (halved) sides up to 2^24 and fewer than 2^43 pixels.  A slide with ``H < 3``
+    or ``W < 3`` has no evaluated pixel: zeros, without a launch.
+
+    Returns a dict: ``n``, ``s1``, ``s2`` NumPy int64 ``[Gy, Gx]`` (evaluated pixels, the sum of the Laplacian, the sum of its
+    squares) and ``sharpness`` float64 ``s2 / n - (s1 / n)**2``, NaN where a cell has no evaluated pixel; with ``rows`` (None, or
+    ``[M, 7]`` as :func:`detect_region` returns them; only the four coordinates are read) also ``boxes`` int64 ``[M, 3]`` = (n, s1,
+    s2), ``box_sharpness`` float64 ``[M]`` and ``flags`` (bit 1: a coordinate not finite; such a row gets zeros).  Sharpness depends
+    on the texture of the tissue and the strength of the stain as well as on focus: see :func:`focus_summary`."""
+    H, W, cell, bg_level = _check_focus("focus_map", raster, shrink, cell, bg_level)
+    strip = _whole(strip, 3, 2 ** 31 - 1, "focus_map: strip")
+    if rows is not None and (len(getattr(rows, "shape", ())) != 2 or rows.shape[1] != 7):
+        raise ValueError(f"focus_map: rows must be [M,7] or None, got {tuple(getattr(rows, 'shape', ())) or type(rows).__name__}")
+    gy, gx, _ = tile_grid(H, W, cell)
+    M = 0 if rows is None else int(rows.shape[0])
+    if H < 3 or W < 3:
+        c, b, f = np.zeros((gy, gx, 3), np.int64), np.zeros((M, 3), np.int64), 0
+    else:
+        from .stats import _slide_array
+        T = min(strip, H)
+        stream = RegionTileStream(raster, T, 1, shrink, overlap=2)
+        dev = stream.dev
+        cells = torch.zeros(gy, gx, 3, device=dev, dtype=torch.int64)
+        if rows is not None:
+            rows = _slide_array(rows, 7, dev)
+            boxes = torch.zeros(M, 3, device=dev, dtype=torch.int64)
+            flags = torch.zeros(1, device=dev, dtype=torch.int32)
+        L = _lib.lib()
+        for jy, k, valid, width in stream._strip_loop():
+            y0, held = jy * stream.step, valid // stream.shrink
+            check(L.ay_focus_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, y0, H, W, y0 + 1, y0 + held - 1, bg_level,
+                                cell, ptr(cells), ptr(rows) if M else None, M, ptr(boxes) if M else None, ptr(flags) if M else None,
+                                _lib.stream_ptr()), "ay_focus_u8")
+            stream._release(k)
+        c = cells.cpu().numpy()
+        b, f = (boxes.cpu().numpy(), int(flags.item())) if M else (np.zeros((0, 3), np.int64), 0)
+    n, s1, s2 = (np.ascontiguousarray(c[:, :, i]) for i in range(3))
+    out = {"n": n, "s1": s1, "s2": s2, "sharpness": _sharpness(n, s1, s2)}
+    if rows is not None:
+        out["boxes"], out["box_sharpness"], out["flags"] = b, _sharpness(b[:, 0], b[:, 1], b[:, 2]), f
+    return out
+
+
+def focus_summary(focus, tissue=None, min_sharpness=None, min_pixels=1):
+    """What a focus map says about a slide; host arithmetic on :func:`focus_map`'s dict.
+
+    ``evaluated_fraction``: the evaluated pixels over the tissue pixels of the slide, with ``tissue`` an integer map ``[Gy, Gx]`` on
+    the same grid, ``bg_level`` and raster (``stain_load(...)["tissue"]``, ``tissue_counts(raster, cell)``); NaN without ``tissue``
+    or without tissue.  Thin or ragged tissue has few pixels with a whole tissue neighbourhood, and its cells say little.
+
+    With ``min_sharpness`` also ``in_focus``, a bool map: ``n >= min_pixels`` and ``sharpness >= min_sharpness``, and
+    ``in_focus_fraction``, the share of the evaluated pixels that lie in in-focus cells (NaN if none was evaluated).  With
+    ``min_sharpness=None`` no classification is returned.
+
+    NO DEFAULT THRESHOLD IS OFFERED: the variance of the Laplacian grows with the texture of the tissue and the strength of the stain
+    as well as with focus, so a threshold holds for one tissue, stain protocol, scanner and ``shrink`` only.  Derive it from slides of
+    that kind that are known to be sharp (for instance a low percentile of their cells' sharpness), not from this docstring."""
+    n = np.asarray(focus["n"])
+    sharp = np.asarray(focus["sharpness"], np.float64)
+    if n.ndim != 2 or n.dtype.kind not in "iu" or sharp.shape != n.shape or (n < 0).any():
+        raise ValueError(f"focus_summary: focus must be focus_map's dict (n {n.dtype} {n.shape}, sharpness {sharp.shape})")
+    min_pixels = _whole(min_pixels, 1, 2 ** 62, "focus_summary: min_pixels")
+    total = int(n.sum())
+    out = {"evaluated_fraction": math.nan}
+    if tissue is not None:
+        t = np.asarray(tissue)
+        if t.shape != n.shape or t.dtype.kind not in "iu" or (t < 0).any():
+            raise ValueError(f"focus_summary: tissue {t.dtype} {t.shape} is no count map on the grid {n.shape}")
+        n_t = int(t.sum(dtype=np.int64))
+        if n_t:
+            out["evaluated_fraction"] = total / n_t
+    if min_sharpness is not None:
+        if isinstance(min_sharpness, bool) or not 0.0 <= float(min_sharpness) < math.inf:       # a NaN fails both comparisons
+            raise ValueError(f"focus_summary: min_sharpness {min_sharpness!r} is no variance >= 0")
+        with np.errstate(invalid="ignore"):
+            out["in_focus"] = (n >= min_pixels) & (sharp >= float(min_sharpness))                # NaN compares False
+        out["in_focus_fraction"] = int(n[out["in_focus"]].sum()) / total if total else math.nan
     return out
 
 

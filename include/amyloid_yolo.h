@@ -896,6 +896,58 @@ int ay_stain_load_u8(const void* region_hwc_u8, int region_h, int region_w, size
                      int cell, uint64_t* cells /* or NULL */, const float* rows, int n_rows, uint64_t* boxes,
                      int32_t* flags /* NULL iff n_rows == 0 */, ay_stream_t stream);
 
+/* ---- focus map: image sharpness per map cell and per detection (wsi.focus_map, wsi.focus_summary, wsi.quantify_region(focus=True);
+ *      csrc/ay_focus.hip) ------------------------------------------------------------------------------------------------------------
+ * Every number of a slide assumes that the scanner was in focus where it counted; a blurred patch is still tissue, loses its
+ * detections and reads as "low burden".  The variance of the Laplacian of the luma over tissue is the read-out, on THE BURDEN RULE's
+ * grid and inside every detection's box.  The reference has no such read-out: PARITY IS UNPINNED, the behaviour is the rule below,
+ * restated in NumPy by tests/focus_reference.py.
+ *
+ * THE FOCUS RULE (integers only; a function of the inputs alone, the same bytes on every run).
+ *   Bytes.  (b0, b1, b2) of pixel (X, Y) of the (halved) H x W slide are THE TISSUE RULE's: for shrink == 2 the ingest's 2x2
+ *     round-half-up means.
+ *   Luma.  g = (77 * b0 + 150 * b1 + 29 * b2 + 128) >> 8, in 0 .. 255.
+ *   Evaluated pixel.  (X, Y) is EVALUATED iff 1 <= X <= W - 2 and 1 <= Y <= H - 2 and the pixel and its four edge neighbours
+ *     (X - 1, Y), (X + 1, Y), (X, Y - 1), (X, Y + 1) are all TISSUE at bg_level (min(b0, b1, b2) < bg_level).  A tissue / glass edge is
+ *     not texture and never counts as sharpness.
+ *   Laplacian.  lap = 4 * g(X, Y) - g(X - 1, Y) - g(X + 1, Y) - g(X, Y - 1) - g(X, Y + 1), in -1020 .. 1020.
+ *   Sums.  Per owner: n = its evaluated pixels, s1 = the sum of lap over them (signed), s2 = the sum of lap * lap, as int64 in two's
+ *     complement.  A cell of the grid wsi.tile_grid(H, W, cell, 0) (Gy = ceil(H / cell), Gx = ceil(W / cell)) owns the evaluated
+ *     pixels with (X, Y) in it -- cell (Y / cell, X / cell); the neighbours may lie in another cell.  A box (rows [M][7] fp32, columns
+ *     0 .. 3 read) owns the evaluated pixels THE LOAD RULE gives it: lo_x <= X < hi_x, lo_y <= Y < hi_y with the four edges computed in
+ *     fp32 exactly as there (centre in [x1, x2) x [y1, y2), clamped to the slide); overlapping boxes are independent.  A row with a
+ *     coordinate that is not finite sets AY_FOCUS_FLAG_NONFINITE in the flags word and gets nothing.
+ *   Host, float64.  sharpness = s2 / n - (s1 / n)^2, the variance of the Laplacian; NaN where n == 0.  It depends on the texture of
+ *     the tissue and on the strength of the stain as well as on focus: it compares regions of one slide, or slides of one protocol.
+ *   Limits.  cell >= AY_FOCUS_MIN_CELL = 16; H, W <= 2^24; H * W < 2^43, so that s2 fits int64 (1020^2 * 2^43 < 2^63).
+ *   Accumulation.  A call sees one resident region that holds whole rows of the slide, origin_y .. origin_y + region_h / shrink - 1,
+ *     (region_w / shrink == W), and is told the rows it OWNS: it ADDS the sums of the evaluated pixels with own_y0 <= Y < own_y1, and
+ *     nothing else, to cells and boxes, and ORs into flags.  The rows it needs resident are max(own_y0, 1) - 1 .. min(own_y1, H - 1),
+ *     one more than it owns on either side.  The caller zeroes the outputs once and makes the owned ranges of its calls a partition of
+ *     1 .. H - 2 (wsi.focus_map: strips that share two rows).  A call that owns no row of 1 .. H - 2, or any call when W < 3, has no
+ *     pixel to evaluate: it needs no row, launches nothing, adds nothing and flags nothing.
+ *
+ * ay_focus_u8: kernel launches only -- no allocation, no memset node, no host read, no scratch -- so it can sit in a captured step.
+ *   cells == NULL skips the cell pass; n_rows == 0 skips the box pass (rows, boxes and flags may then be NULL).  Refused (-1, nothing
+ *   launched, nothing written): a needed row that is not resident; a null region, a bad shape or stride, shrink outside {1, 2},
+ *   bg_level outside 0 .. 256, cell < AY_FOCUS_MIN_CELL (with or without cells), slide_h or slide_w outside 1 .. 2^24 or their product
+ *   not below 2^43, region_w / shrink != slide_w, a region that does not lie inside the slide, own_y0 < 0, own_y0 > own_y1, own_y1 >
+ *   slide_h, n_rows < 0 or rows without boxes and flags, cells or boxes not 8-byte aligned.
+ *   The cell pass is a read stream with ay_stain_load_u8's items and choice of loads (16-byte loads when the base and
+ *   row_stride_bytes are multiples of 16, byte loads otherwise, the same sums).  A work unit is up to 32 centre rows x 32 items (512
+ *   pixels, 256 of the halved image); its rows and one halo row above and below go through LDS once as a luma byte and a tissue bit
+ *   per pixel, the pixels left and right of the unit with them, and the four neighbours of every pixel come from LDS.  A lane sums
+ *   at most 4 x 16 pixels in int32 registers (s2 <= 66 585 600), a workgroup its unit in a uint64 LDS table, and memory sees one 64-bit
+ *   integer atomic per (workgroup, unit, cell, sum) that is not 0: no 32-bit word ever holds more than one lane's share.  The box pass
+ *   is a gather for detection boxes: one wavefront per box, an integer intersection with the owned rows first, at most three 64-bit
+ *   atomics per box and call; correct for any box, but ONE HUGE BOX RUNS ON ONE WAVEFRONT. */
+#define AY_FOCUS_MIN_CELL 16
+#define AY_FOCUS_FLAG_NONFINITE 1
+int ay_focus_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int origin_y, int slide_h,
+                int slide_w, int own_y0, int own_y1, int bg_level, int cell, int64_t* cells /* [Gy][Gx][3], or NULL */,
+                const float* rows, int n_rows, int64_t* boxes /* [M][3] */, int32_t* flags /* NULL iff n_rows == 0 */,
+                ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call (the once-per-slide calls ay_seam_merge and ay_slide_match excepted:
  * they memset, read a few words back and synchronise the stream, and are not for capture; ay_burden_bin and ay_field_select, also
