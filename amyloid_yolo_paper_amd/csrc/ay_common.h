@@ -211,33 +211,6 @@ __device__ __forceinline__ void region_tap(const Colour& colour, const typename 
     if (region_tap_u8(reg, stride, shrink, H, W, X, Y, b)) colour.map(tab, b, px);
 }
 
-// byte j of a row segment held in dwords (the read streams over a region: ay_tissue.hip, ay_stain.hip)
-__device__ __forceinline__ int byte_of(const uint32_t* w, int j) { return (int)((w[j >> 2] >> (8 * (j & 3))) & 0xffu); }
-
-// bytes [o, o + 48) of one row into w[0..11]; bytes at or behind row_bytes read as 0 (they are never part of a counted pixel): the
-// 48-byte item, 16 whole pixels, of the stain histogram and the load pass (ay_stain.hip, ay_load.hip)
-template <bool WIDE>
-__device__ __forceinline__ void load48(const uint8_t* __restrict__ row, unsigned o, unsigned row_bytes, uint32_t w[12]) {
-    if (WIDE && o + 48 <= row_bytes) {   // row and o are multiples of 16
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const u32x4 a = *(const u32x4*)(row + o + 16 * k);
-            w[4 * k] = a[0], w[4 * k + 1] = a[1], w[4 * k + 2] = a[2], w[4 * k + 3] = a[3];
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < 12; ++d) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const unsigned at = o + 4 * d + b;
-                if (at < row_bytes) v |= (uint32_t)row[at] << (8 * b);
-            }
-            w[d] = v;
-        }
-    }
-}
-
 static inline hipStream_t S(ay_stream_t s) { return (hipStream_t)s; }
 
 }  // namespace ay

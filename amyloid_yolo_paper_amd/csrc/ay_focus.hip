@@ -3,8 +3,8 @@
 // cell of the burden grid and per detection box, out of a resident strip of the slide.  The first kernels here whose result at a pixel
 // depends on the rows above and below it: a call is told which centre rows it OWNS and needs one more row on either side resident.
 //
-//   focus_cells_kernel   the hot path: a read stream over the image with ay_load.hip's 48-byte items (16 whole pixels of a row, 8 of the
-//                        halved image) and its choice of 16-byte or byte loads.  A work unit is a band of up to 32 centre rows x up to 32
+//   focus_cells_kernel   the hot path: a read stream over the image in ay_slide_pass.h's 48-byte items (16 whole pixels of a row, 8 of the
+//                        halved image; 16-byte or byte loads).  A work unit is a band of up to 32 centre rows x up to 32
 //                        items.  Phase A: every row of the band plus one halo row above and below goes through LDS once, a luma byte per
 //                        pixel and a tissue bit per pixel (one 16-bit mask per item); the pixel left of the unit's first item and the one
 //                        right of its last are tapped with byte loads into a spare item slot on either side, so that an item's neighbour
@@ -19,22 +19,20 @@
 //                        rows of the unit (|lap| <= 1020: s2 <= 4 * 16 * 1 040 400 = 66 585 600 < 2^31) and adds them, whenever the cell
 //                        row changes and at the end of the unit, to the workgroup's table in LDS, uint64 [3 cell rows][33 cells][3]
 //                        (64-bit LDS atomics; s1 in two's complement), which therefore cannot overflow for any unit size.  After
-//                        every unit the used part of the table goes to memory with one 64-bit integer atomic per (cell, sum) that is not
-//                        0, lanes on consecutive words, and is zeroed.  The sums in memory are bounded by the rule's H * W < 2^43.
-//   focus_boxes_kernel   a gather: one wavefront per box, boxes grid-stride.  THE LOAD RULE's box (ay_box.h), intersected with the owned
-//                        rows and with columns 1 .. W - 2 first (most boxes miss the strip), the lanes over the pixels of the intersection,
-//                        five byte taps per tissue pixel (region_tap_u8), 64-bit sums per lane, a wave reduction and at most three 64-bit
-//                        atomics per box and call.  Correct for any box; ONE HUGE BOX RUNS ON ONE WAVE.
+//                        every unit the used part of the table goes to memory and is zeroed (flush_cell_table, ay_slide_pass.h).  The
+//                        sums in memory are bounded by the rule's H * W < 2^43.
+//   focus_boxes_kernel   a gather: ay_slide_pass.h's box_walk, one wavefront per box.  THE LOAD RULE's box (ay_box.h), intersected with
+//                        the owned rows and with columns 1 .. W - 2 first (most boxes miss the strip), the lanes over the pixels of the
+//                        intersection, five byte taps per tissue pixel (region_tap_u8), 64-bit sums per lane, a wave reduction and at
+//                        most three 64-bit atomics per box and call.
 //
 // Integers and order-free integer atomics only: the same bytes every run.  Kernel launches only: no allocation, no memset node, no
 // host read, no scratch.
-#include "ay_box.h"
-#include "ay_common.h"
+#include "ay_slide_pass.h"
 
 namespace ay {
 
 constexpr int FOCUS_BAND = 32;    // centre rows of a work unit
-constexpr int FOCUS_ITEM = 48;    // bytes of a row a lane takes at a time: 16 pixels, 8 of the halved image
 constexpr int FOCUS_XQ = 32;      // items of a row in a work unit: 512 pixels, 256 of the halved image
 constexpr int FOCUS_ROWS = FOCUS_BAND + 2;
 constexpr int FOCUS_RSTEP = 256 / FOCUS_XQ;   // a lane's rows are this far apart
@@ -42,7 +40,6 @@ constexpr int FOCUS_RSTEP = 256 / FOCUS_XQ;   // a lane's rows are this far apar
 constexpr int FOCUS_CX = FOCUS_XQ * 16 / AY_FOCUS_MIN_CELL + 1;
 constexpr int FOCUS_CY = FOCUS_BAND / AY_FOCUS_MIN_CELL + 1;
 constexpr int FOCUS_WORDS = FOCUS_CY * FOCUS_CX * 3;
-constexpr int FOCUS_MAX_SIDE = 1 << 24;
 static_assert((FOCUS_BAND / FOCUS_RSTEP) * 16 * 1020 * 1020 < (1ll << 31), "a lane's int32 s2");
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -66,7 +63,7 @@ __global__ void __launch_bounds__(256) focus_cells_kernel(const uint8_t* __restr
                                                            int oy, int c0, int c1, int cell, int gx, int n_xc, long long units,
                                                            unsigned long long* __restrict__ cells) {
     constexpr int BPP = 3 * SHRINK;                          // source bytes of one row per image pixel
-    constexpr int PPI = FOCUS_ITEM / BPP;                    // pixels of an item: 16 or 8
+    constexpr int PPI = SLIDE_ITEM / BPP;                    // pixels of an item: 16 or 8
     constexpr int GW = PPI / 4;                              // dwords of an item's lumas
     constexpr int LS = PPI * (FOCUS_XQ + 2);                 // bytes of a row of lumas: a spare item slot on either side
     constexpr int TS = FOCUS_XQ + 2;
@@ -75,36 +72,25 @@ __global__ void __launch_bounds__(256) focus_cells_kernel(const uint8_t* __restr
     __shared__ unsigned long long lc[FOCUS_WORDS];
     const int tid = threadIdx.x, qi = tid % FOCUS_XQ, r0 = tid / FOCUS_XQ;
     for (int i = tid; i < FOCUS_WORDS; i += 256) lc[i] = 0;
-    const unsigned row_bytes = (unsigned)RW * 3;
-    const unsigned nq = ((unsigned)W * BPP + FOCUS_ITEM - 1) / FOCUS_ITEM;
+    const unsigned row_bytes = (unsigned)RW * 3, nq = ((unsigned)W * BPP + SLIDE_ITEM - 1) / SLIDE_ITEM;
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers
-        const unsigned q0 = (unsigned)(u % n_xc) * FOCUS_XQ, wq = min((unsigned)FOCUS_XQ, nq - q0);
-        const int yb = c0 + (int)(u / n_xc) * FOCUS_BAND, nc = min(FOCUS_BAND, c1 - yb);   // centre rows yb .. yb + nc - 1 of the slide
-        // ---- phase A: rows yb - 1 .. yb + nc of the slide -> LDS rows 0 .. nc + 1
+        const auto [q0, wq, yb, y_end, nc] = slide_unit<FOCUS_BAND, FOCUS_XQ>(u, n_xc, nq, c0, c1);
+        // ---- phase A: the unit's centre rows are yb .. yb + nc - 1 of the slide; rows yb - 1 .. yb + nc -> LDS rows 0 .. nc + 1
         if ((unsigned)qi < wq) {
-            const unsigned o = (q0 + qi) * FOCUS_ITEM;
+            const unsigned o = (q0 + qi) * SLIDE_ITEM;
             const int X0 = (int)(q0 + qi) * PPI;
             for (int r = r0; r < nc + 2; r += FOCUS_RSTEP) {
                 const int y = yb - 1 + r - oy;               // row of the (halved) image the region holds: 0 <= y < h_img (host check)
                 uint32_t w0[12], w1[12];
-                if (SHRINK == 1) {
-                    load48<WIDE>(reg + (size_t)y * stride, o, row_bytes, w0);
-                } else {
-                    load48<WIDE>(reg + (size_t)(2 * y) * stride, o, row_bytes, w0);
-                    load48<WIDE>(reg + (size_t)(2 * y + 1) * stride, o, row_bytes, w1);
-                }
+                item_load<WIDE, SHRINK>(reg, stride, y, o, row_bytes, w0, w1);
                 uint32_t g[GW] = {};
                 unsigned t = 0;
 #pragma unroll
                 for (int p = 0; p < PPI; ++p) {              // the pixels of the item lie at the same bytes in every lane
-                    const int j = p * BPP;
                     int b[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        b[c] = SHRINK == 1 ? byte_of(w0, j + c)
-                                           : (byte_of(w0, j + c) + byte_of(w0, j + 3 + c) + byte_of(w1, j + c) + byte_of(w1, j + 3 + c) + 2) >> 2;
+                    item_pixel<SHRINK>(w0, w1, p, b);
                     g[p >> 2] |= (uint32_t)focus_luma(b) << (8 * (p & 3));
-                    if (X0 + p < W && min(min(b[0], b[1]), b[2]) < bg) t |= 1u << p;   // behind the row's last pixel: not tissue
+                    if (X0 + p < W && tissue_px(b, bg)) t |= 1u << p;   // behind the row's last pixel: not tissue
                 }
                 uint8_t* d = lum + r * LS + PPI * (1 + qi);
                 if constexpr (GW == 4) *(u32x4*)d = u32x4{g[0], g[1], g[2], g[3]};
@@ -117,22 +103,19 @@ __global__ void __launch_bounds__(256) focus_cells_kernel(const uint8_t* __restr
             const unsigned X = right ? (q0 + wq) * PPI : q0 * PPI - 1u;   // q0 == 0: wraps, outside
             int b[3] = {255, 255, 255};
             const bool in = region_tap_u8(reg, stride, SHRINK, h_img, W, X, (unsigned)(yb - 1 + r - oy), b);
-            const bool t = in && min(min(b[0], b[1]), b[2]) < bg;
+            const bool t = in && tissue_px(b, bg);
             lum[r * LS + (right ? PPI * (1 + (int)wq) : PPI - 1)] = (uint8_t)focus_luma(b);
             tm[r * TS + (right ? 1 + (int)wq : 0)] = (uint16_t)(t ? (right ? 1u : 1u << (PPI - 1)) : 0u);
         }
         __syncthreads();
         // ---- phase B: the unit's cells are rows cy0 .. cy0 + ncy - 1 (ncy <= 3), columns cx0 .. cx0 + ncx - 1
-        const int cy0 = yb / cell, ncy = (yb + nc - 1) / cell - cy0 + 1;
-        const int cut1 = (cy0 + 1) * cell, cut2 = cut1 + cell;   // slide rows from cut1 (cut2) on lie in cell row cy0 + 1 (+ 2); < 2^26
-        const int cx0 = (int)(q0 * PPI) / cell, ncx = (min((int)(q0 + wq) * PPI, W) - 1) / cell - cx0 + 1;
+        const UnitCells uc = unit_cells(yb, yb + nc, (int)(q0 * PPI), min((int)(q0 + wq) * PPI, W), cell);
+        const int cut1 = (uc.cy0 + 1) * cell, cut2 = cut1 + cell;   // slide rows from cut1 (cut2) on lie in cell row cy0 + 1 (+ 2); < 2^26
         if ((unsigned)qi < wq) {
-            const int X0 = (int)(q0 + qi) * PPI;
-            const int ca = X0 / cell, xb = (ca + 1) * cell - X0;   // pixels p >= xb of the item lie in cell ca + 1; xb >= 1
-            const unsigned low = xb >= PPI ? 0xffffu : (1u << xb) - 1u;
+            const ItemCells ic = item_cells<PPI>((int)(q0 + qi) * PPI, cell);
             int na = 0, nb = 0, s1 = 0, s1a = 0, s2 = 0, s2a = 0, cur = 0;   // n left / right of xb; sums: all, left of xb
             auto spill = [&]() {
-                unsigned long long* a = lc + (cur * FOCUS_CX + (ca - cx0)) * 3;
+                unsigned long long* a = lc + (cur * FOCUS_CX + (ic.ca - uc.cx0)) * 3;
                 if (na) {
                     atomicAdd(a, (unsigned long long)na);
                     atomicAdd(a + 1, (unsigned long long)(long long)s1a);
@@ -168,78 +151,48 @@ __global__ void __launch_bounds__(256) focus_cells_kernel(const uint8_t* __restr
                     lap = (ev >> p) & 1u ? lap : 0;
                     const int sq = lap * lap;
                     s1 += lap, s2 += sq;
-                    if (p < xb) s1a += lap, s2a += sq;
+                    if (p < ic.xb) s1a += lap, s2a += sq;
                 }
-                na += __builtin_popcount(ev & low), nb += __builtin_popcount(ev & ~low);
+                na += __builtin_popcount(ev & ic.low), nb += __builtin_popcount(ev & ~ic.low);
             }
             spill();
         }
         __syncthreads();
         // the flush; the next unit's phase A writes lum and tm only, and its barrier stands before the next add to lc
-        const int per_row = ncx * 3, n = ncy * per_row;
-        for (int k = tid; k < n; k += 256) {
-            const int r = k / per_row, at = k - r * per_row;
-            unsigned long long* s = lc + r * (FOCUS_CX * 3) + at;
-            const unsigned long long v = *s;
-            if (v) {
-                atomicAdd(cells + ((size_t)(cy0 + r) * gx + cx0) * 3 + at, v);
-                *s = 0;
-            }
-        }
+        flush_cell_table<unsigned long long, FOCUS_CX>(lc, uc.ncy, uc.ncx, uc.cy0, uc.cx0, gx, cells);
     }
 }
 
 __global__ void __launch_bounds__(256) focus_boxes_kernel(const uint8_t* __restrict__ reg, int h_img, int W, size_t stride, int shrink, int bg,
                                                            int oy, int slide_h, int c0, int c1, const float* __restrict__ rows, int M,
                                                            unsigned long long* __restrict__ boxes, int32_t* __restrict__ flags) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const long long n_waves = (long long)gridDim.x * 4;
-    for (long long m = (long long)blockIdx.x * 4 + (tid >> 6); m < M; m += n_waves) {   // m is uniform over the wavefront
-        const float* r = rows + (size_t)m * 7;
-        const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
-        if (!(load_finite(x1) && load_finite(y1) && load_finite(x2) && load_finite(y2))) {
-            if (lane == 0) atomicOr(flags, AY_FOCUS_FLAG_NONFINITE);
-            continue;
-        }
+    box_walk<3>(
+        rows, M, slide_h, W, flags, AY_FOCUS_FLAG_NONFINITE,
         // the box's pixels that this call owns and that can be evaluated: rows c0 .. c1 - 1, columns 1 .. W - 2 of the slide
-        const int ax = max(load_edge(x1, W), 1), bx = min(load_edge(x2, W), W - 1);
-        const int ay_ = max(load_edge(y1, slide_h), c0), by = min(load_edge(y2, slide_h), c1);
-        if (ax >= bx || ay_ >= by) continue;                 // empty, inverted, or not on these rows
-        const int w = bx - ax, h = by - ay_;
-        const int dy = 64 / w, dx = 64 % w;                  // a lane's step of 64 pixels, in rows and columns
-        int x = lane % w, y = lane / w;
-        unsigned long long n = 0, s1 = 0, s2 = 0;            // 64-bit per lane: a box may be the whole slide; s1 in two's complement
-        while (y < h) {
-            const unsigned X = (unsigned)(ax + x), Y = (unsigned)(ay_ + y - oy);   // Y: row of the region's image; Y - 1 .. Y + 1 resident
+        [&](int& ax, int& bx, int& ay_, int& by) { ax = max(ax, 1), bx = min(bx, W - 1), ay_ = max(ay_, c0), by = min(by, c1); },
+        [&](int x, int y, unsigned long long* s) {           // n, s1 in two's complement, s2
+            const unsigned X = (unsigned)x, Y = (unsigned)(y - oy);   // Y: row of the region's image; Y - 1 .. Y + 1 resident
             int b[3] = {255, 255, 255};
             int g[5];
             bool ok = true;
 #pragma unroll
             for (int k = 0; k < 5 && ok; ++k) {              // the centre first: most pixels of a slide are glass
                 const unsigned tx = k == 1 ? X - 1 : k == 2 ? X + 1 : X, ty = k == 3 ? Y - 1 : k == 4 ? Y + 1 : Y;
-                ok = region_tap_u8(reg, stride, shrink, h_img, W, tx, ty, b) && min(min(b[0], b[1]), b[2]) < bg;
+                ok = region_tap_u8(reg, stride, shrink, h_img, W, tx, ty, b) && tissue_px(b, bg);
                 g[k] = focus_luma(b);
             }
             if (ok) {
                 const int lap = 4 * g[0] - g[1] - g[2] - g[3] - g[4];
-                ++n, s1 += (unsigned long long)(long long)lap, s2 += (unsigned long long)(lap * lap);
+                ++s[0], s[1] += (unsigned long long)(long long)lap, s[2] += (unsigned long long)(lap * lap);
             }
-            x += dx, y += dy;
-            if (x >= w) x -= w, ++y;
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            n += __shfl_down(n, d, 64);
-            s1 += __shfl_down(s1, d, 64);
-            s2 += __shfl_down(s2, d, 64);
-        }
-        if (lane == 0 && n) {
+        },
+        [&](long long m, int, int, const unsigned long long* s) {
+            if (!s[0]) return;
             unsigned long long* o = boxes + (size_t)m * 3;
-            atomicAdd(o, n);
-            if (s1) atomicAdd(o + 1, s1);
-            if (s2) atomicAdd(o + 2, s2);
-        }
-    }
+            atomicAdd(o, s[0]);
+            if (s[1]) atomicAdd(o + 1, s[1]);
+            if (s[2]) atomicAdd(o + 2, s[2]);
+        });
 }
 
 }  // namespace ay
@@ -249,19 +202,15 @@ extern "C" int ay_focus_u8(const void* region_hwc_u8, int region_h, int region_w
                            int n_rows, int64_t* boxes, int32_t* flags, ay_stream_t stream) {
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8, "ay_focus_u8: null");
-    AY_CHECK_ARG(region_h > 0 && region_w > 0 && region_w <= (1 << 30) / 3 && row_stride_bytes >= (size_t)region_w * 3 &&
-                     (shrink == 1 || shrink == 2),
-                 "ay_focus_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    if (!check_region("ay_focus_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
     AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && cell >= AY_FOCUS_MIN_CELL, "ay_focus_u8: bg_level %d, cell %d", bg_level, cell);
     const int h_img = region_h / shrink, W = region_w / shrink;
-    AY_CHECK_ARG(slide_h >= 1 && slide_h <= FOCUS_MAX_SIDE && slide_w >= 1 && slide_w <= FOCUS_MAX_SIDE &&
+    AY_CHECK_ARG(slide_h >= 1 && slide_h <= SLIDE_MAX_SIDE && slide_w >= 1 && slide_w <= SLIDE_MAX_SIDE &&
                      (long long)slide_h * slide_w < (1ll << 43) && W == slide_w && origin_y >= 0 && origin_y <= slide_h - h_img,
                  "ay_focus_u8: a %dx%d image at row %d of a %dx%d slide (the region holds whole rows of the slide)", h_img, W, origin_y,
                  slide_h, slide_w);
     AY_CHECK_ARG(own_y0 >= 0 && own_y0 <= own_y1 && own_y1 <= slide_h, "ay_focus_u8: owned rows %d .. %d of %d", own_y0, own_y1, slide_h);
-    AY_CHECK_ARG(n_rows >= 0 && (n_rows == 0 || (rows && boxes && flags)) && ((uintptr_t)cells & 7) == 0 && ((uintptr_t)boxes & 7) == 0,
-                 "ay_focus_u8: %d rows %p, boxes %p, flags %p, cells %p", n_rows, (const void*)rows, (void*)boxes, (void*)flags,
-                 (void*)cells);
+    if (!check_cells_boxes("ay_focus_u8", n_rows, rows, boxes, flags, cells)) return AY_ERR_ARG;
     const int c0 = own_y0 > 1 ? own_y0 : 1, c1 = own_y1 < slide_h - 1 ? own_y1 : slide_h - 1;   // the centre rows: c0 <= Y < c1
     const bool some = c0 < c1 && W >= 3;
     AY_CHECK_ARG(!some || (c0 - 1 >= origin_y && c1 <= origin_y + h_img - 1),
@@ -269,27 +218,18 @@ extern "C" int ay_focus_u8(const void* region_hwc_u8, int region_h, int region_w
     if (!some) return AY_OK;                                  // no pixel to evaluate: nothing is launched, added or flagged
     if (cells) {
         const int gx = (slide_w + cell - 1) / cell;           // before the clamp: the caller's grid
-        if (cell > FOCUS_MAX_SIDE) cell = FOCUS_MAX_SIDE;     // one cell either way, and (c + 1) * cell stays an int
-        const unsigned nq = ((unsigned)W * 3 * shrink + FOCUS_ITEM - 1) / FOCUS_ITEM;
-        const int n_xc = (int)((nq + FOCUS_XQ - 1) / FOCUS_XQ);
-        const long long units = (long long)((c1 - c0 + FOCUS_BAND - 1) / FOCUS_BAND) * n_xc;
-        const unsigned blocks = (unsigned)(units > 256 * 8 ? 256 * 8 : units);
-        const bool wide = ((uintptr_t)region_hwc_u8 & 15) == 0 && row_stride_bytes % 16 == 0;
-#define AY_FOCUS_LAUNCH(WIDE, SHRINK)                                                                                                 \
-    hipLaunchKernelGGL((focus_cells_kernel<WIDE, SHRINK>), dim3(blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, h_img, W, \
-                       region_w, row_stride_bytes, bg_level, origin_y, c0, c1, cell, gx, n_xc, units, (unsigned long long*)cells)
-        if (wide && shrink == 1) AY_FOCUS_LAUNCH(true, 1);
-        else if (wide) AY_FOCUS_LAUNCH(true, 2);
-        else if (shrink == 1) AY_FOCUS_LAUNCH(false, 1);
-        else AY_FOCUS_LAUNCH(false, 2);
-#undef AY_FOCUS_LAUNCH
+        if (cell > SLIDE_MAX_SIDE) cell = SLIDE_MAX_SIDE;     // one cell either way, and (c + 1) * cell stays an int
+        const SlideUnits g = slide_units(W, shrink, c1 - c0, FOCUS_BAND, FOCUS_XQ);
+        launch_wide_shrink(region_hwc_u8, row_stride_bytes, shrink, [&](auto wide, auto sh) {
+            hipLaunchKernelGGL((focus_cells_kernel<wide.value, sh.value>), dim3(g.blocks), dim3(256), 0, S(stream),
+                               (const uint8_t*)region_hwc_u8, h_img, W, region_w, row_stride_bytes, bg_level, origin_y, c0, c1, cell, gx,
+                               g.n_xc, g.units, (unsigned long long*)cells);
+        });
         AY_CHECK_LAUNCH("focus_cells_kernel");
     }
     if (n_rows) {
-        const int want = (n_rows + 3) / 4;
-        hipLaunchKernelGGL(focus_boxes_kernel, dim3((unsigned)(want > 256 * 8 ? 256 * 8 : want)), dim3(256), 0, S(stream),
-                           (const uint8_t*)region_hwc_u8, h_img, W, row_stride_bytes, shrink, bg_level, origin_y, slide_h, c0, c1, rows,
-                           n_rows, (unsigned long long*)boxes, flags);
+        hipLaunchKernelGGL(focus_boxes_kernel, dim3(box_walk_blocks(n_rows)), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, h_img,
+                           W, row_stride_bytes, shrink, bg_level, origin_y, slide_h, c0, c1, rows, n_rows, (unsigned long long*)boxes, flags);
         AY_CHECK_LAUNCH("focus_boxes_kernel");
     }
     return AY_OK;

@@ -1,30 +1,26 @@
 // Stain normalisation for whole-slide detection (wsi.stain_stats, wsi.StainMap, wsi.detect_region(stain=...), wsi.normalize_region;
 // THE STAIN RULE is stated in include/amyloid_yolo.h and restated in NumPy fp32 by tests/stain_reference.py).
 //
-//   stain_hist_u8_kernel    histograms of the two stain concentrations over the tissue pixels of a resident region: a read stream with
-//                           ay_tissue.hip's choice of loads (16-byte loads when base and stride allow, byte loads otherwise) that
-//                           walks the IMAGE.  A work unit is 16 rows x up to 2048 items; an item is 48 consecutive bytes of a row, 16
-//                           whole pixels (8 of the halved image, with the same bytes of the next row), so that pixel p of the item
-//                           sits at the same bytes in every lane: the unrolled pixel loop extracts at constant positions and its
-//                           branches diverge only on the tissue test.  A lane unmixes the TISSUE pixels of its item (od in LDS, D
-//                           in scalar registers; most of a slide is glass and costs a minimum and a compare) and counts them in the
-//                           workgroup's int32 LDS histograms, which go to the uint64 histogram in memory with integer atomics when
-//                           the workgroup is done, and every HIST_FLUSH units before that: HIST_FLUSH * 16 * 2048 * 16 < 2^31.
+//   stain_hist_u8_kernel    histograms of the two stain concentrations over the tissue pixels of a resident region: a read stream
+//                           that walks the IMAGE in ay_slide_pass.h's 48-byte items and work units, here of 16 rows x up to 2048
+//                           items; the branches of the unrolled pixel loop diverge only on the tissue test.  A lane unmixes the
+//                           TISSUE pixels of its item (od in LDS, D in scalar registers; most of a slide is glass and costs a
+//                           minimum and a compare) and counts them in the workgroup's int32 LDS histograms, which go to the uint64
+//                           histogram in memory with integer atomics when the workgroup is done, and every HIST_FLUSH units before
+//                           that: HIST_FLUSH * 16 * 2048 * 16 < 2^31.
 //   stain_apply_u8_kernel   the mapped (halved) image in the uint8 form, one pixel per thread.
 //   The stain CUT is the cut kernel / the views kernel of ay_cut.h instantiated here with StainColour (ay_common.h) as colour stage.
 //
 // Every entry point is kernel launches only: no allocation, no host synchronisation, no memset or copy node, no scratch.
 #include "ay_cut.h"
+#include "ay_slide_pass.h"
 
 namespace ay {
 
 constexpr int HIST_BAND = 16;      // rows of a work unit
-constexpr int HIST_ITEM = 48;      // bytes of a row a lane takes at a time: 16 pixels, 8 of the halved image
 constexpr int HIST_XQ = 2048;      // items of a row in a work unit
 constexpr int HIST_FLUSH = 2048;   // units between two flushes of a workgroup: 2048 * 16 * 2048 * 16 pixels = 1.07e9 < 2^31
 constexpr int HIST_WORDS = 2 * AY_STAIN_BINS + 1;
-
-// load48 (ay_common.h): the item's bytes, shared with the load pass
 
 template <bool WIDE, int SHRINK>
 __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __restrict__ reg, int H, int W, int RW, size_t stride, int bg,
@@ -41,7 +37,7 @@ __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __res
     for (int i = tid; i < HIST_WORDS; i += 256) lh[i] = 0;
     __syncthreads();
     const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * BPP;   // bytes of a source row; those that belong to a pixel
-    const unsigned nq = (used + HIST_ITEM - 1) / HIST_ITEM;
+    const unsigned nq = (used + SLIDE_ITEM - 1) / SLIDE_ITEM;
     int cnt = 0, pending = 0;
     auto flush = [&]() {
         if (cnt) atomicAdd(&lh[2 * AY_STAIN_BINS], cnt);
@@ -57,29 +53,18 @@ __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __res
         __syncthreads();
     };
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of flush
-        const unsigned q0 = (unsigned)(u % n_xc) * HIST_XQ, wq = min((unsigned)HIST_XQ, nq - q0);
-        const int y_lo = (int)(u / n_xc) * HIST_BAND, y_hi = min(y_lo + HIST_BAND, H);
-        const unsigned items = (unsigned)(y_hi - y_lo) * wq;
+        const SlideUnit un = slide_unit<HIST_BAND, HIST_XQ>(u, n_xc, nq, 0, H);
+        const unsigned items = (unsigned)(un.y_hi - un.y_lo) * un.wq;
         for (unsigned i = tid; i < items; i += 256) {
-            const unsigned o = (q0 + i % wq) * HIST_ITEM;
-            const int Y = y_lo + (int)(i / wq);
+            const unsigned o = (un.q0 + i % un.wq) * SLIDE_ITEM;
             uint32_t w0[12], w1[12];
-            if (SHRINK == 1) {
-                load48<WIDE>(reg + (size_t)Y * stride, o, row_bytes, w0);
-            } else {
-                load48<WIDE>(reg + (size_t)(2 * Y) * stride, o, row_bytes, w0);
-                load48<WIDE>(reg + (size_t)(2 * Y + 1) * stride, o, row_bytes, w1);
-            }
+            item_load<WIDE, SHRINK>(reg, stride, un.y_lo + (int)(i / un.wq), o, row_bytes, w0, w1);
 #pragma unroll
-            for (int p = 0; p < 48 / BPP; ++p) {                 // the pixels of the item lie at the same bytes in every lane
-                const int j = p * BPP;
-                if (o + j >= used) continue;                     // behind the last pixel of the row
+            for (int p = 0; p < SLIDE_ITEM / BPP; ++p) {         // the pixels of the item lie at the same bytes in every lane
+                if (o + p * BPP >= used) continue;               // behind the last pixel of the row
                 int b[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    b[c] = SHRINK == 1 ? byte_of(w0, j + c)
-                                       : (byte_of(w0, j + c) + byte_of(w0, j + 3 + c) + byte_of(w1, j + c) + byte_of(w1, j + 3 + c) + 2) >> 2;
-                if (min(min(b[0], b[1]), b[2]) >= bg) continue;  // THE TISSUE RULE: most of a slide is glass
+                item_pixel<SHRINK>(w0, w1, p, b);
+                if (!tissue_px(b, bg)) continue;
                 ++cnt;
                 const float o0 = od[b[0]], o1 = od[b[1]], o2 = od[b[2]];
 #pragma unroll
@@ -123,26 +108,16 @@ extern "C" int ay_stain_hist_u8(const void* region_hwc_u8, int region_h, int reg
                                 const ay_stain_params* params_device, uint64_t* hist, ay_stream_t stream) {
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && params_device && hist, "ay_stain_hist_u8: null");
-    AY_CHECK_ARG(region_h > 0 && region_w > 0 && region_w <= (1 << 30) / 3 && row_stride_bytes >= (size_t)region_w * 3 &&
-                     (shrink == 1 || shrink == 2),
-                 "ay_stain_hist_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    if (!check_region("ay_stain_hist_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
     AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && ((uintptr_t)hist & 7) == 0, "ay_stain_hist_u8: bg_level %d, hist %p", bg_level,
                  (void*)hist);
     const int H = region_h / shrink, W = region_w / shrink;
     if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
-    const unsigned nq = ((unsigned)W * 3 * shrink + HIST_ITEM - 1) / HIST_ITEM;
-    const int n_xc = (int)((nq + HIST_XQ - 1) / HIST_XQ);
-    const long long units = (long long)((H + HIST_BAND - 1) / HIST_BAND) * n_xc;
-    const unsigned blocks = (unsigned)(units > 256 * 8 ? 256 * 8 : units);
-    const bool wide = ((uintptr_t)region_hwc_u8 & 15) == 0 && row_stride_bytes % 16 == 0;
-#define AY_STAIN_HIST_LAUNCH(WIDE, SHRINK)                                                                                          \
-    hipLaunchKernelGGL((stain_hist_u8_kernel<WIDE, SHRINK>), dim3(blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, H, W, \
-                       region_w, row_stride_bytes, bg_level, n_xc, units, params_device, (unsigned long long*)hist)
-    if (wide && shrink == 1) AY_STAIN_HIST_LAUNCH(true, 1);
-    else if (wide) AY_STAIN_HIST_LAUNCH(true, 2);
-    else if (shrink == 1) AY_STAIN_HIST_LAUNCH(false, 1);
-    else AY_STAIN_HIST_LAUNCH(false, 2);
-#undef AY_STAIN_HIST_LAUNCH
+    const SlideUnits g = slide_units(W, shrink, H, HIST_BAND, HIST_XQ);
+    launch_wide_shrink(region_hwc_u8, row_stride_bytes, shrink, [&](auto wide, auto sh) {
+        hipLaunchKernelGGL((stain_hist_u8_kernel<wide.value, sh.value>), dim3(g.blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
+                           H, W, region_w, row_stride_bytes, bg_level, g.n_xc, g.units, params_device, (unsigned long long*)hist);
+    });
     AY_CHECK_LAUNCH("stain_hist_u8_kernel");
     return AY_OK;
 }
@@ -152,8 +127,7 @@ extern "C" int ay_ingest_region_tiles_stain_u8(const void* region_hwc_u8, int re
                                                const ay_stain_params* params_device, int out_size, float* out_nchw, ay_stream_t stream) {
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && out_nchw && origins_xy && views && params_device, "ay_ingest_region_tiles_stain_u8: null");
-    AY_CHECK_ARG(region_h > 0 && region_w > 0 && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2),
-                 "ay_ingest_region_tiles_stain_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    if (!check_region("ay_ingest_region_tiles_stain_u8", region_h, region_w, row_stride_bytes, shrink, false)) return AY_ERR_ARG;
     AY_CHECK_ARG(tile > 0 && tile <= (1 << 24) && n > 0 && out_size > 0, "ay_ingest_region_tiles_stain_u8: %d tiles of %d -> %d", n, tile,
                  out_size);
     if (n_views == 1 && views[0] == 0)   // the list cut's geometry and kernel
@@ -167,8 +141,7 @@ extern "C" int ay_stain_apply_u8(const void* region_hwc_u8, int region_h, int re
                                  const ay_stain_params* params_device, uint8_t* out_hwc_u8, size_t out_stride_bytes, ay_stream_t stream) {
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && params_device && out_hwc_u8, "ay_stain_apply_u8: null");
-    AY_CHECK_ARG(region_h > 0 && region_w > 0 && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2),
-                 "ay_stain_apply_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    if (!check_region("ay_stain_apply_u8", region_h, region_w, row_stride_bytes, shrink, false)) return AY_ERR_ARG;
     const int H = region_h / shrink, W = region_w / shrink;
     AY_CHECK_ARG(out_stride_bytes >= (size_t)W * 3, "ay_stain_apply_u8: out rows of %d pixels %zu bytes apart", W, out_stride_bytes);
     if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image

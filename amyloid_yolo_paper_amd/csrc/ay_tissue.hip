@@ -13,7 +13,7 @@
 // load when base and row stride are 16-byte multiples, byte loads otherwise and at a row's ragged end) plus the 8 behind them,
 // builds the mask of bytes below bg and ORs three neighbouring bits at the byte positions where a pixel starts (row offset % 3 == 0;
 // % 6 == 0 on the halved image, whose byte value is the 2x2 round-half-up mean of four source bytes 3 apart and a row apart).
-#include "ay_common.h"
+#include "ay_slide_pass.h"
 
 namespace ay {
 
@@ -41,8 +41,6 @@ __device__ __forceinline__ void load24(const uint8_t* __restrict__ row, unsigned
         }
     }
 }
-
-// byte_of (ay_common.h): byte j of such a segment, shared with the stain histogram
 
 // tiles (per axis) that contain the interval [lo, hi), which no tile boundary cuts: t * step <= lo and hi <= t * step + tile
 __device__ __forceinline__ void tile_range(int lo, int hi, int tile, int step, int tiles, int& t_lo, int& t_hi) {
@@ -119,9 +117,7 @@ extern "C" int ay_tile_tissue_u8(const void* region_hwc_u8, int region_h, int re
                                  int step, int tiles_y, int tiles_x, int bg_level, int32_t* counts, ay_stream_t stream) {
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && counts, "ay_tile_tissue_u8: null");
-    AY_CHECK_ARG(region_h > 0 && region_w > 0 && region_w <= (1 << 30) / 3 && row_stride_bytes >= (size_t)region_w * 3 &&
-                     (shrink == 1 || shrink == 2),
-                 "ay_tile_tissue_u8: region %dx%d stride %zu shrink %d", region_h, region_w, row_stride_bytes, shrink);
+    if (!check_region("ay_tile_tissue_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
     AY_CHECK_ARG(tile > 0 && tile <= 46340 /* a count is at most tile^2: int32 */ && step > 0 && step <= tile && tiles_y > 0 && tiles_x > 0 && (long long)tiles_y * tiles_x <= (1 << 30) &&
                      bg_level >= 0 && bg_level <= 256,
                  "ay_tile_tissue_u8: tile grid %dx%d of %d step %d, bg_level %d", tiles_y, tiles_x, tile, step, bg_level);
@@ -135,15 +131,10 @@ extern "C" int ay_tile_tissue_u8(const void* region_hwc_u8, int region_h, int re
     const int band = 32, n_bands = (step + band - 1) / band;   // rows of one unit: enough units to fill the chip on one strip
     const long long units = (long long)n_yint * n_bands * n_xint;
     const unsigned blocks = (unsigned)(units > 256 * 32 ? 256 * 32 : units);
-    const bool wide = ((uintptr_t)region_hwc_u8 & 15) == 0 && row_stride_bytes % 16 == 0;
-#define AY_TISSUE_LAUNCH(WIDE, SHRINK)                                                                                                \
-    hipLaunchKernelGGL((tile_tissue_u8_kernel<WIDE, SHRINK>), dim3(blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8, H, W, \
-                       region_w, row_stride_bytes, tile, step, tiles_y, tiles_x, bg_level, band, n_bands, n_xint, units, counts)
-    if (wide && shrink == 1) AY_TISSUE_LAUNCH(true, 1);
-    else if (wide) AY_TISSUE_LAUNCH(true, 2);
-    else if (shrink == 1) AY_TISSUE_LAUNCH(false, 1);
-    else AY_TISSUE_LAUNCH(false, 2);
-#undef AY_TISSUE_LAUNCH
+    launch_wide_shrink(region_hwc_u8, row_stride_bytes, shrink, [&](auto wide, auto sh) {
+        hipLaunchKernelGGL((tile_tissue_u8_kernel<wide.value, sh.value>), dim3(blocks), dim3(256), 0, S(stream), (const uint8_t*)region_hwc_u8,
+                           H, W, region_w, row_stride_bytes, tile, step, tiles_y, tiles_x, bg_level, band, n_bands, n_xint, units, counts);
+    });
     AY_CHECK_LAUNCH("tile_tissue_u8_kernel");
     return AY_OK;
 }

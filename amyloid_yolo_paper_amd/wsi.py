@@ -320,6 +320,18 @@ class RegionTileStream:
             yield cur[:fill * V], w0
 
 
+def _each_strip(stream, call):
+    """``call(k, j, rows, width)`` on every block of :meth:`RegionTileStream._strip_loop`, released behind the kernels the call issues"""
+    for j, k, valid, width in stream._strip_loop():
+        call(k, j, valid, width)
+        stream._release(k)
+
+
+def _strip_args(stream, k, valid, width):
+    """the leading arguments of every entry point that reads a strip: region, rows, width, row stride in bytes, shrink"""
+    return ptr(stream._strips[k]), valid, width, width * 3, stream.shrink
+
+
 def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
     """Tissue pixels per tile of the ``tile_grid(H, W, tile, overlap)`` grid over ``raster`` -> NumPy int32 ``[tiles_y, tiles_x]``.
 
@@ -338,10 +350,9 @@ def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
     stream = RegionTileStream(raster, tile, tile, shrink, overlap)
     L = _lib.lib()
     counts = torch.empty(stream.tiles_y, stream.tiles_x, device=stream.dev, dtype=torch.int32)
-    for j, k, valid, width in stream._strip_loop():
-        check(L.ay_tile_tissue_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, stream.tile, stream.step, 1,
-                                  stream.tiles_x, bg_level, ptr(counts[j]), _lib.stream_ptr()), "ay_tile_tissue_u8")
-        stream._release(k)
+    _each_strip(stream, lambda k, j, valid, width: check(
+        L.ay_tile_tissue_u8(*_strip_args(stream, k, valid, width), stream.tile, stream.step, 1, stream.tiles_x, bg_level, ptr(counts[j]),
+                            _lib.stream_ptr()), "ay_tile_tissue_u8"))
     return counts.cpu().numpy()
 
 
@@ -603,6 +614,13 @@ def densest_fields(counts, tissue=None, field=8, top_k=5, need_tissue=0):
     return fields.cpu().numpy(), n_found.cpu().numpy()
 
 
+def _field_sums(picked, filled, F, maps):
+    """for every filled field ``picked[c, k]`` of :func:`densest_fields`: ``(c, k, [the sum of each map over the field's F x F cells])``"""
+    for c, k in zip(*np.nonzero(filled)):
+        fy, fx = int(picked[c, k, 0]), int(picked[c, k, 1])
+        yield c, k, [int(m[fy:fy + F, fx:fx + F].sum()) for m in maps]
+
+
 def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
                     dab_thres=None, load=False, focus=False, min_sharpness=None, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
@@ -715,18 +733,14 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         out["load_tissue"], out["load_positive"], out["load_map"] = ld["tissue"], ld["positive"], ld["load"]
         out["total_load"], out["box_load"] = ld["total_load"], ld["boxes"]
         out["field_load"] = np.full((num_classes, K), np.nan)
-        for c, k in zip(*np.nonzero(filled)):
-            fy, fx = int(picked[c, k, 0]), int(picked[c, k, 1])
-            t = int(ld["tissue"][fy:fy + F, fx:fx + F].sum())
+        for c, k, (t, p) in _field_sums(picked, filled, F, (ld["tissue"], ld["positive"])):
             if t:
-                out["field_load"][c, k] = float(int(ld["positive"][fy:fy + F, fx:fx + F].sum())) / t
+                out["field_load"][c, k] = float(p) / t
     if focus:
         fm = focus_map(raster, rows, cell, shrink, bg_level)
         out["focus_n"], out["focus_sharpness"], out["box_sharpness"] = fm["n"], fm["sharpness"], fm["box_sharpness"]
         out["field_sharpness"] = np.full((num_classes, K), np.nan)
-        for c, k in zip(*np.nonzero(filled)):
-            fy, fx = int(picked[c, k, 0]), int(picked[c, k, 1])
-            n, s1, s2 = (int(fm[key][fy:fy + F, fx:fx + F].sum()) for key in ("n", "s1", "s2"))
+        for c, k, (n, s1, s2) in _field_sums(picked, filled, F, (fm["n"], fm["s1"], fm["s2"])):
             if n:
                 out["field_sharpness"][c, k] = s2 / n - (s1 / n) ** 2
         if min_sharpness is not None:
@@ -909,10 +923,8 @@ def stain_stats(raster, shrink=1, bg_level=220, probe_stride=16, basis=H_DAB):
     stream = RegionTileStream(raster, min(1536, max(1, raster.shape[0] // shrink)), 1, shrink)
     L = _lib.lib()
     hist = torch.zeros(2 * STAIN_BINS + 1, device=stream.dev, dtype=torch.int64)
-    for j, k, valid, width in stream._strip_loop():
-        check(L.ay_stain_hist_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, bg_level, ptr(params), ptr(hist),
-                                 _lib.stream_ptr()), "ay_stain_hist_u8")
-        stream._release(k)
+    _each_strip(stream, lambda k, j, valid, width: check(
+        L.ay_stain_hist_u8(*_strip_args(stream, k, valid, width), bg_level, ptr(params), ptr(hist), _lib.stream_ptr()), "ay_stain_hist_u8"))
     h = hist.cpu().numpy()
     return StainStats(h[:2 * STAIN_BINS].reshape(2, STAIN_BINS), h[2 * STAIN_BINS], basis)
 
@@ -930,11 +942,13 @@ def normalize_region(raster, stain, shrink=1, device=False):
     L = _lib.lib()
     params = stain.params
     out = torch.empty(H, W, 3, device=stream.dev, dtype=torch.uint8)
-    for j, k, valid, width in stream._strip_loop():
+
+    def apply(k, j, valid, width):
         if valid // shrink:
-            check(L.ay_stain_apply_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, ptr(params),
-                                      ptr(out[j * stream.tile:]), W * 3, _lib.stream_ptr()), "ay_stain_apply_u8")
-        stream._release(k)
+            check(L.ay_stain_apply_u8(*_strip_args(stream, k, valid, width), ptr(params), ptr(out[j * stream.tile:]), W * 3,
+                                      _lib.stream_ptr()), "ay_stain_apply_u8")
+
+    _each_strip(stream, apply)
     return out if device else out.cpu().numpy()
 
 
@@ -954,8 +968,8 @@ def _thres_bin(thres, what):
     return min(int(round(thres * 64.0)), STAIN_BINS)
 
 
-def _check_load(what, raster, shrink, cell, bg_level, stain, basis):
-    """the host checks :func:`stain_load` and ``quantify_region(load=True)`` share -> (H, W, cell, bg_level)"""
+def _check_cell_pass(what, raster, shrink, cell, bg_level, max_pixels=None):
+    """the host checks of a pass over the cells of the burden grid (:func:`stain_load`, :func:`focus_map`) -> (H, W, cell, bg_level)"""
     if shrink not in (1, 2):
         raise ValueError(f"{what}: shrink {shrink!r} is neither 1 nor 2")
     if getattr(raster, "ndim", 0) != 3 or raster.shape[2] != 3 or raster.dtype != np.uint8:
@@ -963,18 +977,49 @@ def _check_load(what, raster, shrink, cell, bg_level, stain, basis):
     H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
     if H < 1 or W < 1:
         raise ValueError(f"{what}: raster {tuple(raster.shape)} has no (halved) pixel")
-    if max(H, W) > LOAD_MAX_SIDE:
-        raise ValueError(f"{what}: a (halved) slide of {H} x {W} exceeds {LOAD_MAX_SIDE} pixels per side")
+    if max(H, W) > LOAD_MAX_SIDE or (max_pixels is not None and H * W >= max_pixels):
+        raise ValueError(f"{what}: a (halved) slide of {H} x {W} exceeds {LOAD_MAX_SIDE} pixels per side"
+                         + ("" if max_pixels is None else f" or 2**{max_pixels.bit_length() - 1} pixels"))
     cell = _whole(cell, LOAD_MIN_CELL, 2 ** 31 - 1, f"{what}: cell")
     gy, gx, _ = tile_grid(H, W, cell)
     if gy * gx > LOAD_MAX_CELLS:
         raise ValueError(f"{what}: {gy} x {gx} cells exceed {LOAD_MAX_CELLS}; choose a larger cell")
-    bg_level = _whole(bg_level, 0, 256, f"{what}: bg_level")
+    return H, W, cell, _whole(bg_level, 0, 256, f"{what}: bg_level")
+
+
+def _check_load(what, raster, shrink, cell, bg_level, stain, basis):
+    """the host checks :func:`stain_load` and ``quantify_region(load=True)`` share -> (H, W, cell, bg_level)"""
+    checked = _check_cell_pass(what, raster, shrink, cell, bg_level)
     if isinstance(stain, bool) or stain not in (0, 1):
         raise ValueError(f"{what}: stain {stain!r} is neither 0 nor 1")
     if not isinstance(basis, StainBasis):
         raise ValueError(f"{what}: basis must be a wsi.StainBasis")
-    return H, W, cell, bg_level
+    return checked
+
+
+def _check_rows(what, rows):
+    if rows is not None and (len(getattr(rows, "shape", ())) != 2 or rows.shape[1] != 7):
+        raise ValueError(f"{what}: rows must be [M,7] or None, got {tuple(getattr(rows, 'shape', ())) or type(rows).__name__}")
+
+
+def _cell_box_pass(stream, gy, gx, rows, n_box_sums, call):
+    """What :func:`stain_load` and :func:`focus_map` share: ``cells`` int64 [gy,gx,3] and, with ``rows`` ([M,7] or None), ``boxes`` int64
+    [M,n_box_sums] and ``flags`` are zeroed once; every strip adds to them in ``call(k, j, rows, width, cells, rows, M, boxes, flags)``
+    (device pointers; without a box None, 0, None, None); one read-back -> the three cell maps, ``boxes``, ``flags`` (None without rows)"""
+    from .stats import _slide_array
+    cells = torch.zeros(gy, gx, 3, device=stream.dev, dtype=torch.int64)
+    box_args = (None, 0, None, None)
+    if rows is not None:
+        rows = _slide_array(rows, 7, stream.dev)
+        M = int(rows.shape[0])
+        boxes = torch.zeros(M, n_box_sums, device=stream.dev, dtype=torch.int64)
+        flags = torch.zeros(1, device=stream.dev, dtype=torch.int32)
+        if M:
+            box_args = (ptr(rows), M, ptr(boxes), ptr(flags))
+    _each_strip(stream, lambda k, j, valid, width: call(k, j, valid, width, ptr(cells), *box_args))
+    c = cells.cpu().numpy()
+    maps = tuple(np.ascontiguousarray(c[:, :, i]) for i in range(3))
+    return maps + ((None, None) if rows is None else (boxes.cpu().numpy(), int(flags.item())))
 
 
 def stain_load(raster, rows=None, cell=128, shrink=1, bg_level=220, thres=0.15, stain=1, basis=H_DAB):
@@ -1002,34 +1047,20 @@ def stain_load(raster, rows=None, cell=128, shrink=1, bg_level=220, thres=0.15, 
     them into areas -- and ``flags`` (bit 1: a coordinate not finite)."""
     H, W, cell, bg_level = _check_load("stain_load", raster, shrink, cell, bg_level, stain, basis)
     j = _thres_bin(thres, "stain_load")
-    if rows is not None and (len(getattr(rows, "shape", ())) != 2 or rows.shape[1] != 7):
-        raise ValueError(f"stain_load: rows must be [M,7] or None, got {tuple(getattr(rows, 'shape', ())) or type(rows).__name__}")
-    from .stats import _slide_array
+    _check_rows("stain_load", rows)
     stream = RegionTileStream(raster, min(1536, H), 1, shrink)
-    dev = stream.dev
     params = StainMap.identity(basis).params
     gy, gx, _ = tile_grid(H, W, cell)
-    cells = torch.zeros(gy, gx, 3, device=dev, dtype=torch.int64)
-    M = 0
-    if rows is not None:
-        rows = _slide_array(rows, 7, dev)
-        M = int(rows.shape[0])
-        boxes = torch.zeros(M, 4, device=dev, dtype=torch.int64)
-        flags = torch.zeros(1, device=dev, dtype=torch.int32)
     L = _lib.lib()
-    for jy, k, valid, width in stream._strip_loop():
-        check(L.ay_stain_load_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, jy * stream.tile, 0, H, W, bg_level,
-                                 ptr(params), int(stain), j, cell, ptr(cells), ptr(rows) if M else None, M, ptr(boxes) if M else None,
-                                 ptr(flags) if M else None, _lib.stream_ptr()), "ay_stain_load_u8")
-        stream._release(k)
-    c = cells.cpu().numpy()
-    tissue, positive, bin_sum = (np.ascontiguousarray(c[:, :, i]) for i in range(3))
+    tissue, positive, bin_sum, boxes, flags = _cell_box_pass(stream, gy, gx, rows, 4, lambda k, jy, valid, width, cells, *box_args: check(
+        L.ay_stain_load_u8(*_strip_args(stream, k, valid, width), jy * stream.tile, 0, H, W, bg_level, ptr(params), int(stain), j, cell,
+                           cells, *box_args, _lib.stream_ptr()), "ay_stain_load_u8"))
     n_t, n_p = int(tissue.sum()), int(positive.sum())
     out = {"tissue": tissue, "positive": positive, "bin_sum": bin_sum,
            "load": positive.astype(np.float64) / np.where(tissue > 0, tissue, np.nan),
            "total_load": float(n_p) / n_t if n_t else math.nan, "thres": j / 64.0}
     if rows is not None:
-        out["boxes"], out["flags"] = boxes.cpu().numpy(), int(flags.item())
+        out["boxes"], out["flags"] = boxes, flags
     return out
 
 
@@ -1055,26 +1086,13 @@ def box_morphometry(boxes, mpp=None):
 
 
 # ---- focus map: sharpness per map cell and per detection ------------------------------------------------------------------------------
-FOCUS_MIN_CELL, FOCUS_MAX_SIDE, FOCUS_FLAG_NONFINITE = 16, 1 << 24, 1    # include/amyloid_yolo.h, THE FOCUS RULE
+FOCUS_MIN_CELL, FOCUS_MAX_SIDE, FOCUS_FLAG_NONFINITE = 16, 1 << 24, 1    # include/amyloid_yolo.h, THE FOCUS RULE: THE LOAD RULE's
 FOCUS_MAX_PIXELS = 1 << 43                                               # H * W below it: s2 fits int64
 
 
 def _check_focus(what, raster, shrink, cell, bg_level):
-    """the host checks :func:`focus_map` and ``quantify_region(focus=True)`` share (:func:`_check_load`'s) -> (H, W, cell, bg_level)"""
-    if shrink not in (1, 2):
-        raise ValueError(f"{what}: shrink {shrink!r} is neither 1 nor 2")
-    if getattr(raster, "ndim", 0) != 3 or raster.shape[2] != 3 or raster.dtype != np.uint8:
-        raise ValueError(f"{what}: raster must be a uint8 [H,W,3] array")
-    H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
-    if H < 1 or W < 1:
-        raise ValueError(f"{what}: raster {tuple(raster.shape)} has no (halved) pixel")
-    if max(H, W) > FOCUS_MAX_SIDE or H * W >= FOCUS_MAX_PIXELS:
-        raise ValueError(f"{what}: a (halved) slide of {H} x {W} exceeds {FOCUS_MAX_SIDE} pixels per side or 2**43 pixels")
-    cell = _whole(cell, FOCUS_MIN_CELL, 2 ** 31 - 1, f"{what}: cell")
-    gy, gx, _ = tile_grid(H, W, cell)
-    if gy * gx > LOAD_MAX_CELLS:
-        raise ValueError(f"{what}: {gy} x {gx} cells exceed {LOAD_MAX_CELLS}; choose a larger cell")
-    return H, W, cell, _whole(bg_level, 0, 256, f"{what}: bg_level")
+    """the host checks :func:`focus_map` and ``quantify_region(focus=True)`` share -> (H, W, cell, bg_level)"""
+    return _check_cell_pass(what, raster, shrink, cell, bg_level, FOCUS_MAX_PIXELS)
 
 
 def _sharpness(n, s1, s2):
@@ -1103,32 +1121,21 @@ def focus_map(raster, rows=None, cell=128, shrink=1, bg_level=220, strip=1536):
     on the texture of the tissue and the strength of the stain as well as on focus: see :func:`focus_summary`."""
     H, W, cell, bg_level = _check_focus("focus_map", raster, shrink, cell, bg_level)
     strip = _whole(strip, 3, 2 ** 31 - 1, "focus_map: strip")
-    if rows is not None and (len(getattr(rows, "shape", ())) != 2 or rows.shape[1] != 7):
-        raise ValueError(f"focus_map: rows must be [M,7] or None, got {tuple(getattr(rows, 'shape', ())) or type(rows).__name__}")
+    _check_rows("focus_map", rows)
     gy, gx, _ = tile_grid(H, W, cell)
-    M = 0 if rows is None else int(rows.shape[0])
     if H < 3 or W < 3:
-        c, b, f = np.zeros((gy, gx, 3), np.int64), np.zeros((M, 3), np.int64), 0
+        n, s1, s2 = (np.zeros((gy, gx), np.int64) for _ in range(3))
+        b, f = (None, None) if rows is None else (np.zeros((int(rows.shape[0]), 3), np.int64), 0)
     else:
-        from .stats import _slide_array
-        T = min(strip, H)
-        stream = RegionTileStream(raster, T, 1, shrink, overlap=2)
-        dev = stream.dev
-        cells = torch.zeros(gy, gx, 3, device=dev, dtype=torch.int64)
-        if rows is not None:
-            rows = _slide_array(rows, 7, dev)
-            boxes = torch.zeros(M, 3, device=dev, dtype=torch.int64)
-            flags = torch.zeros(1, device=dev, dtype=torch.int32)
+        stream = RegionTileStream(raster, min(strip, H), 1, shrink, overlap=2)
         L = _lib.lib()
-        for jy, k, valid, width in stream._strip_loop():
+
+        def call(k, jy, valid, width, cells, *box_args):
             y0, held = jy * stream.step, valid // stream.shrink
-            check(L.ay_focus_u8(ptr(stream._strips[k]), valid, width, width * 3, stream.shrink, y0, H, W, y0 + 1, y0 + held - 1, bg_level,
-                                cell, ptr(cells), ptr(rows) if M else None, M, ptr(boxes) if M else None, ptr(flags) if M else None,
+            check(L.ay_focus_u8(*_strip_args(stream, k, valid, width), y0, H, W, y0 + 1, y0 + held - 1, bg_level, cell, cells, *box_args,
                                 _lib.stream_ptr()), "ay_focus_u8")
-            stream._release(k)
-        c = cells.cpu().numpy()
-        b, f = (boxes.cpu().numpy(), int(flags.item())) if M else (np.zeros((0, 3), np.int64), 0)
-    n, s1, s2 = (np.ascontiguousarray(c[:, :, i]) for i in range(3))
+
+        n, s1, s2, b, f = _cell_box_pass(stream, gy, gx, rows, 3, call)
     out = {"n": n, "s1": s1, "s2": s2, "sharpness": _sharpness(n, s1, s2)}
     if rows is not None:
         out["boxes"], out["box_sharpness"], out["flags"] = b, _sharpness(b[:, 0], b[:, 1], b[:, 2]), f
