@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import AyError, check
+from .upload import pack_records, pinned, record_offset
 
 # numpy mirror of ay_aug_params (include/amyloid_yolo.h; _lib.AugParams is the ctypes mirror)
 AUG_DTYPE = np.dtype([("src_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("inv", "<f4", (6,)), ("flip", "<i4"),
@@ -215,7 +216,6 @@ def augment_ingest_device(tiles, params, img_size, out=None):
         assert (int(recs[i]["h"]), int(recs[i]["w"])) == (t.shape[0], t.shape[1]), "record %d is for another tile size" % i
     recs["src_offset"] = offs[:B]
     n_img = int(offs[B])
-    tab = (n_img + 15) // 16 * 16              # the table starts on 16 bytes behind the pixels
     rec_bytes = torch.from_numpy(recs.view(np.uint8).reshape(-1))
     dev = torch.device("cuda", torch.cuda.current_device())
     if resident is None and all(t.is_cuda for t in tiles):
@@ -224,10 +224,10 @@ def augment_ingest_device(tiles, params, img_size, out=None):
         table = rec_bytes.to(dev, non_blocking=True)
         src_ptr, table_ptr = resident.data_ptr(), table.data_ptr()
     else:
-        host = torch.empty(tab + rec_bytes.numel(), dtype=torch.uint8, pin_memory=True)
+        host = pinned(record_offset(n_img) + rec_bytes.numel())
         for i, t in enumerate(tiles):
             host[int(offs[i]):int(offs[i + 1])].copy_(t.reshape(-1))
-        host[tab:].copy_(rec_bytes)
+        tab = pack_records(host.numpy(), n_img, recs)
         resident = host.to(dev, non_blocking=True)
         src_ptr, table_ptr = resident.data_ptr(), resident.data_ptr() + tab
     if out is None:
@@ -325,10 +325,9 @@ def augment_ingest_windows_device(src, table, img_size, out=None):
         resident, tab_dev = src, rec_bytes.to(dev, non_blocking=True)
         src_ptr, table_ptr = src.data_ptr(), tab_dev.data_ptr()
     else:
-        tab = (n + 15) // 16 * 16              # the table starts on 16 bytes behind the pixels
-        host = torch.empty(tab + rec_bytes.numel(), dtype=torch.uint8, pin_memory=True)
+        host = pinned(record_offset(n) + rec_bytes.numel())
         host[:n].copy_(src.reshape(-1))
-        host[tab:].copy_(rec_bytes)
+        tab = pack_records(host.numpy(), n, recs)
         resident = host.to(dev, non_blocking=True)
         src_ptr, table_ptr = resident.data_ptr(), resident.data_ptr() + tab
     if out is None:

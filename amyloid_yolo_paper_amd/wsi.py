@@ -3,8 +3,11 @@ reference (``crop.py:13-25`` writes 1536-px JPEG tiles with pyvips ``dzsave``, `
 
 A slide (any ``[H, W, 3]`` uint8 array: a NumPy memmap of a decoded level, a pyvips/openslide region fetched by the caller)
 is walked in full-width strips of one tile row.  A strip is one contiguous slice of the raster: it goes to the device in a
-single copy from a pinned staging buffer on a copy stream (two buffers, so strip i+1 uploads while strip i computes), and
-``ay_ingest_region_tiles_step_u8`` cuts the row of tiles out of it on the device -- at ``step == tile`` dzsave's 'google' layout:
+single copy from a pinned staging buffer on a copy stream (two buffers, so strip i+1 uploads while strip i computes).  Three
+layers: ``upload.Uploader`` holds that double-buffer protocol and nothing about slides; :class:`StripStream` feeds it the strips
+of a raster (height, step, shrink, optionally column spans and the strips to visit) and is all the slide passes below need;
+:class:`RegionTileStream` owns a strip stream and adds the tile side (views, stain, masks, batches).
+``ay_ingest_region_tiles_step_u8`` cuts the row of tiles out of a strip on the device -- at ``step == tile`` dzsave's 'google' layout:
 a ``tile`` grid from the top-left corner, edge tiles padded with the background 255 -- with the optional 40x -> 20x halving
 (``crop.py:44-47``) and the detect-time ``/255`` + nearest resize fused in.  Detections come back in slide coordinates.
 
@@ -42,13 +45,13 @@ FOCUS RULE) into a sharpness map, :func:`focus_summary` reads it, and ``quantify
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
 import math
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .upload import Uploader, pack_records, record_offset
 from .utils import nms_device, non_max_suppression
 from .views import check_views, nms_views_device
 
@@ -101,6 +104,68 @@ def probe_view(raster, tile, shrink=1, overlap=0, probe_stride=16):
     return view, tile // d, overlap // d
 
 
+class StripStream:
+    """Strips of a uint8 ``[H, W, 3]`` raster on the device, one after another: strip ``j`` is rows ``[j * step, j * step +
+    height)`` of the (halved, for ``shrink == 2``) slide, ``tile_grid``'s ``max(1, ceil((H - (height - step)) / step))`` of them
+    (``count``).  ``jobs`` (default: every strip at full width) lists the strips to visit as ``(j, c0, c1)`` with the span of
+    SOURCE columns ``[c0, c1)`` to stage.
+
+    The iteration yields ``(j, k, rows, width)`` once the current stream waits for the upload of strip ``j``: a ``rows x width``
+    block of source pixels, rows ``3 * width`` bytes apart, whose leading kernel arguments are ``args(k, rows, width)``.  The user
+    issues every kernel that reads the block on the current stream and then calls ``release(k)``; :meth:`each` does both around a
+    call.  Staging, upload and their order are ``upload.Uploader``'s, with the buffers for the largest job allocated here."""
+
+    def __init__(self, raster, height, step, shrink=1, jobs=None):
+        if not torch.cuda.is_available():
+            raise _lib.AyError("no HIP device: the strip stream has no CPU fallback")
+        assert raster.ndim == 3 and raster.shape[2] == 3 and raster.dtype == np.uint8, "uint8 [H,W,3] raster"
+        assert shrink in (1, 2)
+        self.raster, self.height, self.step, self.shrink = raster, int(height), int(step), int(shrink)
+        self.count = tile_grid(raster.shape[0] // shrink, 1, self.height, self.height - self.step)[0]
+        self.jobs = [(j, 0, raster.shape[1]) for j in range(self.count)] if jobs is None else jobs
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        rows = self.height * self.shrink
+        self._chunk = -(-rows // 4)
+        self._up = Uploader(self.dev, rows * 3 * max((c1 - c0 for _, c0, c1 in self.jobs), default=0))
+        self.blocks = [None, None]      # the device buffer that holds block k
+
+    def staged_bytes(self):
+        """bytes of the raster that one pass stages and uploads"""
+        rows, first = self.height * self.shrink, self.step * self.shrink
+        return sum(len(range(j * first, min(j * first + rows, self.raster.shape[0]))) * (c1 - c0) * 3 for j, c0, c1 in self.jobs)
+
+    def _fill(self, idx, host):
+        """host side of a strip: raster rows (the job's columns) -> pinned buffer, as one contiguous block"""
+        j, c0, c1 = self.jobs[idx]
+        first = j * self.step * self.shrink
+        src = self.raster[first:first + self.height * self.shrink, c0:c1]
+        n, w = src.shape[0], src.shape[1]
+        # staging copy by NumPy (memcpy speed; torch's uint8 copy_ ran at a quarter of it), rows split over a few threads --
+        # the copy releases the GIL -- so that one strip stages faster than the GPU consumes it
+        dst = host(n * w * 3)[:n * w * 3].reshape(n, w, 3)
+        parts = [(a, min(a + self._chunk, n)) for a in range(0, n, self._chunk)]
+        list(self._up.pool.map(lambda ab: np.copyto(dst[ab[0]:ab[1]], src[ab[0]:ab[1]]), parts))
+        return (j, n, w), n * w * 3
+
+    def __iter__(self):
+        for k, (j, n, w), block, _ in self._up.run(len(self.jobs), self._fill):
+            self.blocks[k] = block
+            yield j, k, n, w
+
+    def args(self, k, rows, width):
+        """the leading arguments of every entry point that reads a strip: region, rows, width, row stride in bytes, shrink"""
+        return ptr(self.blocks[k]), rows, width, width * 3, self.shrink
+
+    def release(self, k):
+        self._up.release(k)
+
+    def each(self, call):
+        """``call(k, j, rows, width)`` on every block, released behind the kernels the call issues"""
+        for j, k, rows, width in self:
+            call(k, j, rows, width)
+            self.release(k)
+
+
 class RegionTileStream:
     """Iterates over the tile rows of ``raster`` and yields ``(tiles [n,3,S,S] float32 on the device, [(ty, tx), ...])``.
 
@@ -128,29 +193,19 @@ class RegionTileStream:
         self.stain = stain
         if not torch.cuda.is_available():
             raise _lib.AyError("no HIP device: RegionTileStream has no CPU fallback")
-        assert raster.ndim == 3 and raster.shape[2] == 3 and raster.dtype == np.uint8, "uint8 [H,W,3] raster"
-        assert shrink in (1, 2)
         self.raster, self.tile, self.S, self.shrink = raster, int(tile), int(img_size), int(shrink)
         H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
         self.overlap = int(overlap)
         self.tiles_y, self.tiles_x, self.step = tile_grid(H, W, self.tile, self.overlap)
         self.tile_mask = None if tile_mask is None else check_tile_mask(tile_mask, H, W, self.tile, self.overlap)
-        self._jobs = self._strip_jobs()
-        self.dev = torch.device("cuda", torch.cuda.current_device())
-        rows = self.tile * shrink
-        self._pinned = [torch.empty(rows, raster.shape[1], 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._strips = [torch.empty(rows, raster.shape[1], 3, dtype=torch.uint8, device=self.dev) for _ in range(2)]
-        self._copy = torch.cuda.Stream(device=self.dev)
-        self._pool = ThreadPoolExecutor(max_workers=4)      # row chunks of one staging copy
-        self._stager = ThreadPoolExecutor(max_workers=1)    # one strip ahead of the consumer
-        self._chunk = -(-rows // 4)
-        self._uploaded = [None, None]   # event: strip landed in _strips[k]
-        self._consumed = [None, None]   # event: every ingest kernel that read _strips[k] is done
+        self._strips = StripStream(raster, self.tile, self.step, self.shrink, self._strip_jobs())
+        self.dev = self._strips.dev
+        self._view_ids = (C.c_int * len(self.views))(*self.views)
 
     def _strip_jobs(self):
-        """the strips that are staged: ``[(j, c0, c1)]`` = tile row and its span of SOURCE columns ``[c0, c1)`` (computed once)"""
+        """with a mask, the strips that are staged: ``[(j, c0, c1)]`` = tile row and its span of SOURCE columns ``[c0, c1)``"""
         if self.tile_mask is None:
-            return [(j, 0, self.raster.shape[1]) for j in range(self.tiles_y)]
+            return None
         W, out = self.raster.shape[1] // self.shrink, []
         for j in range(self.tiles_y):
             txs = np.flatnonzero(self.tile_mask[j])
@@ -160,68 +215,11 @@ class RegionTileStream:
 
     def _staged_bytes(self):
         """bytes of the raster that one pass stages and uploads"""
-        rows, first = self.tile * self.shrink, self.step * self.shrink
-        return sum(len(range(j * first, min(j * first + rows, self.raster.shape[0]))) * (c1 - c0) * 3 for j, c0, c1 in self._jobs)
+        return self._strips.staged_bytes()
 
     def __len__(self):
         """the number of strips the iteration yields: ``tiles_y`` without a mask, the tile rows that hold a wanted tile with one"""
-        return len(self._jobs)
-
-    def _stage(self, idx, job):
-        """host side of a strip: raster rows (the job's columns) -> pinned buffer, as one contiguous block with rows ``3 * width``
-        bytes apart (runs on the staging thread, under the consumer's GPU work) -> (rows, width) of the block"""
-        k = idx & 1
-        j, c0, c1 = job
-        rows = self.tile * self.shrink
-        first = j * self.step * self.shrink
-        src = self.raster[first:first + rows, c0:c1]
-        n, w = src.shape[0], src.shape[1]
-        if self._uploaded[k] is not None:
-            self._uploaded[k].synchronize()      # the host buffer is free again once its last copy has run
-        # staging copy by NumPy (memcpy speed; torch's uint8 copy_ ran at a quarter of it), rows split over a few threads --
-        # the copy releases the GIL -- so that one strip stages faster than the GPU consumes it
-        dst = self._pinned[k].numpy().reshape(-1)[:n * w * 3].reshape(n, w, 3)
-        parts = [(a, min(a + self._chunk, n)) for a in range(0, n, self._chunk)]
-        list(self._pool.map(lambda ab: np.copyto(dst[ab[0]:ab[1]], src[ab[0]:ab[1]]), parts))
-        return n, w
-
-    def _copy_to_device(self, idx, nbytes):
-        k = idx & 1
-        if self._consumed[k] is not None:
-            self._copy.wait_event(self._consumed[k])
-        with torch.cuda.stream(self._copy):
-            self._strips[k].view(-1)[:nbytes].copy_(self._pinned[k].view(-1)[:nbytes], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self._copy)
-        self._uploaded[k] = ev
-
-    def _strip_loop(self):
-        """The strip machinery every user shares: stage (one strip ahead, on the staging thread), pinned upload on the copy stream,
-        two buffers.  Yields ``(j, k, rows, width)`` once the current stream waits for the upload of tile row ``j`` into
-        ``_strips[k]``: a ``rows x width`` block of source pixels, rows ``3 * width`` bytes apart.  The user issues every kernel that
-        reads the block on the current stream and then calls ``_release(k)``; the buffer is refilled only behind that point."""
-        jobs = self._jobs
-        main = torch.cuda.current_stream()
-        dev_index = self.dev.index
-
-        def stage(idx):
-            torch.cuda.set_device(dev_index)
-            return self._stage(idx, jobs[idx])
-
-        fut = self._stager.submit(stage, 0) if jobs else None
-        for idx, (j, _, _) in enumerate(jobs):
-            k = idx & 1
-            n, w = fut.result()
-            self._copy_to_device(idx, n * w * 3)
-            if idx + 1 < len(jobs):  # staged while the consumer's model + NMS of this strip run
-                fut = self._stager.submit(stage, idx + 1)
-            main.wait_event(self._uploaded[k])
-            yield j, k, n, w
-
-    def _release(self, k):
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream())
-        self._consumed[k] = done
+        return len(self._strips.jobs)
 
     def _wanted(self):
         """``[(ty, tx)]`` of the tiles the stream yields, in grid order"""
@@ -232,52 +230,47 @@ class RegionTileStream:
     def _wanted_table(self):
         """for the list ingest, on the device: the origin of every wanted tile inside its strip's block, int32 [n][2] = (x, 0) in
         grid order, and per tile row the index of its first wanted tile (host)"""
-        span0 = {j: c0 // self.shrink for j, c0, _ in self._jobs}
+        span0 = {j: c0 // self.shrink for j, c0, _ in self._strips.jobs}
         xy = np.array([(i * self.step - span0[j], 0) for j, i in self._wanted()], np.int32).reshape(-1, 2)
         starts = np.r_[0, np.cumsum(self.tile_mask.sum(1))]
         return torch.from_numpy(xy).to(self.dev), starts
 
-    def _ingest_list(self, L, k, n, w, origins, m, out):
-        """tiles ``origins[:m]`` of the block in ``_strips[k]`` -> ``out[:m * V]``, every tile in the stream's views"""
-        if self.stain is not None:
-            ids = (C.c_int * len(self.views))(*self.views)
-            check(L.ay_ingest_region_tiles_stain_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, ids,
-                                                    len(ids), ptr(self.stain.params), self.S, ptr(out), _lib.stream_ptr()),
-                  "ay_ingest_region_tiles_stain_u8")
-            return
-        if self.views != (0,):
-            ids = (C.c_int * len(self.views))(*self.views)
-            check(L.ay_ingest_region_tiles_views_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, ids,
-                                                    len(ids), self.S, ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_views_u8")
-            return
-        check(L.ay_ingest_region_tiles_list_u8(ptr(self._strips[k]), n, w, w * 3, self.shrink, self.tile, ptr(origins), m, self.S,
-                                               ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_list_u8")
+    def _cut(self, L, k, n, w, origins, m, out):
+        """tiles ``origins[:m]`` of strip block ``k`` -> ``out[:m * V]``, every tile in the stream's views; ``origins=None``: the
+        ``m`` tiles of a full row, ``step`` apart (the origins are computed, not read: faster than the list entry)"""
+        strip, ids = self._strips.args(k, n, w), self._view_ids
+        if origins is None:     # overlap == 0 is step == tile
+            check(L.ay_ingest_region_tiles_step_u8(*strip, self.tile, self.step, 1, m, self.S, ptr(out), _lib.stream_ptr()),
+                  "ay_ingest_region_tiles_step_u8")
+        elif self.stain is not None:
+            check(L.ay_ingest_region_tiles_stain_u8(*strip, self.tile, ptr(origins), m, ids, len(ids), ptr(self.stain.params), self.S,
+                                                    ptr(out), _lib.stream_ptr()), "ay_ingest_region_tiles_stain_u8")
+        elif self.views != (0,):
+            check(L.ay_ingest_region_tiles_views_u8(*strip, self.tile, ptr(origins), m, ids, len(ids), self.S, ptr(out),
+                                                    _lib.stream_ptr()), "ay_ingest_region_tiles_views_u8")
+        else:
+            check(L.ay_ingest_region_tiles_list_u8(*strip, self.tile, ptr(origins), m, self.S, ptr(out), _lib.stream_ptr()),
+                  "ay_ingest_region_tiles_list_u8")
 
     def __iter__(self):
         L = _lib.lib()
         V = len(self.views)
+        row = None
         if self.tile_mask is not None:
             table, starts = self._wanted_table()
             coords = self._wanted()
         elif self.views != (0,) or self.stain is not None:     # the views and stain entries take a list of origins: those of a full tile row
             row = torch.tensor([(i * self.step, 0) for i in range(self.tiles_x)], dtype=torch.int32, device=self.dev)
-        for j, k, valid, width in self._strip_loop():
+        for j, k, valid, width in self._strips:
             if self.tile_mask is None:
-                out = torch.empty(self.tiles_x * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
-                if self.views != (0,) or self.stain is not None:
-                    self._ingest_list(L, k, valid, width, row, self.tiles_x, out)
-                else:    # the grid origins are computed, not read: faster than the list entry; overlap == 0 is step == tile
-                    check(L.ay_ingest_region_tiles_step_u8(ptr(self._strips[k]), valid, width, width * 3, self.shrink, self.tile,
-                                                           self.step, 1, self.tiles_x, self.S, ptr(out), _lib.stream_ptr()),
-                          "ay_ingest_region_tiles_step_u8")
-                self._release(k)
-                yield out, [(j, i) for i in range(self.tiles_x)]
+                origins, m, cs = row, self.tiles_x, [(j, i) for i in range(self.tiles_x)]
             else:
                 a, b = int(starts[j]), int(starts[j + 1])
-                out = torch.empty((b - a) * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
-                self._ingest_list(L, k, valid, width, table[a:], b - a, out)
-                self._release(k)
-                yield out, coords[a:b]
+                origins, m, cs = table[a:], b - a, coords[a:b]
+            out = torch.empty(m * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32)
+            self._cut(L, k, valid, width, origins, m, out)
+            self._strips.release(k)
+            yield out, cs
 
     def batches(self, per_call):
         """The iteration as detect_region takes it, one item per model call: ``(tiles [n * V,3,S,S], [(ty, tx)] * n)`` with ``n <=
@@ -302,34 +295,22 @@ class RegionTileStream:
         table, starts = self._wanted_table()
         V = len(self.views)
         cur, fill, w0 = None, 0, 0
-        for j, k, valid, width in self._strip_loop():
+        for j, k, valid, width in self._strips:
             a, b = int(starts[j]), int(starts[j + 1])
             ready = []
             while a < b:
                 if cur is None:
                     cur, fill, w0 = torch.empty(batch_size * V, 3, self.S, self.S, device=self.dev, dtype=torch.float32), 0, a
                 m = min(b - a, batch_size - fill)
-                self._ingest_list(L, k, valid, width, table[a:], m, cur[fill * V:])
+                self._cut(L, k, valid, width, table[a:], m, cur[fill * V:])
                 fill, a = fill + m, a + m
                 if fill == batch_size:
                     ready.append((cur, w0))
                     cur = None
-            self._release(k)
+            self._strips.release(k)
             yield from ready
         if cur is not None:
             yield cur[:fill * V], w0
-
-
-def _each_strip(stream, call):
-    """``call(k, j, rows, width)`` on every block of :meth:`RegionTileStream._strip_loop`, released behind the kernels the call issues"""
-    for j, k, valid, width in stream._strip_loop():
-        call(k, j, valid, width)
-        stream._release(k)
-
-
-def _strip_args(stream, k, valid, width):
-    """the leading arguments of every entry point that reads a strip: region, rows, width, row stride in bytes, shrink"""
-    return ptr(stream._strips[k]), valid, width, width * 3, stream.shrink
 
 
 def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
@@ -338,7 +319,7 @@ def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
     A pixel of the (halved, for ``shrink=2``: the ingest's 2x2 round-half-up means) slide is tissue iff ``min(R, G, B) < bg_level``
     (``bg_level`` in 0 .. 256; the default suits scanned glass); pixels of a shared band count for every tile that holds them, the
     padding outside the slide never counts (THE TISSUE RULE in ``include/amyloid_yolo.h``, ``ay_tile_tissue_u8``).  The raster goes
-    through the strips of :class:`RegionTileStream` once and the counts come back in one read.  Meant for a low-resolution level
+    through a :class:`StripStream` once and the counts come back in one read.  Meant for a low-resolution level
     of the slide, with ``tile`` and ``overlap`` divided by that level's downsample (any ``[H, W, 3]`` uint8 array, strided views
     such as :func:`probe_view`'s included), and exact on any raster: on the full one it costs a full upload of the slide.  A strip
     reaches the kernel with rows ``3 * width`` bytes apart: the kernel's 16-byte loads need that to be a multiple of 16 (a width
@@ -347,12 +328,14 @@ def tissue_counts(raster, tile, shrink=1, overlap=0, bg_level=220):
     bg_level = int(bg_level)
     if not 0 <= bg_level <= 256:
         raise ValueError(f"tissue_counts: bg_level {bg_level} outside 0 .. 256")
-    stream = RegionTileStream(raster, tile, tile, shrink, overlap)
+    tile = int(tile)
+    tiles_y, tiles_x, step = tile_grid(raster.shape[0] // shrink, raster.shape[1] // shrink, tile, overlap)
+    strips = StripStream(raster, tile, step, shrink)
     L = _lib.lib()
-    counts = torch.empty(stream.tiles_y, stream.tiles_x, device=stream.dev, dtype=torch.int32)
-    _each_strip(stream, lambda k, j, valid, width: check(
-        L.ay_tile_tissue_u8(*_strip_args(stream, k, valid, width), stream.tile, stream.step, 1, stream.tiles_x, bg_level, ptr(counts[j]),
-                            _lib.stream_ptr()), "ay_tile_tissue_u8"))
+    counts = torch.empty(tiles_y, tiles_x, device=strips.dev, dtype=torch.int32)
+    strips.each(lambda k, j, valid, width: check(
+        L.ay_tile_tissue_u8(*strips.args(k, valid, width), tile, step, 1, tiles_x, bg_level, ptr(counts[j]), _lib.stream_ptr()),
+        "ay_tile_tissue_u8"))
     return counts.cpu().numpy()
 
 
@@ -909,7 +892,7 @@ def stain_stats(raster, shrink=1, bg_level=220, probe_stride=16, basis=H_DAB):
     """Stain statistics of a slide -> :class:`StainStats`: the two concentration histograms over its TISSUE pixels (THE TISSUE RULE
     with ``bg_level``), by ``ay_stain_hist_u8``.  The probe is :func:`tissue_mask`'s: every ``probe_stride``-th pixel of the (halved)
     slide, single source pixels (:func:`probe_view`); ``probe_stride=1`` is the exact rule, the 2x2 means of ``shrink=2`` included,
-    at the cost of a full upload.  The strips of :class:`RegionTileStream` accumulate on the device; one read-back at the end."""
+    at the cost of a full upload.  The strips of a :class:`StripStream` accumulate on the device; one read-back at the end."""
     bg_level, d = int(bg_level), int(probe_stride)
     if not 0 <= bg_level <= 256:
         raise ValueError(f"stain_stats: bg_level {bg_level} outside 0 .. 256")
@@ -920,11 +903,12 @@ def stain_stats(raster, shrink=1, bg_level=220, probe_stride=16, basis=H_DAB):
     if d > 1:
         raster, shrink = probe_view(raster, d, shrink, 0, d)[0], 1
     params = StainMap.identity(basis).params
-    stream = RegionTileStream(raster, min(1536, max(1, raster.shape[0] // shrink)), 1, shrink)
+    T = min(1536, max(1, raster.shape[0] // shrink))
+    strips = StripStream(raster, T, T, shrink)
     L = _lib.lib()
-    hist = torch.zeros(2 * STAIN_BINS + 1, device=stream.dev, dtype=torch.int64)
-    _each_strip(stream, lambda k, j, valid, width: check(
-        L.ay_stain_hist_u8(*_strip_args(stream, k, valid, width), bg_level, ptr(params), ptr(hist), _lib.stream_ptr()), "ay_stain_hist_u8"))
+    hist = torch.zeros(2 * STAIN_BINS + 1, device=strips.dev, dtype=torch.int64)
+    strips.each(lambda k, j, valid, width: check(
+        L.ay_stain_hist_u8(*strips.args(k, valid, width), bg_level, ptr(params), ptr(hist), _lib.stream_ptr()), "ay_stain_hist_u8"))
     h = hist.cpu().numpy()
     return StainStats(h[:2 * STAIN_BINS].reshape(2, STAIN_BINS), h[2 * STAIN_BINS], basis)
 
@@ -938,17 +922,18 @@ def normalize_region(raster, stain, shrink=1, device=False):
     if getattr(raster, "ndim", 0) != 3 or raster.shape[0] // shrink < 1 or raster.shape[1] // shrink < 1:
         raise ValueError("normalize_region: raster must be a uint8 [H,W,3] array with at least one (halved) pixel")
     H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
-    stream = RegionTileStream(raster, min(1536, H), 1, shrink)
+    T = min(1536, H)
+    strips = StripStream(raster, T, T, shrink)
     L = _lib.lib()
     params = stain.params
-    out = torch.empty(H, W, 3, device=stream.dev, dtype=torch.uint8)
+    out = torch.empty(H, W, 3, device=strips.dev, dtype=torch.uint8)
 
     def apply(k, j, valid, width):
         if valid // shrink:
-            check(L.ay_stain_apply_u8(*_strip_args(stream, k, valid, width), ptr(params), ptr(out[j * stream.tile:]), W * 3,
-                                      _lib.stream_ptr()), "ay_stain_apply_u8")
+            check(L.ay_stain_apply_u8(*strips.args(k, valid, width), ptr(params), ptr(out[j * T:]), W * 3, _lib.stream_ptr()),
+                  "ay_stain_apply_u8")
 
-    _each_strip(stream, apply)
+    strips.each(apply)
     return out if device else out.cpu().numpy()
 
 
@@ -1016,7 +1001,7 @@ def _cell_box_pass(stream, gy, gx, rows, n_box_sums, call):
         flags = torch.zeros(1, device=stream.dev, dtype=torch.int32)
         if M:
             box_args = (ptr(rows), M, ptr(boxes), ptr(flags))
-    _each_strip(stream, lambda k, j, valid, width: call(k, j, valid, width, ptr(cells), *box_args))
+    stream.each(lambda k, j, valid, width: call(k, j, valid, width, ptr(cells), *box_args))
     c = cells.cpu().numpy()
     maps = tuple(np.ascontiguousarray(c[:, :, i]) for i in range(3))
     return maps + ((None, None) if rows is None else (boxes.cpu().numpy(), int(flags.item())))
@@ -1027,7 +1012,7 @@ def stain_load(raster, rows=None, cell=128, shrink=1, bg_level=220, thres=0.15, 
     ``tile_grid(H, W, cell)`` -- :func:`burden_map`'s -- the tissue pixels, the pixels whose concentration of ``stain`` (0 or 1;
     default 1, DAB on ``H_DAB``) reaches the threshold, and the sum of their bins; with ``rows`` the same inside every box.
 
-    The raster goes ONCE through the strips of :class:`RegionTileStream`, at full resolution, without a probe: the exact rule, the
+    The raster goes ONCE through the strips of a :class:`StripStream`, at full resolution, without a probe: the exact rule, the
     2x2 means of ``shrink=2`` included.  The tables are ``StainMap.identity(basis)``'s (only ``od`` and ``D`` are read); the outputs
     are zeroed once, every strip adds to them on the device and they are read back once.  ``cell >= 16``; (halved) sides up to 2^24.
 
@@ -1048,13 +1033,14 @@ def stain_load(raster, rows=None, cell=128, shrink=1, bg_level=220, thres=0.15, 
     H, W, cell, bg_level = _check_load("stain_load", raster, shrink, cell, bg_level, stain, basis)
     j = _thres_bin(thres, "stain_load")
     _check_rows("stain_load", rows)
-    stream = RegionTileStream(raster, min(1536, H), 1, shrink)
+    T = min(1536, H)
+    stream = StripStream(raster, T, T, shrink)
     params = StainMap.identity(basis).params
     gy, gx, _ = tile_grid(H, W, cell)
     L = _lib.lib()
     tissue, positive, bin_sum, boxes, flags = _cell_box_pass(stream, gy, gx, rows, 4, lambda k, jy, valid, width, cells, *box_args: check(
-        L.ay_stain_load_u8(*_strip_args(stream, k, valid, width), jy * stream.tile, 0, H, W, bg_level, ptr(params), int(stain), j, cell,
-                           cells, *box_args, _lib.stream_ptr()), "ay_stain_load_u8"))
+        L.ay_stain_load_u8(*stream.args(k, valid, width), jy * T, 0, H, W, bg_level, ptr(params), int(stain), j, cell, cells, *box_args,
+                           _lib.stream_ptr()), "ay_stain_load_u8"))
     n_t, n_p = int(tissue.sum()), int(positive.sum())
     out = {"tissue": tissue, "positive": positive, "bin_sum": bin_sum,
            "load": positive.astype(np.float64) / np.where(tissue > 0, tissue, np.nan),
@@ -1107,7 +1093,7 @@ def focus_map(raster, rows=None, cell=128, shrink=1, bg_level=220, strip=1536):
     pixels: those that are tissue at ``bg_level`` with all four edge neighbours, so that a tissue / glass edge never counts as
     sharpness; with ``rows`` the same inside every box (the pixels :func:`stain_load` gives it).
 
-    The raster goes ONCE through the strips of :class:`RegionTileStream` at full resolution; a pixel needs the rows above and below
+    The raster goes ONCE through the strips of a :class:`StripStream` at full resolution; a pixel needs the rows above and below
     it, so consecutive strips share two rows: with ``T = min(strip, H)`` strip ``j`` starts at row ``j * (T - 2)`` and owns the centre
     rows ``[j * (T - 2) + 1, j * (T - 2) + T - 1)``, clipped to what it holds, and every row ``1 .. H - 2`` is owned exactly once:
     the result does not depend on ``strip`` (an integer ``>= 3``).  The outputs are zeroed once, every strip adds to them on the
@@ -1127,12 +1113,12 @@ def focus_map(raster, rows=None, cell=128, shrink=1, bg_level=220, strip=1536):
         n, s1, s2 = (np.zeros((gy, gx), np.int64) for _ in range(3))
         b, f = (None, None) if rows is None else (np.zeros((int(rows.shape[0]), 3), np.int64), 0)
     else:
-        stream = RegionTileStream(raster, min(strip, H), 1, shrink, overlap=2)
+        stream = StripStream(raster, min(strip, H), min(strip, H) - 2, shrink)     # a two-row halo
         L = _lib.lib()
 
         def call(k, jy, valid, width, cells, *box_args):
             y0, held = jy * stream.step, valid // stream.shrink
-            check(L.ay_focus_u8(*_strip_args(stream, k, valid, width), y0, H, W, y0 + 1, y0 + held - 1, bg_level, cell, cells, *box_args,
+            check(L.ay_focus_u8(*stream.args(k, valid, width), y0, H, W, y0 + 1, y0 + held - 1, bg_level, cell, cells, *box_args,
                                 _lib.stream_ptr()), "ay_focus_u8")
 
         n, s1, s2, b, f = _cell_box_pass(stream, gy, gx, rows, 3, call)
@@ -1235,7 +1221,8 @@ class SlideSampler:
     min_visible=min_visible)``, the label rule of tile training.
 
     A host raster is staged per batch: of every sample only ``footprint ∩ block`` (``context=False``: the window) is copied into a
-    pinned buffer, with the records behind the pixels, one batch ahead on a worker thread, and uploaded on a copy stream.
+    pinned buffer, with the records behind the pixels, one batch ahead on a worker thread, and uploaded on a copy stream
+    (``upload.Uploader``; the plan is drawn in its ``fill``); of a resident raster only the records go up, the same way.
     ``batches`` (default ``ceil(sum(weights) / batch_size)``) is ``len()``.  With ``world > 1`` every rank builds its own sampler
     with its ``rank`` and the same ``batches``.  Callables in ``hooks`` see every ``(imgs, targets)`` that leaves."""
 
@@ -1267,7 +1254,7 @@ class SlideSampler:
             raise ValueError("SlideSampler: neither an annotation nor a wanted tile inside any block")
         self._cum = np.cumsum(w) / w.sum()
         self.batches = int(batches) if batches is not None else int(math.ceil(w.sum() / self.B))
-        self._stager = self._ahead = None
+        self._up = None      # upload.Uploader, made on the first iteration
 
     # ---- set-up -----------------------------------------------------------------------------------------------------------------
     def _slide(self, item, mask, min_tissue):
@@ -1436,86 +1423,33 @@ class SlideSampler:
         hi = max(s.raster.data_ptr() + (s.raster.shape[0] - 1) * s.raster.stride(0) + s.raster.shape[1] * 3 for s in self.slides)
         return lo, hi - lo
 
-    def _prepare(self, idx):
-        """runs on the staging thread: plan the batch, and for host rasters fill the pinned buffer ``idx & 1`` (pixels, then the
-        records on the next 16 bytes) -> (plan, record bytes, bytes of pixels, offset of the records)"""
-        plan = self.plan_batch()
-        if self.resident:
-            table = self.window_table(plan, self._resident_span()[0])
-            return plan, torch.from_numpy(table.dev.view(np.uint8).reshape(-1).copy()), 0, 0
-        table = self.window_table(plan)
-        n = max(self.staged_bytes(plan), 1)
-        tab = (n + 15) // 16 * 16
-        rec = table.dev.view(np.uint8).reshape(-1)
-        k = idx & 1
-        if self._uploaded[k] is not None:
-            self._uploaded[k].synchronize()          # the host buffer is free again once its last copy has run
-        if self._pinned[k] is None or self._pinned[k].numel() < tab + rec.size:
-            self._pinned[k] = torch.empty((tab + rec.size) * 5 // 4, dtype=torch.uint8).pin_memory()
-        host = self._pinned[k].numpy()
-        self.stage(plan, table, host, self._pool)
-        host[tab:tab + rec.size] = rec
-        return plan, None, n, tab
-
     def __iter__(self):
         from .augment import launch_windows
         if not torch.cuda.is_available():
             raise _lib.AyError("no HIP device: SlideSampler has no CPU fallback")
         dev = torch.device("cuda", torch.cuda.current_device())
-        if self._stager is None:
-            self._stager = ThreadPoolExecutor(max_workers=1)    # one batch ahead of the consumer
-            self._pool = ThreadPoolExecutor(max_workers=4)      # the samples of one staging copy
-            self._copy = torch.cuda.Stream(device=dev)
-            self._pinned, self._device = [None, None], [None, None]
-            self._uploaded = [None, None]    # event: the batch landed in _device[k]
-            self._consumed = [None, None]    # event: the kernel that read _device[k] is done
-        if self._ahead is not None:                            # an iteration that was left early: its staged batch is dropped
-            self._ahead.result()
-        main = torch.cuda.current_stream()
+        if self._up is None:
+            self._up = Uploader(dev)
+        base, span = self._resident_span() if self.resident else (0, 0)
 
-        def prepare(idx):
-            torch.cuda.set_device(dev.index)
-            return self._prepare(idx)
+        def fill(idx, host):
+            """on the staging thread: plan the batch and write the pixels (host rasters only) and, behind them, the records"""
+            plan = self.plan_batch()
+            table = self.window_table(plan, base)
+            n = 0 if self.resident else max(self.staged_bytes(plan), 1)
+            rec = table.dev.view(np.uint8).reshape(-1)
+            buf = host(record_offset(n) + rec.size)
+            if not self.resident:
+                self.stage(plan, table, buf, self._up.pool)
+            tab = pack_records(buf, n, rec)
+            return (plan, n, tab), tab + rec.size
 
-        fut = self._ahead = self._stager.submit(prepare, 0) if self.batches else None
-        for idx in range(self.batches):
-            k = idx & 1
-            plan, rec_bytes, n, tab = fut.result()
-            self._ahead = None
+        for k, (plan, n, tab), buf, _ in self._up.run(self.batches, fill):     # staged while the consumer's training step runs
             out = torch.empty(self.B, 3, self.S, self.S, device=dev, dtype=torch.float32)
-            if self.resident:
-                base, span = self._resident_span()
-                table = rec_bytes.to(dev, non_blocking=True)
-                if idx + 1 < self.batches:
-                    fut = self._ahead = self._stager.submit(prepare, idx + 1)
-                launch_windows(base, span, table.data_ptr(), self.B, self.S, out)
-            else:
-                total = tab + self.B * self._rec_size()
-                if self._consumed[k] is not None:
-                    self._copy.wait_event(self._consumed[k])
-                if self._device[k] is None or self._device[k].numel() < total:
-                    if self._consumed[k] is not None:
-                        self._consumed[k].synchronize()
-                    self._device[k] = torch.empty(self._pinned[k].numel(), dtype=torch.uint8, device=dev)
-                    self._copy.wait_stream(main)               # the memory may have served the current stream until now
-                with torch.cuda.stream(self._copy):
-                    self._device[k][:total].copy_(self._pinned[k][:total], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._copy)
-                self._uploaded[k] = ev
-                if idx + 1 < self.batches:                     # staged while the consumer's training step runs
-                    fut = self._ahead = self._stager.submit(prepare, idx + 1)
-                main.wait_event(ev)
-                launch_windows(self._device[k].data_ptr(), n, self._device[k].data_ptr() + tab, self.B, self.S, out)
-                done = torch.cuda.Event()
-                done.record(main)
-                self._consumed[k] = done
+            src = (base, span) if self.resident else (buf.data_ptr(), n)
+            launch_windows(*src, buf.data_ptr() + tab, self.B, self.S, out)
+            self._up.release(k)
             targets = torch.from_numpy(plan.targets).float().to(dev)
             for hook in self.hooks:
                 hook(out, targets)
             yield out, targets
-
-    @staticmethod
-    def _rec_size():
-        from .augment import AUG_WINDOW_DTYPE
-        return AUG_WINDOW_DTYPE.itemsize
