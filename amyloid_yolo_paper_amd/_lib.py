@@ -174,6 +174,7 @@ _SIGS = {
     "ay_stain_apply_u8": (_I, [_P, _I, _I, _SZ, _I, _P, _P, _SZ, _P]),
     "ay_stain_load_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "ay_focus_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "ay_box_segments_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

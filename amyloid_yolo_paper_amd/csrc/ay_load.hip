@@ -28,12 +28,6 @@ constexpr int LOAD_CX = LOAD_XQ * 16 / AY_LOAD_MIN_CELL + 1;
 // 511: 33 488 896 < 2^31.
 constexpr int LOAD_WORDS = 2 * LOAD_CX * 3;
 
-// THE STAIN RULE's bin of the chosen stain's concentration
-__device__ __forceinline__ int load_bin(const float* od, const int b[3], float d0, float d1, float d2) {
-    const float c = (od[b[0]] * d0 + od[b[1]] * d1) + od[b[2]] * d2;
-    return c < 0.0f ? 0 : (c < 8.0f ? (int)(c * 64.0f) : AY_STAIN_BINS - 1);
-}
-
 template <bool WIDE, int SHRINK>
 __global__ void __launch_bounds__(256) stain_load_cells_kernel(const uint8_t* __restrict__ reg, int H, int W, int RW, size_t stride, int bg,
                                                                 int oy, int ox, int cell, int gx, int n_xc, long long units,

@@ -1,7 +1,8 @@
 // What the slide-level passes over a resident uint8 HWC region share (ay_stain.hip, ay_load.hip, ay_focus.hip; of ay_tissue.hip the
-// launcher and check_region): the 48-byte item of the read stream, the work units, the launch of the four (WIDE, SHRINK) instances,
-// the place of an item and a unit on the cell grid, the flush of a workgroup's cell table, the box walk and the host checks.  Helper
-// functions only: how a pass accumulates (int32 table, uint64 table with spills, LDS histogram) is its own and stays in its file.
+// launcher and check_region; of ay_segment.hip tissue_px, load_bin, check_region and the box edges): the 48-byte item of the read
+// stream, the work units, the launch of the four (WIDE, SHRINK) instances, the place of an item and a unit on the cell grid, the flush
+// of a workgroup's cell table, the box walk and the host checks.  Helper functions only: how a pass accumulates (int32 table, uint64
+// table with spills, LDS histogram) is its own and stays in its file.
 #pragma once
 #include <type_traits>
 
@@ -61,6 +62,12 @@ __device__ __forceinline__ void item_pixel(const uint32_t* w0, const uint32_t* w
 
 // THE TISSUE RULE: most of a slide is glass
 __device__ __forceinline__ bool tissue_px(const int b[3], int bg) { return min(min(b[0], b[1]), b[2]) < bg; }
+
+// THE STAIN RULE's bin of the chosen stain's concentration (THE LOAD RULE and THE SEGMENT RULE: ay_load.hip, ay_segment.hip)
+__device__ __forceinline__ int load_bin(const float* od, const int b[3], float d0, float d1, float d2) {
+    const float c = (od[b[0]] * d0 + od[b[1]] * d1) + od[b[2]] * d2;
+    return c < 0.0f ? 0 : (c < 8.0f ? (int)(c * 64.0f) : AY_STAIN_BINS - 1);
+}
 
 // ---- the work units: a band of BAND rows x up to XQ items of a row; workgroups of 256 take units grid-stride
 struct SlideUnits { unsigned nq; int n_xc; long long units; unsigned blocks; };   // items of a row, units across a row, units, workgroups

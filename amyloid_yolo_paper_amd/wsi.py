@@ -42,6 +42,10 @@ and ``quantify_region(load=True)`` puts the load map next to the count maps.
 Focus: :func:`focus_map` sums the Laplacian of the luma over the tissue of every map cell and detection box (``ay_focus_u8``, THE
 FOCUS RULE) into a sharpness map, :func:`focus_summary` reads it, and ``quantify_region(focus=True)`` reports it next to the counts.
 
+Plaque segmentation: :func:`segment_boxes` labels the connected stain-positive component under every detection (``ay_box_segments_u8``,
+THE SEGMENT RULE), :func:`plaque_morphometry` turns its words into area, core fraction, centroid, perimeter and compactness, and
+``quantify_region(segment=True)`` reports them next to the counts.
+
 No CPU fallback: the product path needs the HIP library and a GPU."""
 import ctypes as C
 import math
@@ -605,7 +609,8 @@ def _field_sums(picked, filled, F, maps):
 
 
 def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
-                    dab_thres=None, load=False, focus=False, min_sharpness=None, **detect_region_kwargs):
+                    dab_thres=None, load=False, focus=False, min_sharpness=None, segment=False, seg_margin=None, core_thres=None,
+                    min_area=None, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
 
     1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
@@ -650,7 +655,18 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
        ``in_focus_fraction``.  The fields are picked as before: sharpness is reported, never used.  Without ``focus`` the result has
        the keys it had.
 
+    8. With ``segment=True`` (``dab_thres`` is then required, as for ``load=True``; the basis by the same precedence) one more pass,
+       ``segment_boxes(raster, rows, seg_margin, shrink, bg_level, dab_thres, core_thres, 1, basis, min_area)`` (``seg_margin``
+       default 8, ``core_thres`` default None, ``min_area`` default 1; any of them without ``segment=True`` is a ``ValueError``) --
+       THE SEGMENT RULE; only the strips that hold a detection's window are uploaded -- adds ``segments`` int32 [M,20] and
+       ``segment_flags``, ``plaque`` (:func:`plaque_morphometry` of them, with ``mpp`` and the slide's sides) and ``class_area_px``
+       float64 [C,3]: the quartiles (25, 50, 75 %) of ``area_px`` per class over the rows with ``conf >= min_conf`` and a selected
+       component, NaN for a class without one.  The segments are reported, never used: no detection is moved, re-scored or dropped.
+       Without ``segment`` the result has the keys it had.
+
     The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
+    if not segment and not (seg_margin is None and core_thres is None and min_area is None):
+        raise ValueError("quantify_region: seg_margin, core_thres and min_area need segment=True")
     if min_sharpness is not None:
         if not focus:
             raise ValueError("quantify_region: min_sharpness needs focus=True")
@@ -660,6 +676,9 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         if dab_thres is None:
             raise ValueError("quantify_region: load=True needs dab_thres")
         _thres_bin(dab_thres, "quantify_region")
+    elif segment:
+        if dab_thres is None:
+            raise ValueError("quantify_region: segment=True needs dab_thres")
     elif (stain_stats is None) != (dab_thres is None):
         raise ValueError("quantify_region: stain_stats and dab_thres go together")
     if stain_stats is not None:
@@ -690,6 +709,11 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         _check_load("quantify_region", raster, shrink, cell, bg_level, 1, load_basis)
     if focus:
         _check_focus("quantify_region", raster, shrink, cell, bg_level)
+    if segment:
+        st = detect_region_kwargs.get("stain")
+        seg_basis = stain_stats.basis if stain_stats is not None else st.basis if isinstance(st, StainMap) else H_DAB
+        seg_margin, min_area = 8 if seg_margin is None else seg_margin, 1 if min_area is None else min_area
+        _check_segment("quantify_region", raster, shrink, bg_level, dab_thres, core_thres, 1, seg_basis, seg_margin, min_area)
     min_conf = float(min_conf)
     need = max(1, math.ceil(float(field_min_tissue) * (F * cell) ** 2))
     H, W = raster.shape[0] // shrink, raster.shape[1] // shrink
@@ -729,6 +753,18 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         if min_sharpness is not None:
             fs = focus_summary(fm, None, min_sharpness)
             out["in_focus"], out["in_focus_fraction"] = fs["in_focus"], fs["in_focus_fraction"]
+    if segment:
+        sg = segment_boxes(raster, rows, seg_margin, shrink, bg_level, dab_thres, core_thres, 1, seg_basis, min_area)
+        out["segments"], out["segment_flags"] = sg["segments"], sg["flags"]
+        out["plaque"] = plaque_morphometry(sg["segments"], mpp, (H, W))
+        out["class_area_px"] = np.full((num_classes, 3), np.nan)
+        r = rows.detach().cpu().numpy() if torch.is_tensor(rows) else np.asarray(rows)
+        with np.errstate(invalid="ignore"):
+            counted = (r[:, 4] >= min_conf) & np.isfinite(out["plaque"]["area_px"])
+        for c in range(num_classes):
+            a = out["plaque"]["area_px"][counted & (r[:, 6] == c)]
+            if len(a):
+                out["class_area_px"][c] = np.percentile(a, [25.0, 50.0, 75.0])
     if mpp is not None:
         mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue
         out["density_per_mm2"] = bm["counts"].cpu().numpy().astype(np.float64) / mm2(tissue)[None]
@@ -1067,6 +1103,126 @@ def box_morphometry(boxes, mpp=None):
     out = {"area_px": some, "fill": positive / np.where(pixels > 0, pixels, np.nan), "mean_od": (bin_sum / some + 0.5) / 64.0}
     if mpp is not None:
         out["area_um2"] = some * float(mpp) ** 2
+        out["equiv_diameter_um"] = 2.0 * np.sqrt(out["area_um2"] / math.pi)
+    return out
+
+
+# ---- plaque segmentation: the stained component under every detection ------------------------------------------------------------------
+SEG_COLS, SEG_MAX_SIDE, SEG_MAX_MARGIN = 20, 255, 127                    # include/amyloid_yolo.h, THE SEGMENT RULE
+SEG_NONFINITE, SEG_EMPTY, SEG_LARGE, SEG_NOT_RESIDENT, SEG_INTERNAL = 1, 2, 4, 8, 16
+
+
+def _check_segment(what, raster, shrink, bg_level, thres, core_thres, stain, basis, margin, min_area):
+    """the host checks :func:`segment_boxes` and ``quantify_region(segment=True)`` share -> (H, W, bg_level, thres_bin, core_bin,
+    margin, min_area)"""
+    H, W, _, bg_level = _check_load(what, raster, shrink, LOAD_MAX_SIDE, bg_level, stain, basis)       # one cell: no grid here
+    j = _thres_bin(thres, what)
+    core = STAIN_BINS if core_thres is None else _thres_bin(core_thres, f"{what}: core_thres")
+    if core < j:
+        raise ValueError(f"{what}: core_thres {core_thres!r} lies below thres {thres!r}")
+    return (H, W, bg_level, j, core, _whole(margin, 0, SEG_MAX_MARGIN, f"{what}: margin"),
+            _whole(min_area, 1, 2 ** 31 - 1, f"{what}: min_area"))
+
+
+def _segment_owner_rows(rows, H, W, margin):
+    """THE SEGMENT RULE's owner row of every row, on the host in float32 by the rule's steps: ``wy0`` with a window, else 0"""
+    r = np.asarray(rows, np.float32).reshape(-1, 7)[:, :4]
+    finite = np.isfinite(r).all(1)
+    r = np.where(finite[:, None], r, np.float32(0))
+    edge = lambda v, n: np.minimum(np.maximum(np.ceil(v - np.float32(0.5)), np.float32(0)), np.float32(n)).astype(np.int64)
+    lo_x, lo_y, hi_x, hi_y = edge(r[:, 0], W), edge(r[:, 1], H), edge(r[:, 2], W), edge(r[:, 3], H)
+    return np.where(finite & (lo_x < hi_x) & (lo_y < hi_y), np.maximum(lo_y - margin, 0), 0)
+
+
+def segment_boxes(raster, rows, margin=8, shrink=1, bg_level=220, thres=0.15, core_thres=None, stain=1, basis=H_DAB, min_area=1,
+                  strip=2048):
+    """The stained object under every detection (``ay_box_segments_u8``, THE SEGMENT RULE in ``include/amyloid_yolo.h``): per row of
+    ``rows`` the 8-connected component of stain-positive pixels that reaches into the box, out of a WINDOW, the box grown by
+    ``margin`` (0 .. 127) pixels on every side and cut to the slide.
+
+    Pixel classes are :func:`stain_load`'s: a pixel is positive iff it is tissue at ``bg_level`` and its bin of ``stain`` (on
+    ``basis``) reaches ``thres`` (an optical density, moved to a bin edge); it is CORE iff it also reaches ``core_thres``
+    (``None``: no pixel is core; below ``thres``: ``ValueError``).  A component is a candidate iff it has a pixel in the box proper and
+    at least ``min_area`` pixels; the largest candidate is selected, among equals the one with the lowest raster index in the window.
+    Neighbouring plaques that poke into the box, and speckle, are other components; what the box cut off is part of this one.
+
+    ``rows``: ``[M, 7]`` as :func:`detect_region` returns them (concatenated; pixels of the (halved) slide; on the host or the device);
+    only the four coordinates are read.  A window of more than 255 pixels a side is flagged ``SEG_LARGE`` and not segmented.
+
+    Strips: with ``T = min(strip, H)`` the strips are ``T - 254`` rows apart (``strip`` an integer ``>= 255``; a slide with ``H < 255``
+    is one strip), strip ``j`` owns the rows whose window starts in ``[j * step, (j + 1) * step)``, the last through ``H``, and every
+    window of at most 255 rows lies wholly in the strip that owns it: the result does not depend on ``strip``.  The owner rows are
+    computed on the host, and ONLY THE STRIPS THAT OWN A ROW ARE STAGED AND UPLOADED, at full width.
+
+    Returns a dict: ``segments`` NumPy int32 ``[M, 20]`` (status, window, positives, candidates, and of the selected component area,
+    core pixels, bin sum, perimeter, coordinate sums, tight box, window sides touched, pixels inside the box: the table in the
+    header; :func:`plaque_morphometry` turns them into numbers), ``flags`` (the OR of the statuses), ``thres`` and ``core_thres`` as
+    they took effect (``core_thres`` 8.0: none), ``strips`` = (visited, total).  ``M == 0``: empty arrays, no launch."""
+    H, W, bg_level, j, core, margin, min_area = _check_segment("segment_boxes", raster, shrink, bg_level, thres, core_thres, stain, basis,
+                                                               margin, min_area)
+    _check_rows("segment_boxes", rows)
+    if rows is None:
+        raise ValueError("segment_boxes: rows must be [M,7]")
+    strip = _whole(strip, SEG_MAX_SIDE, 2 ** 31 - 1, "segment_boxes: strip")
+    T = min(strip, H)
+    step = T - (SEG_MAX_SIDE - 1) if H >= SEG_MAX_SIDE else T
+    total = tile_grid(H, 1, T, T - step)[0]
+    M = int(rows.shape[0])
+    out = {"segments": np.zeros((M, SEG_COLS), np.int32), "flags": 0, "thres": j / 64.0, "core_thres": core / 64.0, "strips": (0, total)}
+    if M == 0:
+        return out
+    host_rows = rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows
+    owners = np.minimum(_segment_owner_rows(host_rows, H, W, margin) // step, total - 1)
+    visit = [int(v) for v in np.unique(owners)]
+    stream = StripStream(raster, T, step, shrink, [(v, 0, raster.shape[1]) for v in visit])
+    from .stats import _slide_array
+    rows = _slide_array(rows, 7, stream.dev)
+    params = StainMap.identity(basis).params
+    seg = torch.zeros(M, SEG_COLS, device=stream.dev, dtype=torch.int32)
+    flags = torch.zeros(1, device=stream.dev, dtype=torch.int32)
+    L = _lib.lib()
+    stream.each(lambda k, v, valid, width: check(
+        L.ay_box_segments_u8(*stream.args(k, valid, width), v * step, 0, H, W, v * step, H if v == total - 1 else (v + 1) * step, bg_level,
+                             ptr(params), int(stain), j, core, margin, min_area, ptr(rows), M, ptr(seg), ptr(flags), _lib.stream_ptr()),
+        "ay_box_segments_u8"))
+    out["segments"], out["flags"], out["strips"] = seg.cpu().numpy(), int(flags.item()), (len(visit), total)
+    return out
+
+
+def plaque_morphometry(segments, mpp=None, slide_hw=None):
+    """Per-detection morphometry of the selected components from :func:`segment_boxes`' ``segments`` ``[M, 20]``; host arithmetic in
+    float64 -> a dict of ``[M]`` arrays, NaN (``truncated``: False) where the status is not 0 or nothing was selected:
+    ``area_px``; ``core_fraction = core / area``; ``mean_od = (bin_sum / area + 0.5) / 64`` (bin centres, as
+    :func:`box_morphometry`); ``centroid_x = wx0 + sum_x / area + 0.5`` and ``centroid_y`` likewise, in slide coordinates with pixel
+    centres at halves; ``tight_box`` ``[M, 4]`` = (x1, y1, x2, y2), the high edges exclusive; ``perimeter_px``, the crack length: the
+    pixel edges between the component and what is not it; ``compactness = 16 * area / perimeter**2``: 1 for a square and about pi / 4
+    for a digital disc -- THIS IS NOT A EUCLIDEAN CIRCULARITY: the crack length of a digital disc is that of its bounding square;
+    ``outside_fraction = 1 - in_box / area``: how much of the plaque the detector's box missed; ``truncated``: the component touches
+    a side of its window that is not a border of the slide (without ``slide_hw`` = (H, W): any side), so the window cut it and the
+    numbers are lower bounds; ``candidates``.  With ``mpp`` (microns per pixel of the (halved) slide) also ``area_um2`` and
+    ``equiv_diameter_um = 2 * sqrt(area_um2 / pi)``."""
+    s = np.asarray(segments)
+    if s.ndim != 2 or s.shape[1] != SEG_COLS or s.dtype.kind not in "iu":
+        raise ValueError(f"plaque_morphometry: segments must be [M, {SEG_COLS}] integers, got {s.dtype} {s.shape}")
+    if mpp is not None and not 0.0 < float(mpp) < math.inf:
+        raise ValueError(f"plaque_morphometry: mpp {mpp!r} is no positive number of microns per pixel")
+    s = s.astype(np.int64)
+    ok = (s[:, 0] == 0) & (s[:, 7] > 0)
+    f = lambda col: np.where(ok, s[:, col], 0).astype(np.float64)
+    area = np.where(ok, s[:, 7], np.nan).astype(np.float64)
+    sides = s[:, 17].copy()
+    if slide_hw is not None:
+        Hs, Ws = (_whole(v, 1, 2 ** 31 - 1, "plaque_morphometry: slide_hw") for v in slide_hw)
+        sides &= ~(np.where(s[:, 1] == 0, 1, 0) | np.where(s[:, 2] == 0, 2, 0) | np.where(s[:, 1] + s[:, 3] == Ws, 4, 0)
+                   | np.where(s[:, 2] + s[:, 4] == Hs, 8, 0))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = {"area_px": area, "core_fraction": f(8) / area, "mean_od": (f(9) / area + 0.5) / 64.0,
+               "centroid_x": f(1) + f(11) / area + 0.5, "centroid_y": f(2) + f(12) / area + 0.5,
+               "tight_box": np.where(ok[:, None], s[:, 13:17], np.nan).astype(np.float64), "perimeter_px": np.where(ok, s[:, 10], np.nan).astype(np.float64),
+               "compactness": 16.0 * area / np.where(ok, s[:, 10], np.nan).astype(np.float64) ** 2, "outside_fraction": 1.0 - f(18) / area,
+               "truncated": ok & (sides != 0), "candidates": np.where(ok, s[:, 6], np.nan).astype(np.float64)}
+    if mpp is not None:
+        out["area_um2"] = area * float(mpp) ** 2
         out["equiv_diameter_um"] = 2.0 * np.sqrt(out["area_um2"] / math.pi)
     return out
 

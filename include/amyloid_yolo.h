@@ -948,6 +948,78 @@ int ay_focus_u8(const void* region_hwc_u8, int region_h, int region_w, size_t ro
                 const float* rows, int n_rows, int64_t* boxes /* [M][3] */, int32_t* flags /* NULL iff n_rows == 0 */,
                 ay_stream_t stream);
 
+/* ---- plaque segmentation: the stained component under every detection (wsi.segment_boxes, wsi.plaque_morphometry,
+ *      wsi.quantify_region(segment=True); csrc/ay_segment.hip) ------------------------------------------------------------------------
+ * ay_stain_load_u8's box sums count every positive pixel in the detector's rectangle: the neighbouring plaque that pokes into it and
+ * the speckle included, the part of the plaque the box cuts off excluded.  The object itself is the connected stained component under
+ * the detection: its area, core, perimeter, centre and tight box.  The reference has no such read-out: PARITY IS UNPINNED, the
+ * behaviour is the rule below, restated in NumPy (with a plain flood fill) by tests/segment_reference.py.
+ *
+ * THE SEGMENT RULE (integers, and the fp32 steps of THE LOAD RULE's box; a function of the inputs alone, the same bytes on every run).
+ *   Pixel classes.  TISSUE and the bin q of the chosen stain s in {0, 1} are exactly THE LOAD RULE's (the 2x2 round-half-up means for
+ *     shrink == 2, od, D, the same expression, the same clamp).  A pixel is POSITIVE iff it is tissue and q >= thres_bin, and CORE iff
+ *     it is positive and q >= core_bin; 0 <= thres_bin <= core_bin <= 512, and a core_bin of 512 makes no pixel core.
+ *   Box and window.  A row's edges lo_x, hi_x, lo_y, hi_y are THE LOAD RULE's (the same four fp32 steps).  A row with a coordinate
+ *     that is not finite is NONFINITE; one with lo_x >= hi_x or lo_y >= hi_y is EMPTY.  Every other row has a WINDOW, the box grown by
+ *     `margin` (0 .. AY_SEG_MAX_MARGIN = 127) pixels on every side and cut to the H x W slide: wx0 = max(lo_x - margin, 0), wx1 =
+ *     min(hi_x + margin, W), wy0 and wy1 the same with lo_y, hi_y and H, ww = wx1 - wx0, wh = wy1 - wy0.  A row with ww or wh above
+ *     AY_SEG_MAX_SIDE = 255 is LARGE (a window then holds at most 65 025 pixels: a pixel's index in it and a sentinel fit 16 bits); any
+ *     other row is normal.
+ *   Components.  The 8-connected sets of the positive pixels of the window; pixels outside the window connect nothing.  A component
+ *     is a CANDIDATE iff at least one of its pixels lies in the box proper (lo_x <= X < hi_x, lo_y <= Y < hi_y) and its area -- its
+ *     pixels in the whole window -- is >= min_area (>= 1).  The SELECTED component is the candidate with the largest area, among
+ *     equals the one that holds the lowest window raster index (Y - wy0) * ww + (X - wx0).
+ *   Output.  int32 [M][AY_SEG_COLS = 20] per row:
+ *      0       status: 0, or exactly one of AY_SEG_NONFINITE, AY_SEG_EMPTY, AY_SEG_LARGE, AY_SEG_NOT_RESIDENT, AY_SEG_INTERNAL
+ *      1 .. 4  wx0, wy0, ww, wh (0 for NONFINITE and EMPTY)
+ *      5       the positive pixels of the window
+ *      6       the number of candidates
+ *      7       area of the selected component
+ *      8       its core pixels
+ *      9       bin_sum: the sum of q over it (at most 65 025 * 511 < 2^31)
+ *     10       perimeter: the number of pairs (pixel of the component, one of its four edge neighbours) whose neighbour is not in the
+ *              component, outside the window counting as "not": one pixel has 4, a 2x2 block 8, two diagonal pixels 8
+ *     11, 12   the sums of X - wx0 and of Y - wy0 over the component (at most 65 025 * 254)
+ *     13 .. 16 its tight bounding box bx0, by0, bx1, by1 in slide pixels, the high edges exclusive
+ *     17       sides: bit 1 / 2 / 4 / 8 iff it has a pixel in the window's first column / first row / last column / last row
+ *     18       its pixels inside the box proper
+ *     19       0
+ *     Words 5 .. 19 are 0 for any status other than 0; words 7 .. 18 are 0 when nothing is selected.  The flags word gets the OR of
+ *     every status written.
+ *   Ownership.  Every row has an OWNER ROW: wy0 if it has a window (LARGE rows included), else 0.  A call sees one resident region
+ *     whose (halved) image has its top-left pixel at (origin_y, origin_x) of the slide, like ay_stain_load_u8, and is told a range
+ *     [own_y0, own_y1): it WRITES all 20 words of exactly the rows whose owner row lies in that range and touches no other row.  An
+ *     owned normal row whose window is not wholly inside the region gets AY_SEG_NOT_RESIDENT (the window words filled, the rest 0):
+ *     the caller's error, reported and not guessed around.  The caller makes the owned ranges of its calls a partition of [0, H);
+ *     the result does not depend on how the slide was cut (wsi.segment_boxes: strips 254 rows short of their height apart, so that
+ *     every window lies wholly in the strip that owns it).
+ *
+ * ay_box_segments_u8: kernel launches only -- no allocation, no memset node, no host read, no scratch, no workspace beyond `out` --
+ *   so it can sit in a captured step.  n_rows == 0 returns AY_OK without a launch.  Refused (-1, nothing launched, nothing written): a
+ *   null region or params, a bad shape or stride, shrink outside {1, 2}, bg_level outside 0 .. 256, stain outside {0, 1}, thres_bin
+ *   or core_bin outside 0 .. 512 or core_bin < thres_bin, margin outside 0 .. 127, min_area < 1, slide_h or slide_w outside 1 .. 2^24,
+ *   a region that does not lie inside the slide, own_y0 < 0, own_y0 > own_y1, own_y1 > slide_h, n_rows < 0, null rows, out or flags
+ *   with n_rows > 0.
+ *   One workgroup of 256 per owned row, the rows grid-stride; a row that is not owned costs its four fp32 edges.  The window is
+ *   classified once into a positive and a core bit plane in LDS and labelled there by a union-find over its row runs (32-bit parents,
+ *   LDS atomicMin; one pass, no sweeps to convergence: a one-pixel spiral costs what a disc costs), then the areas per root, the
+ *   selection, and one pass of sums over the selected component.  Two instances run one after the other: windows up to 96 pixels a
+ *   side (22 KiB of LDS, several workgroups per CU) and up to 255 (147 KiB).  Every find and union loop has a strictly decreasing
+ *   variable and a cap on top; a workgroup that hits the cap writes AY_SEG_INTERNAL for that row and goes on: it never appears unless
+ *   the labelling has a bug. */
+#define AY_SEG_COLS 20
+#define AY_SEG_MAX_SIDE 255
+#define AY_SEG_MAX_MARGIN 127
+#define AY_SEG_NONFINITE 1
+#define AY_SEG_EMPTY 2
+#define AY_SEG_LARGE 4
+#define AY_SEG_NOT_RESIDENT 8
+#define AY_SEG_INTERNAL 16
+int ay_box_segments_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int origin_y,
+                       int origin_x, int slide_h, int slide_w, int own_y0, int own_y1, int bg_level,
+                       const ay_stain_params* params_device, int stain, int thres_bin, int core_bin, int margin, int min_area,
+                       const float* rows, int n_rows, int32_t* out /* [M][20] */, int32_t* flags, ay_stream_t stream);
+
 /* Replaying a captured HIP graph of these calls.  Every entry point is plain stream work -- kernel launches only: no allocation,
  * no host copy, no memset node, no symbol access inside a call (the once-per-slide calls ay_seam_merge and ay_slide_match excepted:
  * they memset, read a few words back and synchronise the stream, and are not for capture; ay_burden_bin and ay_field_select, also
