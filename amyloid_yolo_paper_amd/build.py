@@ -1,4 +1,5 @@
 """Build libamyloid_yolo_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
+import glob
 import os
 import shutil
 import subprocess
@@ -30,7 +31,7 @@ def _stale(target, deps):
 
 def build_library(force=False, verbose=True):
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "ay_common.h"), os.path.join(CSRC, "ay_box.h"), os.path.join(CSRC, "ay_conv_common.h"), os.path.join(CSRC, "ay_pack.h"), os.path.join(CSRC, "ay_cut.h"), os.path.join(CSRC, "ay_slide_pass.h"),os.path.join(HERE, "..", "include", "amyloid_yolo.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "amyloid_yolo.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

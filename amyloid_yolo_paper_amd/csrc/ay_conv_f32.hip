@@ -3,7 +3,7 @@
 // to 1e-4 (tests, precision="fp32" mode of the Darknet host class).  The cfg format's shapes (1x1 / 3x3, stride 1 / 2) run on
 // the exact-fp32 MFMA kernel of ay_conv_f32_mfma.hip; the VALU kernel below serves any other shape.
 // Route concat + nearest x2 upsample (models.py:86-96,244-245) are folded into the loader.
-#include "ay_common.h"
+#include "ay_conv_nchw.h"
 
 namespace ay {
 
@@ -76,12 +76,7 @@ static int conv_fwd_f32(const ay_conv_desc* d, const float* src1, int cin1, int 
                         const float* w_oihw, const float* scale, const float* shift, const float* residual, float* out,
                         ay_stream_t stream, bool allow_mfma) {
     using namespace ay;
-    AY_CHECK_ARG(d && src1 && w_oihw && scale && shift && out, "ay_conv_fwd_f32: null argument");
-    AY_CHECK_ARG(cin1 > 0 && cin1 <= d->cin && (cin1 == d->cin || src2), "ay_conv_fwd_f32: channel split %d/%d", cin1, d->cin);
-    AY_CHECK_ARG(up1 == 0 || up1 == 1, "ay_conv_fwd_f32: up1");
-    const int pad = (d->ksize - 1) / 2;
-    AY_CHECK_ARG(d->hout == (d->hin + 2 * pad - d->ksize) / d->stride + 1 && d->wout == (d->win + 2 * pad - d->ksize) / d->stride + 1,
-                 "ay_conv_fwd_f32: output size mismatch");
+    if (const int rc = nchw_check_entry("ay_conv_fwd_f32", d, src1, cin1, up1, src2, w_oihw, scale, shift, out)) return rc;
     if (allow_mfma) {
         bool taken = false;
         const int rc = conv_fwd_f32_mfma(d, src1, cin1, up1, src2, w_oihw, scale, shift, residual, out, S(stream), &taken);

@@ -15,23 +15,11 @@
 //   LDS filters  [kc][tap][64 + 1] floats: the on-the-fly transposition OIHW -> [ci][tap][co] writes with a stride of 65
 //                floats (conflict-free), the A operand reads 32 consecutive channels
 // Route concatenation + nearest x2 upsampling (models.py:86-96, 244-245) are folded into the loader exactly as in the VALU
-// kernel: channels [0, cin1) come from src1 (at half resolution when up1), the rest from src2.
-// Epilogue in the reference's operation order, unfused (-ffp-contract=off): y = acc * scale + shift; LeakyReLU; + residual.
-#include "ay_common.h"
+// kernel.  The item walk, the geometry of the sources, the filter descriptor and the host side are the frame of
+// ay_conv_nchw.h, shared with ay_conv_split.hip.
+#include "ay_conv_nchw.h"
 
 namespace ay {
-
-struct F32Args {
-    const float* s1;
-    const float* s2;
-    const float* w;
-    const float* scale;
-    const float* shift;
-    const float* res;
-    float* out;
-    int cin, cin1, up1, cout, hin, win, hout, wout, leaky;
-    int tiles_x, tiles_y, n_cgroups, n_items;
-};
 
 constexpr int pad_mod64(int v, int want) {  // smallest value >= v that is `want` modulo 64
     int r = v;
@@ -40,8 +28,8 @@ constexpr int pad_mod64(int v, int want) {  // smallest value >= v that is `want
 }
 
 template <int KS, int STRIDE, int KC, bool DUAL>
-__global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
-    constexpr int BN = 64, TH = 8, TW = 32;
+__global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(NchwArgs a) {
+    constexpr int BN = NCHW_BN, TH = NCHW_TH, TW = NCHW_TW;
     constexpr int PAD = (KS - 1) / 2, KK2 = KS * KS;
     constexpr int IN_H = (TH - 1) * STRIDE + KS, IN_W = (TW - 1) * STRIDE + KS;
     constexpr int XPL = IN_H * IN_W;
@@ -59,32 +47,19 @@ __global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
     float* const lw = lds + KC * XSTR;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, hh = lane >> 5;
 
-    // workgroup -> item: the workgroups of one XCD (id & 7) walk a contiguous range of items, channel groups of a pixel tile
-    // adjacent: the input halo tile is fetched from HBM once and then hit in that XCD's L2
-    const int per_xcd = (a.n_items + 7) >> 3;
-    const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || item >= a.n_items) return;
-    const int cg = item % a.n_cgroups;
-    const int pt = item / a.n_cgroups;
-    const int b = pt / (a.tiles_x * a.tiles_y);
-    const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
-    const int co0 = cg * BN;
+    int item;
+    if (!nchw_item_index(a, item)) return;
+    const NchwItem it = nchw_item(a, item);
+    const int b = it.b, y0 = it.y0, x0 = it.x0, co0 = it.co0;
 
-    // ---- staging maps, fixed for the K loop: element e = i * 256 + tid of the stage's pixel block / filter block ------------
-    // Every load is a raw buffer load: a wave-uniform descriptor (rebuilt per stage: base = first channel of the stage, range =
-    // what is left of the tensor) + ONE 32-bit per-lane offset that never changes.  Lanes with nothing to fetch (zero padding,
-    // channels / filters beyond the tensor) carry an offset beyond every range and read zeros: no 64-bit per-lane addresses, no
-    // branches -- with plain pointers the 29 addresses of a stage cost 58 registers and the kernel spilled.
-    constexpr unsigned OOB = 0x80000000u;
-    const int cin2 = a.cin - a.cin1;
-    const int h1 = a.hin >> a.up1, w1 = a.win >> a.up1;
-    const unsigned plane1 = (unsigned)(h1 * w1), plane2 = (unsigned)(a.hin * a.win);
-    const float* const img1 = a.s1 + (size_t)b * a.cin1 * plane1;
-    const float* const img2 = cin2 > 0 ? a.s2 + (size_t)b * cin2 * plane2 : nullptr;
+    // ---- staging maps, fixed for the K loop: element e = i * 256 + tid of the stage's pixel / filter block (ay_conv_nchw.h)
+    const NchwSource src(a, b);
+    const int w1 = src.w1;
+    const unsigned plane1 = src.plane1, plane2 = src.plane2;
+    const float *const img1 = src.img1, *const img2 = src.img2;
     unsigned xo1[DUAL ? NX : 1], xo2[NX];  // byte offset from the stage's first channel in src1 (DUAL only) / in the plain source
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
@@ -93,10 +68,10 @@ __global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
         const int iy = y0 * STRIDE - PAD + P / IN_W, ix = x0 * STRIDE - PAD + P % IN_W;
         const bool in = e < KC * XPL && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win;
         if constexpr (DUAL) {
-            xo1[i] = in ? (unsigned)(kc * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : OOB;
-            xo2[i] = in ? (unsigned)(kc * plane2 + iy * a.win + ix) * 4u : OOB;
+            xo1[i] = in ? (unsigned)(kc * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : NCHW_OOB;
+            xo2[i] = in ? (unsigned)(kc * plane2 + iy * a.win + ix) * 4u : NCHW_OOB;
         } else {  // one source, possibly at half resolution (a lazily upsampled layer)
-            xo2[i] = in ? (unsigned)(kc * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : OOB;
+            xo2[i] = in ? (unsigned)(kc * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : NCHW_OOB;
         }
     }
     unsigned wo[NW];  // byte offset of this thread's filter taps from W[0][stage's first channel][0]
@@ -104,7 +79,7 @@ __global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
     for (int i = 0; i < NW; ++i) {
         const int u = i * 256 + tid;
         const int co = co0 + u / (KC * KK2), j = u % (KC * KK2);
-        wo[i] = (u < BN * KC * KK2 && co < a.cout) ? (unsigned)((co * a.cin) * KK2 + j) * 4u : OOB;
+        wo[i] = (u < BN * KC * KK2 && co < a.cout) ? (unsigned)((co * a.cin) * KK2 + j) * 4u : NCHW_OOB;
     }
     float rx[NX], rw[NW];
     auto issue = [&](int s) __attribute__((always_inline)) {
@@ -119,10 +94,8 @@ __global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
             if constexpr (DUAL) off = from1 ? xo1[i] : xo2[i];
             rx[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off, 0, 0));
         }
-        // filters: the range ends with the last filter; a channel tail (cin % KC != 0: the 3-channel stem) is masked by hand, since
-        // an offset past the row of one filter lands in the next filter's row, not out of range
-        const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w) + (size_t)ci0 * KK2, 0,
-                                                                             (a.cout * a.cin - ci0) * KK2 * 4, 0x00020000);
+        // filters: a channel tail (cin % KC != 0: the 3-channel stem) is masked by hand
+        const __amdgpu_buffer_rsrc_t wr = nchw_filter_rsrc(a, KK2, ci0, 0);
         const int live = (a.cin - ci0) * KK2;   // taps of a filter row that belong to real channels
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
@@ -146,11 +119,7 @@ __global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
 
     f32x16 acc[2][2];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+    for (int i = 0; i < 64; ++i) acc[i >> 5][(i >> 4) & 1][i & 15] = 0.f;
 
     // fragment bases: A = filters of channel c (+32 m), k-half hh; B = pixel (row 2 wave + n, column c), k-half hh
     const float* const fa = lw + hh * WSTR + c;
@@ -211,26 +180,9 @@ __global__ void __launch_bounds__(256, 2) conv_f32_mfma_kernel(F32Args a) {
 template <int KS, int STRIDE, int KC>
 static int launch_f32_mfma(const ay_conv_desc* d, const float* src1, int cin1, int up1, const float* src2, const float* w, const float* scale,
                            const float* shift, const float* residual, float* out, hipStream_t st) {
-    F32Args a;
-    a.s1 = src1, a.s2 = src2, a.w = w, a.scale = scale, a.shift = shift, a.res = residual, a.out = out;
-    a.cin = d->cin, a.cin1 = cin1, a.up1 = up1, a.cout = d->cout, a.hin = d->hin, a.win = d->win, a.hout = d->hout, a.wout = d->wout;
-    a.leaky = d->leaky;
-    a.tiles_x = (d->wout + 31) / 32;
-    a.tiles_y = (d->hout + 7) / 8;
-    a.n_cgroups = (d->cout + 63) / 64;
-    const long long n = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
-    if (n <= 0 || n > 0x3fffffffLL) {
-        set_error("ay_conv_fwd_f32: grid out of range (%lld)", n);
-        return AY_ERR_ARG;
-    }
-    a.n_items = (int)n;
-    const unsigned grid = 8u * (unsigned)((n + 7) / 8);
-    if (cin1 < d->cin)
-        hipLaunchKernelGGL((conv_f32_mfma_kernel<KS, STRIDE, KC, true>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_f32_mfma_kernel<KS, STRIDE, KC, false>), dim3(grid), dim3(256), 0, st, a);
-    AY_CHECK_LAUNCH("conv_f32_mfma_kernel");
-    return AY_OK;
+    NchwArgs a;
+    if (const int rc = nchw_fill_args("ay_conv_fwd_f32", d, src1, cin1, up1, src2, w, scale, shift, residual, out, a)) return rc;
+    return nchw_launch(conv_f32_mfma_kernel<KS, STRIDE, KC, true>, conv_f32_mfma_kernel<KS, STRIDE, KC, false>, "conv_f32_mfma_kernel", a, st);
 }
 
 // ay_conv_f32.hip: the shapes of the cfg format (1x1 / 3x3, stride 1 / 2) go to the matrix cores; anything else stays on the VALU
@@ -238,10 +190,8 @@ static int launch_f32_mfma(const ay_conv_desc* d, const float* src1, int cin1, i
 int conv_fwd_f32_mfma(const ay_conv_desc* d, const float* src1, int cin1, int up1, const float* src2, const float* w, const float* scale,
                       const float* shift, const float* residual, float* out, hipStream_t st, bool* taken) {
     const int kc = d->ksize == 1 ? 16 : d->stride == 2 ? 4 : 8;
-    // buffer descriptors address one image of either source and the filter tensor with 32-bit offsets; a route boundary lies
-    // on a stage boundary (the cfgs' routes join 128 / 256-channel tensors)
-    const bool fits = (long long)d->cin * d->hin * d->win * 4 < (1ll << 31) && (long long)d->cout * d->cin * d->ksize * d->ksize * 4 < (1ll << 31);
-    const bool on = fits && (cin1 == d->cin || cin1 % kc == 0);
+    // a route boundary lies on a stage boundary (the cfgs' routes join 128 / 256-channel tensors)
+    const bool on = nchw_fits_descriptors(d) && (cin1 == d->cin || cin1 % kc == 0);
     *taken = true;
     if (on && d->ksize == 3 && d->stride == 1) return launch_f32_mfma<3, 1, 8>(d, src1, cin1, up1, src2, w, scale, shift, residual, out, st);
     if (on && d->ksize == 3 && d->stride == 2) return launch_f32_mfma<3, 2, 4>(d, src1, cin1, up1, src2, w, scale, shift, residual, out, st);

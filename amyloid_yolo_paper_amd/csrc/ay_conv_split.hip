@@ -9,10 +9,8 @@
 // the leading bits then rounds once per tap instead of six times (measured against float64: 0.2 .. 0.5 of the exact-fp32 kernel's
 // own error, against 0.7 .. 1.2 with one set -- which missed the model-level 1e-4 bar on one fixture).
 //
-// Kept from the fp32 kernel: the workgroup tile (64 output channels x 8 x 32 pixels, 4 waves, 2 x 2 accumulator tiles of
-// 32 x 32 per wave), the XCD-contiguous item walk, buffer-descriptor loads with one fixed 32-bit offset per lane and an
-// out-of-range offset for padding and tails, the register-staged prefetch of the next fill under the MFMAs of this one, the
-// epilogue.
+// The frame is ay_conv_nchw.h's, shared with the fp32 kernel: the workgroup tile, the item walk, the geometry of the sources,
+// the filter descriptor, the host side.  As there, the next fill is prefetched into registers under the MFMAs of this one.
 //
 // Stage = 16 input channels = the K of one MFMA (the 3-channel stem and a cin % 16 tail are zero-filled).  A loader thread owns
 // one K-HALF (8 channels) of one pixel or of one (tap, filter): 8 plane-strided loads (coalesced across lanes along the pixels),
@@ -33,21 +31,9 @@
 // workgroups per CU), 1x1: 20 / 30 KiB, stride 2: 81 / 122 KiB (one workgroup per CU).  static_assert below.
 // Registers: the second accumulator set of nsplit = 3 leaves the 3x3 stride-1 instance no room for the prefetch at two workgroups
 // per CU (LATE_LOADS below).
-#include "ay_common.h"
+#include "ay_conv_nchw.h"
 
 namespace ay {
-
-struct SplitArgs {
-    const float* s1;
-    const float* s2;
-    const float* w;
-    const float* scale;
-    const float* shift;
-    const float* res;
-    float* out;
-    int cin, cin1, up1, cout, hin, win, hout, wout, leaky;
-    int tiles_x, tiles_y, n_cgroups, n_items;
-};
 
 // THE SPLIT RULE on 8 values: plane p of v[0..7] as 8 bf16 in 4 dwords
 template <int NSPLIT>
@@ -66,7 +52,7 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&pl)[NSPLIT])
 
 template <int KS, int STRIDE, int NSPLIT>
 struct SplitGeom {
-    static constexpr int BN = 64, TH = 8, TW = 32, KC = 16;
+    static constexpr int BN = NCHW_BN, TH = NCHW_TH, TW = NCHW_TW, KC = 16;
     static constexpr int TP = KS;                 // taps per fill: one kernel row
     static constexpr int IN_H = (TH - 1) * STRIDE + KS, IN_W = (TW - 1) * STRIDE + KS;
     static constexpr int XPL = IN_H * IN_W;
@@ -83,7 +69,7 @@ struct SplitGeom {
 };
 
 template <int KS, int STRIDE, int NSPLIT, bool DUAL>
-__global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU)) conv_split_kernel(SplitArgs a) {
+__global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU)) conv_split_kernel(NchwArgs a) {
     using G = SplitGeom<KS, STRIDE, NSPLIT>;
     constexpr int BN = G::BN, TH = G::TH, TW = G::TW, KC = G::KC, TP = G::TP;
     constexpr int PAD = (KS - 1) / 2, KK2 = KS * KS, NPASS = KS;
@@ -99,30 +85,19 @@ __global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU
     unsigned char* const lw = lds + NSPLIT * XPLANE;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, hh = lane >> 5;
 
-    // workgroup -> item: the workgroups of one XCD (id & 7) walk a contiguous range of items, channel groups of a pixel tile
-    // adjacent (ay_conv_f32_mfma.hip)
-    const int per_xcd = (a.n_items + 7) >> 3;
-    const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || item >= a.n_items) return;
-    const int cg = item % a.n_cgroups;
-    const int pt = item / a.n_cgroups;
-    const int b = pt / (a.tiles_x * a.tiles_y);
-    const int y0 = ((pt / a.tiles_x) % a.tiles_y) * TH, x0 = (pt % a.tiles_x) * TW;
-    const int co0 = cg * BN;
+    int item;
+    if (!nchw_item_index(a, item)) return;
+    const NchwItem it = nchw_item(a, item);
+    const int b = it.b, y0 = it.y0, x0 = it.x0, co0 = it.co0;
 
-    // ---- staging maps, fixed for the K loop.  Raw buffer loads: a wave-uniform descriptor per stage (base = first channel of the
-    // stage, range = what is left of that source) + one 32-bit per-lane offset; lanes with nothing to fetch carry an offset beyond
-    // every range (it stays beyond after the channel term j * plane * 4 < 2^31 is added) and read zeros.
-    constexpr unsigned OOB = 0x80000000u;
-    const int cin2 = a.cin - a.cin1;
-    const int h1 = a.hin >> a.up1, w1 = a.win >> a.up1;
-    const unsigned plane1 = (unsigned)(h1 * w1), plane2 = (unsigned)(a.hin * a.win);
-    const float* const img1 = a.s1 + (size_t)b * a.cin1 * plane1;
-    const float* const img2 = cin2 > 0 ? a.s2 + (size_t)b * cin2 * plane2 : nullptr;
+    // ---- staging maps, fixed for the K loop: one fixed 32-bit offset per unit (ay_conv_nchw.h); the loads add j * plane * 4 < 2^31
+    const NchwSource src(a, b);
+    const int w1 = src.w1;
+    const unsigned plane1 = src.plane1, plane2 = src.plane2;
+    const float *const img1 = src.img1, *const img2 = src.img2;
     unsigned xo1[DUAL ? NXU : 1], xo2[NXU];  // byte offset of channel 8 * half of the stage in src1 (DUAL only) / in the plain source
 #pragma unroll
     for (int i = 0; i < NXU; ++i) {
@@ -131,10 +106,10 @@ __global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU
         const int iy = y0 * STRIDE - PAD + P / IN_W, ix = x0 * STRIDE - PAD + P % IN_W;
         const bool in = e < 2 * XPL && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win;
         if constexpr (DUAL) {
-            xo1[i] = in ? (unsigned)(half * 8 * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : OOB;
-            xo2[i] = in ? (unsigned)(half * 8 * plane2 + iy * a.win + ix) * 4u : OOB;
+            xo1[i] = in ? (unsigned)(half * 8 * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : NCHW_OOB;
+            xo2[i] = in ? (unsigned)(half * 8 * plane2 + iy * a.win + ix) * 4u : NCHW_OOB;
         } else {  // one source, possibly at half resolution (a lazily upsampled layer)
-            xo2[i] = in ? (unsigned)(half * 8 * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : OOB;
+            xo2[i] = in ? (unsigned)(half * 8 * plane1 + (iy >> a.up1) * w1 + (ix >> a.up1)) * 4u : NCHW_OOB;
         }
     }
     // filter unit u -> (co = u / (2 TP), half = (u / TP) & 1, tap of the fill = u % TP): byte offset of W[co][8 half][tap] from
@@ -144,7 +119,7 @@ __global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU
     for (int i = 0; i < NWU; ++i) {
         const int u = i * 256 + tid;
         const int co = co0 + u / (2 * TP), half = (u / TP) & 1, t = u % TP;
-        wo[i] = (u < 2 * TP * BN && co < a.cout) ? (unsigned)((co * a.cin + half * 8) * KK2 + t) * 4u : OOB;
+        wo[i] = (u < 2 * TP * BN && co < a.cout) ? (unsigned)((co * a.cin + half * 8) * KK2 + t) * 4u : NCHW_OOB;
     }
 
     float rx[NXU][8], rw[NWU][8];
@@ -165,11 +140,8 @@ __global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU
         }
     };
     auto issue_w = [&](int s, int pass) __attribute__((always_inline)) {
-        const int ci0 = s * KC;
-        // the range ends with the last filter; a channel tail (cin % 16 != 0: the 3-channel stem) is masked by hand in commit_w,
-        // since an offset past the row of one filter lands in the next filter's row, not out of range
-        const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w) + (size_t)ci0 * KK2 + pass * TP, 0,
-                                                                             ((a.cout * a.cin - ci0) * KK2 - pass * TP) * 4, 0x00020000);
+        // a channel tail (cin % 16 != 0: the 3-channel stem) is masked by hand in commit_w
+        const __amdgpu_buffer_rsrc_t wr = nchw_filter_rsrc(a, KK2, s * KC, pass * TP);
 #pragma unroll
         for (int i = 0; i < NWU; ++i)
 #pragma unroll
@@ -210,23 +182,14 @@ __global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
     // nsplit = 3: the five correction products go to a second accumulator set, added to the first in the epilogue, so that the
     // chain that carries the result's leading bits rounds once per tap, not six times
     constexpr bool TWO_SETS = NSPLIT == 3;
-    f32x16 cor[TWO_SETS ? 2 : 1][TWO_SETS ? 2 : 1];
-    if constexpr (TWO_SETS) {
+    f32x16 cor[2][2];   // left alone, and no registers, with one set
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) cor[m][n][r] = 0.f;
+    for (int i = 0; i < 64; ++i) {
+        acc[i >> 5][(i >> 4) & 1][i & 15] = 0.f;
+        if constexpr (TWO_SETS) cor[i >> 5][(i >> 4) & 1][i & 15] = 0.f;
     }
 
     // fragment bases: A = filter c (+32 m), k-half hh; B = pixel (row 2 wave + n, column c), k-half hh
@@ -323,21 +286,15 @@ __global__ void __launch_bounds__(256, (SplitGeom<KS, STRIDE, NSPLIT>::WG_PER_CU
 }
 
 template <int KS, int STRIDE, int NSPLIT>
-static int launch_split(const SplitArgs& a, bool dual, hipStream_t st) {
-    const unsigned grid = 8u * (unsigned)((a.n_items + 7) / 8);
-    if (dual)
-        hipLaunchKernelGGL((conv_split_kernel<KS, STRIDE, NSPLIT, true>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_split_kernel<KS, STRIDE, NSPLIT, false>), dim3(grid), dim3(256), 0, st, a);
-    AY_CHECK_LAUNCH("conv_split_kernel");
-    return AY_OK;
+static int launch_split(const NchwArgs& a, hipStream_t st) {
+    return nchw_launch(conv_split_kernel<KS, STRIDE, NSPLIT, true>, conv_split_kernel<KS, STRIDE, NSPLIT, false>, "conv_split_kernel", a, st);
 }
 
 template <int NSPLIT>
-static int dispatch_split(const ay_conv_desc* d, const SplitArgs& a, bool dual, hipStream_t st) {
-    if (d->ksize == 3 && d->stride == 1) return launch_split<3, 1, NSPLIT>(a, dual, st);
-    if (d->ksize == 3 && d->stride == 2) return launch_split<3, 2, NSPLIT>(a, dual, st);
-    return launch_split<1, 1, NSPLIT>(a, dual, st);
+static int dispatch_split(const ay_conv_desc* d, const NchwArgs& a, hipStream_t st) {
+    if (d->ksize == 3 && d->stride == 1) return launch_split<3, 1, NSPLIT>(a, st);
+    if (d->ksize == 3 && d->stride == 2) return launch_split<3, 2, NSPLIT>(a, st);
+    return launch_split<1, 1, NSPLIT>(a, st);
 }
 
 }  // namespace ay
@@ -346,31 +303,16 @@ extern "C" int ay_conv_fwd_split(const ay_conv_desc* d, const float* src1, int c
                                  const float* scale, const float* shift, const float* residual, float* out, int nsplit,
                                  ay_stream_t stream) {
     using namespace ay;
-    AY_CHECK_ARG(d && src1 && w_oihw && scale && shift && out, "ay_conv_fwd_split: null argument");
+    const char* const entry = "ay_conv_fwd_split";
+    if (const int rc = nchw_check_entry(entry, d, src1, cin1, up1, src2, w_oihw, scale, shift, out)) return rc;
     AY_CHECK_ARG(nsplit == 2 || nsplit == 3, "ay_conv_fwd_split: nsplit %d (2 = bf16x3, 3 = bf16x6)", nsplit);
     AY_CHECK_ARG(d->batch > 0 && d->cin > 0 && d->cout > 0 && d->hin > 0 && d->win > 0, "ay_conv_fwd_split: empty tensor");
-    AY_CHECK_ARG(cin1 > 0 && cin1 <= d->cin && (cin1 == d->cin || src2), "ay_conv_fwd_split: channel split %d/%d", cin1, d->cin);
-    AY_CHECK_ARG(up1 == 0 || (up1 == 1 && d->hin % 2 == 0 && d->win % 2 == 0), "ay_conv_fwd_split: up1");
     AY_CHECK_ARG((d->ksize == 3 && (d->stride == 1 || d->stride == 2)) || (d->ksize == 1 && d->stride == 1),
                  "ay_conv_fwd_split: %dx%d stride %d is not covered (3x3 stride 1 / 2, 1x1 stride 1)", d->ksize, d->ksize, d->stride);
-    const int pad = (d->ksize - 1) / 2;
-    AY_CHECK_ARG(d->hout == (d->hin + 2 * pad - d->ksize) / d->stride + 1 && d->wout == (d->win + 2 * pad - d->ksize) / d->stride + 1,
-                 "ay_conv_fwd_split: output size mismatch");
     // a stage of 16 channels never straddles the route boundary
     AY_CHECK_ARG(cin1 == d->cin || cin1 % 16 == 0, "ay_conv_fwd_split: a route's first source needs a multiple of 16 channels (got %d)", cin1);
-    // buffer descriptors address one image of either source and the filter tensor with 32-bit offsets
-    AY_CHECK_ARG((long long)d->cin * d->hin * d->win * 4 < (1ll << 31) && (long long)d->cout * d->cin * d->ksize * d->ksize * 4 < (1ll << 31),
-                 "ay_conv_fwd_split: an image or the filter tensor exceeds the 32-bit descriptor range");
-    SplitArgs a;
-    a.s1 = src1, a.s2 = src2, a.w = w_oihw, a.scale = scale, a.shift = shift, a.res = residual, a.out = out;
-    a.cin = d->cin, a.cin1 = cin1, a.up1 = up1, a.cout = d->cout, a.hin = d->hin, a.win = d->win, a.hout = d->hout, a.wout = d->wout;
-    a.leaky = d->leaky;
-    a.tiles_x = (d->wout + 31) / 32;
-    a.tiles_y = (d->hout + 7) / 8;
-    a.n_cgroups = (d->cout + 63) / 64;
-    const long long n = (long long)a.tiles_x * a.tiles_y * d->batch * a.n_cgroups;
-    AY_CHECK_ARG(n > 0 && n <= 0x3fffffffLL, "ay_conv_fwd_split: grid out of range (%lld)", n);
-    a.n_items = (int)n;
-    const bool dual = cin1 < d->cin;
-    return nsplit == 2 ? dispatch_split<2>(d, a, dual, S(stream)) : dispatch_split<3>(d, a, dual, S(stream));
+    AY_CHECK_ARG(nchw_fits_descriptors(d), "ay_conv_fwd_split: an image or the filter tensor exceeds the 32-bit descriptor range");
+    NchwArgs a;
+    if (const int rc = nchw_fill_args(entry, d, src1, cin1, up1, src2, w_oihw, scale, shift, residual, out, a)) return rc;
+    return nsplit == 2 ? dispatch_split<2>(d, a, S(stream)) : dispatch_split<3>(d, a, S(stream));
 }

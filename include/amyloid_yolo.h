@@ -163,7 +163,9 @@ int ay_nchw_f32_to_blocked_f16(const float* src, void* dst, int batch, int c, in
 /* ---- fp32 parity path (reference layout) ------------------------------------------------------ */
 
 /* Same block in nchw f32 with OIHW fp32 weights; src2/c-split/up1 implement route+upsample in the
- * loader: channels [0,cin1) come from src1 read at (y>>up1, x>>up1), [cin1,cin) from src2. */
+ * loader: channels [0,cin1) come from src1 read at (y>>up1, x>>up1), [cin1,cin) from src2.
+ * up1 is 0 or 1; with up1 == 1 src1 is (hin/2) x (win/2) and hin, win must be even (an x2 upsample's sides are): an odd side is
+ * refused with AY_ERR_ARG and `out` is not touched.  The same holds for ay_conv_fwd_f32_valu and ay_conv_fwd_split. */
 int ay_conv_fwd_f32(const ay_conv_desc* d, const float* src1, int cin1, int up1, const float* src2,
                     const float* w_oihw, const float* scale, const float* shift, const float* residual,
                     float* out, ay_stream_t stream);

@@ -274,6 +274,10 @@ RECT_F32_CASES = [
     (24, 0, 0, 40, 3, 1, 13, 40, True, True, 2),        # wide, two channel groups (the second ragged), shortcut
     (32, 16, 1, 24, 1, 1, 26, 12, True, False, 2),      # tall, route [upsampled x2 | direct]
     (16, 0, 0, 32, 3, 2, 13, 20, True, False, 2),       # stride 2, odd and even side mixed
+    # 3x3 over the route [upsampled x2 | direct]: halo and padding through >> up1, the route boundary on a stage boundary of
+    # every stage size (4, 8, 16), both sources inside one stage loop
+    (16, 16, 1, 24, 3, 1, 12, 20, True, True, 2),       # stride 1, shortcut, ragged channel group
+    (16, 32, 1, 24, 3, 2, 12, 20, True, False, 1),      # stride 2: the upsampled source's halo meets the padding on the even / odd column split
 ]
 
 

@@ -327,6 +327,36 @@ def test_conv_f32_exact_rect(dev, case, entry):
     run_f32(dev, case, entry)
 
 
+@pytest.mark.parametrize("entry", ["ay_conv_fwd_f32", "ay_conv_fwd_f32_valu"])
+def test_conv_f32_refuses_odd_upsampled_side(dev, entry):
+    """up1 = 1 reads src1 at (y >> 1, x >> 1) of a plane of (hin >> 1) x (win >> 1): an odd side would address a row or column
+    past it.  Refused on the host: AY_ERR_ARG, a message, the output untouched"""
+    L = _lib.lib()
+    t = torch.zeros(1 << 12, device=dev)
+    for hin, win in ((13, 12), (12, 13)):
+        d = ConvDesc(1, 8, 8, hin, win, hin, win, 1, 1, 1, 0, 8)
+        out = Guarded((1, 8, hin, win), "f32", dev)
+        rc = getattr(L, entry)(C.byref(d), ptr(t), 8, 1, None, ptr(t), ptr(t), ptr(t), None, ptr(out.t), _lib.stream_ptr())
+        torch.cuda.synchronize()
+        assert rc == -1                      # AY_ERR_ARG
+        assert len(L.ay_last_error()) > 0 and b"up1" in L.ay_last_error()
+        assert bool(torch.isnan(out.t).all()) and out.intact()
+
+
+@pytest.mark.parametrize("entry", ["ay_conv_fwd_f32", "ay_conv_fwd_f32_valu"])
+def test_conv_f32_refuses_zero_stride(dev, entry):
+    """the shared output-size check divides by the stride: stride 0 is refused on the host before it, the output untouched"""
+    L = _lib.lib()
+    t = torch.zeros(1 << 12, device=dev)
+    d = ConvDesc(1, 8, 8, 12, 12, 12, 12, 1, 0, 1, 0, 8)
+    out = Guarded((1, 8, 12, 12), "f32", dev)
+    rc = getattr(L, entry)(C.byref(d), ptr(t), 8, 0, None, ptr(t), ptr(t), ptr(t), None, ptr(out.t), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == -1                      # AY_ERR_ARG
+    assert b"output size" in L.ay_last_error()
+    assert bool(torch.isnan(out.t).all()) and out.intact()
+
+
 def run_f32_grads(dev, case):
     cin, cout, k, s, H, W, B = case
     L = _lib.lib()
