@@ -31,16 +31,14 @@
 
 namespace ay {
 
-#ifdef AY_PHASE_CLOCK
-// instrumented build only (AY_PHASE_CLOCK=1 python build.py, AY_DBG=8 at run time): 100 MHz ticks of wave 0, summed over
-// workgroups: [0] stage loops, [1] epilogues, [2] items, [3] workgroups, [4] whole kernel per workgroup, [5] waits for landed
-// stages (vmcnt + barrier, both kinds), [6] slowest workgroup, [7] straddle step + its barrier, [8] the part of [5] spent in the
-// first wait of an item (end of its first even stage: the only wait with the previous item's output stores in front of it)
-__device__ unsigned long long g_phase_ticks_m16[10];
-#define AY_CLK(...) __VA_ARGS__
-#else
-#define AY_CLK(...)
-#endif
+// Phase clock (ay_phase_clock.h), wave 0, summed over workgroups: stage loops, epilogues, items, workgroups, whole kernel per workgroup,
+// waits for landed stages (vmcnt + barrier, both kinds), the slowest workgroup (a maximum), straddle step + its barrier, the part of the waits
+// spent in the first wait of an item (end of its first even stage: the only wait with the previous item's output stores in front of it)
+enum M16Tick {
+    M16_TK_STAGES, M16_TK_EPILOGUE, M16_TK_ITEMS, M16_TK_WGS, M16_TK_TOTAL, M16_TK_WAIT, M16_TK_SLOWEST, M16_TK_STRADDLE, M16_TK_WAIT_FIRST,
+    M16_TK_COUNT
+};
+AY_PHASE_TICKS(g_phase_ticks_m16, M16_TK_COUNT);
 
 template <bool HAS_RES, typename DT = Bf16>
 __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, int n_items) {
@@ -175,10 +173,11 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
     asm volatile("" ::: "memory");
 
     int par = 0;
-    AY_CLK(const bool clk = (a.dbg & 8) && wave == 0; unsigned long long tk_stage = 0, tk_epi = 0, tk_items = 0, tk_wait = 0, tk_wait0 = 0, tk_str = 0, tk0 = 0, tkw = 0;
-           const unsigned long long tk_begin = wall_clock64();)
+    AY_PCLK_BEGIN(g_phase_ticks_m16, AY_DBGBIT(a, DBG_CLOCK) && wave == 0, AY_PCLK_V(M16_TK_STAGES), AY_PCLK_V(M16_TK_EPILOGUE), AY_PCLK_V(M16_TK_ITEMS),
+                 AY_PCLK_V(M16_TK_WAIT), AY_PCLK_V(M16_TK_WAIT_FIRST), AY_PCLK_V(M16_TK_STRADDLE), AY_PCLK_V(T_ITEM), AY_PCLK_V(T_WAIT), AY_PCLK_V(T_BEGIN));
+    AY_PCLK_SET(T_BEGIN);
     while (true) {
-        AY_CLK(if (clk) tk0 = wall_clock64();)
+        AY_PCLK_MARK(T_ITEM);
         const int it = rg.item_of(item);
         const int cg = it % a.n_cgroups;
         const int pt = it / a.n_cgroups;
@@ -301,11 +300,14 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             step(I2{}, I0{}, I3{}, I0{}, I0{}, T{}, I0{}, false, 1);
             step(I3{}, I0{}, I4{}, I0{}, I1{}, F{}, I0{}, false, 1);
             advance_loader();
-            AY_CLK(if (clk) tkw = wall_clock64();)
+            AY_PCLK_MARK(T_WAIT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the odd stage has landed
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            AY_CLK(if (clk) { const unsigned long long t = wall_clock64(); tk_wait += t - tkw; if (s == 0) tk_wait0 += t - tkw; tkw = t; })
+            if (AY_PCLK_ON) {
+                const unsigned long long waited = AY_PCLK_LAPV(T_WAIT, M16_TK_WAIT);
+                if (s == 0) AY_PCLK_ADD(M16_TK_WAIT_FIRST, waited);
+            }
             // ---- tap 8 of both stages in one K32-step.  Every wave is through with the filter taps 0..7 of slot 0 (barrier
             // above), the straddle reads tap 8 and the pixels only: the next stage's taps 0..7 stream into slot 0 already
             const bool issued = !ld_done;
@@ -313,7 +315,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             step(I4{}, I0{}, I0{}, I1{}, I0{}, T{}, I3{}, issued, 0);
             __builtin_amdgcn_s_barrier();  // every wave is through with slot 0: its pixels and tap 8 may follow
             asm volatile("" ::: "memory");
-            AY_CLK(if (clk) tk_str += wall_clock64() - tkw;)
+            AY_PCLK_TICK(T_WAIT, M16_TK_STRADDLE);
             // ---- odd stage (slot 1); the rest of stage s+2 of this item, or of stage 0 of the next, streams into slot 0
             step(I0{}, I1{}, I1{}, I1{}, I1{}, T{}, I4{}, issued, 0);
             step(I1{}, I1{}, I2{}, I1{}, I0{}, T{}, I0{}, false, 0);
@@ -321,15 +323,15 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             step(I3{}, I1{}, I0{}, I0{}, I0{}, F{}, I0{}, false, 0);
             if (issued) advance_loader();
             if (!(last_pair && !has_next)) {
-                AY_CLK(if (clk) tkw = wall_clock64();)
+                AY_PCLK_MARK(T_WAIT);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next even stage has landed
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                AY_CLK(if (clk) tk_wait += wall_clock64() - tkw;)
+                AY_PCLK_TICK(T_WAIT, M16_TK_WAIT);
                 if (!last_pair) load_all(I0{}, I0{}, I0{});
             }
         }
-        AY_CLK(if (clk) { const unsigned long long t = wall_clock64(); tk_stage += t - tk0; tk0 = t; })
+        AY_PCLK_LAP(T_ITEM, M16_TK_STAGES);
 
         const int fetched = dealer.fetch(seq_c);
 
@@ -393,19 +395,19 @@ __global__ void __launch_bounds__(512, 2) conv3x3_m16_ring_kernel(ConvArgs a, in
             }
         }
         dealer.post(seq_c, fetched);
-        AY_CLK(if (clk) { tk_epi += wall_clock64() - tk0; ++tk_items; })
+        if (AY_PCLK_ON) AY_PCLK_ADD(M16_TK_EPILOGUE, AY_PCLK_SINCE(T_ITEM)), AY_PCLK_ADD(M16_TK_ITEMS, 1);
         if (!has_next) break;
         item = next_item;
         ++seq_c;
         par = (par + 1) & 3;
     }
     dealer.leave();
-    AY_CLK(if (clk && lane == 0) {
-        const unsigned long long tot = wall_clock64() - tk_begin;
-        atomicAdd(&g_phase_ticks_m16[0], tk_stage); atomicAdd(&g_phase_ticks_m16[1], tk_epi); atomicAdd(&g_phase_ticks_m16[2], tk_items);
-        atomicAdd(&g_phase_ticks_m16[3], 1ull); atomicAdd(&g_phase_ticks_m16[4], tot); atomicAdd(&g_phase_ticks_m16[5], tk_wait);
-        atomicMax(&g_phase_ticks_m16[6], tot); atomicAdd(&g_phase_ticks_m16[7], tk_str); atomicAdd(&g_phase_ticks_m16[8], tk_wait0);
-    })
+    if (AY_PCLK_ON && lane == 0) {
+        const unsigned long long total = AY_PCLK_SINCE(T_BEGIN);
+        AY_PCLK_FLUSH(M16_TK_STAGES), AY_PCLK_FLUSH(M16_TK_EPILOGUE), AY_PCLK_FLUSH(M16_TK_ITEMS), AY_PCLK_FLUSH_V(M16_TK_WGS, 1ull);
+        AY_PCLK_FLUSH_V(M16_TK_TOTAL, total), AY_PCLK_FLUSH(M16_TK_WAIT), AY_PCLK_FLUSH_MAX(M16_TK_SLOWEST, total), AY_PCLK_FLUSH(M16_TK_STRADDLE),
+            AY_PCLK_FLUSH(M16_TK_WAIT_FIRST);
+    }
 }
 
 }  // namespace ay
@@ -434,20 +436,14 @@ static int conv3x3_m16_fwd(const ay_conv_desc* d, const void* src, const void* w
     if (int rc = launch_ring(residual ? conv3x3_m16_ring_kernel<true, DT> : conv3x3_m16_ring_kernel<false, DT>, a, nblk, true, st, "conv",
                              "conv3x3_m16_ring_kernel"))
         return rc;
-#ifdef AY_PHASE_CLOCK
-    if (a.dbg & 8) {  // timing experiments only: synchronous phase report per launch
-        unsigned long long t[10] = {0};
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_phase_ticks_m16), sizeof(t));
-        const int nwait = d->cin / 16 - 1;  // waits of an item that is not a workgroup's last, the first one included
-        if (t[3])
-            fprintf(stderr, "[ay phase m16] cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (of it waits for landed stages %.2f = first wait %.2f + others %.2f each, straddle+barrier %.2f; %d stages), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
-                    d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[2] / t[3], t[0] * 0.01 / t[2], t[5] * 0.01 / t[2], t[8] * 0.01 / t[2],
-                    nwait ? (t[5] - t[8]) * 0.01 / t[2] / nwait : 0.0, t[7] * 0.01 / t[2], d->cin / 16, t[1] * 0.01 / t[2], t[4] * 0.01 / t[3], t[6] * 0.01);
-        unsigned long long z[10] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks_m16), z, sizeof(z));
-    }
-#endif
+    unsigned long long t[M16_TK_COUNT];
+    const int nwait = d->cin / 16 - 1;  // waits of an item that is not a workgroup's last, the first one included
+    if (phase_clock_read(st, HIP_SYMBOL(g_phase_ticks_m16), t, M16_TK_COUNT) && t[M16_TK_WGS])
+        fprintf(stderr, "[ay phase m16] cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (of it waits for landed stages %.2f = first wait %.2f + others %.2f each, straddle+barrier %.2f; %d stages), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
+                d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[M16_TK_ITEMS] / t[M16_TK_WGS], t[M16_TK_STAGES] * 0.01 / t[M16_TK_ITEMS],
+                t[M16_TK_WAIT] * 0.01 / t[M16_TK_ITEMS], t[M16_TK_WAIT_FIRST] * 0.01 / t[M16_TK_ITEMS],
+                nwait ? (t[M16_TK_WAIT] - t[M16_TK_WAIT_FIRST]) * 0.01 / t[M16_TK_ITEMS] / nwait : 0.0, t[M16_TK_STRADDLE] * 0.01 / t[M16_TK_ITEMS],
+                d->cin / 16, t[M16_TK_EPILOGUE] * 0.01 / t[M16_TK_ITEMS], t[M16_TK_TOTAL] * 0.01 / t[M16_TK_WGS], t[M16_TK_SLOWEST] * 0.01);
     return AY_OK;
 }
 }  // namespace ay

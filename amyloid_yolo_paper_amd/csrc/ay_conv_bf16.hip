@@ -18,9 +18,6 @@
 //   LDS filters  [kstep][tap][half][BN][8 bf16]
 #include <stdlib.h>
 
-#include <atomic>
-#include <mutex>
-
 #include "ay_conv_common.h"
 
 namespace ay {
@@ -202,14 +199,13 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(ConvArgs a, DecodeArg
 //   * three slots: every wave issues the same number PW of 1-KiB DMA pieces per stage (the piece list is padded with dummy
 //     pieces that copy zeros into a scratch KiB), so "stage g+1 has landed" is one constant `s_waitcnt vmcnt(PW)`; two slots:
 //     every wait is `vmcnt(0)` and the padding pieces are skipped.
-// AY_DBG&8: phase clock of the ring kernel, summed over workgroups (wave 0): [0] stage loops, [1] epilogues, [2] items,
-// [3] workgroups, [4] whole-kernel ticks per workgroup, [5] first stages, [6] slowest workgroup, [7] stage-end waits (last MFMA
-// group to the barrier's return) of the first stage of an item, [8] of all other stages, [9] their number; 100 MHz ticks (s_memrealtime)
-__device__ unsigned long long g_phase_ticks[10];
-// dynamic item dealing: 64 rotating sets of {8 per-XCD item counters, exit counter}; zero at load, reset by the last workgroup
-constexpr int DEAL_SETS = 64, DEAL_STREAMS = 16;
-__device__ unsigned g_deal[DEAL_STREAMS * DEAL_SETS][16];
-
+// Phase clock (ay_phase_clock.h), wave 0, summed over workgroups: stage loops, epilogues, items, workgroups, whole kernel per workgroup, first
+// stages, the slowest workgroup (a maximum), stage-end waits (last MFMA group to the barrier's return) of first stages, of other stages, their number
+enum RingTick {
+    RING_TK_STAGES, RING_TK_EPILOGUE, RING_TK_ITEMS, RING_TK_WGS, RING_TK_TOTAL, RING_TK_FIRST, RING_TK_SLOWEST, RING_TK_WAIT_FIRST,
+    RING_TK_WAIT, RING_TK_NWAIT, RING_TK_COUNT
+};
+AY_PHASE_TICKS(g_phase_ticks, RING_TK_COUNT);
 template <int KS, int STRIDE, int BN, int WM, int WN, int TH, int TW, int NK, int NBUF, bool HAS_RES, bool CAT = false, bool CANVAS = false,
           typename DT = Bf16, bool PAIR = false>
 __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int n_items) {
@@ -468,12 +464,12 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
 
     int cur = 0;  // ring slot of the stage the MFMAs read
     int par = 0;  // scale/shift region of the item the MFMAs work on
-    // phase clock (instrumented build only, see AY_DBGBIT): wave-uniform tick counters
-    const bool clk = AY_DBGBIT(a, 8) && wave == 0;
-    unsigned long long tk_stage = 0, tk_epi = 0, tk_items = 0, tk0 = 0, tk_begin = 0, tk_s0 = 0, tk_w0 = 0, tk_w = 0, tk_nw = 0, tkw = 0;
-    if (clk) tk_begin = wall_clock64();
+    AY_PCLK_BEGIN(g_phase_ticks, AY_DBGBIT(a, DBG_CLOCK) && wave == 0, AY_PCLK_V(RING_TK_STAGES), AY_PCLK_V(RING_TK_EPILOGUE), AY_PCLK_V(RING_TK_ITEMS),
+                 AY_PCLK_V(T_ITEM), AY_PCLK_V(T_BEGIN), AY_PCLK_V(RING_TK_FIRST), AY_PCLK_V(RING_TK_WAIT_FIRST), AY_PCLK_V(RING_TK_WAIT),
+                 AY_PCLK_V(RING_TK_NWAIT), AY_PCLK_V(T_WAIT));
+    AY_PCLK_MARK(T_BEGIN);
     while (true) {
-        if (clk) tk0 = wall_clock64();
+        AY_PCLK_MARK(T_ITEM);
         const int it = rg.item_of(item);
         int cg = it % a.n_cgroups;
         const int cls = PAIR ? (cg & 1) * 2 : UP2 ? (cg & 3) : 0;
@@ -505,7 +501,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
             // the stage is waited for at the end of this one, and a piece lands ~1.1 us after its issue under load, so all of
             // it goes out behind the first NE steps (3x3: two pieces per tap, five of nine taps in the stride-2 kernel; otherwise
             // the first half of the steps).
-            const bool issued = !ld_done && !AY_DBGBIT(a, 1);
+            const bool issued = !ld_done && !AY_DBGBIT(a, DBG_NO_STAGING);
             int slot_ld = cur + (NBUF - 1);
             if (slot_ld >= NBUF) slot_ld -= NBUF;
             constexpr bool EARLY_RES = (MT * NT <= 4);  // 32 VGPRs of residual; larger wave tiles load it in the epilogue
@@ -529,11 +525,11 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
                         fb[n] = *reinterpret_cast<const vec8*>(L + kk * PIX_SLAB + pb[n] + (kh * IN_W + kw) * 16);
                 }
             };
-            if (!AY_DBGBIT(a, 2)) load_frags(0, af[0], bfr[0]);
+            if (!AY_DBGBIT(a, DBG_NO_MFMA)) load_frags(0, af[0], bfr[0]);
 #pragma unroll
             for (int t = 0; t < NSTEP; ++t) {
-                if (AY_DBGBIT(a, 2)) break;
-                if (t + 1 < NSTEP && !AY_DBGBIT(a, 64)) load_frags(t + 1, af[(t + 1) & 1], bfr[(t + 1) & 1]);
+                if (AY_DBGBIT(a, DBG_NO_MFMA)) break;
+                if (t + 1 < NSTEP && !AY_DBGBIT(a, DBG_NO_PREFETCH)) load_frags(t + 1, af[(t + 1) & 1], bfr[(t + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
                 // (unequal priorities for the two waves of a SIMD were measured slower: 21.4 vs 20.0 us compute-only)
                 __builtin_amdgcn_s_setprio(3);
@@ -550,7 +546,7 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
                         if (i >= t * PW / NE && i < (t + 1) * PW / NE) issue_piece(i, slot_ld);
                 }
             }
-            if (clk) tkw = wall_clock64();
+            AY_PCLK_MARK(T_WAIT);
             if (issued) advance_loader();
             // stage g+1 must have landed before anyone reads it: everything but the stage(s) issued after it
             if (!(last_stage && !has_next)) {
@@ -564,47 +560,30 @@ __global__ void __launch_bounds__(512, 2) conv_bf16_ring_kernel(ConvArgs a, int 
                 }
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                if (clk) {
-                    const unsigned long long t = wall_clock64() - tkw;
-                    if (s == 0)
-                        tk_w0 += t;
-                    else
-                        tk_w += t, ++tk_nw;
+                if (AY_PCLK_ON) {
+                    const unsigned long long t = AY_PCLK_SINCE(T_WAIT);
+                    s == 0 ? AY_PCLK_ADD(RING_TK_WAIT_FIRST, t) : (AY_PCLK_ADD(RING_TK_WAIT, t), AY_PCLK_ADD(RING_TK_NWAIT, 1));
                 }
             }
             if (++cur == NBUF) cur = 0;
-            if (clk && s == 0) tk_s0 += wall_clock64() - tk0;
+            if (AY_PCLK_ON && s == 0) AY_PCLK_ADD(RING_TK_FIRST, AY_PCLK_SINCE(T_ITEM));
         }
-        if (clk) {
-            const unsigned long long t = wall_clock64();
-            tk_stage += t - tk0;
-            tk0 = t;
-        }
+        AY_PCLK_LAP(T_ITEM, RING_TK_STAGES);
         const int fetched = dealer.fetch(seq_c);  // id[c+D]; posted after the epilogue
         conv_epilogue<BN, MT, NT, TW, false, HAS_RES, (MT * NT > 4), 1, CANVAS, UP2, DT, PAIR>(a, acc, rr, b, cg, wm, wn, c, hh, y0, x0,
                                                                             reinterpret_cast<const float*>(lds + SS_BASE + par * SSR), cls);
         dealer.post(seq_c, fetched);
-        if (clk) {
-            tk_epi += wall_clock64() - tk0;
-            ++tk_items;
-        }
+        if (AY_PCLK_ON) AY_PCLK_ADD(RING_TK_EPILOGUE, AY_PCLK_SINCE(T_ITEM)), AY_PCLK_ADD(RING_TK_ITEMS, 1);
         if (!has_next) break;
         item = next_item;
         ++seq_c;
         par = (par + 1) & 3;
     }
     dealer.leave();
-    if (clk && lane == 0) {
-        atomicAdd(&g_phase_ticks[0], tk_stage);
-        atomicAdd(&g_phase_ticks[1], tk_epi);
-        atomicAdd(&g_phase_ticks[2], tk_items);
-        atomicAdd(&g_phase_ticks[3], 1ull);
-        atomicAdd(&g_phase_ticks[4], wall_clock64() - tk_begin);
-        atomicAdd(&g_phase_ticks[5], tk_s0);
-        atomicMax(&g_phase_ticks[6], wall_clock64() - tk_begin);
-        atomicAdd(&g_phase_ticks[7], tk_w0);
-        atomicAdd(&g_phase_ticks[8], tk_w);
-        atomicAdd(&g_phase_ticks[9], tk_nw);
+    if (AY_PCLK_ON && lane == 0) {
+        AY_PCLK_FLUSH(RING_TK_STAGES), AY_PCLK_FLUSH(RING_TK_EPILOGUE), AY_PCLK_FLUSH(RING_TK_ITEMS), AY_PCLK_FLUSH_V(RING_TK_WGS, 1ull);
+        AY_PCLK_FLUSH_V(RING_TK_TOTAL, AY_PCLK_SINCE(T_BEGIN)), AY_PCLK_FLUSH(RING_TK_FIRST), AY_PCLK_FLUSH_MAX(RING_TK_SLOWEST, AY_PCLK_SINCE(T_BEGIN));
+        AY_PCLK_FLUSH(RING_TK_WAIT_FIRST), AY_PCLK_FLUSH(RING_TK_WAIT), AY_PCLK_FLUSH(RING_TK_NWAIT);
     }
 }
 
@@ -613,57 +592,6 @@ constexpr int ring_depth() {
     constexpr int in_pix = ((TH - 1) * STRIDE + KS) * ((TW - 1) * STRIDE + KS);
     constexpr int buf = NK * (((2 * in_pix + 63) / 64) * 1024 + KS * KS * 2 * BN * 16);
     return (3 * buf + 1024 + 4 * 2048 + 64 <= 160 * 1024) ? 3 : 2;
-}
-
-static int current_device() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    return dev < 0 || dev >= 64 ? 0 : dev;
-}
-int conv_num_cus() {
-    static std::atomic<int> cus[64];  // per device
-    const int dev = current_device();
-    int n = cus[dev].load(std::memory_order_relaxed);
-    if (!n) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n < 8) n = 256;
-        if (getenv("AY_CUS")) n = atoi(getenv("AY_CUS"));  // timing experiments only
-        n -= n % 8;
-        cus[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
-}
-
-// Counter set of the next ring-kernel launch on `st` (nullptr: static dealing).  The sets of one stream are used in rotation
-// by launches that the stream serialises -- the last workgroup of a launch hands its set back zeroed before the next launch
-// on that stream starts -- so a set must never be shared by two streams, whose launches may overlap: every (device, stream)
-// pair owns DEAL_SETS sets of its own, up to DEAL_STREAMS streams per device; further streams deal statically.  A set pointer
-// baked into a captured graph node stays valid under the same rule: replay the graph on the stream it was captured on, or on
-// any stream as long as nothing else on the CAPTURE stream runs concurrently.
-unsigned* next_deal_set(hipStream_t st) {
-    struct PerDevice {
-        unsigned* base = nullptr;
-        hipStream_t streams[DEAL_STREAMS] = {};
-        unsigned seq[DEAL_STREAMS] = {};
-        int n = 0;
-    };
-    static std::mutex mu;
-    static PerDevice devs[64];
-    std::lock_guard<std::mutex> lock(mu);
-    PerDevice& pd = devs[current_device()];
-    if (!pd.base) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_deal)) != hipSuccess) return nullptr;  // this device's copy of the symbol
-        pd.base = (unsigned*)p;
-    }
-    int k = 0;
-    while (k < pd.n && pd.streams[k] != st) ++k;
-    if (k == pd.n) {
-        if (pd.n == DEAL_STREAMS) return nullptr;
-        pd.streams[pd.n++] = st;
-    }
-    return pd.base + ((size_t)k * DEAL_SETS + (pd.seq[k]++ % DEAL_SETS)) * 16;
 }
 
 // canvas tiling (ConvArgs::canvas_gx) applies to stride-1 same-size layers that save tiles that way and whose tensors stay below
@@ -688,55 +616,6 @@ static int canvas_plan(const ay_conv_desc* d, int th, int tw, int* tiles_x, int*
         }
     }
     return best * 10 <= image_tiles * 9 ? best_gx : 0;  // worth it from a tenth fewer tiles
-}
-
-void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* w, const float* scale, const float* shift,
-               const void* residual, void* out, int TH, int TW, int BN) {
-    a = ConvArgs{};
-    a.src = (const uint8_t*)src;
-    a.w = (const uint8_t*)w;
-    a.scale = scale;
-    a.shift = shift;
-    a.residual = (const uint8_t*)residual;
-    a.out = (uint8_t*)out;
-    a.batch = d->batch;
-    a.cin = d->cin;
-    a.cout_pad = d->cout_pad;
-    a.hin = d->hin;
-    a.win = d->win;
-    a.hout = d->hout;
-    a.wout = d->wout;
-    a.tiles_x = (d->wout + TW - 1) / TW;
-    a.tiles_y = (d->hout + TH - 1) / TH;
-    a.n_cgroups = d->cout_pad / BN;
-    a.leaky = d->leaky;
-    a.dbg = 0;
-    a.src1 = nullptr;
-    a.c1 = 0;
-    a.deal = nullptr;
-    a.canvas_gx = 0;
-    a.w_class_stride = 0;
-    a.reverse = conv_traversal_reverse();
-}
-
-// Per host thread: a launch takes the direction in force on the thread that issues it (a captured launch keeps it in its node)
-static thread_local int t_traversal_reverse = 0;
-int conv_traversal_reverse() { return t_traversal_reverse; }
-}  // namespace ay
-extern "C" void ay_conv_set_traversal(int reverse) { ay::t_traversal_reverse = reverse != 0; }
-extern "C" int ay_conv_get_traversal(void) { return ay::t_traversal_reverse; }
-namespace ay {
-
-int conv_dbg() {
-    static const int dbg = getenv("AY_DBG") ? atoi(getenv("AY_DBG")) : 0;
-    return dbg;
-}
-
-unsigned persistent_grid(long long n_items, int wgs_per_cu) {
-    if (n_items <= 0 || n_items > 0x7fffffffLL) return 0;
-    const long long per_xcd = (n_items + 7) / 8;
-    const long long cu_slots = (long long)wgs_per_cu * (conv_num_cus() / 8);
-    return (unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots));
 }
 
 // The tile grid of `a` and its number of items.  canvas_ok: images that leave much of their tiles empty (canvas_plan) are tiled as a
@@ -792,20 +671,13 @@ static int launch(const ay_conv_desc* d, const void* src, const void* w, const f
         }
         AY_CHECK_LAUNCH("conv_bf16_kernel");
     }
-#ifdef AY_PHASE_CLOCK
-    if (RING && (a.dbg & 8)) {  // timing experiments only: synchronous phase report per launch
-        unsigned long long t[10] = {0};
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_phase_ticks), sizeof(t));
-        if (t[3])
-            fprintf(stderr, "[ay phase] k%d s%d BN%d tile%dx%d cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (first stage %.2f of %d; stage-end wait: first stage %.2f, other stages %.2f each), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
-                    KS, STRIDE, BN, TH, TW, d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[2] / t[3], t[0] * 0.01 / t[2],
-                    t[5] * 0.01 / t[2], d->cin / (16 * NK), t[7] * 0.01 / t[2], t[9] ? t[8] * 0.01 / t[9] : 0.0, t[1] * 0.01 / t[2], t[4] * 0.01 / t[3],
-                    t[6] * 0.01);
-        unsigned long long z[10] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), z, sizeof(z));
-    }
-#endif
+    unsigned long long t[RING_TK_COUNT];
+    if (RING && phase_clock_read(st, HIP_SYMBOL(g_phase_ticks), t, RING_TK_COUNT) && t[RING_TK_WGS])
+        fprintf(stderr, "[ay phase] k%d s%d BN%d tile%dx%d cin%d cout%d h%d res%d: items/wg %.1f  per item: stages %.2f us (first stage %.2f of %d; stage-end wait: first stage %.2f, other stages %.2f each), epilogue %.2f us; wg total %.1f us (slowest %.1f)\n",
+                KS, STRIDE, BN, TH, TW, d->cin, d->cout, d->hout, residual ? 1 : 0, (double)t[RING_TK_ITEMS] / t[RING_TK_WGS],
+                t[RING_TK_STAGES] * 0.01 / t[RING_TK_ITEMS], t[RING_TK_FIRST] * 0.01 / t[RING_TK_ITEMS], d->cin / (16 * NK),
+                t[RING_TK_WAIT_FIRST] * 0.01 / t[RING_TK_ITEMS], t[RING_TK_NWAIT] ? t[RING_TK_WAIT] * 0.01 / t[RING_TK_NWAIT] : 0.0,
+                t[RING_TK_EPILOGUE] * 0.01 / t[RING_TK_ITEMS], t[RING_TK_TOTAL] * 0.01 / t[RING_TK_WGS], t[RING_TK_SLOWEST] * 0.01);
     return AY_OK;
 }
 
@@ -853,9 +725,6 @@ static int launch_dgrad_s2(const ay_conv_desc* d, const void* dz, const void* w,
     return launch_ring(kernel, a, nblk, true, st, "dgrad", "conv_bf16_ring_kernel(dgrad s2)");
 }
 
-}  // namespace ay
-
-namespace ay {
 template <typename DT>
 static int conv1x1_cat_fwd(const ay_conv_desc* d, const void* src1_halfres, int c1, const void* src2, const void* w_packed,
                            const float* scale, const float* shift, void* out, ay_stream_t stream) {
@@ -960,9 +829,6 @@ static int conv_fwd_16(const ay_conv_desc* d, const void* src, const void* w_pac
     if (d->out_f32) return launch<1, 1, 32, 1, 4, 8, 32, 1, true, false, DT>(d, src, w_packed, scale, shift, residual, out, st);
     return launch<1, 1, 32, 1, 4, 8, 32, 1, false, false, DT>(d, src, w_packed, scale, shift, residual, out, st);
 }
-}  // namespace ay
-
-namespace ay {
 // A detection head with its decode: the linear 1x1 convolution of models.py:33-40 (heads 81 / 93 / 105: bias, no BatchNorm, no
 // activation) through conv_bf16_kernel<..., DECODE>, whose epilogue writes rows [row_offset, row_offset + A G G) of pred.
 template <typename DT>

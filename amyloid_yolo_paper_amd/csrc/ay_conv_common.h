@@ -1,15 +1,7 @@
 // Pieces shared by the bf16 MFMA convolution kernels: argument block, residual registers, fused epilogue.
 #pragma once
 #include "ay_common.h"
-
-// Timing-experiment hooks (AY_DBG bits: 1 no staging, 2 no MFMA phase, 4 no output stores, 8 phase clock, 64 MFMA-only) exist
-// only in a library built with -DAY_PHASE_CLOCK (AY_PHASE_CLOCK=1 python build.py).  In the product build AY_DBGBIT() is a
-// compile-time 0: run-time branches inside the unrolled MFMA loops cost the register-saturated kernels 20-30 VGPRs of spills.
-#ifdef AY_PHASE_CLOCK
-#define AY_DBGBIT(a, bit) ((a).dbg & (bit))
-#else
-#define AY_DBGBIT(a, bit) 0
-#endif
+#include "ay_phase_clock.h"
 
 namespace ay {
 
@@ -23,7 +15,7 @@ struct ConvArgs {
     int batch, cin, cout_pad, hin, win, hout, wout;
     int tiles_x, tiles_y, n_cgroups;
     int leaky;
-    int dbg;  // timing experiments only (AY_DBG): 1 = no staging in the stage loop, 2 = no MFMA phase
+    int dbg;  // instrumented build only: the AY_DBG bits (ay_phase_clock.h: DbgBit); the product kernels never read it
     const uint8_t* src1;  // ring kernel, CAT variant: the first c1 input channels come from this tensor at half resolution
     int c1;               // (nearest x2 upsample folded into the loader); `src` then holds channels c1..cin-1
     unsigned* deal;  // ring kernel: per-launch work counters (8 per-XCD item counters + 1 exit counter), nullptr = static dealing
@@ -303,8 +295,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
     for (int n = 0; n < NT; ++n) {
         const int p = (wn * NT + n) * 32 + c;
         int oy = y0 + p / TW, ox = x0 + p % TW, bn = b;  // bn: the image of this lane's pixel (canvas mode: per lane)
-        bool ok = (oy < a.hout) && (ox < a.wout) && !AY_DBGBIT(a, 4);
-        if constexpr (CANVAS) ok = canvas_px(a, y0 + p / TW, x0 + p % TW, bn, oy, ox) && !AY_DBGBIT(a, 4);
+        bool ok = (oy < a.hout) && (ox < a.wout) && !AY_DBGBIT(a, DBG_NO_STORES);
+        if constexpr (CANVAS) ok = canvas_px(a, y0 + p / TW, x0 + p % TW, bn, oy, ox) && !AY_DBGBIT(a, DBG_NO_STORES);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             const int t = n * MT + m;
@@ -389,8 +381,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
         for (int n = 0; n < NT; ++n) {
             const int p = (wn * NT + n) * 32 + c;
             int oy = y0 + p / TW, ox = x0 + p % TW, bn = 0;
-            bool ok = (oy < a.hout) && (ox < a.wout) && !AY_DBGBIT(a, 4);
-            if constexpr (CANVAS) ok = canvas_px(a, y0 + p / TW, x0 + p % TW, bn, oy, ox) && !AY_DBGBIT(a, 4);
+            bool ok = (oy < a.hout) && (ox < a.wout) && !AY_DBGBIT(a, DBG_NO_STORES);
+            if constexpr (CANVAS) ok = canvas_px(a, y0 + p / TW, x0 + p % TW, bn, oy, ox) && !AY_DBGBIT(a, DBG_NO_STORES);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 int chf, clm;
@@ -457,9 +449,9 @@ __device__ __forceinline__ void head_decode_epilogue(const ConvArgs& a, const De
     }
 }
 
-// ---- host side of the launches (defined in ay_conv_bf16.hip) -------------------------------------------------------------
+// ---- host side of the launches (defined in ay_conv_host.hip) -------------------------------------------------------------
 int conv_num_cus();
-// AY_DBG, read once (timing experiments: only the instrumented build's kernels look at ConvArgs::dbg)
+// AY_DBG, read once (ay_phase_clock.h: only the instrumented build's kernels look at the bits)
 int conv_dbg();
 // direction of the persistent conv launches this host thread issues next (ay_conv_set_traversal)
 int conv_traversal_reverse();

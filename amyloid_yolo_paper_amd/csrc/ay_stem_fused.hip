@@ -14,17 +14,15 @@
 namespace ay {
 
 __device__ __attribute__((aligned(64))) uint32_t g_zero_page_st[16];
-#ifdef AY_PHASE_CLOCK
-__device__ unsigned long long g_stem_ticks[8];  // [0] DMA issue, [1] phase B, [2] barrier, [3] phase C, [4] epilogue, [5] tail wait, [6] items
-#define STEM_TICK(k)                                   \
-    if (wave == 0) {                                   \
-        const unsigned long long t_ = wall_clock64();  \
-        tk[k] += t_ - tk_last;                         \
-        tk_last = t_;                                  \
-    }
-#else
-#define STEM_TICK(k)
-#endif
+// Phase clocks (ay_phase_clock.h), summed over workgroups, each interval from its wave's previous lap.  stem_s2_fused_kernel, wave 0:
+enum StemTick { STEM_TK_ISSUE, STEM_TK_STEM, STEM_TK_BARRIER, STEM_TK_LAYER1, STEM_TK_EPILOGUE, STEM_TK_TAIL, STEM_TK_ITEMS, STEM_TK_COUNT };
+AY_PHASE_TICKS(g_stem_ticks, STEM_TK_COUNT);
+// stem_s2_fused_v2_kernel: wave 0 for the producers' loop (P: tile issue, stem phase, wait + barrier; iterations), wave 8 for the consumers' (C)
+enum Stem2Tick {
+    STEM2_TK_P_ISSUE, STEM2_TK_P_STEM, STEM2_TK_P_WAIT, STEM2_TK_C_ISSUE, STEM2_TK_C_LAYER1, STEM2_TK_C_EPILOGUE, STEM2_TK_ITERS,
+    STEM2_TK_C_WAIT, STEM2_TK_COUNT
+};
+AY_PHASE_TICKS(g_stem2_ticks, STEM2_TK_COUNT);
 
 struct StemFusedArgs {
     const float* x;         // [B][3][H][W] f32
@@ -150,9 +148,9 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
     }
     __syncthreads();  // tile 0 landed; filters and scale/shift tables written
     int ib = 0;
-#ifdef AY_PHASE_CLOCK
-    unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tk_last = wall_clock64();
-#endif
+    AY_PCLK_BEGIN(g_stem_ticks, AY_DBGBIT(a, DBG_CLOCK) && wave == 0, AY_PCLK_V(STEM_TK_ISSUE), AY_PCLK_V(STEM_TK_STEM), AY_PCLK_V(STEM_TK_BARRIER),
+                 AY_PCLK_V(STEM_TK_LAYER1), AY_PCLK_V(STEM_TK_EPILOGUE), AY_PCLK_V(STEM_TK_TAIL), AY_PCLK_V(STEM_TK_ITEMS), AY_PCLK_V(T_LAST));
+    AY_PCLK_MARK(T_LAST);
     while (true) {
         const int pt = rg.item_of(item);
         const int b = pt / tiles_per_img;
@@ -163,7 +161,7 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
         const float* img = reinterpret_cast<const float*>(lds + ib * IMG_BYTES);
         // tile of item i+2 -> the buffer item i-1 read (every wave has passed two barriers since)
         if (has_next2) issue_image(next_item + slots, ib >= 1 ? ib - 1 : NIB - 1);
-        STEM_TICK(0)
+        AY_PCLK_LAP(T_LAST, STEM_TK_ISSUE);
 
         // ---- B: stem by MFMA into the slabs ----------------------------------------------------------------
         for (int blk = wave; blk < S_PIXP / 32; blk += 16) {
@@ -210,11 +208,11 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
                 *reinterpret_cast<uint2*>(dst) = make_uint2(pack2_scalar<DT>(o[0], o[1]), pack2_scalar<DT>(o[2], o[3]));
             }
         }
-        STEM_TICK(1)
+        AY_PCLK_LAP(T_LAST, STEM_TK_STEM);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // raw barriers: __syncthreads would drain the DMAs (vmcnt(0))
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        STEM_TICK(2)
+        AY_PCLK_LAP(T_LAST, STEM_TK_BARRIER);
 
         // ---- C: layer 1, 2 chunks x 9 taps ------------------------------------------------------------------
         f32x16 acc1[MT][NT];
@@ -236,15 +234,13 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
                 for (int m = 0; m < MT; ++m) acc1[m][0] = DT::mfma32(af[m], bfr, acc1[m][0]);
             }
         }
-        STEM_TICK(3)
+        AY_PCLK_LAP(T_LAST, STEM_TK_LAYER1);
         // ---- D: epilogue ----------------------------------------------------------------------------------
         ResRegs<MT, NT> rr;
         conv_epilogue<BN, MT, NT, TW, false, false, false, 2, false, false, DT>(a, acc1, rr, b, 0, wm, wn, c, hh, y0, x0,
                                                               reinterpret_cast<const float*>(lds + OFF_SS1));
-        STEM_TICK(4)
-#ifdef AY_PHASE_CLOCK
-        if (wave == 0) ++tk[6];
-#endif
+        AY_PCLK_LAP(T_LAST, STEM_TK_EPILOGUE);
+        AY_PCLK_COUNT(STEM_TK_ITEMS, 1);
         if (!has_next) break;
         // tile i+1 has landed: in issue order this wave's younger operations are the DMAs of tile i+2 (if any) and the two
         // output stores of this item (none if its pixel row lies outside the image); everyone is done reading the slabs
@@ -264,14 +260,13 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
         }
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        STEM_TICK(5)
+        AY_PCLK_LAP(T_LAST, STEM_TK_TAIL);
         item = next_item;
         ib = ib + 1 == NIB ? 0 : ib + 1;
     }
-#ifdef AY_PHASE_CLOCK
-    if (wave == 0 && lane == 0)
-        for (int k = 0; k < 7; ++k) atomicAdd(&g_stem_ticks[k], tk[k]);
-#endif
+    if (AY_PCLK_ON && lane == 0)
+        AY_PCLK_FLUSH(STEM_TK_ISSUE), AY_PCLK_FLUSH(STEM_TK_STEM), AY_PCLK_FLUSH(STEM_TK_BARRIER), AY_PCLK_FLUSH(STEM_TK_LAYER1),
+            AY_PCLK_FLUSH(STEM_TK_EPILOGUE), AY_PCLK_FLUSH(STEM_TK_TAIL), AY_PCLK_FLUSH(STEM_TK_ITEMS);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -381,17 +376,10 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-#ifdef AY_PHASE_CLOCK
-    unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tk_last = wall_clock64();
-#define STEM2_TICK(w0, kk)                                   \
-    if (wave == w0) {                                        \
-        const unsigned long long t_ = wall_clock64();        \
-        tk[kk] += t_ - tk_last;                              \
-        tk_last = t_;                                        \
-    }
-#else
-#define STEM2_TICK(w0, kk)
-#endif
+    AY_PCLK_BEGIN(g_stem2_ticks, AY_DBGBIT(a, DBG_CLOCK) && (wave == 0 || wave == 8), AY_PCLK_V(STEM2_TK_P_ISSUE), AY_PCLK_V(STEM2_TK_P_STEM),
+                 AY_PCLK_V(STEM2_TK_P_WAIT), AY_PCLK_V(STEM2_TK_C_ISSUE), AY_PCLK_V(STEM2_TK_C_LAYER1), AY_PCLK_V(STEM2_TK_C_EPILOGUE),
+                 AY_PCLK_V(STEM2_TK_ITERS), AY_PCLK_V(STEM2_TK_C_WAIT), AY_PCLK_V(T_LAST));  // the first wave of either loop
+    AY_PCLK_MARK(T_LAST);
 
     // iteration k = 0 .. nk: producers compute the stem of item k into slab set k & 1 (from tile buffer k % 3), consumers run layer 1
     // of item k-1 from set (k-1) & 1; the tile of item k+2 is issued by every wave into buffer (k+2) % 3 = the one item k-1 was
@@ -449,8 +437,8 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
                 cC = coord_of(k + 2);
                 issue_image(cC, (k + 2) % NIB);
             }
-            STEM2_TICK(0, 0)
-            if (k < nk && !AY_DBGBIT(a, 16)) {
+            AY_PCLK_LAP(T_LAST, STEM2_TK_P_ISSUE);
+            if (k < nk && !AY_DBGBIT(a, DBG_NO_STEM)) {
                 const int y0 = cA.y0, x0 = cA.x0;
                 const float* img = reinterpret_cast<const float*>(lds + (k % NIB) * IMG_BYTES);
                 uint8_t* set = lds + OFF_STEM + (k & 1) * SET;
@@ -493,7 +481,7 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
                 block(1);
                 if (wave + 16 < NBLK) block(2);
             }
-            STEM2_TICK(0, 1)
+            AY_PCLK_LAP(T_LAST, STEM2_TK_P_STEM);
             // the tile of item k+1 must have landed (issued in iteration k-1 or the prologue); younger: the DMA of tile k+2 if issued
             if (issue2)
                 asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
@@ -503,10 +491,8 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
             asm volatile("" ::: "memory");
             cA = cB;
             cB = cC;
-            STEM2_TICK(0, 2)
-#ifdef AY_PHASE_CLOCK
-            if (wave == 0) ++tk[6];
-#endif
+            AY_PCLK_LAP(T_LAST, STEM2_TK_P_WAIT);
+            AY_PCLK_COUNT(STEM2_TK_ITERS, 1);
         }
     } else {
         // layer 1: 8 waves = 2 (32-channel halves) x 4 (output rows); filters [chunk][tap][half][64][8] straight from HBM into registers
@@ -527,8 +513,8 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
                 issue_image(cC, (k + 2) % NIB);
             }
             bool stored = false;
-            STEM2_TICK(8, 3)
-            if (k >= 1 && !AY_DBGBIT(a, 32)) {
+            AY_PCLK_LAP(T_LAST, STEM2_TK_C_ISSUE);
+            if (k >= 1 && !AY_DBGBIT(a, DBG_NO_LAYER1)) {
                 const uint8_t* set = lds + OFF_STEM + ((k - 1) & 1) * SET;
                 f32x16 acc1[MT][NT];
 #pragma unroll
@@ -550,13 +536,13 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
                         acc1[0][0] = DT::mfma32(wf[n * 3 + kw], fb[n & 1][kw], acc1[0][0]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                STEM2_TICK(8, 4)
+                AY_PCLK_LAP(T_LAST, STEM2_TK_C_LAYER1);
                 ResRegs<MT, NT> rr;
                 conv_epilogue<BN, MT, NT, TW, false, false, false, 2, false, false, DT>(a, acc1, rr, cP.b, 0, wm, wn, c, hh, cP.y0, cP.x0,
                                                                       reinterpret_cast<const float*>(lds + OFF_SS1));
                 stored = (cP.y0 + wn) < a.hout;
             }
-            STEM2_TICK(8, 5)
+            AY_PCLK_LAP(T_LAST, STEM2_TK_C_EPILOGUE);
             // as for the producers, plus the two output stores of this wave's item (younger than both DMAs)
             if (issue2) {
                 if (stored)
@@ -574,13 +560,12 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
             cP = cA;
             cA = cB;
             cB = cC;
-            STEM2_TICK(8, 7)
+            AY_PCLK_LAP(T_LAST, STEM2_TK_C_WAIT);
         }
     }
-#ifdef AY_PHASE_CLOCK
-    if ((wave == 0 || wave == 8) && lane == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_stem_ticks[k], tk[k]);
-#endif
+    if (AY_PCLK_ON && lane == 0)
+        AY_PCLK_FLUSH(STEM2_TK_P_ISSUE), AY_PCLK_FLUSH(STEM2_TK_P_STEM), AY_PCLK_FLUSH(STEM2_TK_P_WAIT), AY_PCLK_FLUSH(STEM2_TK_C_ISSUE),
+            AY_PCLK_FLUSH(STEM2_TK_C_LAYER1), AY_PCLK_FLUSH(STEM2_TK_C_EPILOGUE), AY_PCLK_FLUSH(STEM2_TK_ITERS), AY_PCLK_FLUSH(STEM2_TK_C_WAIT);
 }
 
 }  // namespace ay
@@ -621,20 +606,16 @@ static int stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const
     else
         hipLaunchKernelGGL(stem_s2_fused_kernel<DT>, grid, dim3(1024), 0, S(stream), s, (int)n_items);
     AY_CHECK_LAUNCH("stem_s2_fused_kernel");
-#ifdef AY_PHASE_CLOCK
-    if (conv_dbg() & 8) {
-        unsigned long long t[8] = {0}, z[8] = {0};
-        (void)hipStreamSynchronize(S(stream));
-        (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_stem_ticks), sizeof(t));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stem_ticks), z, sizeof(z));
-        if (t[6] && v2)
-            fprintf(stderr, "[ay stem v2] per iteration (us): producer issue %.2f, stem %.2f, wait %.2f | consumer issue %.2f, layer-1 %.2f, epilogue %.2f, wait %.2f\n",
-                    t[0] * 0.01 / t[6], t[1] * 0.01 / t[6], t[2] * 0.01 / t[6], t[3] * 0.01 / t[6], t[4] * 0.01 / t[6], t[5] * 0.01 / t[6], t[7] * 0.01 / t[6]);
-        else if (t[6])
-            fprintf(stderr, "[ay stem] per item (us): dma issue %.2f, stem MFMA %.2f, barrier %.2f, layer-1 MFMA %.2f, epilogue %.2f, tail wait %.2f\n",
-                    t[0] * 0.01 / t[6], t[1] * 0.01 / t[6], t[2] * 0.01 / t[6], t[3] * 0.01 / t[6], t[4] * 0.01 / t[6], t[5] * 0.01 / t[6]);
-    }
-#endif
+    unsigned long long t[STEM2_TK_COUNT];
+    if (v2 && phase_clock_read(S(stream), HIP_SYMBOL(g_stem2_ticks), t, STEM2_TK_COUNT) && t[STEM2_TK_ITERS])
+        fprintf(stderr, "[ay stem v2] per iteration (us): producer issue %.2f, stem %.2f, wait %.2f | consumer issue %.2f, layer-1 %.2f, epilogue %.2f, wait %.2f\n",
+                t[STEM2_TK_P_ISSUE] * 0.01 / t[STEM2_TK_ITERS], t[STEM2_TK_P_STEM] * 0.01 / t[STEM2_TK_ITERS], t[STEM2_TK_P_WAIT] * 0.01 / t[STEM2_TK_ITERS],
+                t[STEM2_TK_C_ISSUE] * 0.01 / t[STEM2_TK_ITERS], t[STEM2_TK_C_LAYER1] * 0.01 / t[STEM2_TK_ITERS],
+                t[STEM2_TK_C_EPILOGUE] * 0.01 / t[STEM2_TK_ITERS], t[STEM2_TK_C_WAIT] * 0.01 / t[STEM2_TK_ITERS]);
+    if (!v2 && phase_clock_read(S(stream), HIP_SYMBOL(g_stem_ticks), t, STEM_TK_COUNT) && t[STEM_TK_ITEMS])
+        fprintf(stderr, "[ay stem] per item (us): dma issue %.2f, stem MFMA %.2f, barrier %.2f, layer-1 MFMA %.2f, epilogue %.2f, tail wait %.2f\n",
+                t[STEM_TK_ISSUE] * 0.01 / t[STEM_TK_ITEMS], t[STEM_TK_STEM] * 0.01 / t[STEM_TK_ITEMS], t[STEM_TK_BARRIER] * 0.01 / t[STEM_TK_ITEMS],
+                t[STEM_TK_LAYER1] * 0.01 / t[STEM_TK_ITEMS], t[STEM_TK_EPILOGUE] * 0.01 / t[STEM_TK_ITEMS], t[STEM_TK_TAIL] * 0.01 / t[STEM_TK_ITEMS]);
     return AY_OK;
 }
 }  // namespace ay

@@ -11,11 +11,9 @@
 // dimension and the partial filters are added to dW with fp32 atomics (dW is zeroed first).
 // LDS slots are XOR-swizzled (slot = px ^ ((px>>3 & 1) << 2)), through the DMA source address, so that the two 4-row blocks
 // a 32-lane half reads land on different banks.
-#include <stdlib.h>
-
 #include <type_traits>
 
-#include "ay_common.h"
+#include "ay_conv_common.h"
 
 namespace ay {
 
@@ -31,22 +29,14 @@ struct WgradArgs {
     unsigned m_nseg, m_ho;   // floor(2^32 / nseg_x), floor(2^32 / ho) (0xffffffff for a divisor of 1): multiply-high division in the K loop
     float* slab;       // split-K partial filters [gridDim.z][dw_elems] (plain stores, summed in fixed order by wgrad_reduce_kernel);
     size_t dw_elems;   // nullptr: the partial sums are added to dw with fp32 atomics
+    int dbg;           // instrumented build only: the AY_DBG bits (ay_phase_clock.h), of which this kernel honours DBG_CLOCK
 };
 
 __device__ __forceinline__ int swz(int px) { return px ^ (((px >> 3) & 1) << 2); }
-#ifdef AY_PHASE_CLOCK
-// instrumented build only: 100 MHz ticks of wave 0 summed over workgroups: [0] stage body (reads + MFMAs + DMA issue), [1] wait for the
-// next stage's DMA, [2] barrier, [3] epilogue, [4] K steps, [5] workgroups, [6] prologue
-__device__ unsigned long long g_wgrad_ticks[8];
-#define WG_TICK(k)                                      \
-    if (wave == 0) {                                    \
-        const unsigned long long t_ = wall_clock64();   \
-        wtk[k] += t_ - wtk_last;                        \
-        wtk_last = t_;                                  \
-    }
-#else
-#define WG_TICK(k)
-#endif
+// Phase clock (ay_phase_clock.h), wave 0 of every workgroup, summed over workgroups, each interval from the previous lap: stage bodies
+// (reads + MFMAs + DMA issue), waits for the next stage's DMA, stage barriers, epilogues; number of K steps, number of workgroups
+enum WgradTick { WGRAD_TK_BODY, WGRAD_TK_DMA_WAIT, WGRAD_TK_BARRIER, WGRAD_TK_EPILOGUE, WGRAD_TK_STEPS, WGRAD_TK_WGS, WGRAD_TK_COUNT };
+AY_PHASE_TICKS(g_wgrad_ticks, WGRAD_TK_COUNT);
 
 // SEGS: row segments per K step (and per barrier).  1x1 layers have 4 MFMAs per wave and segment: one segment per step left the
 // kernel barrier-bound (173 us per launch on average at B=32 / 1024^2 against ~70 us of HBM time); they take 4 segments per step
@@ -229,9 +219,9 @@ __global__ void __launch_bounds__(512, (CO_PL * CI_PL >= 32 ? 2 : 4)) wgrad_bf16
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-#ifdef AY_PHASE_CLOCK
-    unsigned long long wtk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wtk_last = wall_clock64();
-#endif
+    AY_PCLK_BEGIN(g_wgrad_ticks, AY_DBGBIT(a, DBG_CLOCK) && wave == 0, AY_PCLK_V(WGRAD_TK_BODY), AY_PCLK_V(WGRAD_TK_DMA_WAIT), AY_PCLK_V(WGRAD_TK_BARRIER),
+                 AY_PCLK_V(WGRAD_TK_EPILOGUE), AY_PCLK_V(WGRAD_TK_STEPS), AY_PCLK_V(WGRAD_TK_WGS), AY_PCLK_V(T_LAST));
+    AY_PCLK_MARK(T_LAST);
     int cur = 0, nxt = (NBUF - 1) % NBUF;
     constexpr int NGROUP = SEGS * KK2;   // MFMA groups (one tap of one segment: COW MFMAs) per stage; the stage's PWS pieces are spread over them
     for (int k = 0; k < nstep; ++k) {
@@ -295,19 +285,17 @@ __global__ void __launch_bounds__(512, (CO_PL * CI_PL >= 32 ? 2 : 4)) wgrad_bf16
         else
             stage_body(std::integral_constant<int, 0>{});
         if (do_issue) ++issued;
-        WG_TICK(0)
+        AY_PCLK_LAP(T_LAST, WGRAD_TK_BODY);
         if (k + 1 < nstep) {
             wait_landed(issued - (k + 1) - 1);  // stages issued beyond k+1 may stay in flight
-            WG_TICK(1)
+            AY_PCLK_LAP(T_LAST, WGRAD_TK_DMA_WAIT);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            WG_TICK(2)
+            AY_PCLK_LAP(T_LAST, WGRAD_TK_BARRIER);
         }
         if (++cur == NBUF) cur = 0;
     }
-#ifdef AY_PHASE_CLOCK
-    if (wave == 0) wtk[4] += nstep, wtk[5] += 1;
-#endif
+    if (AY_PCLK_ON) AY_PCLK_ADD(WGRAD_TK_STEPS, nstep), AY_PCLK_ADD(WGRAD_TK_WGS, 1);
 
     // ---- epilogue: the workgroup's partial filters go to its split-K slab (plain contiguous stores) or, without a workspace, to
     // dW by fp32 atomics; either way coalesced.  D of one 16x16 tile: row (co) = 4*(lane>>4) + reg, col (ci) = lane & 15.
@@ -343,11 +331,10 @@ __global__ void __launch_bounds__(512, (CO_PL * CI_PL >= 32 ? 2 : 4)) wgrad_bf16
         }
         __builtin_amdgcn_wave_barrier();
     }
-#ifdef AY_PHASE_CLOCK
-    WG_TICK(3)
-    if (wave == 0 && lane == 0)
-        for (int k = 0; k < 6; ++k) atomicAdd(&g_wgrad_ticks[k], wtk[k]);
-#endif
+    AY_PCLK_LAP(T_LAST, WGRAD_TK_EPILOGUE);
+    if (AY_PCLK_ON && lane == 0)
+        AY_PCLK_FLUSH(WGRAD_TK_BODY), AY_PCLK_FLUSH(WGRAD_TK_DMA_WAIT), AY_PCLK_FLUSH(WGRAD_TK_BARRIER), AY_PCLK_FLUSH(WGRAD_TK_EPILOGUE),
+            AY_PCLK_FLUSH(WGRAD_TK_STEPS), AY_PCLK_FLUSH(WGRAD_TK_WGS);
 }
 
 // dw[i] = (accumulate ? dw[i] : 0) + sum_s slab[s][i] in a FIXED order: the same bits on every run.  Replaces ks x |dW| fp32 atomics
@@ -489,6 +476,7 @@ extern "C" int ay_conv_wgrad_bf16_ws(const ay_conv_desc* d, const void* x_blocke
     const bool slabs = workspace != nullptr && workspace_bytes >= (size_t)ks * dw_elems * sizeof(float);
     a.slab = slabs ? (float*)workspace : nullptr;
     a.dw_elems = dw_elems;
+    a.dbg = conv_dbg();
     // without a workspace the kernel ADDS its split-K partial sums to dw (fp32 atomics): accumulate = 0 starts from zero
     if (!slabs && !accumulate && hipMemsetAsync(dw_oihw, 0, sizeof(float) * dw_elems, st) != hipSuccess) {
         set_error("ay_conv_wgrad_bf16: memset failed");
@@ -513,18 +501,11 @@ extern "C" int ay_conv_wgrad_bf16_ws(const ay_conv_desc* d, const void* x_blocke
     else
         hipLaunchKernelGGL((wgrad_bf16_kernel<1, 1, WGRAD_SEGS_1X1, 3>), grid, block, 0, st, a);
     AY_CHECK_LAUNCH("wgrad_bf16_kernel");
-#ifdef AY_PHASE_CLOCK
-    if (getenv("AY_DBG") && (atoi(getenv("AY_DBG")) & 8)) {
-        unsigned long long t[8] = {0}, z[8] = {0};
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_wgrad_ticks), sizeof(t));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_ticks), z, sizeof(z));
-        if (t[4])
-            fprintf(stderr, "[ay wgrad] k%d s%d %d->%d @%d ks %lld: per K step (us): body %.2f, dma wait %.2f, barrier %.2f; per workgroup: %.0f steps, epilogue %.1f us\n",
-                    d->ksize, d->stride, d->cin, d->cout, d->hout, ks, t[0] * 0.01 / t[4], t[1] * 0.01 / t[4], t[2] * 0.01 / t[4], (double)t[4] / t[5],
-                    t[3] * 0.01 / t[5]);
-    }
-#endif
+    unsigned long long t[WGRAD_TK_COUNT];
+    if (phase_clock_read(st, HIP_SYMBOL(g_wgrad_ticks), t, WGRAD_TK_COUNT) && t[WGRAD_TK_STEPS])
+        fprintf(stderr, "[ay wgrad] k%d s%d %d->%d @%d ks %lld: per K step (us): body %.2f, dma wait %.2f, barrier %.2f; per workgroup: %.0f steps, epilogue %.1f us\n",
+                d->ksize, d->stride, d->cin, d->cout, d->hout, ks, t[WGRAD_TK_BODY] * 0.01 / t[WGRAD_TK_STEPS], t[WGRAD_TK_DMA_WAIT] * 0.01 / t[WGRAD_TK_STEPS],
+                t[WGRAD_TK_BARRIER] * 0.01 / t[WGRAD_TK_STEPS], (double)t[WGRAD_TK_STEPS] / t[WGRAD_TK_WGS], t[WGRAD_TK_EPILOGUE] * 0.01 / t[WGRAD_TK_WGS]);
     if (slabs) {
         if (dw_elems % 4) {
             hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3((unsigned)((dw_elems + 255) / 256)), dim3(256), 0, st, a.slab, dw_oihw, dw_elems, (int)ks,
