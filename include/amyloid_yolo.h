@@ -131,7 +131,8 @@ int ay_resblock_fwd_bf16(const void* x, const void* w1_packed, const float* scal
 int ay_concat_upsample_bf16(const void* src1, int c1, int up1, const void* src2, int c2, void* out,
                             int batch, int h, int w, ay_stream_t stream);
 
-/* layout converters (tests, fp32<->bf16 path bridges) */
+/* layout converters (tests, fp32<->bf16 path bridges): to blocked rounds to nearest even and writes +0 into the lanes C .. 16*ceil(C/16);
+ * from blocked never reads those lanes */
 int ay_blocked_bf16_to_nchw_f32(const void* src, float* dst, int batch, int c, int h, int w, ay_stream_t stream);
 int ay_blocked_f32_to_nchw_f32(const float* src, float* dst, int batch, int c, int h, int w, ay_stream_t stream);
 int ay_nchw_f32_to_blocked_bf16(const float* src, void* dst, int batch, int c, int h, int w, ay_stream_t stream);
@@ -158,6 +159,8 @@ int ay_resblock_fwd_f16(const void* x, const void* w1_packed, const float* scale
                         const void* w2_packed, const float* scale2, const float* shift2, int leaky2, void* out, int batch,
                         int channels, int h, int w, ay_stream_t stream);
 int ay_blocked_f16_to_nchw_f32(const void* src, float* dst, int batch, int c, int h, int w, ay_stream_t stream);
+/* Rounds to nearest even like ay_nchw_f32_to_blocked_bf16 (subnormal results included), with ONE difference from IEEE: a finite value
+ * that would round to +-inf is stored as +-65504 (every kernel that stores halves saturates); +-inf and NaN pass through. */
 int ay_nchw_f32_to_blocked_f16(const float* src, void* dst, int batch, int c, int h, int w, ay_stream_t stream);
 
 /* ---- fp32 parity path (reference layout) ------------------------------------------------------ */
@@ -252,7 +255,10 @@ int ay_nms_merge(float* pred, int batch, int n_rows, int num_classes, float conf
 
 /* Train-mode BatchNorm2d + LeakyReLU forward (models.py:43-45): batch statistics over (B,H,W), biased variance for the
  * normalisation, running stats updated with PyTorch semantics running = (1-momentum)*running + momentum*batch
- * (unbiased variance), momentum = 0.9 in the reference.  z = raw conv output, y = block output. */
+ * (unbiased variance), momentum = 0.9 in the reference.  z = raw conv output, y = block output.
+ * n = B*H*W = 1 has no unbiased variance (n / (n - 1)): running_var then receives the BIASED variance, 0 (PyTorch refuses that
+ * input in training mode).  Statistics are summed in fp64 and rounded to fp32 once (mean, invstd), so a channel mean far above
+ * its spread does not cancel; a channel of constants has invstd = 1 / sqrt(eps). */
 int ay_bn_train_fwd_f32(const float* z, const float* gamma, const float* beta, float* running_mean, float* running_var,
                         float momentum, float eps, int leaky, float* y, float* save_mean, float* save_invstd,
                         int batch, int channels, int hw, ay_stream_t stream);
