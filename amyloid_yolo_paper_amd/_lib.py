@@ -47,6 +47,11 @@ class StainParams(C.Structure):
     _fields_ = [("od", C.c_float * 256), ("D", C.c_float * 9), ("A", C.c_float * 9), ("T", C.c_float * 257)]
 
 
+class StainBasisParams(C.Structure):
+    """ay_stain_basis_params (include/amyloid_yolo.h, THE BASIS RULE): the integer optical density of every byte"""
+    _fields_ = [("odq", C.c_int32 * 256)]
+
+
 class AyError(RuntimeError):
     pass
 
@@ -172,6 +177,8 @@ _SIGS = {
     "ay_stain_hist_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _P, _P]),
     "ay_ingest_region_tiles_stain_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, C.POINTER(C.c_int), _I, _P, _I, _P, _P]),
     "ay_stain_apply_u8": (_I, [_P, _I, _I, _SZ, _I, _P, _P, _SZ, _P]),
+    "ay_stain_moments_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _P, _P, _P]),
+    "ay_stain_direction_hist_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ay_stain_load_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "ay_focus_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "ay_box_segments_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),

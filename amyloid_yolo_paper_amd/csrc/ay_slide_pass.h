@@ -1,4 +1,4 @@
-// What the slide-level passes over a resident uint8 HWC region share (ay_stain.hip, ay_load.hip, ay_focus.hip; of ay_tissue.hip the
+// What the slide-level passes over a resident uint8 HWC region share (ay_stain.hip, ay_stain_basis.hip, ay_load.hip, ay_focus.hip; of ay_tissue.hip the
 // launcher and check_region; of ay_segment.hip tissue_px, load_bin, check_region and the box edges): the 48-byte item of the read
 // stream, the work units, the launch of the four (WIDE, SHRINK) instances, the place of an item and a unit on the cell grid, the flush
 // of a workgroup's cell table, the box walk and the host checks.  Helper functions only: how a pass accumulates (int32 table, uint64

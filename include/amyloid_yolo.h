@@ -854,6 +854,68 @@ int ay_ingest_region_tiles_stain_u8(const void* region_hwc_u8, int region_h, int
 int ay_stain_apply_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink,
                       const ay_stain_params* params_device, uint8_t* out_hwc_u8, size_t out_stride_bytes, ay_stream_t stream);
 
+/* ---- stain basis estimation: each slide's own two stain vectors (wsi.estimate_basis, wsi.StainEstimate, wsi.StainMap(remix=True);
+ *      csrc/ay_stain_basis.hip) --------------------------------------------------------------------------------------------------------
+ * THE STAIN RULE unmixes on a basis that is given.  The DAB hue shifts with the chromogen batch, the counterstain and the scanner; a
+ * gain corrects a stain's strength and cannot correct its direction.  This is the producer of a basis: a Macenko-style estimate of the
+ * plane the optical densities of a slide lie in and of the two extreme directions inside it.  PARITY WITH ANY OUTSIDE
+ * STAIN-NORMALISATION PACKAGE IS UNPINNED: the behaviour is the rule below, restated in NumPy and Python integers by
+ * tests/stain_basis_reference.py.
+ *
+ * THE BASIS RULE (integers only on the device, float64 on the host; a function of the inputs alone, the same bytes on every run).
+ *   Pixels.  (b0, b1, b2) are the bytes of the (halved) image; for shrink == 2 the ingest's 2x2 round-half-up means.  TISSUE is THE
+ *     TISSUE RULE's: min(b0, b1, b2) < bg_level.
+ *   Integer optical density.  odq[v] = rint(-log10((v + 1) / 256) * 1024), built on the host in float64 (ay_stain_basis_params);
+ *     odq[255] == 0, odq[0] == 2466.  With o_c = odq[b_c], a tissue pixel is SELECTED iff min(o_0, o_1, o_2) >= beta_q, beta_q =
+ *     rint(beta * 1024): Macenko's beta, default 0.15 (beta_q = 154).
+ *   Pass 1, moments (ay_stain_moments_u8).  Output uint64 [11]: n_tissue, n_sel, S_c = sum of o_c (3 words), P_cd = sum of o_c * o_d
+ *     for c <= d (6 words, in the order 00, 01, 02, 11, 12, 22); n_tissue counts the tissue pixels, the other ten run over the selected
+ *     pixels.  The call ADDS to the output: the caller zeroes it once and the strips accumulate with no host synchronisation.  Bounds:
+ *     one pixel adds at most 2466^2 = 6 081 156 to a word, so an item of 16 pixels fits int32 (97 298 496); whatever is summed over more
+ *     than one item is 64 bits wide (a lane sees up to 128 items of a work unit).
+ *   Host, the plane (float64).  With n = n_sel the numerators n * P_cd - S_c * S_d are taken in exact (Python) integers, divided by
+ *     n * (n - 1) and given to a symmetric eigensolver (numpy.linalg.eigh).  e1 is the eigenvector of the largest eigenvalue with the
+ *     sign that makes e1_0 + e1_1 + e1_2 > 0; e2 that of the second eigenvalue with the sign that makes its component of largest
+ *     magnitude positive (the lowest index on ties).  eq1 = rint(1024 * e1), eq2 = rint(1024 * e2), int32.  n_sel < 2 or a second
+ *     eigenvalue that is not positive is an error: such a slide has no stain plane.
+ *   Pass 2, direction histogram (ay_stain_direction_hist_u8).  For every selected pixel, in int32: p1 = sum of o_c * eq1_c, p2 = sum of
+ *     o_c * eq2_c.  |eq_c| <= 1024 (the entry point refuses more) keeps |256 * p2| <= 2466 * 1024 * 3 * 256 = 1 939 341 312 < 2^31.
+ *     p1 <= 0: hist[512] += 1 (the "outside" count).  Otherwise k = floor(256 * p2 / (p1 + |p2|)) -- the floor, not C's truncation: for
+ *     p2 < 0 it is -ceil(256 * |p2| / (p1 + |p2|)) -- which lies in -256 .. 255, and hist[k + 256] += 1.  Every selected pixel:
+ *     hist[513] += 1.  Output uint64 [514], ADDED to.  d = p2 / (p1 + |p2|) is monotone in the angle atan2(p2, p1) on the half plane p1
+ *     > 0, so a percentile of the angle is a percentile of d: no division by a float and no transcendental runs on the device.
+ *   Host, the vectors (float64).  n = the sum of hist[0 .. 511].  For K_lo = max(1, ceil(alpha * n / 100)) and K_hi = max(1,
+ *     ceil((100 - alpha) * n / 100)): b the first bin whose cumulative count reaches K, d = (b - 256 + 0.5) / 256, v = (1 - |d|) * eq1 +
+ *     d * eq2, normalised.  alpha = 1 is Macenko's.  The two vectors go to stain 0 and stain 1 of a prior basis (default H_DAB) by the
+ *     pairing with the larger sum of dot products (the straight pairing on a tie).  n == 0 is an error.
+ *   Guard.  A vector further than max_angle degrees from its prior vector is replaced by the prior's and reported.  The default is half
+ *     the angle between the prior's two vectors (H_DAB: about 18.6 degrees): the two results can then neither swap nor coincide.
+ *   Limit.  The extreme on the DAB side is the alpha-th percentile of the selected pixels: on a slide whose DAB-positive share of
+ *     selected pixels is below alpha per cent it is not DAB, and the guard catches it or the caller lowers alpha.
+ *
+ * Both entry points: ay_stain_hist_u8's read stream (48-byte items, work units of 16 rows x up to 2048 items, 16-byte loads when the
+ *   base and row_stride_bytes are multiples of 16, byte loads otherwise, the same sums), the tissue test before anything else, odq in
+ *   LDS; kernel launches only -- no allocation, no memset node, no host read, no scratch.  A region without a halved image returns
+ *   AY_OK.  Refused (-1, nothing launched, nothing written): a null pointer, a bad shape or stride, shrink outside {1, 2}, bg_level
+ *   outside 0 .. 256, beta_q outside 0 .. 2466, an output that is not 8-byte aligned, |eq_c| > 1024.
+ * ay_stain_moments_u8: a lane sums an item in int32 registers and its items in 64-bit registers; a wavefront reduction, the four
+ *   wavefronts through LDS, and at most 11 64-bit integer atomics per workgroup.
+ * ay_stain_direction_hist_u8: eq1 and eq2 by value (scalar registers); per-workgroup int32 LDS bins flushed with 64-bit integer atomics
+ *   as ay_stain_hist_u8 flushes its own, with the same overflow argument. */
+#define AY_BASIS_OD_SCALE 1024
+#define AY_BASIS_OD_MAX 2466
+#define AY_BASIS_MOMENT_WORDS 11
+#define AY_BASIS_DIR_BINS 512
+#define AY_BASIS_HIST_WORDS 514
+typedef struct ay_stain_basis_params {
+    int32_t odq[256];
+} ay_stain_basis_params;
+int ay_stain_moments_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int bg_level,
+                        int beta_q, const ay_stain_basis_params* params_device, uint64_t* moments, ay_stream_t stream);
+int ay_stain_direction_hist_u8(const void* region_hwc_u8, int region_h, int region_w, size_t row_stride_bytes, int shrink, int bg_level,
+                               int beta_q, int eq1_0, int eq1_1, int eq1_2, int eq2_0, int eq2_1, int eq2_2,
+                               const ay_stain_basis_params* params_device, uint64_t* hist, ay_stream_t stream);
+
 /* ---- amyloid load: stain-positive area per map cell and per detection (wsi.stain_load, wsi.box_morphometry,
  *      wsi.quantify_region(load=True); csrc/ay_load.hip) ----------------------------------------------------------------------------------
  * The field's second read-out next to object counts: the share of tissue area that is DAB-positive, on THE BURDEN RULE's grid, and the
