@@ -15,7 +15,7 @@
 //     rounds (at most 64 pairs in LDS) and keeps the maximum of the 64-bit key (n << 32) | (0xffffffff - index), which is the largest
 //     count with ties to the lowest index; a wave shuffle and one LDS step make it the workgroup's.
 // Kernel launches only: no memset node, no allocation, no host read.
-#include "ay_common.h"
+#include "ay_box_grid.h"   // WsCarver
 
 namespace ay {
 
@@ -194,8 +194,6 @@ __global__ void __launch_bounds__(BURDEN_SELECT_THREADS) burden_select_kernel(co
     if (tid == 0) n_found[c] = found;
 }
 
-static inline size_t burden_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct BurdenWs {
     int32_t *rowsum, *fieldsum;
     size_t bytes;
@@ -206,10 +204,10 @@ static BurdenWs burden_carve(void* ws, int C, int gy, int gx, int F) {
     BurdenWs w;
     const size_t ny = gy >= F ? (size_t)(gy - F + 1) : 0, nx = gx >= F ? (size_t)(gx - F + 1) : 0;
     const size_t planes = (size_t)C + 1;
-    const size_t row_bytes = burden_align(4 * planes * (ny ? (size_t)gy * nx : 0)), field_bytes = burden_align(4 * planes * ny * nx);
-    w.rowsum = (int32_t*)ws;
-    w.fieldsum = (int32_t*)((char*)ws + row_bytes);
-    w.bytes = row_bytes + field_bytes;
+    WsCarver cv(ws);
+    w.rowsum = cv.take<int32_t>(planes * (ny ? (size_t)gy * nx : 0));
+    w.fieldsum = cv.take<int32_t>(planes * ny * nx);
+    w.bytes = cv.bytes();
     return w;
 }
 

@@ -27,6 +27,16 @@ void set_error(const char* fmt, ...);
         }                                                                          \
     } while (0)
 
+// a HIP runtime call (memset, copy, synchronise) of an entry point: its error string, or go on
+#define AY_CHECK_HIP(call, what)                                                   \
+    do {                                                                           \
+        hipError_t e_ = (call);                                                    \
+        if (e_ != hipSuccess) {                                                    \
+            ay::set_error("%s: %s", what, hipGetErrorString(e_));                  \
+            return AY_ERR_LAUNCH;                                                  \
+        }                                                                          \
+    } while (0)
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

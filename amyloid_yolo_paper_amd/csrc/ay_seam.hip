@@ -17,44 +17,28 @@
 //     different tile_id and ov(i, j) > seam_thres.  Otherwise it is kept.  Exact greedy suppression: a row whose only stronger
 //     partner was itself dropped is kept.  Rows of one tile never suppress each other (the per-tile merge-NMS has seen them).
 //
-// HOW.  The work is local (a box only meets boxes near it), so the rows are binned by the grid cell of their centre (counting
-// sort: histogram, scan, scatter) and a row searches the 3x3 cells around its own.  The cell side c comes from the data (a
-// histogram of the box sides: the smallest power of two that all but a handful of rows fit into): every row with w + 1 <= c and h + 1 <= c is "regular", and two regular rows that share a pixel
-// have centres less than c - 1 apart, hence lie in neighbouring cells.  All other rows (larger than a cell, or not finite) form the
-// OVERSIZE list, the last segment of the sorted array: a regular row tests it in full, an oversize row tests every row.  The
-// result therefore equals the rule for every input, whatever the box sizes.
+// HOW.  The work is local (a box only meets boxes near it), so the rows are binned by ay_box_grid.h (the grid cell of a row's
+// centre, a cell side c chosen from the data) and a row searches the 3x3 cells around its own.  A row is REGULAR iff w + 1 <= c
+// and h + 1 <= c (w = x2 - x1 + 1, likewise h) and x1, y1 are finite: two regular rows that share a pixel have centres less than
+// c - 1 apart, hence lie in neighbouring cells.  All other rows (larger than a cell, or not finite) form the OVERSIZE list, the
+// last segment of the sorted array: a regular row tests it in full, an oversize row tests every row.  The result therefore equals
+// the rule for every input, whatever the box sizes and whatever the cell side.
 // The greedy order is resolved in parallel over three states undecided / kept / dropped: a row is dropped as soon as one of its
 // potential suppressors (earlier rank, same class, other tile, ov > thres) is kept, kept once all of them are dropped (or there
 // are none).  The undecided row of best rank can always be decided, so every round makes progress and the loop ends after at
 // most M rounds; the number of rounds is the longest dependency chain and is NOT capped.  A row's final state is a function of
 // the input alone (the unique fixed point of the rule), so nothing in the result depends on the order in which threads run,
 // on the order of the rows inside a cell (the scatter's cursor is an integer atomic) or on how many rounds a launch resolves.
-#include <math.h>
-#include <string.h>
-
-#include "ay_box.h"
-#include "ay_common.h"
+#include "ay_box_grid.h"
 
 namespace ay {
 
 enum { SEAM_UNDECIDED = 0, SEAM_KEPT = 1, SEAM_DROPPED = 2 };
-constexpr int SEAM_STATS_BLOCKS = 256;   // per-block partials of the geometry reduction (finished on the host)
-constexpr int SEAM_SIDE_BINS = 32;
-constexpr int SEAM_STATS_WORDS = 4 + SEAM_SIDE_BINS;
 constexpr int SEAM_TRIES = 4;            // attempts of an undecided row inside one round launch
 constexpr int SEAM_ROUNDS_PER_SYNC = 8;  // round launches between two reads of the "rows undecided" counter
 
 // ---- append ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int seam_clamp_count(int c, int max_det) { return c < 0 ? 0 : (c > max_det ? max_det : c); }
-
-__device__ __forceinline__ int seam_block_sum(int v, int* red /* [4] */) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // one workgroup per image: the image's slot range starts at slide_count[0] + the ordered prefix over the (clamped) counts of the
 // images before it, so rows land in tile order and, within a tile, in NMS output order
@@ -67,7 +51,7 @@ __global__ void __launch_bounds__(256) seam_append_kernel(const float* __restric
     const int b = blockIdx.x;
     int part = 0;
     for (int k = threadIdx.x; k < b; k += 256) part += seam_clamp_count(count[k], max_det);
-    const long long base = (long long)slide_count[0] + seam_block_sum(part, red);
+    const long long base = (long long)slide_count[0] + block_sum_256(part, red);
     const int n = seam_clamp_count(count[b], max_det);
     const float ox = origins_xy[2 * b], oy = origins_xy[2 * b + 1];
     const int32_t id = tile_ids[b];
@@ -96,8 +80,8 @@ __global__ void __launch_bounds__(256) seam_append_commit_kernel(const int32_t* 
         part += seam_clamp_count(count[k], max_det);
         over += count[k] > max_det;
     }
-    const int total = seam_block_sum(part, red);
-    const int any_over = seam_block_sum(over, red);
+    const int total = block_sum_256(part, red);
+    const int any_over = block_sum_256(over, red);
     if (threadIdx.x == 0) {
         const long long want = (long long)slide_count[0] + total;
         int flags = slide_count[1];
@@ -109,89 +93,27 @@ __global__ void __launch_bounds__(256) seam_append_commit_kernel(const int32_t* 
 }
 
 // ---- merge -------------------------------------------------------------------------------------------------------------------
-struct SeamGrid {
-    float x0, y0, c;
-    int gx, gy;
+// the rows as the centre grid sees them (ay_box_grid.h): all of them, sides with the +1 pixel convention
+struct SeamRows {
+    const float* __restrict__ rows;
+    __device__ __forceinline__ float4 box(int i) const {
+        const float* r = rows + (size_t)i * 7;
+        return make_float4(r[0], r[1], r[2], r[3]);
+    }
+    __device__ __forceinline__ bool live(const float4) const { return true; }
+    static __device__ __forceinline__ float extent(float lo, float hi) { return hi - lo + 1.0f; }
+    static __device__ __forceinline__ float side(float w, float h) { return fmaxf(fmaxf(w, h), 0.0f) + 1.0f; }
+    static __device__ __forceinline__ bool regular(const float4 b, float c) {
+        const float w = b.z - b.x + 1.0f, h = b.w - b.y + 1.0f;
+        return w + 1.0f <= c && h + 1.0f <= c && finite_f(b.x) && finite_f(b.y);
+    }
 };
 
-// per-block partials: min / max of the box centres (4 floats) and a histogram of the box sides (SEAM_SIDE_BINS ints; bin k counts
-// the rows with 2^(k-1) < max(w, h) + 1 <= 2^k), over the rows whose coordinates are finite.  Integer counts and min / max: the
-// partials are the same bytes in every run.
-__global__ void __launch_bounds__(256) seam_stats_kernel(const float* __restrict__ rows, int M, float* __restrict__ partials) {
-    __shared__ float sh[256];
-    __shared__ int hist[SEAM_SIDE_BINS];
-    if (threadIdx.x < SEAM_SIDE_BINS) hist[threadIdx.x] = 0;
-    __syncthreads();
-    float mnx = 3.0e38f, mxx = -3.0e38f, mny = 3.0e38f, mxy = -3.0e38f;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += SEAM_STATS_BLOCKS * 256) {
-        const float* r = rows + (size_t)i * 7;
-        const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
-        const float w = x2 - x1 + 1.0f, h = y2 - y1 + 1.0f;
-        if (!(finite_f(x1) && finite_f(y1) && finite_f(x2) && finite_f(y2) && finite_f(w) && finite_f(h))) continue;
-        const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
-        mnx = fminf(mnx, cx), mxx = fmaxf(mxx, cx), mny = fminf(mny, cy), mxy = fmaxf(mxy, cy);
-        const int bits = __float_as_int(fmaxf(fmaxf(w, h), 0.0f) + 1.0f);   // >= 1: exponent >= 0
-        const int bin = ((bits >> 23) & 255) - 127 + ((bits & 0x7fffff) != 0);  // ceil(log2(side + 1))
-        atomicAdd(&hist[min(bin, SEAM_SIDE_BINS - 1)], 1);
-    }
-    float v[4] = {mnx, mxx, mny, mxy};
-    for (int q = 0; q < 4; ++q) {
-        __syncthreads();
-        sh[threadIdx.x] = v[q];
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) {
-                const float a = sh[threadIdx.x], b = sh[threadIdx.x + o];
-                sh[threadIdx.x] = (q & 1) ? fmaxf(a, b) : fminf(a, b);
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partials[blockIdx.x * SEAM_STATS_WORDS + q] = sh[0];
-    }
-    if (threadIdx.x < SEAM_SIDE_BINS) partials[blockIdx.x * SEAM_STATS_WORDS + 4 + threadIdx.x] = __int_as_float(hist[threadIdx.x]);
-}
-
-// cell of a row: the grid cell of its centre (clamped into the grid), or n_cells for the oversize list
-__device__ __forceinline__ int seam_cell(const float* r, const SeamGrid g) {
-    const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
-    const float w = x2 - x1 + 1.0f, h = y2 - y1 + 1.0f;
-    if (!(w + 1.0f <= g.c) || !(h + 1.0f <= g.c) || !finite_f(x1) || !finite_f(y1)) return g.gx * g.gy;
-    const float fx = floorf(((x1 + x2) * 0.5f - g.x0) / g.c), fy = floorf(((y1 + y2) * 0.5f - g.y0) / g.c);
-    const int ix = (int)fminf(fmaxf(fx, 0.0f), (float)(g.gx - 1)), iy = (int)fminf(fmaxf(fy, 0.0f), (float)(g.gy - 1));
-    return iy * g.gx + ix;
-}
-
-__global__ void __launch_bounds__(256) seam_bin_count_kernel(const float* __restrict__ rows, int M, SeamGrid g, int32_t* __restrict__ cell_of,
+__global__ void __launch_bounds__(256) seam_bin_count_kernel(SeamRows items, int M, BoxGrid g, int32_t* __restrict__ cell_of,
                                                               int32_t* __restrict__ cell_start) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M) return;
-    const int c = seam_cell(rows + (size_t)i * 7, g);
-    cell_of[i] = c;
-    atomicAdd(&cell_start[c], 1);
-}
-
-// exclusive scan of a[0 .. n) in place, a[n] = total; one workgroup, a contiguous chunk per thread
-__global__ void __launch_bounds__(1024) seam_scan_kernel(int32_t* __restrict__ a, int n) {
-    __shared__ int sums[1024];
-    const int chunk = (n + 1023) / 1024;
-    const int lo = min(threadIdx.x * chunk, n), hi = min(lo + chunk, n);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {   // Hillis-Steele inclusive scan of the 1024 chunk sums
-        const int v = threadIdx.x >= o ? sums[threadIdx.x - o] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = sums[threadIdx.x] - s;
-    for (int i = lo; i < hi; ++i) {
-        const int v = a[i];
-        a[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 1023) a[n] = sums[1023];
+    grid_count(i, grid_cell<SeamRows>(items.box(i), g), cell_of, cell_start);
 }
 
 // sorted records: box (x1, y1, x2, y2) and meta (score bits, cls bits, tile id, original row)
@@ -202,7 +124,7 @@ __global__ void __launch_bounds__(256) seam_scatter_kernel(const float* __restri
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M) return;
     const int c = cell_of[i];
-    const int p = cell_start[c] + atomicAdd(&cursor[c], 1);
+    const int p = grid_slot(c, cell_start, cursor);
     const float* r = rows + (size_t)i * 7;
     box[p] = make_float4(r[0], r[1], r[2], r[3]);
     const float score = r[4] * r[5];
@@ -240,7 +162,7 @@ __device__ __forceinline__ int seam_scan_range(int lo, int hi, int p, const floa
 }
 
 // one round: every undecided row (thread p = its position in the cell-sorted order) looks its potential suppressors up again
-__global__ void __launch_bounds__(256) seam_round_kernel(int M, SeamGrid g, float thres, const float4* __restrict__ box,
+__global__ void __launch_bounds__(256) seam_round_kernel(int M, BoxGrid g, float thres, const float4* __restrict__ box,
                                                           const int4* __restrict__ meta, const int32_t* __restrict__ sorted_cell,
                                                           const int32_t* __restrict__ cell_start, int32_t* state,
                                                           int32_t* __restrict__ undecided /* nullable */) {
@@ -251,7 +173,7 @@ __global__ void __launch_bounds__(256) seam_round_kernel(int M, SeamGrid g, floa
         const float4 bp = box[p];
         const int4 mp = meta[p];
         const float area_p = (bp.z - bp.x + 1.0f) * (bp.w - bp.y + 1.0f);
-        const int n_cells = g.gx * g.gy, c = sorted_cell[p];
+        const int n_cells = g.n_cells(), c = sorted_cell[p];
         const int over_lo = cell_start[n_cells];
         for (int t = 0; t < SEAM_TRIES && open; ++t) {
             int res = 1;
@@ -291,14 +213,11 @@ __global__ void __launch_bounds__(256) seam_finish_kernel(int M, const int4* __r
         k = state[p] == SEAM_KEPT;
         keep[meta[p].w] = (uint8_t)k;
     }
-    const int total = seam_block_sum(k, red);
+    const int total = block_sum_256(k, red);
     if (threadIdx.x == 0 && total) atomicAdd(&stats[0], total);   // one atomic per workgroup
 }
 
 __global__ void seam_set_rounds_kernel(int32_t* stats, int rounds) { stats[1] = rounds; }
-
-static inline size_t seam_align(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline size_t seam_cell_cap(int n_rows) { return (size_t)(n_rows > 2048 ? n_rows : 2048) * 2; }
 
 struct SeamWs {
     int32_t* undecided;
@@ -311,68 +230,19 @@ struct SeamWs {
 
 static SeamWs seam_carve(void* ws, int n_rows) {
     SeamWs w;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += seam_align(bytes);
-        return p;
-    };
-    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), cells = seam_cell_cap(n_rows);
-    w.undecided = (int32_t*)take(256);
-    w.partials = (float*)take(sizeof(float) * SEAM_STATS_BLOCKS * SEAM_STATS_WORDS);
-    w.box = (float4*)take(sizeof(float4) * n);
-    w.meta = (int4*)take(sizeof(int4) * n);
-    w.cell_of = (int32_t*)take(4 * n);
-    w.sorted_cell = (int32_t*)take(4 * n);
-    w.state = (int32_t*)take(4 * n);
-    w.cell_start = (int32_t*)take(4 * (cells + 2));
-    w.cursor = (int32_t*)take(4 * (cells + 2));
-    w.bytes = off;
+    WsCarver cv(ws);
+    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), cells = grid_cell_cap(n_rows);
+    w.undecided = cv.take<int32_t>(1);
+    w.partials = cv.take<float>(GRID_STATS_BLOCKS * GRID_STATS_WORDS);
+    w.box = cv.take<float4>(n);
+    w.meta = cv.take<int4>(n);
+    w.cell_of = cv.take<int32_t>(n);
+    w.sorted_cell = cv.take<int32_t>(n);
+    w.state = cv.take<int32_t>(n);
+    w.cell_start = cv.take<int32_t>(cells + 2);
+    w.cursor = cv.take<int32_t>(cells + 2);
+    w.bytes = cv.bytes();
     return w;
-}
-
-#define AY_SEAM_HIP(call, what)                                             \
-    do {                                                                    \
-        hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) {                                             \
-            ay::set_error("%s: %s", what, hipGetErrorString(e_));           \
-            return AY_ERR_LAUNCH;                                           \
-        }                                                                   \
-    } while (0)
-
-// cell side and grid from the reduction's partials.  Any cell side gives the right result; the choice is about work.  The cell
-// side is the smallest power of two (>= 8) that leaves at most max(16, M / 4096) rows larger than a cell: a handful of outliers
-// (a box as large as a tile) must not blow the cells up for everyone, and the oversize list, which every row tests in full, stays
-// a vanishing share of the rows.  (An estimate of pair tests, 9 c^2 M / area per regular row + the oversize list, minimised over
-// c, was measured against this rule on a slide with a heavy tail of large boxes: 61 ms against 31 ms of round kernels.)
-static SeamGrid seam_choose_grid(const float* partials, int M, size_t cell_cap) {
-    double mnx = 3.0e38, mxx = -3.0e38, mny = 3.0e38, mxy = -3.0e38;
-    long long hist[SEAM_SIDE_BINS] = {0}, cnt = 0;
-    for (int b = 0; b < SEAM_STATS_BLOCKS; ++b) {
-        const float* v = partials + b * SEAM_STATS_WORDS;
-        mnx = fmin(mnx, v[0]), mxx = fmax(mxx, v[1]), mny = fmin(mny, v[2]), mxy = fmax(mxy, v[3]);
-        for (int k = 0; k < SEAM_SIDE_BINS; ++k) {
-            int32_t n;
-            memcpy(&n, v + 4 + k, sizeof(n));
-            hist[k] += n, cnt += n;
-        }
-    }
-    SeamGrid g = {0.0f, 0.0f, 8.0f, 1, 1};
-    if (cnt < 1) return g;   // no finite row: everything goes to the oversize list
-    const long long allowed = M / 4096 > 16 ? M / 4096 : 16;
-    int bin = SEAM_SIDE_BINS - 2;   // (the last bin is open-ended: never taken for "fits")
-    long long above = hist[SEAM_SIDE_BINS - 1] + ((long long)M - cnt);   // rows that are not finite are oversize whatever the cell
-    while (bin > 3 && above + hist[bin] <= allowed) above += hist[bin--];
-    double c = ldexp(1.0, bin);
-    for (;;) {
-        const double nx = floor((mxx - mnx) / c) + 1.0, ny = floor((mxy - mny) / c) + 1.0;
-        if (nx * ny <= (double)cell_cap) {
-            g.x0 = (float)mnx, g.y0 = (float)mny, g.c = (float)c, g.gx = (int)nx, g.gy = (int)ny;
-            return g;
-        }
-        c *= 2.0;
-    }
 }
 
 }  // namespace ay
@@ -399,7 +269,7 @@ extern "C" int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile,
     AY_CHECK_ARG(n_rows >= 0 && n_rows <= (1 << 28), "ay_seam_merge: n_rows %d", n_rows);
     AY_CHECK_ARG(stats, "ay_seam_merge: null stats");
     hipStream_t st = S(stream);
-    AY_SEAM_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(int32_t), st), "ay_seam_merge: memset");
+    AY_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(int32_t), st), "ay_seam_merge: memset");
     if (n_rows == 0) return AY_OK;
     AY_CHECK_ARG(slide_rows && slide_tile && keep && workspace, "ay_seam_merge: null");
     const SeamWs w = seam_carve(workspace, n_rows);
@@ -409,21 +279,22 @@ extern "C" int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile,
     const unsigned blocks = (unsigned)((M + 255) / 256);
 
     // 1. geometry reduction -> cell side and grid (host)
-    hipLaunchKernelGGL(seam_stats_kernel, dim3(SEAM_STATS_BLOCKS), dim3(256), 0, st, slide_rows, M, w.partials);
-    AY_CHECK_LAUNCH("seam_stats_kernel");
-    float partials[SEAM_STATS_BLOCKS * SEAM_STATS_WORDS];
-    AY_SEAM_HIP(hipMemcpyAsync(partials, w.partials, sizeof(partials), hipMemcpyDeviceToHost, st), "ay_seam_merge: copy");
-    AY_SEAM_HIP(hipStreamSynchronize(st), "ay_seam_merge: sync");
-    const SeamGrid g = seam_choose_grid(partials, M, seam_cell_cap(M));
-    const int n_cells = g.gx * g.gy;
+    const SeamRows items = {slide_rows};
+    hipLaunchKernelGGL(grid_stats_kernel<SeamRows>, dim3(GRID_STATS_BLOCKS), dim3(256), 0, st, items, M, w.partials);
+    AY_CHECK_LAUNCH("grid_stats_kernel");
+    float partials[GRID_STATS_BLOCKS * GRID_STATS_WORDS];
+    AY_CHECK_HIP(hipMemcpyAsync(partials, w.partials, sizeof(partials), hipMemcpyDeviceToHost, st), "ay_seam_merge: copy");
+    AY_CHECK_HIP(hipStreamSynchronize(st), "ay_seam_merge: sync");
+    const BoxGrid g = grid_choose(partials, M, /* rows that are not finite are oversize whatever the cell */ true, grid_cell_cap(M), 0.0f);
+    const int n_cells = g.n_cells();
 
     // 2. counting sort by cell (the oversize list is cell n_cells)
-    AY_SEAM_HIP(hipMemsetAsync(w.cell_start, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_seam_merge: memset");
-    AY_SEAM_HIP(hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_seam_merge: memset");
-    hipLaunchKernelGGL(seam_bin_count_kernel, dim3(blocks), dim3(256), 0, st, slide_rows, M, g, w.cell_of, w.cell_start);
+    AY_CHECK_HIP(hipMemsetAsync(w.cell_start, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_seam_merge: memset");
+    AY_CHECK_HIP(hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_seam_merge: memset");
+    hipLaunchKernelGGL(seam_bin_count_kernel, dim3(blocks), dim3(256), 0, st, items, M, g, w.cell_of, w.cell_start);
     AY_CHECK_LAUNCH("seam_bin_count_kernel");
-    hipLaunchKernelGGL(seam_scan_kernel, dim3(1), dim3(1024), 0, st, w.cell_start, n_cells + 1);
-    AY_CHECK_LAUNCH("seam_scan_kernel");
+    hipLaunchKernelGGL(grid_scan_kernel, dim3(1), dim3(1024), 0, st, w.cell_start, n_cells + 1);
+    AY_CHECK_LAUNCH("grid_scan_kernel");
     hipLaunchKernelGGL(seam_scatter_kernel, dim3(blocks), dim3(256), 0, st, slide_rows, slide_tile, M, (const int32_t*)w.cell_of,
                        (const int32_t*)w.cell_start, w.cursor, w.box, w.meta, w.sorted_cell, w.state);
     AY_CHECK_LAUNCH("seam_scatter_kernel");
@@ -431,7 +302,7 @@ extern "C" int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile,
     // 3. rounds until no row is undecided (no cap: the longest dependency chain decides)
     int rounds = 0;
     for (;;) {
-        AY_SEAM_HIP(hipMemsetAsync(w.undecided, 0, sizeof(int32_t), st), "ay_seam_merge: memset");
+        AY_CHECK_HIP(hipMemsetAsync(w.undecided, 0, sizeof(int32_t), st), "ay_seam_merge: memset");
         for (int r = 0; r < SEAM_ROUNDS_PER_SYNC; ++r, ++rounds) {
             hipLaunchKernelGGL(seam_round_kernel, dim3(blocks), dim3(256), 0, st, M, g, seam_thres, (const float4*)w.box,
                                (const int4*)w.meta, (const int32_t*)w.sorted_cell, (const int32_t*)w.cell_start, w.state,
@@ -439,8 +310,8 @@ extern "C" int ay_seam_merge(const float* slide_rows, const int32_t* slide_tile,
             AY_CHECK_LAUNCH("seam_round_kernel");
         }
         int32_t left = 0;
-        AY_SEAM_HIP(hipMemcpyAsync(&left, w.undecided, sizeof(left), hipMemcpyDeviceToHost, st), "ay_seam_merge: copy");
-        AY_SEAM_HIP(hipStreamSynchronize(st), "ay_seam_merge: sync");
+        AY_CHECK_HIP(hipMemcpyAsync(&left, w.undecided, sizeof(left), hipMemcpyDeviceToHost, st), "ay_seam_merge: copy");
+        AY_CHECK_HIP(hipStreamSynchronize(st), "ay_seam_merge: sync");
         if (left == 0) break;
     }
 

@@ -7,16 +7,16 @@
 //
 // HOW.  The walk only looks sequential.  A row's candidate is its own first-maximum IoU target whatever earlier rows did; rows are
 // coupled only through which of them reaches a target first.  So the rule is an argmax per row and a minimum per target:
-//   1. the non-ignored targets are binned by the grid cell of their centre (counting sort: histogram, one-workgroup scan, scatter;
-//      the original index travels with the box, the tie-break needs it).  A target with x2 - x1 or y2 - y1 above c - 2 (c = the cell
-//      side), or with a coordinate that is not finite, goes to the OVERSIZE list behind the last cell.
+//   1. the non-ignored targets are binned by ay_box_grid.h (the grid cell of a target's centre; the original index travels with the
+//      box, the tie-break needs it).  A target is REGULAR iff x2 - x1 <= c - 2 and y2 - y1 <= c - 2 (c = the cell side) and its four
+//      coordinates are finite; the others go to the OVERSIZE list behind the last cell.
 //   2. one lane per row scans the cells that can hold the centre of a regular target sharing a pixel with the row, plus the oversize
 //      list, and keeps the maximum by (IoU descending, original index ascending): torch's first maximum.  A target shares a pixel
 //      with the row only if tx2 > rx1 - 1 and tx1 < rx2 + 1; with a width of at most c - 2 its centre then lies inside
 //      (rx1 - c / 2, rx2 + c / 2).  The scanned interval is wider by a slack of 2 px + 2^-20 of the magnitudes involved, which
-//      covers every fp32 rounding on the way, and the row's cell bounds go through the same expression floor((v - x0) / c) as the
-//      target's cell -- every step of it is monotone in v, so a centre inside the interval cannot land in a cell outside the range.
-//      Both are clamped into the grid the same way.  A row whose range exceeds SLIDE_WIDE_CELLS cells (a box over half the slide) is
+//      covers every fp32 rounding on the way, and the row's cell bounds go through the same expression as the target's cell
+//      (grid_cell_coord) -- every step of it is monotone in v, so a centre inside the interval cannot land in a cell outside the
+//      range.  Both are clamped into the grid the same way.  A row whose range exceeds SLIDE_WIDE_CELLS cells (a box over half the slide) is
 //      scanned by its whole wavefront instead of one lane.
 //      Whatever the cell side, the cells scanned hold every target with a positive IoU, so the result does not depend on it.
 //   3. an eligible row takes part in claim_key[k][best_target] = min over ((0xFFFFFFFF - score bits) << 32 | row index): one 64-bit
@@ -24,23 +24,12 @@
 //      order like the values).
 //   4. a last kernel turns the keys into claim / tp and counts.
 // Integer atomics and min / max only: the same bytes on every run, whatever order the threads or the scatter's cursor take.
-#include <math.h>
-#include <string.h>
-
-#include "ay_box.h"
-#include "ay_common.h"
+#include "ay_box_grid.h"
 
 namespace ay {
 
-constexpr int SLIDE_STATS_BLOCKS = 256;   // per-block partials of the geometry reduction (finished on the host)
-constexpr int SLIDE_SIDE_BINS = 32;
-constexpr int SLIDE_STATS_WORDS = 4 + SLIDE_SIDE_BINS;
 constexpr int SLIDE_WIDE_CELLS = 32;      // a row whose cell range is larger is scanned by its wavefront
 
-struct SlideGrid {
-    float x0, y0, c;
-    int gx, gy;
-};
 struct SlideRoi {
     int on;
     float x1, y1, x2, y2;
@@ -69,49 +58,25 @@ __device__ __forceinline__ int slide_class(float v) {
     return (float)c == v ? c : -1;
 }
 
-// cell index of a cell coordinate, clamped into 0 .. n - 1.  The last step is on integers: (float)(n - 1) rounds up to n for some
-// n above 2^24, and an index n would be the first cell of the next grid row.
-__device__ __forceinline__ int slide_clamp_cell(float f, int n) { return min((int)fminf(fmaxf(f, 0.0f), (float)(n - 1)), n - 1); }
-
-// per-block partials over the non-ignored targets with finite coordinates: min / max of the centres (4 floats) and a histogram of
-// the sides (bin k counts the targets with 2^(k-1) < max(x2 - x1, y2 - y1, 0) + 2 <= 2^k)
-__global__ void __launch_bounds__(256) slide_stats_kernel(const float* __restrict__ targets, int T, SlideRoi roi, float* __restrict__ partials) {
-    __shared__ float sh[256];
-    __shared__ int hist[SLIDE_SIDE_BINS];
-    if (threadIdx.x < SLIDE_SIDE_BINS) hist[threadIdx.x] = 0;
-    __syncthreads();
-    float mnx = 3.0e38f, mxx = -3.0e38f, mny = 3.0e38f, mxy = -3.0e38f;
-    for (int t = blockIdx.x * 256 + threadIdx.x; t < T; t += SLIDE_STATS_BLOCKS * 256) {
+// the targets as the centre grid sees them (ay_box_grid.h): the non-ignored ones, plain sides and 2 px of room in a cell
+struct SlideTargets {
+    const float* __restrict__ targets;
+    SlideRoi roi;
+    __device__ __forceinline__ float4 box(int t) const {
         const float* r = targets + (size_t)t * 5;
-        const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
-        const float w = x2 - x1, h = y2 - y1;
-        if (slide_ignored(roi, x1, y1, x2, y2)) continue;
-        if (!(finite_f(x1) && finite_f(y1) && finite_f(x2) && finite_f(y2) && finite_f(w) && finite_f(h))) continue;
-        const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
-        mnx = fminf(mnx, cx), mxx = fmaxf(mxx, cx), mny = fminf(mny, cy), mxy = fmaxf(mxy, cy);
-        const int bits = __float_as_int(fmaxf(fmaxf(w, h), 0.0f) + 2.0f);     // >= 2: exponent >= 1
-        const int bin = ((bits >> 23) & 255) - 127 + ((bits & 0x7fffff) != 0);  // ceil(log2(side + 2))
-        atomicAdd(&hist[min(bin, SLIDE_SIDE_BINS - 1)], 1);
+        return make_float4(r[1], r[2], r[3], r[4]);
     }
-    float v[4] = {mnx, mxx, mny, mxy};
-    for (int q = 0; q < 4; ++q) {
-        __syncthreads();
-        sh[threadIdx.x] = v[q];
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) {
-                const float a = sh[threadIdx.x], b = sh[threadIdx.x + o];
-                sh[threadIdx.x] = (q & 1) ? fmaxf(a, b) : fminf(a, b);
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partials[blockIdx.x * SLIDE_STATS_WORDS + q] = sh[0];
+    __device__ __forceinline__ bool live(const float4 b) const { return !slide_ignored(roi, b.x, b.y, b.z, b.w); }
+    static __device__ __forceinline__ float extent(float lo, float hi) { return hi - lo; }
+    static __device__ __forceinline__ float side(float w, float h) { return fmaxf(fmaxf(w, h), 0.0f) + 2.0f; }
+    static __device__ __forceinline__ bool regular(const float4 b, float c) {
+        const float w = b.z - b.x, h = b.w - b.y;
+        return w <= c - 2.0f && h <= c - 2.0f && finite_f(b.x) && finite_f(b.y) && finite_f(b.z) && finite_f(b.w);
     }
-    if (threadIdx.x < SLIDE_SIDE_BINS) partials[blockIdx.x * SLIDE_STATS_WORDS + 4 + threadIdx.x] = __int_as_float(hist[threadIdx.x]);
-}
+};
 
 // per target: the ignored flag, its cell (-1 = ignored, n_cells = oversize), the cell histogram and the class-presence flag
-__global__ void __launch_bounds__(256) slide_bin_count_kernel(const float* __restrict__ targets, int T, SlideRoi roi, SlideGrid g,
+__global__ void __launch_bounds__(256) slide_bin_count_kernel(const float* __restrict__ targets, int T, SlideRoi roi, BoxGrid g,
                                                                uint8_t* __restrict__ target_ignored, int32_t* __restrict__ cell_of,
                                                                int32_t* __restrict__ cell_start, int32_t* __restrict__ class_flags,
                                                                int32_t* __restrict__ flags_out) {
@@ -142,38 +107,7 @@ __global__ void __launch_bounds__(256) slide_bin_count_kernel(const float* __res
         return;
     }
     if (cls < 0) atomicOr(flags_out, AY_SLIDE_FLAG_CLASS);
-    int c = g.gx * g.gy;
-    const float w = x2 - x1, h = y2 - y1;
-    if (w <= g.c - 2.0f && h <= g.c - 2.0f && finite_f(x1) && finite_f(y1) && finite_f(x2) && finite_f(y2)) {
-        const float fx = floorf(((x1 + x2) * 0.5f - g.x0) / g.c), fy = floorf(((y1 + y2) * 0.5f - g.y0) / g.c);
-        c = slide_clamp_cell(fy, g.gy) * g.gx + slide_clamp_cell(fx, g.gx);
-    }
-    cell_of[t] = c;
-    atomicAdd(&cell_start[c], 1);
-}
-
-// exclusive scan of a[0 .. n) in place, a[n] = total; one workgroup, a contiguous chunk per thread
-__global__ void __launch_bounds__(1024) slide_scan_kernel(int32_t* __restrict__ a, int n) {
-    __shared__ int sums[1024];
-    const int chunk = (n + 1023) / 1024;
-    const int lo = min(threadIdx.x * chunk, n), hi = min(lo + chunk, n);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {   // Hillis-Steele inclusive scan of the 1024 chunk sums
-        const int v = threadIdx.x >= o ? sums[threadIdx.x - o] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = sums[threadIdx.x] - s;
-    for (int i = lo; i < hi; ++i) {
-        const int v = a[i];
-        a[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 1023) a[n] = sums[1023];
+    grid_count(t, grid_cell<SlideTargets>(make_float4(x1, y1, x2, y2), g), cell_of, cell_start);
 }
 
 __global__ void __launch_bounds__(256) slide_scatter_kernel(const float* __restrict__ targets, int T, const int32_t* __restrict__ cell_of,
@@ -183,7 +117,7 @@ __global__ void __launch_bounds__(256) slide_scatter_kernel(const float* __restr
     if (t >= T) return;
     const int c = cell_of[t];
     if (c < 0) return;
-    const int p = cell_start[c] + atomicAdd(&cursor[c], 1);
+    const int p = grid_slot(c, cell_start, cursor);
     const float* r = targets + (size_t)t * 5;
     box[p] = make_float4(r[1], r[2], r[3], r[4]);
     orig[p] = t;
@@ -203,7 +137,7 @@ __device__ __forceinline__ void slide_scan_range(int lo, int hi, int stride, flo
 }
 
 // one lane per row: best target, eligibility per threshold, claim keys
-__global__ void __launch_bounds__(256) slide_match_kernel(const float* __restrict__ rows, int M, int T, SlideRoi roi, SlideGrid g, SlideThres thr,
+__global__ void __launch_bounds__(256) slide_match_kernel(const float* __restrict__ rows, int M, int T, SlideRoi roi, BoxGrid g, SlideThres thr,
                                                            const float4* __restrict__ box, const int32_t* __restrict__ orig,
                                                            const int32_t* __restrict__ cell_start, const int32_t* __restrict__ class_flags,
                                                            float* __restrict__ best_iou, int32_t* __restrict__ best_target,
@@ -218,15 +152,15 @@ __global__ void __launch_bounds__(256) slide_match_kernel(const float* __restric
     }
     const bool ign = in && slide_ignored(roi, x1, y1, x2, y2);
     const bool live = in && !ign;
-    const int n_cells = g.gx * g.gy;
+    const int n_cells = g.n_cells();
     const int over_lo = cell_start[n_cells], over_hi = cell_start[n_cells + 1];
     // cells whose regular targets can share a pixel with the row (see the head of the file)
     const float sx = 2.0f + (fabsf(x1) + fabsf(x2) + fabsf(g.x0) + g.c) * 0x1p-20f;
     const float sy = 2.0f + (fabsf(y1) + fabsf(y2) + fabsf(g.y0) + g.c) * 0x1p-20f;
-    const int xa = slide_clamp_cell(floorf((x1 - 0.5f * g.c - sx - g.x0) / g.c), g.gx);
-    const int xb = slide_clamp_cell(floorf((x2 + 0.5f * g.c + sx - g.x0) / g.c), g.gx);
-    const int ya = slide_clamp_cell(floorf((y1 - 0.5f * g.c - sy - g.y0) / g.c), g.gy);
-    const int yb = slide_clamp_cell(floorf((y2 + 0.5f * g.c + sy - g.y0) / g.c), g.gy);
+    const int xa = grid_cell_coord(x1 - 0.5f * g.c - sx, g.x0, g.c, g.gx);
+    const int xb = grid_cell_coord(x2 + 0.5f * g.c + sx, g.x0, g.c, g.gx);
+    const int ya = grid_cell_coord(y1 - 0.5f * g.c - sy, g.y0, g.c, g.gy);
+    const int yb = grid_cell_coord(y2 + 0.5f * g.c + sy, g.y0, g.c, g.gy);
     const bool wide = live && (long long)(xb - xa + 1) * (yb - ya + 1) > SLIDE_WIDE_CELLS;
     float best = 0.0f;
     int arg = -1;
@@ -274,16 +208,15 @@ __global__ void __launch_bounds__(256) slide_match_kernel(const float* __restric
     elig[i] = mask;
 }
 
-// tp of every row and claim of every target at every threshold, grid-stride; the counts go through registers, a wave shuffle and
-// LDS to one atomic per workgroup, threshold and counter; thread 0 adds the number of oversize targets
+// tp of every row and claim of every target at every threshold, grid-stride; the counts go through registers and block_sum_256 to
+// one atomic per workgroup, threshold and counter; thread 0 adds the number of oversize targets
 constexpr int SLIDE_FINISH_BLOCKS = 256;
 __global__ void __launch_bounds__(256) slide_finish_kernel(int M, int T, int K, int n_cells, const uint32_t* __restrict__ elig,
                                                             const int32_t* __restrict__ best_target,
                                                             const unsigned long long* __restrict__ claim_key,
                                                             const int32_t* __restrict__ cell_start, uint8_t* __restrict__ tp,
                                                             int32_t* __restrict__ claim, int32_t* __restrict__ stats) {
-    __shared__ int red[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int red[4];
     const long long n = M > T ? M : T, stride = (long long)gridDim.x * 256;
     for (int k = 0; k < K; ++k) {
         int n_elig = 0, n_claimed = 0;
@@ -302,23 +235,13 @@ __global__ void __launch_bounds__(256) slide_finish_kernel(int M, int T, int K, 
                 n_claimed += claimed;
             }
         }
-        for (int o = 32; o > 0; o >>= 1) n_elig += __shfl_down(n_elig, o, 64), n_claimed += __shfl_down(n_claimed, o, 64);
-        __syncthreads();
-        if (lane == 0) red[0][wave] = n_elig, red[1][wave] = n_claimed;
-        __syncthreads();
+        const int e = block_sum_256(n_elig, red), c = block_sum_256(n_claimed, red);   // (k and K are uniform over the workgroup)
         if (threadIdx.x == 0) {
-            const int e = red[0][0] + red[0][1] + red[0][2] + red[0][3], c = red[1][0] + red[1][1] + red[1][2] + red[1][3];
             if (e) atomicAdd(&stats[2 * k], e);
             if (c) atomicAdd(&stats[2 * k + 1], c);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) stats[2 * K + 1] = cell_start[n_cells + 1] - cell_start[n_cells];
-}
-
-static inline size_t slide_align(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline size_t slide_cell_cap(int n_targets) {   // cells of the grid at most (cell indices stay in int32)
-    const size_t want = (size_t)(n_targets > 2048 ? n_targets : 2048) * 2;
-    return want < ((size_t)1 << 30) ? want : ((size_t)1 << 30);
 }
 
 struct SlideWs {
@@ -332,71 +255,20 @@ struct SlideWs {
 
 static SlideWs slide_carve(void* ws, int n_rows, int n_targets, int n_thres) {
     SlideWs w;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += slide_align(bytes);
-        return p;
-    };
-    const size_t m = (size_t)(n_rows > 0 ? n_rows : 1), t = (size_t)(n_targets > 0 ? n_targets : 1), cells = slide_cell_cap(n_targets);
+    WsCarver cv(ws);
+    const size_t m = (size_t)(n_rows > 0 ? n_rows : 1), t = (size_t)(n_targets > 0 ? n_targets : 1), cells = grid_cell_cap(n_targets);
     const size_t k = (size_t)(n_thres > 0 ? n_thres : 1);
-    w.partials = (float*)take(sizeof(float) * SLIDE_STATS_BLOCKS * SLIDE_STATS_WORDS);
-    w.class_flags = (int32_t*)take(4 * (size_t)AY_SLIDE_MAX_CLASSES);
-    w.claim_key = (unsigned long long*)take(8 * k * t);
-    w.box = (float4*)take(sizeof(float4) * t);
-    w.orig = (int32_t*)take(4 * t);
-    w.cell_of = (int32_t*)take(4 * t);
-    w.elig = (uint32_t*)take(4 * m);
-    w.cell_start = (int32_t*)take(4 * (cells + 2));
-    w.cursor = (int32_t*)take(4 * (cells + 2));
-    w.bytes = off;
+    w.partials = cv.take<float>(GRID_STATS_BLOCKS * GRID_STATS_WORDS);
+    w.class_flags = cv.take<int32_t>(AY_SLIDE_MAX_CLASSES);
+    w.claim_key = cv.take<unsigned long long>(k * t);
+    w.box = cv.take<float4>(t);
+    w.orig = cv.take<int32_t>(t);
+    w.cell_of = cv.take<int32_t>(t);
+    w.elig = cv.take<uint32_t>(m);
+    w.cell_start = cv.take<int32_t>(cells + 2);
+    w.cursor = cv.take<int32_t>(cells + 2);
+    w.bytes = cv.bytes();
     return w;
-}
-
-#define AY_SLIDE_HIP(call, what)                                            \
-    do {                                                                    \
-        hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) {                                             \
-            ay::set_error("%s: %s", what, hipGetErrorString(e_));           \
-            return AY_ERR_LAUNCH;                                           \
-        }                                                                   \
-    } while (0)
-
-// Cell side and grid from the reduction's partials.  Any cell side gives the same result; the choice is about work.  Without a
-// caller's side: the smallest power of two (>= 8) that leaves at most max(16, T / 4096) targets oversize (every row tests those in
-// full, so a few tile-sized annotations must not blow the cells up for everyone).  The side is doubled until the grid over the
-// centres' extent fits cell_cap cells: one target far from all others costs larger cells, never an unbounded grid.
-static SlideGrid slide_choose_grid(const float* partials, int T, size_t cell_cap, float cell_side) {
-    double mnx = 3.0e38, mxx = -3.0e38, mny = 3.0e38, mxy = -3.0e38;
-    long long hist[SLIDE_SIDE_BINS] = {0}, cnt = 0;
-    for (int b = 0; b < SLIDE_STATS_BLOCKS; ++b) {
-        const float* v = partials + b * SLIDE_STATS_WORDS;
-        mnx = fmin(mnx, v[0]), mxx = fmax(mxx, v[1]), mny = fmin(mny, v[2]), mxy = fmax(mxy, v[3]);
-        for (int k = 0; k < SLIDE_SIDE_BINS; ++k) {
-            int32_t n;
-            memcpy(&n, v + 4 + k, sizeof(n));
-            hist[k] += n, cnt += n;
-        }
-    }
-    SlideGrid g = {0.0f, 0.0f, cell_side > 0.0f ? cell_side : 8.0f, 1, 1};
-    if (cnt < 1) return g;   // no finite non-ignored target: one cell, possibly an oversize list
-    double c = cell_side;
-    if (!(cell_side > 0.0f)) {
-        const long long allowed = T / 4096 > 16 ? T / 4096 : 16;
-        int bin = SLIDE_SIDE_BINS - 2;   // (the last bin is open-ended: never taken for "fits")
-        long long above = hist[SLIDE_SIDE_BINS - 1];
-        while (bin > 3 && above + hist[bin] <= allowed) above += hist[bin--];
-        c = ldexp(1.0, bin);
-    }
-    for (;;) {
-        const double nx = floor((mxx - mnx) / c) + 1.0, ny = floor((mxy - mny) / c) + 1.0;
-        if (nx * ny <= (double)cell_cap) {
-            g.x0 = (float)mnx, g.y0 = (float)mny, g.c = (float)c, g.gx = (int)nx, g.gy = (int)ny;
-            return g;
-        }
-        c *= 2.0;
-    }
 }
 
 }  // namespace ay
@@ -428,33 +300,34 @@ extern "C" int ay_slide_match(const float* rows, int n_rows, const float* target
     SlideRoi r = {0, 0.f, 0.f, 0.f, 0.f};
     if (roi) r = SlideRoi{1, roi[0], roi[1], roi[2], roi[3]};
     hipStream_t st = S(stream);
-    AY_SLIDE_HIP(hipMemsetAsync(stats, 0, sizeof(int32_t) * (2 * K + 2), st), "ay_slide_match: memset");
-    AY_SLIDE_HIP(hipMemsetAsync(w.class_flags, 0, sizeof(int32_t) * AY_SLIDE_MAX_CLASSES, st), "ay_slide_match: memset");
-    SlideGrid g = {0.0f, 0.0f, 8.0f, 1, 1};
+    AY_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int32_t) * (2 * K + 2), st), "ay_slide_match: memset");
+    AY_CHECK_HIP(hipMemsetAsync(w.class_flags, 0, sizeof(int32_t) * AY_SLIDE_MAX_CLASSES, st), "ay_slide_match: memset");
+    BoxGrid g = {0.0f, 0.0f, 8.0f, 1, 1};
     if (T > 0) {
         const unsigned tblocks = (unsigned)(((long long)T + 255) / 256);
-        AY_SLIDE_HIP(hipMemsetAsync(w.claim_key, 0xFF, sizeof(unsigned long long) * (size_t)K * T, st), "ay_slide_match: memset");
+        AY_CHECK_HIP(hipMemsetAsync(w.claim_key, 0xFF, sizeof(unsigned long long) * (size_t)K * T, st), "ay_slide_match: memset");
         // 1. geometry reduction over the targets -> cell side and grid (host)
-        hipLaunchKernelGGL(slide_stats_kernel, dim3(SLIDE_STATS_BLOCKS), dim3(256), 0, st, targets, T, r, w.partials);
-        AY_CHECK_LAUNCH("slide_stats_kernel");
-        float partials[SLIDE_STATS_BLOCKS * SLIDE_STATS_WORDS];
-        AY_SLIDE_HIP(hipMemcpyAsync(partials, w.partials, sizeof(partials), hipMemcpyDeviceToHost, st), "ay_slide_match: copy");
-        AY_SLIDE_HIP(hipStreamSynchronize(st), "ay_slide_match: sync");
-        g = slide_choose_grid(partials, T, slide_cell_cap(T), cell_side);
-        const int n_cells = g.gx * g.gy;
+        const SlideTargets items = {targets, r};
+        hipLaunchKernelGGL(grid_stats_kernel<SlideTargets>, dim3(GRID_STATS_BLOCKS), dim3(256), 0, st, items, T, w.partials);
+        AY_CHECK_LAUNCH("grid_stats_kernel");
+        float partials[GRID_STATS_BLOCKS * GRID_STATS_WORDS];
+        AY_CHECK_HIP(hipMemcpyAsync(partials, w.partials, sizeof(partials), hipMemcpyDeviceToHost, st), "ay_slide_match: copy");
+        AY_CHECK_HIP(hipStreamSynchronize(st), "ay_slide_match: sync");
+        g = grid_choose(partials, T, /* ignored targets are on no list */ false, grid_cell_cap(T), cell_side);
+        const int n_cells = g.n_cells();
         // 2. counting sort of the non-ignored targets by cell (the oversize list is cell n_cells)
-        AY_SLIDE_HIP(hipMemsetAsync(w.cell_start, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_slide_match: memset");
-        AY_SLIDE_HIP(hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_slide_match: memset");
+        AY_CHECK_HIP(hipMemsetAsync(w.cell_start, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_slide_match: memset");
+        AY_CHECK_HIP(hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * (n_cells + 2), st), "ay_slide_match: memset");
         hipLaunchKernelGGL(slide_bin_count_kernel, dim3(tblocks), dim3(256), 0, st, targets, T, r, g, target_ignored, w.cell_of, w.cell_start,
                            w.class_flags, stats + 2 * K);
         AY_CHECK_LAUNCH("slide_bin_count_kernel");
-        hipLaunchKernelGGL(slide_scan_kernel, dim3(1), dim3(1024), 0, st, w.cell_start, n_cells + 1);
-        AY_CHECK_LAUNCH("slide_scan_kernel");
+        hipLaunchKernelGGL(grid_scan_kernel, dim3(1), dim3(1024), 0, st, w.cell_start, n_cells + 1);
+        AY_CHECK_LAUNCH("grid_scan_kernel");
         hipLaunchKernelGGL(slide_scatter_kernel, dim3(tblocks), dim3(256), 0, st, targets, T, (const int32_t*)w.cell_of,
                            (const int32_t*)w.cell_start, w.cursor, w.box, w.orig);
         AY_CHECK_LAUNCH("slide_scatter_kernel");
     } else {
-        AY_SLIDE_HIP(hipMemsetAsync(w.cell_start, 0, sizeof(int32_t) * 3, st), "ay_slide_match: memset");
+        AY_CHECK_HIP(hipMemsetAsync(w.cell_start, 0, sizeof(int32_t) * 3, st), "ay_slide_match: memset");
     }
     // 3. best target per row, claim keys
     if (M > 0) {
@@ -467,7 +340,7 @@ extern "C" int ay_slide_match(const float* rows, int n_rows, const float* target
     const long long n = M > T ? M : T;
     if (n > 0) {
         const long long fblocks = (n + 255) / 256;
-        hipLaunchKernelGGL(slide_finish_kernel, dim3((unsigned)(fblocks < SLIDE_FINISH_BLOCKS ? fblocks : SLIDE_FINISH_BLOCKS)), dim3(256), 0, st, M, T, K, g.gx * g.gy,
+        hipLaunchKernelGGL(slide_finish_kernel, dim3((unsigned)(fblocks < SLIDE_FINISH_BLOCKS ? fblocks : SLIDE_FINISH_BLOCKS)), dim3(256), 0, st, M, T, K, g.n_cells(),
                            (const uint32_t*)w.elig, (const int32_t*)best_target, (const unsigned long long*)w.claim_key,
                            (const int32_t*)w.cell_start, tp, claim, stats);
         AY_CHECK_LAUNCH("slide_finish_kernel");

@@ -90,10 +90,7 @@ extern "C" int ay_match_detections(const float* rows, const int32_t* count, int 
     AY_CHECK_ARG(rows && count && tp && overflow && batch > 0 && max_det > 0, "ay_match_detections: bad args");
     AY_CHECK_ARG(n_targets == 0 || targets, "ay_match_detections: targets null");
     hipStream_t st = S(stream);
-    if (hipMemsetAsync(overflow, 0, sizeof(int32_t), st) != hipSuccess) {
-        set_error("ay_match_detections: memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    AY_CHECK_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t), st), "ay_match_detections: memset");
     hipLaunchKernelGGL(match_detections_kernel, dim3(batch), dim3(64), 0, st, rows, count, max_det, targets, n_targets, iou_thres, tp,
                        overflow);
     AY_CHECK_LAUNCH("match_detections_kernel");

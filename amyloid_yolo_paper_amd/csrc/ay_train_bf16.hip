@@ -311,10 +311,7 @@ static int bn_train_fwd(const void* z, const float* gamma, const float* beta, fl
     AY_CHECK_ARG(z && gamma && beta && running_mean && running_var && y && save_mean && save_invstd && sums_ws, "ay_bn_train_fwd_bf16: null");
     hipStream_t st = S(stream);
     const int CP = (channels + 15) / 16, HW = h * w;
-    if (!ws_is_zero && hipMemsetAsync(sums_ws, 0, sizeof(double) * 2 * channels, st) != hipSuccess) {
-        set_error("memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    if (!ws_is_zero) AY_CHECK_HIP(hipMemsetAsync(sums_ws, 0, sizeof(double) * 2 * channels, st), "ay_bn_train_fwd_bf16: memset");
     const int ch = bn_chunks(batch, CP, HW);
     hipLaunchKernelGGL(bn_sums_kernel<false>, dim3(batch * ch, CP), dim3(256), 0, st, (const uint4*)z, nullptr, nullptr, nullptr, nullptr,
                        nullptr, 0, sums_ws, channels, HW, ch);
@@ -362,10 +359,7 @@ static int bn_train_bwd(const void* dy, const void* z, const float* gamma, const
     AY_CHECK_ARG(dy && z && gamma && beta && save_mean && save_invstd && dz && dgamma && dbeta && sums_ws, "ay_bn_train_bwd_bf16: null");
     hipStream_t st = S(stream);
     const int CP = (channels + 15) / 16, HW = h * w;
-    if (!ws_is_zero && hipMemsetAsync(sums_ws, 0, sizeof(double) * 2 * channels, st) != hipSuccess) {
-        set_error("memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    if (!ws_is_zero) AY_CHECK_HIP(hipMemsetAsync(sums_ws, 0, sizeof(double) * 2 * channels, st), "ay_bn_train_bwd_bf16: memset");
     const int ch = bn_chunks(batch, CP, HW);
     hipLaunchKernelGGL(bn_sums_kernel<true>, dim3(batch * ch, CP), dim3(256), 0, st, (const uint4*)dy, (const uint4*)z, save_mean, save_invstd,
                        gamma, beta, leaky, sums_ws, channels, HW, ch);

@@ -532,10 +532,7 @@ extern "C" int ay_bn_train_bwd_f32(const float* dy, const float* y, const float*
 
 static int bias_grad_launch(const float* dz, float* dbias, int accumulate, bool chunked, int batch, int channels, int hw, ay_stream_t stream) {
     AY_CHECK_ARG(dz && dbias, "ay_bias_grad_f32: null");
-    if (!accumulate && hipMemsetAsync(dbias, 0, sizeof(float) * channels, S(stream)) != hipSuccess) {
-        set_error("ay_bias_grad_f32: memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    if (!accumulate) AY_CHECK_HIP(hipMemsetAsync(dbias, 0, sizeof(float) * channels, S(stream)), "ay_bias_grad_f32: memset");
     const long long n = (long long)batch * hw;
     int chunks = chunked ? (int)((n + 16383) / 16384) : 1;  // one chunk: one fixed-order sum per channel (reproducible)
     if (chunks > 256) chunks = 256;
@@ -642,10 +639,8 @@ static int yolo_loss_impl(const float* head_nchw, const float* targets, int n_ta
     unsigned* flags = (unsigned*)(winner + cells);
     float* tcls = (float*)(flags + cells);
     float* sums = tcls + cells * num_classes;
-    if (hipMemsetAsync(winner, 0xff, cells * 4, st) != hipSuccess || hipMemsetAsync(flags, 0, cells * 4 + cells * num_classes * 4 + 64 * 4, st) != hipSuccess) {
-        set_error("ay_yolo_loss_fwd_bwd: memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    AY_CHECK_HIP(hipMemsetAsync(winner, 0xff, cells * 4, st), "ay_yolo_loss_fwd_bwd: memset");
+    AY_CHECK_HIP(hipMemsetAsync(flags, 0, cells * 4 + cells * num_classes * 4 + 64 * 4, st), "ay_yolo_loss_fwd_bwd: memset");
     if (n_targets > 0) {
         hipLaunchKernelGGL(yolo_targets_pass1, dim3((n_targets + 255) / 256), dim3(256), 0, st, targets, n_targets, g, ignore_thres, winner,
                            flags, tcls);
@@ -715,11 +710,9 @@ extern "C" int ay_build_targets(const float* pred_boxes, const float* pred_cls, 
     const size_t cells = (size_t)batch * num_anchors * grid * grid;
     int* winner = (int*)workspace;
     unsigned* flags = (unsigned*)(winner + cells);
-    if (hipMemsetAsync(winner, 0xff, cells * 4, st) != hipSuccess || hipMemsetAsync(flags, 0, cells * 4, st) != hipSuccess ||
-        hipMemsetAsync(tcls, 0, cells * num_classes * 4, st) != hipSuccess) {
-        set_error("ay_build_targets: memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    AY_CHECK_HIP(hipMemsetAsync(winner, 0xff, cells * 4, st), "ay_build_targets: memset");
+    AY_CHECK_HIP(hipMemsetAsync(flags, 0, cells * 4, st), "ay_build_targets: memset");
+    AY_CHECK_HIP(hipMemsetAsync(tcls, 0, cells * num_classes * 4, st), "ay_build_targets: memset");
     if (n_targets > 0) {
         hipLaunchKernelGGL(yolo_targets_pass1, dim3((n_targets + 255) / 256), dim3(256), 0, st, targets, n_targets, g, ignore_thres, winner,
                            flags, tcls);

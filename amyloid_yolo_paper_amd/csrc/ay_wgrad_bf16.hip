@@ -478,10 +478,7 @@ extern "C" int ay_conv_wgrad_bf16_ws(const ay_conv_desc* d, const void* x_blocke
     a.dw_elems = dw_elems;
     a.dbg = conv_dbg();
     // without a workspace the kernel ADDS its split-K partial sums to dw (fp32 atomics): accumulate = 0 starts from zero
-    if (!slabs && !accumulate && hipMemsetAsync(dw_oihw, 0, sizeof(float) * dw_elems, st) != hipSuccess) {
-        set_error("ay_conv_wgrad_bf16: memset failed");
-        return AY_ERR_LAUNCH;
-    }
+    if (!slabs && !accumulate) AY_CHECK_HIP(hipMemsetAsync(dw_oihw, 0, sizeof(float) * dw_elems, st), "ay_conv_wgrad_bf16: memset");
     a.ncob = cob, a.ncib = cib, a.ks = (int)ks;
     AY_CHECK_ARG((long long)cob * cib * ks < 0x7fffffffLL, "ay_conv_wgrad_bf16: grid");
     dim3 grid((unsigned)(cob * cib * ks)), block(512);

@@ -130,7 +130,7 @@ if a.kernel_stats:
     import csv
     import glob
     table = list(csv.DictReader(open(glob.glob(os.path.join(a.kernel_stats, "**", "*_kernel_stats.csv"), recursive=True)[0])))
-    ours = [r for r in table if "slide_" in r["Name"]]
+    ours = [r for r in table if "slide_" in r["Name"] or "grid_" in r["Name"]]   # (the reduction and the scan are ay_box_grid.h's)
     calls = max(int(r["Calls"]) for r in ours)
     say(f"# KERNEL time per call at K=3, from a kernel trace of {calls} calls (mean per dispatch):")
     for r in sorted(ours, key=lambda r: -float(r["TotalDurationNs"])):

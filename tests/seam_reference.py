@@ -159,6 +159,63 @@ def staircase(n=320):
     return np.asarray(rows, F32), (np.arange(n) % 2).astype(np.int32)
 
 
+def far_row(n_obj=150, seed=4):
+    """a small slide + one object 10^6 px away seen by two tiles (the last two rows, the stronger first): the extent of the centres
+    is far more than the cell cap allows at the histogram's side, so the side is doubled until the grid fits"""
+    rows, tile_id = synthetic_slide(n_obj, 2, 2, seed=seed)
+    far = [row(1000000, 1000000, 1000039, 1000039, 0.875, 1.0), row(1000002, 1000001, 1000039, 1000041, 0.75, 1.0)]
+    return np.concatenate([rows, np.asarray(far, F32)]), np.concatenate([tile_id, np.asarray([100, 101], np.int32)])
+
+
+def one_cell(n=72):
+    """concentric boxes of several sizes (every centre is (500.5, 300.5): the extent is 0, the grid 1 x 1), two classes, tile ids
+    alternating; ov of two concentric boxes is 1"""
+    half = (3, 5, 9, 14, 22)
+    rows = []
+    for i in range(n):
+        a, b = half[i % 5], half[(i // 5) % 5]
+        rows.append(row(500 - a, 300 - b, 501 + a, 301 + b, (8 + (5 * i) % 8) / 16.0, (8 + (3 * i) % 9) / 16.0, (i // 2) % 2))
+    return np.asarray(rows, F32), (np.arange(n) % 2).astype(np.int32)
+
+
+def borders():
+    """20 pairs of sightings (rows 2k and 2k + 1, tiles 0 and 1) 96 px apart; the centres of a pair lie on a multiple of 32 px from
+    the smallest centre (row 0's, the grid origin) or half a pixel to either side of it, on each axis: where the cell of a centre
+    flips.  Sides 17 .. 31 px, so that the chosen cell side is 32."""
+    inner = [(-0.5, 0.0), (-0.5, 0.5), (0.0, 0.5), (0.0, -0.5), (0.5, -0.5), (0.0, 0.0)]   # offsets of the two centres from the multiple
+    edge = [(0.0, 0.5), (0.5, 0.0), (0.0, 0.0)]                                             # nothing left of (above) the origin
+    rows = []
+    for k in range(20):
+        mx, my = 3 * (k % 5), 3 * (k // 5)
+        dx = edge[k % 3] if mx == 0 else inner[k % 6]
+        dy = edge[(k // 5) % 3] if my == 0 else inner[(k + k // 5) % 6]
+        for s in (0, 1):
+            box = []
+            for origin, m, d, w in ((1000, mx, dx[s], 17 + (3 * k + 7 * s) % 15), (2000, my, dy[s], 17 + (5 * k + 4 * s) % 15)):
+                c2 = int(2 * (origin + 32 * m + d))      # twice the centre: integer corners need a side of the other parity
+                if (c2 + w) % 2 == 0:
+                    w += 1 if w < 31 else -1
+                box.append(((c2 - (w - 1)) // 2, (c2 + (w - 1)) // 2))
+            conf = (15 - s) / 16.0 if k % 2 == 0 else (14 + s) / 16.0     # the stronger sighting first, or second
+            rows.append(row(box[0][0], box[1][0], box[0][1], box[1][1], conf, 1.0, k % 2))
+    return np.asarray(rows, F32), (np.arange(40) % 2).astype(np.int32)
+
+
+def every_row_oversize():
+    """twelve rows a few hundred px wide: too few for the histogram rule to size the cells by, so all of them are oversize"""
+    rows = []
+    for o, (x, y, w, h) in enumerate([(0, 0, 300, 400), (200, 100, 350, 350), (1000, 50, 250, 300), (1020, 400, 240, 280)]):
+        rows.append(row(x, y, x + w - 1, y + h - 1, (15 - o) / 16.0, 1.0, o % 2))                     # whole
+        rows.append(row(x + w // 2, y + 2, x + w, y + h - 2, (11 - o) / 16.0, 0.75, o % 2))           # the right half, by the next tile
+        rows.append(row(x + 1, y + h // 3, x + w - 2, y + h + 1, (9 + o) / 16.0, 0.5, o % 2))         # the lower two thirds, by the tile below
+    return np.asarray(rows, F32), np.asarray([t for o in range(4) for t in (o, o + 1, o + 4)], np.int32)
+
+
+def geometry_cases():
+    """name -> (rows, tile_id): extents and box sizes at which the centre grid takes another path"""
+    return {"far_row": far_row(), "one_cell": one_cell(), "borders": borders(), "every_row_oversize": every_row_oversize()}
+
+
 def synthetic_slide(n_obj, grid_y, grid_x, tile=192, overlap=48, seed=0, big=0):
     """Objects on a slide covered by a grid of overlapping tiles; every tile reports the clipped view of each object it sees (at
     least 4 px of it on either axis), its corners jittered by up to 2 px.  Integer pixel coordinates, conf (below 1) a multiple of 1/16 and

@@ -199,6 +199,51 @@ def test_seam_merge_boxes_as_large_as_a_tile(dev):
     assert np.array_equal(keep, want)
 
 
+def far_row_not_trivial(rows, want):
+    rest = 1.0 - want[:-2].mean()
+    print(f"far_row: rows {len(rows)}, far pair {want[-2:].tolist()}, dropped among the rest {rest:.3f}")
+    return want[-2:].tolist() == [True, False] and 200 <= len(rows) < 2048 and 0.2 <= rest <= 0.7
+
+
+def one_cell_not_trivial(rows, want):
+    cx, cy = (rows[:, 0] + rows[:, 2]) * np.float32(0.5), (rows[:, 1] + rows[:, 3]) * np.float32(0.5)
+    print(f"one_cell: rows {len(rows)}, kept {int(want.sum())}")
+    return len(rows) >= 64 and (cx == cx[0]).all() and (cy == cy[0]).all() and 0.25 <= want.mean() <= 0.75
+
+
+def borders_not_trivial(rows, want):
+    w, h = rows[:, 2] - rows[:, 0] + 1, rows[:, 3] - rows[:, 1] + 1
+    cx, cy = (rows[:, 0] + rows[:, 2]) * np.float32(0.5), (rows[:, 1] + rows[:, 3]) * np.float32(0.5)
+    off = np.concatenate([cx - cx.min(), cy - cy.min()]) % 32                # 0, 0.5 or 31.5: on a multiple of 32 or half a pixel off
+    print(f"borders: rows {len(rows)}, sides {int(min(w.min(), h.min()))} .. {int(max(w.max(), h.max()))}, offsets {np.unique(off).tolist()}")
+    return (len(rows) >= 17 and min(w.min(), h.min()) >= 17 and max(w.max(), h.max()) <= 31 and (cx[0], cy[0]) == (cx.min(), cy.min())
+            and set(np.unique(off).tolist()) == {0.0, 0.5, 31.5} and (want[0::2] != want[1::2]).all())
+
+
+def every_row_oversize_not_trivial(rows, want):
+    side = np.maximum(rows[:, 2] - rows[:, 0], rows[:, 3] - rows[:, 1])
+    print(f"every_row_oversize: rows {len(rows)}, smallest side {side.min():.0f}, kept {int(want.sum())}")
+    return len(rows) <= 16 and side.min() >= 100 and (~want).sum() >= 1 and want.sum() >= 2
+
+
+GEOMETRY_NOT_TRIVIAL = {"far_row": far_row_not_trivial, "one_cell": one_cell_not_trivial, "borders": borders_not_trivial,
+                        "every_row_oversize": every_row_oversize_not_trivial}
+
+
+@pytest.mark.parametrize("name", sorted(GEOMETRY_NOT_TRIVIAL))
+def test_seam_merge_geometry(dev, name):
+    """extents and box sizes at which the centre grid (csrc/ay_box_grid.h) takes another path: a side doubled until the grid fits
+    the cell cap, a 1 x 1 grid, centres on cell borders, an oversize list that holds every row"""
+    rows, tile_id = sr.geometry_cases()[name]
+    want = sr.seam_merge(rows, tile_id)
+    assert GEOMETRY_NOT_TRIVIAL[name](rows, want)   # asserted on the RESTATEMENT's output, before the kernel is looked at
+    keep, _ = device_merge(dev, rows, tile_id)
+    assert np.array_equal(keep, want)
+    perm = np.random.default_rng(11).permutation(len(rows))
+    keep, _ = device_merge(dev, rows[perm], tile_id[perm])
+    assert np.array_equal(keep, sr.seam_merge(rows[perm], tile_id[perm]))
+
+
 def test_seam_merge_large_slide(dev):
     """a few 10^5 rows on a grid of 2 500 tiles against the binned restatement, which is first shown equal to the plain one"""
     rows, tile_id = sr.synthetic_slide(3000, 6, 7, seed=1)
