@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libamyloid_yolo_hip.so")
-SOURCES = ["ay_layout.hip", "ay_conv_host.hip", "ay_conv_bf16.hip", "ay_conv3x3_m16.hip", "ay_conv_f32.hip", "ay_conv_f32_mfma.hip", "ay_conv_split.hip", "ay_yolo.hip", "ay_nms.hip", "ay_train_f32.hip", "ay_stem_fused.hip", "ay_stem_train.hip", "ay_train_bf16.hip", "ay_wgrad_bf16.hip", "ay_ingest.hip", "ay_resblock_bf16.hip", "ay_stats.hip", "ay_merge.hip", "ay_plan.hip", "ay_seam.hip", "ay_tissue.hip", "ay_augment.hip", "ay_views.hip", "ay_slidematch.hip", "ay_burden.hip", "ay_stain.hip", "ay_stain_basis.hip", "ay_load.hip", "ay_focus.hip", "ay_segment.hip"]
+SOURCES = ["ay_layout.hip", "ay_conv_host.hip", "ay_conv_bf16.hip", "ay_conv3x3_m16.hip", "ay_conv_f32.hip", "ay_conv_f32_mfma.hip", "ay_conv_split.hip", "ay_yolo.hip", "ay_nms.hip", "ay_train_f32.hip", "ay_stem_fused.hip", "ay_stem_train.hip", "ay_train_bf16.hip", "ay_wgrad_bf16.hip", "ay_ingest.hip", "ay_resblock_bf16.hip", "ay_stats.hip", "ay_merge.hip", "ay_plan.hip", "ay_seam.hip", "ay_tissue.hip", "ay_augment.hip", "ay_views.hip", "ay_slidematch.hip", "ay_burden.hip", "ay_stain.hip", "ay_stain_basis.hip", "ay_load.hip", "ay_focus.hip", "ay_segment.hip", "ay_spatial.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 # Instrumented build (csrc/ay_phase_clock.h): the experiment switches and the in-kernel phase clock of the persistent conv kernels
 # (ring, m16, fused stem, wgrad), chosen at run time by the AY_DBG bits; AY_DBG=8 prints the clock's report per launch.  The

@@ -794,6 +794,55 @@ size_t ay_field_select_workspace_bytes(int num_classes, int gy, int gx, int fiel
 int ay_field_select(const int32_t* counts, int num_classes, int gy, int gx, const int32_t* tissue, int field, int need_tissue, int top_k,
                     int32_t* fields, int32_t* n_found, void* workspace, size_t workspace_bytes, ay_stream_t stream);
 
+/* ---- spatial statistics of a slide's detections: pair counts within a radius (wsi.spatial_stats, wsi.quantify_region(spatial_radii=...);
+ *      csrc/ay_spatial.hip) -----------------------------------------------------------------------------------------------------------
+ * How the objects of a slide lie with respect to one another: are the cored plaques clustered, and at which scale; do CAA vessels and
+ * cored plaques occur together more often than their densities predict.  The cross-class pair counts within a radius are what
+ * Ripley's K and L, the pair correlation g and the nearest-neighbour distribution G are made of (on the host, in float64).  The rule
+ * is exact (two fp32 operations, integers after them) and tests/spatial_reference.py restates it in NumPy by brute force.
+ *
+ * THE PAIR RULE.  Input: rows [M][7] fp32 (x1, y1, x2, y2, conf, cls_conf, cls_pred) in pixels of the (halved) slide; the slide's H, W
+ *   with 1 <= H, W <= AY_PAIR_MAX_SIDE (2^21, so that 4W is exact in fp32); C classes, 1 <= C <= AY_PAIR_MAX_CLASSES; min_conf; B
+ *   radii R_0 < R_1 < ... < R_{B-1} as int32 in QUARTER PIXELS, 1 <= B <= AY_PAIR_MAX_RADII, 1 <= R_0, R_{B-1} <=
+ *   AY_PAIR_MAX_RADIUS_Q (with that bound dx^2 + dy^2 fits int32 once |dx|, |dy| <= R_{B-1}); optionally roi_q = (X1, Y1, X2, Y2),
+ *   int32 in quarter pixels, a closed rectangle with X1 <= X2, Y1 <= Y2 (NULL: (0, 0, 4W - 1, 4H - 1)); a flag `border`.
+ *   For each row, in this order:
+ *   Centre: cx = fl32((x1 + x2) * 0.5f), cy alike: THE BURDEN RULE's two operations.
+ *   Flagged / below: exactly THE BURDEN RULE's tests, with its flag bits (AY_BURDEN_FLAG_*), in its order.  Such a row is NOT COUNTED
+ *     and takes part in nothing.
+ *   Position of a counted row: qx = (int)floorf(min(max(fl32(cx * 4.0f), 0), 4W - 1)), qy alike with H: a centre outside the slide
+ *     goes to the nearest border position; the multiply is exact or overflows to an infinity, which the clamp takes.
+ *   Border distance: bd_i = min(qx - X1, X2 - qx, qy - Y1, Y2 - qy), negative when the position lies outside the ROI.
+ *   Eligibility: a counted row i is an ELIGIBLE CENTRE at k iff bd_i >= (border ? R_k : 0).  This is minus-sampling: the partners j may
+ *     lie anywhere, only the centres are restricted.
+ *   Pair: for counted i != j, d2_ij = (qx_i - qx_j)^2 + (qy_i - qy_j)^2 on integers; the pair is WITHIN k iff d2_ij <= R_k^2
+ *     (equality counts; two rows at one position are a pair at distance 0).
+ *   Output: pairs int64 [C][C][B]: pairs[a][b][k] = the sum over the eligible-at-k centres i of class a of the number of counted
+ *     j != i of class b within k (cumulative in k, ordered pairs).  centres int32 [C][B]: the eligible centres of class a at k.
+ *     nn int32 [M][C][2]: for every counted row i, whatever the ROI, and every class b, (d2, j) of the counted j != i of class b with
+ *     the smallest d2 <= R_{B-1}^2, ties to the lowest row index j; (-1, -1) if there is none, and for rows not counted.
+ *     bd int32 [M]: bd_i; -1 for rows not counted and for any negative value.  stats int32 [2C + 3] = rows counted per class, counted
+ *     rows with bd_i >= 0 per class, rows below, rows flagged, flag bits; sum(stats[:C]) + below + flagged == M.
+ *   Integer sums and minima with an index tie-break: a function of the inputs alone, the same bytes on every run.
+ *
+ * ay_pair_counts: rows and every output on the device; radii_q (n_radii int32) and roi_q (4 int32, or NULL) on the HOST: they travel
+ *   as kernel arguments.  Kernel launches only -- no memset node, no allocation, no host read, no synchronisation -- so the call can
+ *   sit in a captured step; a kernel of the call zeroes or fills every output.  n_rows == 0 is legal (rows, nn, bd may then be NULL).
+ *   The counted rows are binned by the cell of their position on a grid that comes from the ARGUMENTS: cell side S = R_{B-1} * 2^m
+ *   quarter pixels, m the smallest for which ceil(4W / S) * ceil(4H / S) stays within the centre grid's cell cap for n_rows; a search
+ *   reads the 3 x 3 cells around its own.  cell_side_q > 0 overrides S (refused below R_{B-1}, or where the grid would exceed 2^30
+ *   cells); the result does not depend on it.  The cost is the number of pairs within 3 x 3 cells.  workspace: 16-byte aligned,
+ *   ay_pair_counts_workspace_bytes(n_rows, slide_h, slide_w, R_{B-1}, cell_side_q) bytes (0 for arguments the call refuses).  No
+ *   scratch. */
+#define AY_PAIR_MAX_CLASSES 8
+#define AY_PAIR_MAX_RADII 32
+#define AY_PAIR_MAX_RADIUS_Q 32767
+#define AY_PAIR_MAX_SIDE 2097152
+size_t ay_pair_counts_workspace_bytes(int n_rows, int slide_h, int slide_w, int r_max_q, int cell_side_q);
+int ay_pair_counts(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf, const int32_t* radii_q,
+                   int n_radii, const int32_t* roi_q, int border, int cell_side_q, int64_t* pairs, int32_t* centres, int32_t* nn,
+                   int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes, ay_stream_t stream);
+
 /* ---- stain normalisation for whole-slide detection (wsi.stain_stats, wsi.StainMap, wsi.detect_region(stain=...); csrc/ay_stain.hip) --
  * Amyloid IHC slides are hematoxylin + DAB and differ in stain strength from batch to batch and from scanner to scanner.  The slide's
  * optical densities are unmixed on a fixed two-stain basis, each stain is scaled by a gain that brings its strength to a target's,
