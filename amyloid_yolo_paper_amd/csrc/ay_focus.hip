@@ -203,12 +203,12 @@ extern "C" int ay_focus_u8(const void* region_hwc_u8, int region_h, int region_w
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8, "ay_focus_u8: null");
     if (!check_region("ay_focus_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
-    AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && cell >= AY_FOCUS_MIN_CELL, "ay_focus_u8: bg_level %d, cell %d", bg_level, cell);
+    if (!check_bg_level("ay_focus_u8", bg_level)) return AY_ERR_ARG;
+    AY_CHECK_ARG(cell >= AY_FOCUS_MIN_CELL, "ay_focus_u8: cell %d", cell);
     const int h_img = region_h / shrink, W = region_w / shrink;
-    AY_CHECK_ARG(slide_h >= 1 && slide_h <= SLIDE_MAX_SIDE && slide_w >= 1 && slide_w <= SLIDE_MAX_SIDE &&
-                     (long long)slide_h * slide_w < (1ll << 43) && W == slide_w && origin_y >= 0 && origin_y <= slide_h - h_img,
-                 "ay_focus_u8: a %dx%d image at row %d of a %dx%d slide (the region holds whole rows of the slide)", h_img, W, origin_y,
-                 slide_h, slide_w);
+    if (!check_on_slide("ay_focus_u8", h_img, W, origin_y, 0, slide_h, slide_w)) return AY_ERR_ARG;
+    AY_CHECK_ARG((long long)slide_h * slide_w < (1ll << 43) && W == slide_w,
+                 "ay_focus_u8: a %dx%d image of a %dx%d slide (the region holds whole rows of the slide)", h_img, W, slide_h, slide_w);
     AY_CHECK_ARG(own_y0 >= 0 && own_y0 <= own_y1 && own_y1 <= slide_h, "ay_focus_u8: owned rows %d .. %d of %d", own_y0, own_y1, slide_h);
     if (!check_cells_boxes("ay_focus_u8", n_rows, rows, boxes, flags, cells)) return AY_ERR_ARG;
     const int c0 = own_y0 > 1 ? own_y0 : 1, c1 = own_y1 < slide_h - 1 ? own_y1 : slide_h - 1;   // the centre rows: c0 <= Y < c1

@@ -35,34 +35,26 @@ __global__ void __launch_bounds__(256) stain_load_cells_kernel(const uint8_t* __
                                                                 unsigned long long* __restrict__ cells) {
     __shared__ float od[256];
     __shared__ int lc[LOAD_WORDS];
-    constexpr int BPP = 3 * SHRINK;                          // source bytes of one row per image pixel
-    constexpr int PPI = SLIDE_ITEM / BPP;                    // pixels of an item
+    constexpr int PPI = SLIDE_ITEM / (3 * SHRINK);           // pixels of an item
     const int tid = threadIdx.x;
     od[tid] = params->od[tid];
     const float d0 = params->D[stain], d1 = params->D[3 + stain], d2 = params->D[6 + stain];   // uniform: scalar registers
     for (int i = tid; i < LOAD_WORDS; i += 256) lc[i] = 0;
     __syncthreads();
-    const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * BPP;   // bytes of a source row; those that belong to a pixel
+    const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * (3 * SHRINK);   // bytes of a source row; those that belong to a pixel
     const unsigned nq = (used + SLIDE_ITEM - 1) / SLIDE_ITEM;
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of the flush
         const SlideUnit un = slide_unit<LOAD_BAND, LOAD_XQ>(u, n_xc, nq, 0, H);
         const UnitCells uc = unit_cells(oy + un.y_lo, oy + un.y_hi, ox + (int)un.q0 * PPI, ox + min((int)(un.q0 + un.wq) * PPI, W), cell);
         const int y_cut = (uc.cy0 + 1) * cell - oy;          // region rows from y_cut on lie in cell row cy0 + 1; ncy <= 2: 16 rows, cell >= 16
-        const unsigned items = (unsigned)(un.y_hi - un.y_lo) * un.wq;
-        for (unsigned i = tid; i < items; i += 256) {
-            const unsigned qi = i % un.wq, o = (un.q0 + qi) * SLIDE_ITEM;
-            const int Y = un.y_lo + (int)(i / un.wq);
-            uint32_t w0[12], w1[12];
-            item_load<WIDE, SHRINK>(reg, stride, Y, o, row_bytes, w0, w1);
-            const ItemCells ic = item_cells<PPI>(ox + (int)(un.q0 + qi) * PPI, cell);
-            unsigned tm = 0, pm = 0;                         // bit p: pixel p is tissue; is positive
-            int qs = 0, qa = 0;                              // bins of the positive pixels: all; those before xb
-#pragma unroll
-            for (int p = 0; p < PPI; ++p) {                  // the pixels of the item lie at the same bytes in every lane
-                if (o + p * BPP >= used) continue;           // behind the last pixel of the row
-                int b[3];
-                item_pixel<SHRINK>(w0, w1, p, b);
-                if (!tissue_px(b, bg)) continue;
+        ItemCells ic;
+        int row;                                             // of the item
+        unsigned tm, pm;                                     // bit p: pixel p is tissue; is positive
+        int qs, qa;                                          // bins of the positive pixels: all; those before xb
+        tissue_walk<WIDE, SHRINK>(
+            reg, stride, row_bytes, used, un, bg,
+            [&](unsigned q, int Y) { ic = item_cells<PPI>(ox + (int)q * PPI, cell), row = Y, tm = pm = 0, qs = qa = 0; },
+            [&](int p, const int* b) {
                 tm |= 1u << p;
                 const int bin = load_bin(od, b, d0, d1, d2);
                 if (bin >= thres_bin) {
@@ -70,9 +62,10 @@ __global__ void __launch_bounds__(256) stain_load_cells_kernel(const uint8_t* __
                     qs += bin;
                     if (p < ic.xb) qa += bin;
                 }
-            }
-            if (tm) {
-                int* a = lc + ((Y >= y_cut ? LOAD_CX : 0) + (ic.ca - uc.cx0)) * 3;
+            },
+            [&]() {
+                if (!tm) return;
+                int* a = lc + ((row >= y_cut ? LOAD_CX : 0) + (ic.ca - uc.cx0)) * 3;
                 const int ta = __builtin_popcount(tm & ic.low), tb = __builtin_popcount(tm & ~ic.low);
                 if (ta) {
                     atomicAdd(a, ta);
@@ -84,8 +77,7 @@ __global__ void __launch_bounds__(256) stain_load_cells_kernel(const uint8_t* __
                     const int pb = __builtin_popcount(pm & ~ic.low);
                     if (pb) atomicAdd(a + 4, pb), atomicAdd(a + 5, qs - qa);
                 }
-            }
-        }
+            });
         __syncthreads();
         flush_cell_table<int, LOAD_CX>(lc, uc.ncy, uc.ncx, uc.cy0, uc.cx0, gx, cells);
         __syncthreads();
@@ -133,13 +125,11 @@ extern "C" int ay_stain_load_u8(const void* region_hwc_u8, int region_h, int reg
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && params_device, "ay_stain_load_u8: null");
     if (!check_region("ay_stain_load_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
-    AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && (stain == 0 || stain == 1) && thres_bin >= 0 && thres_bin <= AY_STAIN_BINS &&
-                     cell >= AY_LOAD_MIN_CELL,
-                 "ay_stain_load_u8: bg_level %d, stain %d, thres_bin %d, cell %d", bg_level, stain, thres_bin, cell);
+    if (!check_bg_level("ay_stain_load_u8", bg_level)) return AY_ERR_ARG;
+    AY_CHECK_ARG((stain == 0 || stain == 1) && thres_bin >= 0 && thres_bin <= AY_STAIN_BINS && cell >= AY_LOAD_MIN_CELL,
+                 "ay_stain_load_u8: stain %d, thres_bin %d, cell %d", stain, thres_bin, cell);
     const int H = region_h / shrink, W = region_w / shrink;
-    AY_CHECK_ARG(slide_h >= 1 && slide_h <= SLIDE_MAX_SIDE && slide_w >= 1 && slide_w <= SLIDE_MAX_SIDE && origin_y >= 0 && origin_x >= 0 &&
-                     origin_y <= slide_h - H && origin_x <= slide_w - W,
-                 "ay_stain_load_u8: a %dx%d image at (%d, %d) of a %dx%d slide", H, W, origin_y, origin_x, slide_h, slide_w);
+    if (!check_on_slide("ay_stain_load_u8", H, W, origin_y, origin_x, slide_h, slide_w)) return AY_ERR_ARG;
     if (!check_cells_boxes("ay_stain_load_u8", n_rows, rows, boxes, flags, cells)) return AY_ERR_ARG;
     if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
     if (cells) {

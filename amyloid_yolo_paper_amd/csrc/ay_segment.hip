@@ -325,14 +325,12 @@ extern "C" int ay_box_segments_u8(const void* region_hwc_u8, int region_h, int r
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && params_device, "ay_box_segments_u8: null");
     if (!check_region("ay_box_segments_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
-    AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && (stain == 0 || stain == 1) && thres_bin >= 0 && thres_bin <= core_bin &&
-                     core_bin <= AY_STAIN_BINS && margin >= 0 && margin <= AY_SEG_MAX_MARGIN && min_area >= 1,
-                 "ay_box_segments_u8: bg_level %d, stain %d, thres_bin %d, core_bin %d, margin %d, min_area %d", bg_level, stain, thres_bin,
-                 core_bin, margin, min_area);
+    if (!check_bg_level("ay_box_segments_u8", bg_level)) return AY_ERR_ARG;
+    AY_CHECK_ARG((stain == 0 || stain == 1) && thres_bin >= 0 && thres_bin <= core_bin && core_bin <= AY_STAIN_BINS && margin >= 0 &&
+                     margin <= AY_SEG_MAX_MARGIN && min_area >= 1,
+                 "ay_box_segments_u8: stain %d, thres_bin %d, core_bin %d, margin %d, min_area %d", stain, thres_bin, core_bin, margin, min_area);
     const int H = region_h / shrink, W = region_w / shrink;
-    AY_CHECK_ARG(slide_h >= 1 && slide_h <= SLIDE_MAX_SIDE && slide_w >= 1 && slide_w <= SLIDE_MAX_SIDE && origin_y >= 0 && origin_x >= 0 &&
-                     origin_y <= slide_h - H && origin_x <= slide_w - W,
-                 "ay_box_segments_u8: a %dx%d image at (%d, %d) of a %dx%d slide", H, W, origin_y, origin_x, slide_h, slide_w);
+    if (!check_on_slide("ay_box_segments_u8", H, W, origin_y, origin_x, slide_h, slide_w)) return AY_ERR_ARG;
     AY_CHECK_ARG(own_y0 >= 0 && own_y0 <= own_y1 && own_y1 <= slide_h, "ay_box_segments_u8: owner rows %d .. %d of %d", own_y0, own_y1, slide_h);
     AY_CHECK_ARG(n_rows >= 0 && (n_rows == 0 || (rows && out && flags)), "ay_box_segments_u8: %d rows %p, out %p, flags %p", n_rows,
                  (const void*)rows, (const void*)out, (const void*)flags);

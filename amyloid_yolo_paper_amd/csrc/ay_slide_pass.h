@@ -1,8 +1,9 @@
 // What the slide-level passes over a resident uint8 HWC region share (ay_stain.hip, ay_stain_basis.hip, ay_load.hip, ay_focus.hip; of ay_tissue.hip the
 // launcher and check_region; of ay_segment.hip tissue_px, load_bin, check_region and the box edges): the 48-byte item of the read
-// stream, the work units, the launch of the four (WIDE, SHRINK) instances, the place of an item and a unit on the cell grid, the flush
-// of a workgroup's cell table, the box walk and the host checks.  Helper functions only: how a pass accumulates (int32 table, uint64
-// table with spills, LDS histogram) is its own and stays in its file.
+// stream, the work units, the walk over a unit's tissue pixels, the flush of a workgroup's LDS histogram, the launch of the four (WIDE,
+// SHRINK) instances, the place of an item and a unit on the cell grid, the flush of a workgroup's cell table, the box walk and the host
+// checks.  Helper functions only: what a pass does with a pixel and how it accumulates (int32 table, uint64 table with spills, LDS
+// bins, registers) is its own and stays in its file.
 #pragma once
 #include <type_traits>
 
@@ -85,6 +86,54 @@ __device__ __forceinline__ SlideUnit slide_unit(long long u, int n_xc, unsigned 
     s.q0 = (unsigned)(u % n_xc) * XQ, s.wq = min((unsigned)XQ, nq - s.q0);
     s.y_lo = y0 + (int)(u / n_xc) * BAND, s.y_hi = min(s.y_lo + BAND, y1), s.ny = min(BAND, y1 - s.y_lo);
     return s;
+}
+
+// ---- the tissue-pixel walk of the read stream: the items of unit `un`, one per lane and step.  item(q, Y) once the item q of row Y is
+// loaded, before its first pixel; tissue(p, b) for every pixel p of the item that is tissue, b its three bytes (glass and what lies behind
+// the last pixel of the row cost a minimum and a compare); item_done() behind the item's last pixel.
+template <bool WIDE, int SHRINK, typename Item, typename Tissue, typename ItemDone>
+__device__ __forceinline__ void tissue_walk(const uint8_t* __restrict__ reg, size_t stride, unsigned row_bytes, unsigned used,
+                                            const SlideUnit& un, int bg, Item item, Tissue tissue, ItemDone item_done) {
+    constexpr int BPP = 3 * SHRINK;                          // source bytes of one row per image pixel
+    const unsigned items = (unsigned)(un.y_hi - un.y_lo) * un.wq;
+    for (unsigned i = threadIdx.x; i < items; i += 256) {
+        const unsigned q = un.q0 + i % un.wq, o = q * SLIDE_ITEM;
+        const int Y = un.y_lo + (int)(i / un.wq);
+        uint32_t w0[12], w1[12];
+        item_load<WIDE, SHRINK>(reg, stride, Y, o, row_bytes, w0, w1);
+        item(q, Y);
+#pragma unroll
+        for (int p = 0; p < SLIDE_ITEM / BPP; ++p) {         // the pixels of the item lie at the same bytes in every lane
+            if (o + p * BPP >= used) continue;               // behind the last pixel of the row
+            int b[3];
+            item_pixel<SHRINK>(w0, w1, p, b);
+            if (!tissue_px(b, bg)) continue;
+            tissue(p, b);
+        }
+        item_done();
+    }
+}
+
+// ---- the LDS histogram of the passes that count tissue pixels in int32 bins (ay_stain.hip, ay_stain_basis.hip): units of 16 rows x
+// up to 2048 items; a workgroup's bins go to memory when it is done, and every HIST_FLUSH units before that
+constexpr int HIST_BAND = 16;      // rows of a work unit
+constexpr int HIST_XQ = 2048;      // items of a row in a work unit
+constexpr int HIST_FLUSH = 2048;   // units between two flushes of a workgroup: 2048 * 16 * 2048 * 16 pixels = 1.07e9 < 2^31
+
+// The lane's count joins word `total` of the workgroup's `words` LDS words lh; then every word that is not 0 goes to the 64-bit
+// histogram in memory with one integer atomic and is zeroed.  It holds two barriers: every lane of the workgroup calls it, or none.
+__device__ __forceinline__ void flush_lds_hist(int* lh, int words, int total, int& cnt, unsigned long long* __restrict__ hist) {
+    if (cnt) atomicAdd(&lh[total], cnt);
+    cnt = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < words; i += 256) {
+        const int v = lh[i];
+        if (v) {
+            atomicAdd(hist + i, (unsigned long long)v);
+            lh[i] = 0;
+        }
+    }
+    __syncthreads();
 }
 
 // ---- the launch: launch(wide, shrink) launches the kernel's <wide.value, shrink.value> instance; 16-byte loads when base and stride allow
@@ -174,6 +223,19 @@ static inline bool check_region(const char* entry, int region_h, int region_w, s
     const bool fits = !bound_w || region_w <= (1 << 30) / 3;
     if (region_h > 0 && region_w > 0 && fits && row_stride_bytes >= (size_t)region_w * 3 && (shrink == 1 || shrink == 2)) return true;
     set_error("%s: region %dx%d stride %zu shrink %d", entry, region_h, region_w, row_stride_bytes, shrink);
+    return false;
+}
+static inline bool check_bg_level(const char* entry, int bg_level) {   // 256: every pixel is tissue
+    if (bg_level >= 0 && bg_level <= 256) return true;
+    set_error("%s: bg_level %d outside 0 .. 256", entry, bg_level);
+    return false;
+}
+// the H x W image of the region lies at (origin_y, origin_x) of a slide_h x slide_w slide, inside it
+static inline bool check_on_slide(const char* entry, int H, int W, int origin_y, int origin_x, int slide_h, int slide_w) {
+    if (slide_h >= 1 && slide_h <= SLIDE_MAX_SIDE && slide_w >= 1 && slide_w <= SLIDE_MAX_SIDE && origin_y >= 0 && origin_x >= 0 &&
+        origin_y <= slide_h - H && origin_x <= slide_w - W)
+        return true;
+    set_error("%s: a %dx%d image at (%d, %d) of a %dx%d slide", entry, H, W, origin_y, origin_x, slide_h, slide_w);
     return false;
 }
 static inline bool check_cells_boxes(const char* entry, int n_rows, const float* rows, const void* boxes, const int32_t* flags,

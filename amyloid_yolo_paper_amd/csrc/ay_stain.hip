@@ -17,9 +17,6 @@
 
 namespace ay {
 
-constexpr int HIST_BAND = 16;      // rows of a work unit
-constexpr int HIST_XQ = 2048;      // items of a row in a work unit
-constexpr int HIST_FLUSH = 2048;   // units between two flushes of a workgroup: 2048 * 16 * 2048 * 16 pixels = 1.07e9 < 2^31
 constexpr int HIST_WORDS = 2 * AY_STAIN_BINS + 1;
 
 template <bool WIDE, int SHRINK>
@@ -28,7 +25,6 @@ __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __res
                                                              unsigned long long* __restrict__ hist) {
     __shared__ float od[256];
     __shared__ int lh[HIST_WORDS];
-    constexpr int BPP = 3 * SHRINK;                          // source bytes of one row per image pixel
     const int tid = threadIdx.x;
     od[tid] = params->od[tid];
     float D[9];                                              // uniform: scalar registers
@@ -36,35 +32,14 @@ __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __res
     for (int i = 0; i < 9; ++i) D[i] = params->D[i];
     for (int i = tid; i < HIST_WORDS; i += 256) lh[i] = 0;
     __syncthreads();
-    const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * BPP;   // bytes of a source row; those that belong to a pixel
+    const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * (3 * SHRINK);   // bytes of a source row; those that belong to a pixel
     const unsigned nq = (used + SLIDE_ITEM - 1) / SLIDE_ITEM;
-    int cnt = 0, pending = 0;
-    auto flush = [&]() {
-        if (cnt) atomicAdd(&lh[2 * AY_STAIN_BINS], cnt);
-        cnt = 0;
-        __syncthreads();
-        for (int i = tid; i < HIST_WORDS; i += 256) {
-            const int v = lh[i];
-            if (v) {
-                atomicAdd(hist + i, (unsigned long long)v);
-                lh[i] = 0;
-            }
-        }
-        __syncthreads();
-    };
-    for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of flush
+    int cnt = 0, pending = 0;                                // the lane's tissue pixels since the last flush
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of the flush
         const SlideUnit un = slide_unit<HIST_BAND, HIST_XQ>(u, n_xc, nq, 0, H);
-        const unsigned items = (unsigned)(un.y_hi - un.y_lo) * un.wq;
-        for (unsigned i = tid; i < items; i += 256) {
-            const unsigned o = (un.q0 + i % un.wq) * SLIDE_ITEM;
-            uint32_t w0[12], w1[12];
-            item_load<WIDE, SHRINK>(reg, stride, un.y_lo + (int)(i / un.wq), o, row_bytes, w0, w1);
-#pragma unroll
-            for (int p = 0; p < SLIDE_ITEM / BPP; ++p) {         // the pixels of the item lie at the same bytes in every lane
-                if (o + p * BPP >= used) continue;               // behind the last pixel of the row
-                int b[3];
-                item_pixel<SHRINK>(w0, w1, p, b);
-                if (!tissue_px(b, bg)) continue;
+        tissue_walk<WIDE, SHRINK>(
+            reg, stride, row_bytes, used, un, bg, [](unsigned, int) {},
+            [&](int, const int* b) {
                 ++cnt;
                 const float o0 = od[b[0]], o1 = od[b[1]], o2 = od[b[2]];
 #pragma unroll
@@ -74,14 +49,11 @@ __global__ void __launch_bounds__(256) stain_hist_u8_kernel(const uint8_t* __res
                     const int bin = c < 0.0f ? 0 : (c < 8.0f ? (int)(c * 64.0f) : AY_STAIN_BINS - 1);
                     atomicAdd(&lh[s * AY_STAIN_BINS + bin], 1);
                 }
-            }
-        }
-        if (++pending == HIST_FLUSH) {
-            flush();
-            pending = 0;
-        }
+            },
+            []() {});
+        if (++pending == HIST_FLUSH) flush_lds_hist(lh, HIST_WORDS, 2 * AY_STAIN_BINS, cnt, hist), pending = 0;
     }
-    flush();
+    flush_lds_hist(lh, HIST_WORDS, 2 * AY_STAIN_BINS, cnt, hist);
 }
 
 __global__ void __launch_bounds__(256) stain_apply_u8_kernel(const uint8_t* __restrict__ reg, int RH, int RW, size_t stride, int shrink,
@@ -109,8 +81,8 @@ extern "C" int ay_stain_hist_u8(const void* region_hwc_u8, int region_h, int reg
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && params_device && hist, "ay_stain_hist_u8: null");
     if (!check_region("ay_stain_hist_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
-    AY_CHECK_ARG(bg_level >= 0 && bg_level <= 256 && ((uintptr_t)hist & 7) == 0, "ay_stain_hist_u8: bg_level %d, hist %p", bg_level,
-                 (void*)hist);
+    if (!check_bg_level("ay_stain_hist_u8", bg_level)) return AY_ERR_ARG;
+    AY_CHECK_ARG(((uintptr_t)hist & 7) == 0, "ay_stain_hist_u8: hist %p", (void*)hist);
     const int H = region_h / shrink, W = region_w / shrink;
     if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
     const SlideUnits g = slide_units(W, shrink, H, HIST_BAND, HIST_XQ);

@@ -17,35 +17,22 @@
 
 namespace ay {
 
-constexpr int BASIS_BAND = 16;      // rows of a work unit: ay_stain_hist_u8's
-constexpr int BASIS_XQ = 2048;      // items of a row in a work unit
-constexpr int BASIS_FLUSH = 2048;   // units between two flushes of a workgroup's bins: 2048 * 16 * 2048 * 16 pixels = 1.07e9 < 2^31
 constexpr int BASIS_EQ_MAX = 1024;  // |eq_c| <= 1024: |256 * p2| <= 2466 * 1024 * 3 * 256 < 2^31
 
-// The items of unit `un`, one per lane and step: tissue() for every tissue pixel of the item, selected(o0, o1, o2) for those whose
-// smallest integer OD reaches beta_q, item_done() behind the item's last pixel.
+// The walk over unit `un` with THE BASIS RULE's selection on top: tissue() for every tissue pixel of the item, selected(o0, o1, o2) for
+// those whose smallest integer OD reaches beta_q, item_done() behind the item's last pixel.
 template <bool WIDE, int SHRINK, typename Tissue, typename Selected, typename ItemDone>
 __device__ __forceinline__ void basis_unit(const uint8_t* __restrict__ reg, size_t stride, unsigned row_bytes, unsigned used,
                                            const SlideUnit& un, const int* odq, int bg, int beta_q, Tissue tissue, Selected selected,
                                            ItemDone item_done) {
-    constexpr int BPP = 3 * SHRINK;                          // source bytes of one row per image pixel
-    const unsigned items = (unsigned)(un.y_hi - un.y_lo) * un.wq;
-    for (unsigned i = threadIdx.x; i < items; i += 256) {
-        const unsigned o = (un.q0 + i % un.wq) * SLIDE_ITEM;
-        uint32_t w0[12], w1[12];
-        item_load<WIDE, SHRINK>(reg, stride, un.y_lo + (int)(i / un.wq), o, row_bytes, w0, w1);
-#pragma unroll
-        for (int p = 0; p < SLIDE_ITEM / BPP; ++p) {         // the pixels of the item lie at the same bytes in every lane
-            if (o + p * BPP >= used) continue;               // behind the last pixel of the row
-            int b[3];
-            item_pixel<SHRINK>(w0, w1, p, b);
-            if (!tissue_px(b, bg)) continue;
+    tissue_walk<WIDE, SHRINK>(
+        reg, stride, row_bytes, used, un, bg, [](unsigned, int) {},
+        [&](int, const int* b) {
             tissue();
             const int o0 = odq[b[0]], o1 = odq[b[1]], o2 = odq[b[2]];
             if (min(min(o0, o1), o2) >= beta_q) selected(o0, o1, o2);
-        }
-        item_done();
-    }
+        },
+        item_done);
 }
 
 template <bool WIDE, int SHRINK>
@@ -64,7 +51,7 @@ __global__ void __launch_bounds__(256) stain_moments_u8_kernel(const uint8_t* __
     unsigned long long acc[N] = {};                          // the lane's sums over its items
     int it[N] = {};                                          // the sums of one item: 16 * 2466^2 < 2^31
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {
-        const SlideUnit un = slide_unit<BASIS_BAND, BASIS_XQ>(u, n_xc, nq, 0, H);
+        const SlideUnit un = slide_unit<HIST_BAND, HIST_XQ>(u, n_xc, nq, 0, H);
         basis_unit<WIDE, SHRINK>(
             reg, stride, row_bytes, used, un, odq, bg, beta_q, [&]() { ++it[0]; },
             [&](int o0, int o1, int o2) {
@@ -107,21 +94,8 @@ __global__ void __launch_bounds__(256) stain_direction_hist_u8_kernel(const uint
     const unsigned row_bytes = (unsigned)RW * 3, used = (unsigned)W * (3 * SHRINK);
     const unsigned nq = (used + SLIDE_ITEM - 1) / SLIDE_ITEM;
     int cnt = 0, pending = 0;                                // the lane's selected pixels since the last flush
-    auto flush = [&]() {
-        if (cnt) atomicAdd(&lh[AY_BASIS_DIR_BINS + 1], cnt);
-        cnt = 0;
-        __syncthreads();
-        for (int i = tid; i < AY_BASIS_HIST_WORDS; i += 256) {
-            const int v = lh[i];
-            if (v) {
-                atomicAdd(hist + i, (unsigned long long)v);
-                lh[i] = 0;
-            }
-        }
-        __syncthreads();
-    };
-    for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of flush
-        const SlideUnit un = slide_unit<BASIS_BAND, BASIS_XQ>(u, n_xc, nq, 0, H);
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // u is workgroup-uniform: so are the barriers of the flush
+        const SlideUnit un = slide_unit<HIST_BAND, HIST_XQ>(u, n_xc, nq, 0, H);
         basis_unit<WIDE, SHRINK>(
             reg, stride, row_bytes, used, un, odq, bg, beta_q, []() {},
             [&](int o0, int o1, int o2) {
@@ -138,12 +112,9 @@ __global__ void __launch_bounds__(256) stain_direction_hist_u8_kernel(const uint
                 atomicAdd(&lh[slot], 1);
             },
             []() {});
-        if (++pending == BASIS_FLUSH) {
-            flush();
-            pending = 0;
-        }
+        if (++pending == HIST_FLUSH) flush_lds_hist(lh, AY_BASIS_HIST_WORDS, AY_BASIS_DIR_BINS + 1, cnt, hist), pending = 0;
     }
-    flush();
+    flush_lds_hist(lh, AY_BASIS_HIST_WORDS, AY_BASIS_DIR_BINS + 1, cnt, hist);
 }
 
 static inline bool check_basis(const char* entry, const void* region, int region_h, int region_w, size_t row_stride_bytes, int shrink,
@@ -153,8 +124,9 @@ static inline bool check_basis(const char* entry, const void* region, int region
         return false;
     }
     if (!check_region(entry, region_h, region_w, row_stride_bytes, shrink, true)) return false;
-    if (bg_level >= 0 && bg_level <= 256 && beta_q >= 0 && beta_q <= AY_BASIS_OD_MAX && ((uintptr_t)out & 7) == 0) return true;
-    set_error("%s: bg_level %d, beta_q %d, output %p", entry, bg_level, beta_q, out);
+    if (!check_bg_level(entry, bg_level)) return false;
+    if (beta_q >= 0 && beta_q <= AY_BASIS_OD_MAX && ((uintptr_t)out & 7) == 0) return true;
+    set_error("%s: beta_q %d, output %p", entry, beta_q, out);
     return false;
 }
 
@@ -168,7 +140,7 @@ extern "C" int ay_stain_moments_u8(const void* region_hwc_u8, int region_h, int 
         return AY_ERR_ARG;
     const int H = region_h / shrink, W = region_w / shrink;
     if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
-    const SlideUnits g = slide_units(W, shrink, H, BASIS_BAND, BASIS_XQ);
+    const SlideUnits g = slide_units(W, shrink, H, HIST_BAND, HIST_XQ);
     launch_wide_shrink(region_hwc_u8, row_stride_bytes, shrink, [&](auto wide, auto sh) {
         hipLaunchKernelGGL((stain_moments_u8_kernel<wide.value, sh.value>), dim3(g.blocks), dim3(256), 0, S(stream),
                            (const uint8_t*)region_hwc_u8, H, W, region_w, row_stride_bytes, bg_level, beta_q, g.n_xc, g.units, params_device,
@@ -191,7 +163,7 @@ extern "C" int ay_stain_direction_hist_u8(const void* region_hwc_u8, int region_
                      eq[i]);
     const int H = region_h / shrink, W = region_w / shrink;
     if (H == 0 || W == 0) return AY_OK;   // a one-pixel region has no halved image
-    const SlideUnits g = slide_units(W, shrink, H, BASIS_BAND, BASIS_XQ);
+    const SlideUnits g = slide_units(W, shrink, H, HIST_BAND, HIST_XQ);
     launch_wide_shrink(region_hwc_u8, row_stride_bytes, shrink, [&](auto wide, auto sh) {
         hipLaunchKernelGGL((stain_direction_hist_u8_kernel<wide.value, sh.value>), dim3(g.blocks), dim3(256), 0, S(stream),
                            (const uint8_t*)region_hwc_u8, H, W, region_w, row_stride_bytes, bg_level, beta_q, eq1_0, eq1_1, eq1_2, eq2_0,

@@ -118,9 +118,9 @@ extern "C" int ay_tile_tissue_u8(const void* region_hwc_u8, int region_h, int re
     using namespace ay;
     AY_CHECK_ARG(region_hwc_u8 && counts, "ay_tile_tissue_u8: null");
     if (!check_region("ay_tile_tissue_u8", region_h, region_w, row_stride_bytes, shrink, true)) return AY_ERR_ARG;
-    AY_CHECK_ARG(tile > 0 && tile <= 46340 /* a count is at most tile^2: int32 */ && step > 0 && step <= tile && tiles_y > 0 && tiles_x > 0 && (long long)tiles_y * tiles_x <= (1 << 30) &&
-                     bg_level >= 0 && bg_level <= 256,
-                 "ay_tile_tissue_u8: tile grid %dx%d of %d step %d, bg_level %d", tiles_y, tiles_x, tile, step, bg_level);
+    AY_CHECK_ARG(tile > 0 && tile <= 46340 /* a count is at most tile^2: int32 */ && step > 0 && step <= tile && tiles_y > 0 && tiles_x > 0 && (long long)tiles_y * tiles_x <= (1 << 30),
+                 "ay_tile_tissue_u8: tile grid %dx%d of %d step %d", tiles_y, tiles_x, tile, step);
+    if (!check_bg_level("ay_tile_tissue_u8", bg_level)) return AY_ERR_ARG;
     const int T = tiles_y * tiles_x;
     hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)((T + 255) / 256 > 1024 ? 1024 : (T + 255) / 256)), dim3(256), 0, S(stream), counts, T);
     AY_CHECK_LAUNCH("zero_i32_kernel");

@@ -1,0 +1,181 @@
+"""Spatial statistics: :func:`spatial_stats` counts the cross-class pairs of a slide's detections within every radius and finds every
+row's nearest neighbour of every class (``ay_pair_counts``, THE PAIR RULE), and turns them into Ripley's K and L, the pair correlation
+and the nearest-neighbour distribution on the host."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import check, ptr
+from ..stats import _slide_array
+from .grid import _whole, check_rows, hip_device
+
+
+PAIR_MAX_CLASSES, PAIR_MAX_RADII, PAIR_MAX_RADIUS_Q, PAIR_MAX_SIDE = 8, 32, 32767, 1 << 21      # include/amyloid_yolo.h, THE PAIR RULE
+
+
+def spatial_radii_q(radii):
+    """radii in pixels -> int32 ``R_k = floor(4 r_k)`` quarter pixels; ``ValueError`` unless they are 1 .. 32 finite values whose
+    ``R_k`` ascend strictly inside 1 .. 32767 (radii that collapse onto one quarter pixel do not)"""
+    try:
+        r = np.asarray(radii, np.float64).reshape(-1) if not isinstance(radii, (str, bytes)) and np.ndim(radii) == 1 else None
+    except (TypeError, ValueError):
+        r = None
+    if r is None or not 1 <= len(r) <= PAIR_MAX_RADII or not np.isfinite(r).all():
+        raise ValueError(f"spatial radii {radii!r}: need a sequence of 1 .. {PAIR_MAX_RADII} finite radii in pixels")
+    q = np.floor(4.0 * r)
+    if q[0] < 1 or q[-1] > PAIR_MAX_RADIUS_Q or (np.diff(q) <= 0).any():
+        raise ValueError(f"spatial radii {radii!r}: floor(4 r) = {q.tolist()} must ascend strictly inside 1 .. {PAIR_MAX_RADIUS_Q} "
+                         "(radii below a quarter pixel apart collapse onto one another)")
+    return q.astype(np.int32)
+
+
+def spatial_roi_q(roi, slide_hw):
+    """``roi`` = (x1, y1, x2, y2) in pixels -> int32 (ceil(4 x1), ceil(4 y1), floor(4 x2), floor(4 y2)) clipped to the positions
+    0 .. 4W-1, 0 .. 4H-1 of the slide: the quarter-pixel positions inside the closed rectangle.  None is the whole slide.
+    ``ValueError`` if no position is left."""
+    H, W = slide_hw
+    if roi is None:
+        return np.array([0, 0, 4 * W - 1, 4 * H - 1], np.int32)
+    try:
+        v = np.asarray(roi, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        v = np.zeros(0)
+    if len(v) != 4 or not np.isfinite(v).all():
+        raise ValueError(f"spatial roi {roi!r}: need (x1, y1, x2, y2), finite, in pixels")
+    q = [max(math.ceil(4.0 * v[0]), 0), max(math.ceil(4.0 * v[1]), 0), min(math.floor(4.0 * v[2]), 4 * W - 1), min(math.floor(4.0 * v[3]), 4 * H - 1)]
+    if q[0] > q[2] or q[1] > q[3]:
+        raise ValueError(f"spatial roi {roi!r} holds no position of the {H} x {W} slide")
+    return np.array(q, np.int32)
+
+
+def _check_spatial(what, slide_hw, radii, num_classes, roi, area, mpp=None):
+    """the host checks of :func:`spatial_stats` -> (H, W, C, radii_q, roi_q, area)"""
+    if slide_hw is None or isinstance(slide_hw, (str, bytes)) or np.ndim(slide_hw) != 1 or len(slide_hw) != 2:
+        raise ValueError(f"{what}: slide_hw {slide_hw!r} is no (H, W)")
+    H, W = (_whole(v, 1, PAIR_MAX_SIDE, f"{what}: slide_hw") for v in slide_hw)
+    nc = _whole(num_classes, 1, PAIR_MAX_CLASSES, f"{what}: num_classes (spatial statistics)")
+    rq = spatial_radii_q(radii)
+    roi_q = spatial_roi_q(roi, (H, W))
+    if area is None:
+        area = float(int(roi_q[2]) - int(roi_q[0]) + 1) * float(int(roi_q[3]) - int(roi_q[1]) + 1) / 16.0
+    elif isinstance(area, bool) or not 0.0 <= float(area) < math.inf:
+        raise ValueError(f"{what}: area {area!r} is no area >= 0 in square pixels")
+    if mpp is not None and (isinstance(mpp, bool) or not 0.0 < float(mpp) < math.inf):
+        raise ValueError(f"{what}: mpp {mpp!r} is no positive number of microns per pixel")
+    return H, W, nc, rq, roi_q, float(area)
+
+
+def pair_counts_device(rows, slide_hw, radii_q, num_classes, min_conf=0.0, roi_q=None, border=True, cell_side_q=0):
+    """``ay_pair_counts`` on rows that live on the device (float32 [M,7], contiguous) -> a dict of int tensors on the device, all views
+    of ONE buffer ``buf`` (so that a caller reads back once): ``pairs`` int64 [C,C,B], ``centres`` int32 [C,B], ``stats`` int32
+    [2C+3], ``bd`` int32 [M], ``nn`` int32 [M,C,2], and ``label`` int32 [M], the rows' ``cls_pred`` as integers (a torch copy, for
+    the host formulas).  Launches only: nothing is read back here.  ``cell_side_q`` overrides the grid's
+    cell side (quarter pixels, at least the largest radius); the result does not depend on it."""
+    H, W = slide_hw
+    M, nc = int(rows.shape[0]), int(num_classes)
+    rq = np.ascontiguousarray(radii_q, np.int32)
+    B = len(rq)
+    L = _lib.lib()
+    sizes = [2 * nc * nc * B, nc * B, 2 * nc + 3, M, 2 * M * nc, M]
+    offs = np.concatenate([[0], np.cumsum([(n + 3) & ~3 for n in sizes])])       # every piece starts on 16 bytes
+    buf = torch.empty(max(int(offs[-1]), 4), device=rows.device, dtype=torch.int32)
+    piece = [buf[int(o):int(o) + n] for o, n in zip(offs[:-1], sizes)]
+    out = {"buf": buf, "pairs": piece[0].view(torch.int64).view(nc, nc, B), "centres": piece[1].view(nc, B), "stats": piece[2], "bd": piece[3],
+           "nn": piece[4].view(M, nc, 2), "label": piece[5]}
+    if M:       # cls_pred as an integer next to the outputs (a value that is no class becomes -1 or a number no class has)
+        out["label"].copy_(torch.nan_to_num(rows[:, 6], nan=-1.0, posinf=-1.0, neginf=-1.0).clamp(-1.0, 255.0))
+    need = int(L.ay_pair_counts_workspace_bytes(M, H, W, int(rq[-1]) if B else 0, int(cell_side_q)))
+    ws = torch.empty(max(need, 16), device=rows.device, dtype=torch.uint8)
+    i32p = C.POINTER(C.c_int32)
+    roi_arg = None if roi_q is None else np.ascontiguousarray(roi_q, np.int32).ctypes.data_as(i32p)
+    check(L.ay_pair_counts(ptr(rows) if M else None, M, nc, H, W, C.c_float(min_conf), rq.ctypes.data_as(i32p), B, roi_arg, int(bool(border)),
+                           int(cell_side_q), ptr(out["pairs"]), ptr(out["centres"]), ptr(out["nn"]) if M else None, ptr(out["bd"]) if M else None,
+                           ptr(out["stats"]), ptr(ws), need, _lib.stream_ptr()), "ay_pair_counts")
+    return out
+
+
+def spatial_summaries(pairs, centres, inside, bd, nn, radii_q, area, mpp=None, labels=None):
+    """The host formulas of :func:`spatial_stats`, float64, NaN wherever a denominator is 0.  ``labels`` int [M]: the class of every
+    counted row (-1: not counted), needed for ``G``."""
+    pairs, centres, inside = np.asarray(pairs, np.float64), np.asarray(centres, np.float64), np.asarray(inside, np.float64)
+    rq = np.asarray(radii_q, np.int64)
+    r = rq / 4.0
+    nc, B = centres.shape
+    with np.errstate(all="ignore"):
+        intensity = inside / area if area > 0 else np.full(nc, np.nan)
+        den = centres[:, None, :] * intensity[None, :, None]
+        K = np.where(den > 0, pairs / den, np.nan)
+        Lf = np.sqrt(K / math.pi)
+        prev_K = np.concatenate([np.zeros((nc, nc, 1)), K[:, :, :-1]], 2)
+        prev_r = np.concatenate([[0.0], r[:-1]])
+        g = (K - prev_K) / (math.pi * (r ** 2 - prev_r ** 2))
+        G = np.full((nc, nc, B), np.nan)
+        bd, nn = np.asarray(bd), np.asarray(nn)
+        for a in range(nc):
+            mine = labels == a
+            for k in range(B):
+                sel = mine & (bd >= rq[k])
+                if sel.any():
+                    d2 = nn[sel, :, 0].astype(np.int64)
+                    G[a, :, k] = ((d2 >= 0) & (d2 <= rq[k] * rq[k])).mean(0)
+    out = {"intensity": intensity, "K": K, "L": Lf, "L_minus_r": Lf - r, "g": g, "G": G}
+    if mpp is not None:
+        out["radii_um"], out["K_um2"] = r * float(mpp), K * float(mpp) ** 2
+    return out
+
+
+def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, border=True, area=None, mpp=None):
+    """Spatial statistics of a slide's detections (``ay_pair_counts``, THE PAIR RULE in ``include/amyloid_yolo.h``): the cross-class
+    pair counts within every radius, and Ripley's K and L, the pair correlation g and the nearest-neighbour distribution G from them.
+
+    ``rows`` [M,7] as :func:`burden_map` takes them; ``slide_hw`` = (H, W), each at most 2**21; ``num_classes`` = C in 1 .. 8.  A row
+    is counted under THE BURDEN RULE's tests (``conf >= min_conf``, a finite centre, a class in 0 .. C-1) and stands at the quarter
+    pixel of its centre.  ``radii`` are in pixels: ``R_k = floor(4 r_k)`` quarter pixels, 1 .. 32 of them, strictly ascending after
+    the conversion and at most 8191.75 px (``ValueError`` otherwise); the effective radii ``R_k / 4`` are returned.  ``roi`` =
+    (x1, y1, x2, y2) in pixels is the window: it becomes (ceil(4 x1), ceil(4 y1), floor(4 x2), floor(4 y2)), clipped to the slide; None
+    is the whole slide.  With ``border=True`` (minus-sampling) a row is a centre at radius k only if it lies at least ``R_k`` inside
+    the window, so that its whole disc was observed; its partners may lie anywhere.  ``border=False`` takes every row inside the
+    window as a centre at every radius.  One call, one read-back.
+
+    Returns a dict.  Raw: ``pairs`` int64 [C,C,B] (ordered pairs, cumulative in k: over the eligible centres of class a, the
+    counted rows of class b within ``r_k``, the centre itself excluded), ``centres`` int32 [C,B], ``nn`` int32 [M,C,2] = (d2 in
+    quarter pixels squared, row index) of the nearest counted row of every class within the largest radius, ties to the lowest
+    index, -1 where there is none, ``nn_index`` int32 [M,C], ``nn_distance`` float64 [M,C] in pixels (NaN where there is none),
+    ``bd`` int32 [M] (quarter pixels to the window's border, -1 outside and for rows not counted), ``counted`` and ``inside`` [C],
+    ``below``, ``flagged``, ``flags``, ``radii`` (effective, px), ``radii_q``, ``roi_q``, ``area``.  Derived, float64 on the host, NaN
+    wherever a denominator is 0: ``intensity[b] = inside[b] / area`` (``area`` in px**2; default: the window's; callers pass
+    tissue pixels), ``K[a,b,k] = pairs / (centres[a,k] * intensity[b])``, ``L = sqrt(K / pi)``, ``L_minus_r``, ``g[k] = (K_k -
+    K_{k-1}) / (pi (r_k**2 - r_{k-1}**2))`` with ``K_{-1} = r_{-1} = 0``, and ``G[a,b,k]``: the share of the class-a rows with
+    ``bd >= R_k`` whose nearest b lies within ``r_k``.  With ``mpp`` also ``radii_um`` and ``K_um2``.  Under complete spatial
+    randomness ``K = pi r**2``, ``L - r = 0`` and ``g = 1``; clustering at a scale shows as larger values there.
+
+    Two limits.  The window is a RECTANGLE: with ``area=`` tissue pixels on a slide whose tissue outline is ragged, centres near a
+    tissue edge have part of their disc over glass, and K is biased low there.  Comparing ``K[a][b]`` with ``K[a][a]`` on the same
+    slide, or working inside a field (``roi=``) that is all tissue, is the robust use.  And the COST is the number of pairs within
+    3 x 3 grid cells of side ``r_max``: quadratic in ``r_max`` at a given density.
+
+    Out of scope: Monte-Carlo envelopes (random relabelling of the classes is the natural follow-up), per-field statistics (pass a
+    field as ``roi=``) and windows that are no rectangles."""
+    H, W, nc, rq, roi_q, area = _check_spatial("spatial_stats", slide_hw, radii, num_classes, roi, area, mpp)
+    check_rows("spatial_stats", rows)
+    min_conf = float(min_conf)
+    dev = hip_device("the spatial statistics have")
+    rows = _slide_array(rows, 7, dev)
+    M = int(rows.shape[0])
+    dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border)
+    host = dv["buf"].cpu()                                              # the one read-back
+    off = lambda t: (t.data_ptr() - dv["buf"].data_ptr()) // 4
+    take = lambda t: host[off(t):off(t) + t.numel() * t.element_size() // 4]
+    pairs = take(dv["pairs"]).view(torch.int64).view(nc, nc, len(rq)).numpy().copy()
+    centres, st = take(dv["centres"]).view(nc, len(rq)).numpy().copy(), take(dv["stats"]).numpy().copy()
+    bd, nn = take(dv["bd"]).numpy().copy(), take(dv["nn"]).view(M, nc, 2).numpy().copy()
+    d2 = nn[:, :, 0].astype(np.float64)
+    labels = np.where(bd >= 0, take(dv["label"]).numpy(), -1)          # G asks rows with bd >= R_k >= 1 only: those are counted
+    out = {"pairs": pairs, "centres": centres, "nn": nn, "nn_index": nn[:, :, 1].copy(), "nn_distance": np.where(d2 >= 0, np.sqrt(np.abs(d2)) / 4.0, np.nan),
+           "bd": bd, "counted": st[:nc].copy(), "inside": st[nc:2 * nc].copy(), "below": int(st[2 * nc]), "flagged": int(st[2 * nc + 1]),
+           "flags": int(st[2 * nc + 2]), "radii": rq / 4.0, "radii_q": rq, "roi_q": roi_q, "area": area}
+    out.update(spatial_summaries(pairs, centres, out["inside"], bd, nn, rq, area, mpp, labels))
+    return out

@@ -214,7 +214,7 @@ def test_estimate_basis_is_the_reference_on_the_same_view(dev, monkeypatch, stri
     if stride == 16 and shrink == 1:
         check_estimate(estimate_basis(r), want)                                       # the defaults
     for strip in (7, 40):                                                             # the result does not depend on the strips
-        monkeypatch.setattr(wsi, "BASIS_STRIP", strip)
+        monkeypatch.setattr(wsi.basis, "BASIS_STRIP", strip)
         check_estimate(estimate_basis(r, shrink=shrink, probe_stride=stride), want)
         check_estimate(estimate_basis(torch.from_numpy(np.array(r)).to(dev), shrink=shrink, probe_stride=stride), want)
     monkeypatch.undo()

@@ -423,7 +423,7 @@ def test_defaults_are_the_path_without_views(tmp_cfg_dir, dev, monkeypatch):
     raster = region_raster()
     kw = dict(tile=TILE, img_size=S, conf_thres=CONF, nms_thres=NMS, batch_size=BATCH)
     calls = []
-    monkeypatch.setattr(wsi, "nms_views_device", lambda *a, **k: calls.append(1) or nms_views_device(*a, **k))
+    monkeypatch.setattr(wsi.detect, "nms_views_device", lambda *a, **k: calls.append(1) or nms_views_device(*a, **k))
     for extra in (dict(), dict(overlap=OVERLAP, seam_thres=SEAM)):
         a = detect_region(m, raster, **kw, **extra)                 # never passes the new arguments
         b = detect_region(m, raster, views=(0,), min_views=1, vote_thres=None, **kw, **extra)
