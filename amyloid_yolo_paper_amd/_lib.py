@@ -176,6 +176,9 @@ _SIGS = {
     "ay_field_select": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "ay_pair_counts_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "ay_pair_counts": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ay_pair_counts_window_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "ay_pair_counts_window": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ,
+                                   _P]),
     "ay_stain_hist_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _P, _P]),
     "ay_ingest_region_tiles_stain_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, C.POINTER(C.c_int), _I, _P, _I, _P, _P]),
     "ay_stain_apply_u8": (_I, [_P, _I, _I, _SZ, _I, _P, _P, _SZ, _P]),

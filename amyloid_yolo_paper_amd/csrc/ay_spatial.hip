@@ -33,6 +33,23 @@
 // wavefront slots; 160 KiB / 2 944 B is far beyond that, so the usual call is not limited by LDS, and at the limits 160 KiB /
 // 33 920 B = 4 workgroups per CU, half the slots: the price of the group tables where C x B is at its largest (32-bit workgroup sums
 // would save 8 KiB there and could overflow on a dense slide).
+//
+// THE PAIR WINDOW RULE (ay_pair_counts_window; stated next to THE PAIR RULE, restated by tests/spatial_window_reference.py): the border
+// distance of minus-sampling measured to the edge of a MASK on cells of mask_cell pixels, not only to the four lines of the ROI.  Two
+// kernels in front of the count kernel, which takes their result as one more bound (wbd) and is otherwise the plain call's:
+//   a. pair_window_bits_kernel, one lane per (chunk of 64 mask rows, mask column), coalesced across the columns: the OUT cells of the
+//      chunk as the bits of one word, bits [ceil(Gy / 64)][Gx].  Every word is written, so nothing is reset.
+//   b. pair_window_dist_kernel, a group of 16 lanes per row: the lanes stride over the mask columns within R_max of the row (and
+//      the virtual columns -1 and Gx, wholly OUT); in a column every position has the same horizontal distance, so the nearest OUT
+//      position of the column is dx and the vertical distance to the nearest OUT cell above or below (or the slide's edge).  That
+//      comes from the column's words: count-leading / count-trailing zeros in the word of the row's own cell row, and where that word
+//      has no OUT cell on a side, a walk over the next words of the column as far as R_max reaches (R_max / (64 Sc) + 1 words, 9 at
+//      the limits).  Both offsets are capped at R_max + 1 <= 32 768, so dx^2 + dy^2 <= 2^31: UNSIGNED 32-bit.  The minimum goes
+//      across the group by four shuffles; wbd = the largest d in -1 .. R_max with d^2 < the minimum, an integer square root (a float
+//      estimate, corrected on integers).  wbd [M] is written for every row (-1 for rows not counted).
+//   The decomposition first built kept, per mask cell, the nearest OUT row above and below (8 bytes a cell, one more kernel): on a
+//   16-px mask writing them was the largest part of what the window added.  Reading the words in the distance kernel instead makes
+//   the call faster at small radii and leaves it level at large ones, with 1/64 of the workspace (profiles/spatial_window.txt).
 #include <limits.h>
 
 #include "ay_box_grid.h"
@@ -90,11 +107,28 @@ __device__ __forceinline__ bool pair_finite(float v) { return fabsf(v) <= 3.4028
 // exact in fp32 (n <= 2^21)
 __device__ __forceinline__ int pair_position(float c, int q_max) { return (int)floorf(fminf(fmaxf(c * 4.0f, 0.0f), (float)q_max)); }
 
-// one lane per row: THE PAIR RULE up to the position; row_q = (qx, qy), row_ck = class | (kmax + 1) << 8 for the scatter
+// THE PAIR RULE's centre and tests of one row: 0 for a counted row (its class in *c), the flag bits of a flagged row, -1 for a row below
+__device__ __forceinline__ int pair_row(const float* __restrict__ r, int C, float min_conf, float* cx, float* cy, int* c) {
+    const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3], conf = r[4], label = r[6];
+    *cx = (x1 + x2) * 0.5f, *cy = (y1 + y2) * 0.5f;
+    int flags = 0;
+    *c = -1;
+    if (!(pair_finite(*cx) && pair_finite(*cy))) flags |= AY_BURDEN_FLAG_NONFINITE;
+    if (label >= 0.0f && label < (float)C) {
+        *c = (int)label;
+        if ((float)*c != label) *c = -1;
+    }
+    if (*c < 0) flags |= AY_BURDEN_FLAG_CLASS;
+    if (flags) return flags;
+    return conf >= min_conf ? 0 : -1;
+}
+
+// one lane per row: THE PAIR RULE up to the position; row_q = (qx, qy), row_ck = class | (kmax + 1) << 8 for the scatter.  wbd: the
+// mask's bound on the border distance per row (THE PAIR WINDOW RULE), NULL for the plain call
 __global__ void __launch_bounds__(PAIR_THREADS) pair_count_kernel(const float* __restrict__ rows, int M, int C, int q_max_x, int q_max_y, float min_conf,
-                                                                   PairRadii rad, PairWindow win, PairGrid g, int32_t* __restrict__ cell_of,
-                                                                   int32_t* __restrict__ cell_start, int2* __restrict__ row_q,
-                                                                   int32_t* __restrict__ row_ck, int32_t* __restrict__ bd,
+                                                                   PairRadii rad, PairWindow win, PairGrid g, const int32_t* __restrict__ wbd,
+                                                                   int32_t* __restrict__ cell_of, int32_t* __restrict__ cell_start,
+                                                                   int2* __restrict__ row_q, int32_t* __restrict__ row_ck, int32_t* __restrict__ bd,
                                                                    int32_t* __restrict__ centres, int32_t* __restrict__ stats) {
     __shared__ int sh[2 * AY_PAIR_MAX_CLASSES + 3];                  // counted per class, inside per class, below, flagged, flag bits
     __shared__ int cen[AY_PAIR_MAX_CLASSES * AY_PAIR_MAX_RADII];     // rows of class a whose largest eligible k is kmax
@@ -104,26 +138,20 @@ __global__ void __launch_bounds__(PAIR_THREADS) pair_count_kernel(const float* _
     __syncthreads();
     const long long i = (long long)blockIdx.x * PAIR_THREADS + threadIdx.x;
     if (i < M) {
-        const float* r = rows + (size_t)i * 7;
-        const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3], conf = r[4], label = r[6];
-        const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
-        int flags = 0, c = -1;
-        if (!(pair_finite(cx) && pair_finite(cy))) flags |= AY_BURDEN_FLAG_NONFINITE;
-        if (label >= 0.0f && label < (float)C) {
-            c = (int)label;
-            if ((float)c != label) c = -1;
-        }
-        if (c < 0) flags |= AY_BURDEN_FLAG_CLASS;
-        if (flags) {
+        float cx, cy;
+        int c;
+        const int flags = pair_row(rows + (size_t)i * 7, C, min_conf, &cx, &cy, &c);
+        if (flags > 0) {
             atomicAdd(&sh[2 * C + 1], 1);
             atomicOr(&sh[2 * C + 2], flags);
             cell_of[i] = -1;
-        } else if (!(conf >= min_conf)) {
+        } else if (flags < 0) {
             atomicAdd(&sh[2 * C], 1);
             cell_of[i] = -1;
         } else {
             const int qx = pair_position(cx, q_max_x), qy = pair_position(cy, q_max_y);
-            const int d = min(min(qx - win.x1, win.x2 - qx), min(qy - win.y1, win.y2 - qy));
+            int d = min(min(qx - win.x1, win.x2 - qx), min(qy - win.y1, win.y2 - qy));
+            if (wbd) d = min(d, wbd[i]);
             int kmax = -1;
             if (win.border) {   // the radii ascend: the eligible k are a prefix (INT_MAX behind the last radius)
 #pragma unroll
@@ -154,6 +182,101 @@ __global__ void __launch_bounds__(PAIR_THREADS) pair_count_kernel(const float* _
         for (int kk = k; kk < B; ++kk) v += cen[a * B + kk];
         if (v) atomicAdd(&centres[e], v);
     }
+}
+
+// ---- THE PAIR WINDOW RULE: the two kernels in front of the count kernel (a, b at the top of this file)
+constexpr int PAIR_WINDOW_CHUNK = 64;                                     // mask rows of one word of `bits`
+constexpr int PAIR_WINDOW_GROUP = 16;                                     // lanes that share a row in pair_window_dist_kernel
+constexpr int PAIR_WINDOW_ROWS = PAIR_THREADS / PAIR_WINDOW_GROUP;        // rows of a workgroup there
+
+struct PairMask {
+    int S, gx, gy;   // cell side in quarter pixels, cells across, cells down
+    __host__ __device__ int n_chunks() const { return (gy + PAIR_WINDOW_CHUNK - 1) / PAIR_WINDOW_CHUNK; }
+};
+
+// the mask grid of the arguments; false where the call refuses them
+static inline bool pair_mask_grid(int H, int W, int mask_cell, PairMask* m) {
+    if (mask_cell < AY_PAIR_WINDOW_MIN_CELL || mask_cell > AY_PAIR_MAX_SIDE) return false;
+    const long long gx = ((long long)W + mask_cell - 1) / mask_cell, gy = ((long long)H + mask_cell - 1) / mask_cell;
+    if (gx * gy > AY_PAIR_WINDOW_MAX_CELLS) return false;
+    m->S = 4 * mask_cell, m->gx = (int)gx, m->gy = (int)gy;
+    return true;
+}
+
+// bits[c][g]: bit r is set iff mask cell (64 c + r, g) is OUT (zero); rows past Gy leave their bits clear
+__global__ void __launch_bounds__(PAIR_THREADS) pair_window_bits_kernel(const uint8_t* __restrict__ mask, PairMask m, unsigned long long* __restrict__ bits) {
+    const int t = blockIdx.x * PAIR_THREADS + threadIdx.x;
+    if (t >= m.n_chunks() * m.gx) return;
+    const int c = t / m.gx, g = t - c * m.gx, y0 = c * PAIR_WINDOW_CHUNK, n = min(PAIR_WINDOW_CHUNK, m.gy - y0);
+    unsigned long long w = 0;
+#pragma unroll 8
+    for (int r = 0; r < n; ++r) w |= (unsigned long long)(mask[(y0 + r) * m.gx + g] == 0) << r;   // (the loads are independent of w)
+    bits[t] = w;
+}
+
+// floor(sqrt(v)) for v < 2^31: a float estimate, corrected on integers (s <= 46 341, so the squares fit 32 bits unsigned)
+__device__ __forceinline__ unsigned pair_isqrt(unsigned v) {
+    unsigned s = (unsigned)sqrtf((float)v);
+    while (s * s > v) --s;
+    while ((s + 1) * (s + 1) <= v) ++s;
+    return s;
+}
+
+// the vertical distance (capped at `cap`) from position qy of mask row cy0 to the nearest OUT position of column g: 0 in an OUT cell,
+// else to the nearest OUT cell above and below from the column's words, or to the slide's edge.  A walk over the words ends where the
+// next word's nearest row is beyond `cap`: what lies further, the slide's edge included, is capped anyway.
+__device__ __forceinline__ int pair_window_dy(const unsigned long long* __restrict__ bits, const PairMask& m, int g, int cy0, int qy, int qh, int cap) {
+    const int c0 = cy0 / PAIR_WINDOW_CHUNK, r = cy0 % PAIR_WINDOW_CHUNK, n_chunks = m.n_chunks();
+    const unsigned long long w = bits[c0 * m.gx + g];
+    if ((w >> r) & 1) return 0;
+    unsigned long long a = w & (~0ull >> (63 - r)), b = w >> r;   // the OUT rows above and below cy0 in its word
+    int ca = c0, cb = c0;
+    while (!a && ca > 0 && qy - (ca * PAIR_WINDOW_CHUNK * m.S - 1) <= cap) a = bits[--ca * m.gx + g];
+    while (!b && cb + 1 < n_chunks && (cb + 1) * PAIR_WINDOW_CHUNK * m.S - qy <= cap) b = bits[++cb * m.gx + g];
+    const int up = a ? ca * PAIR_WINDOW_CHUNK + 63 - __clzll((long long)a) : -1;                                          // -1: the slide's upper edge
+    const int down = b ? (cb == c0 ? cy0 : cb * PAIR_WINDOW_CHUNK) + __ffsll((long long)b) - 1 : m.gy;                     // Gy: its lower edge
+    const int above = qy - ((up + 1) * m.S - 1), below = down >= m.gy ? qh - qy : down * m.S - qy;
+    return min(min(above, below), cap);
+}
+
+// a group of PAIR_WINDOW_GROUP lanes per row: wbd[i] = the largest d in -1 .. r_max with d^2 < the squared distance from row i's
+// position to the nearest OUT position (outside the slide, or in a zero cell of the mask); -1 for rows that are not counted.
+// dx^2 + dy^2 is UNSIGNED 32-bit: both offsets are capped at r_max + 1 <= 32 768, the sum reaches 2^31.
+__global__ void __launch_bounds__(PAIR_THREADS) pair_window_dist_kernel(const float* __restrict__ rows, int M, int C, int q_max_x, int q_max_y, float min_conf,
+                                                                         int r_max, PairMask m, const unsigned long long* __restrict__ bits,
+                                                                         int32_t* __restrict__ wbd) {
+    const int lane = threadIdx.x & (PAIR_WINDOW_GROUP - 1);
+    const long long i = (long long)blockIdx.x * PAIR_WINDOW_ROWS + threadIdx.x / PAIR_WINDOW_GROUP;
+    const int cap = r_max + 1, qw = q_max_x + 1, qh = q_max_y + 1;
+    unsigned best = (unsigned)cap * (unsigned)cap;   // no OUT position within r_max
+    bool counted = false;
+    if (i < M) {
+        float cx, cy;
+        int c;
+        counted = pair_row(rows + (size_t)i * 7, C, min_conf, &cx, &cy, &c) == 0;
+        if (counted) {
+            const int qx = pair_position(cx, q_max_x), qy = pair_position(cy, q_max_y), cy0 = qy / m.S;
+            // the columns within r_max of qx; -1 and Gx are the half-planes left and right of the slide
+            const int g_lo = qx >= r_max ? (qx - r_max) / m.S : -1, g_hi = qx + r_max >= qw ? m.gx : (qx + r_max) / m.S;
+            for (int g = g_lo + lane; g <= g_hi; g += PAIR_WINDOW_GROUP) {
+                int dx, dy = 0;
+                if (g < 0) {
+                    dx = qx + 1;
+                } else if (g >= m.gx) {
+                    dx = qw - qx;
+                } else {
+                    const int x0 = g * m.S, x1 = min(x0 + m.S, qw) - 1;   // (the last cell of a row is cut by the slide)
+                    dx = max(max(x0 - qx, qx - x1), 0);
+                    dy = pair_window_dy(bits, m, g, cy0, qy, qh, cap);
+                }
+                dx = min(dx, cap);
+                best = min(best, (unsigned)(dx * dx) + (unsigned)(dy * dy));
+            }
+        }
+    }
+#pragma unroll
+    for (int o = PAIR_WINDOW_GROUP / 2; o > 0; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o, PAIR_WINDOW_GROUP));
+    if (i < M && lane == 0) wbd[i] = counted && best ? (int)min(pair_isqrt(best - 1), (unsigned)r_max) : -1;
 }
 
 // ---- the scan of the cell histogram in three levels.  grid_scan_kernel is ONE workgroup: right for the grids of the seam merge and the
@@ -309,14 +432,16 @@ __global__ void __launch_bounds__(PAIR_THREADS) __attribute__((amdgpu_num_sgpr(9
 }
 
 struct PairWs {
-    int32_t *cell_of, *row_ck, *sqx, *sqy, *sorig, *cell_start, *cursor, *chunk_sum;
+    int32_t *cell_of, *row_ck, *sqx, *sqy, *sorig, *cell_start, *cursor, *chunk_sum, *wbd;
     int2* row_q;
+    unsigned long long* bits;
     uint8_t* scls;
     int8_t* skmax;
     size_t bytes;
 };
 
-static PairWs pair_carve(void* ws, int n_rows, size_t n_cells) {
+// mask: the mask grid of the window call, NULL for the plain call (whose workspace is then what it was)
+static PairWs pair_carve(void* ws, int n_rows, size_t n_cells, const PairMask* mask) {
     PairWs w;
     WsCarver cv(ws);
     const size_t m = (size_t)(n_rows > 0 ? n_rows : 1);
@@ -331,6 +456,11 @@ static PairWs pair_carve(void* ws, int n_rows, size_t n_cells) {
     w.cell_start = cv.take<int32_t>(n_cells + 2);
     w.cursor = cv.take<int32_t>(n_cells + 2);
     w.chunk_sum = cv.take<int32_t>((n_cells + PAIR_SCAN_CHUNK - 1) / PAIR_SCAN_CHUNK + 2);
+    w.wbd = nullptr, w.bits = nullptr;
+    if (mask) {
+        w.wbd = cv.take<int32_t>(m);
+        w.bits = cv.take<unsigned long long>((size_t)mask->gx * mask->n_chunks());
+    }
     w.bytes = cv.bytes();
     return w;
 }
@@ -345,44 +475,52 @@ static inline unsigned pair_blocks(long long n, long long cap) {
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-}  // namespace ay
-
-extern "C" size_t ay_pair_counts_workspace_bytes(int n_rows, int slide_h, int slide_w, int r_max_q, int cell_side_q) {
-    ay::PairGrid g;
-    if (!ay::pair_dims_ok(n_rows, slide_h, slide_w, r_max_q, cell_side_q) || !ay::pair_grid(n_rows, slide_h, slide_w, r_max_q, cell_side_q, &g)) return 0;
-    return ay::pair_carve(nullptr, n_rows, (size_t)g.n_cells()).bytes;
+static size_t pair_workspace_bytes(int n_rows, int H, int W, int r_max, int cell_side, bool windowed, int mask_cell) {
+    PairGrid g;
+    PairMask mg;
+    if (!pair_dims_ok(n_rows, H, W, r_max, cell_side) || !pair_grid(n_rows, H, W, r_max, cell_side, &g)) return 0;
+    if (windowed && !pair_mask_grid(H, W, mask_cell, &mg)) return 0;
+    return pair_carve(nullptr, n_rows, (size_t)g.n_cells(), windowed ? &mg : nullptr).bytes;
 }
 
-extern "C" int ay_pair_counts(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf, const int32_t* radii_q,
-                              int n_radii, const int32_t* roi_q, int border, int cell_side_q, int64_t* pairs, int32_t* centres, int32_t* nn,
-                              int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes, ay_stream_t stream) {
-    using namespace ay;
+// both entry points: `who` names the one in the messages; windowed adds the two kernels of THE PAIR WINDOW RULE and hands their
+// wbd to the count kernel
+static int pair_counts_run(const char* who, bool windowed, const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf,
+                           const int32_t* radii_q, int n_radii, const int32_t* roi_q, int border, int cell_side_q, const uint8_t* mask, int mask_cell,
+                           int64_t* pairs, int32_t* centres, int32_t* nn, int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes,
+                           ay_stream_t stream) {
     const int M = n_rows, C = num_classes, B = n_radii, H = slide_h, W = slide_w;
-    AY_CHECK_ARG(M >= 0 && (M == 0 || rows), "ay_pair_counts: n_rows %d%s", M, rows ? "" : " with null rows");
-    AY_CHECK_ARG(C >= 1 && C <= AY_PAIR_MAX_CLASSES, "ay_pair_counts: num_classes %d outside 1 .. %d", C, AY_PAIR_MAX_CLASSES);
-    AY_CHECK_ARG(H >= 1 && W >= 1 && H <= AY_PAIR_MAX_SIDE && W <= AY_PAIR_MAX_SIDE, "ay_pair_counts: slide %d x %d outside 1 .. %d", H, W,
-                 AY_PAIR_MAX_SIDE);
-    AY_CHECK_ARG(radii_q && B >= 1 && B <= AY_PAIR_MAX_RADII, "ay_pair_counts: n_radii %d outside 1 .. %d", B, AY_PAIR_MAX_RADII);
+    AY_CHECK_ARG(M >= 0 && (M == 0 || rows), "%s: n_rows %d%s", who, M, rows ? "" : " with null rows");
+    AY_CHECK_ARG(C >= 1 && C <= AY_PAIR_MAX_CLASSES, "%s: num_classes %d outside 1 .. %d", who, C, AY_PAIR_MAX_CLASSES);
+    AY_CHECK_ARG(H >= 1 && W >= 1 && H <= AY_PAIR_MAX_SIDE && W <= AY_PAIR_MAX_SIDE, "%s: slide %d x %d outside 1 .. %d", who, H, W, AY_PAIR_MAX_SIDE);
+    AY_CHECK_ARG(radii_q && B >= 1 && B <= AY_PAIR_MAX_RADII, "%s: n_radii %d outside 1 .. %d", who, B, AY_PAIR_MAX_RADII);
     PairRadii rad;
     rad.n = B;
     for (int k = 0; k < AY_PAIR_MAX_RADII; ++k) rad.r[k] = k < B ? radii_q[k] : INT_MAX;
     for (int k = 0; k < B; ++k)
         AY_CHECK_ARG(rad.r[k] >= 1 && rad.r[k] <= AY_PAIR_MAX_RADIUS_Q && (k == 0 || rad.r[k] > rad.r[k - 1]),
-                     "ay_pair_counts: radii[%d] = %d: the radii ascend strictly inside 1 .. %d quarter pixels", k, rad.r[k], AY_PAIR_MAX_RADIUS_Q);
+                     "%s: radii[%d] = %d: the radii ascend strictly inside 1 .. %d quarter pixels", who, k, rad.r[k], AY_PAIR_MAX_RADIUS_Q);
     const int r_max = rad.r[B - 1];
     PairWindow win = {0, 0, 4 * W - 1, 4 * H - 1, border ? 1 : 0};
     if (roi_q) win.x1 = roi_q[0], win.y1 = roi_q[1], win.x2 = roi_q[2], win.y2 = roi_q[3];
-    AY_CHECK_ARG(win.x1 <= win.x2 && win.y1 <= win.y2, "ay_pair_counts: roi (%d, %d, %d, %d) is empty", win.x1, win.y1, win.x2, win.y2);
+    AY_CHECK_ARG(win.x1 <= win.x2 && win.y1 <= win.y2, "%s: roi (%d, %d, %d, %d) is empty", who, win.x1, win.y1, win.x2, win.y2);
     // (the border distance subtracts a position in 0 .. 2^23 from a bound: keep the bounds where that cannot overflow)
-    AY_CHECK_ARG(win.x1 >= -(1 << 30) && win.y1 >= -(1 << 30) && win.x2 <= (1 << 30) && win.y2 <= (1 << 30), "ay_pair_counts: roi beyond +-2^30");
-    AY_CHECK_ARG(cell_side_q <= 0 || cell_side_q >= r_max, "ay_pair_counts: cell_side %d below the largest radius %d", cell_side_q, r_max);
+    AY_CHECK_ARG(win.x1 >= -(1 << 30) && win.y1 >= -(1 << 30) && win.x2 <= (1 << 30) && win.y2 <= (1 << 30), "%s: roi beyond +-2^30", who);
+    AY_CHECK_ARG(cell_side_q <= 0 || cell_side_q >= r_max, "%s: cell_side %d below the largest radius %d", who, cell_side_q, r_max);
     PairGrid g;
-    AY_CHECK_ARG(pair_grid(M, H, W, r_max, cell_side_q, &g), "ay_pair_counts: cell_side %d gives more than 2^30 cells", cell_side_q);
-    AY_CHECK_ARG(pairs && centres && stats && workspace && (M == 0 || (nn && bd)), "ay_pair_counts: null output or workspace");
+    AY_CHECK_ARG(pair_grid(M, H, W, r_max, cell_side_q, &g), "%s: cell_side %d gives more than 2^30 cells", who, cell_side_q);
+    PairMask mg = {0, 0, 0};
+    if (windowed) {
+        AY_CHECK_ARG(mask, "%s: null mask", who);
+        AY_CHECK_ARG(mask_cell >= AY_PAIR_WINDOW_MIN_CELL && mask_cell <= AY_PAIR_MAX_SIDE, "%s: mask_cell %d outside %d .. %d", who, mask_cell,
+                     AY_PAIR_WINDOW_MIN_CELL, AY_PAIR_MAX_SIDE);
+        AY_CHECK_ARG(pair_mask_grid(H, W, mask_cell, &mg), "%s: mask_cell %d gives more than 2^26 mask cells on a %d x %d slide", who, mask_cell, H, W);
+    }
+    AY_CHECK_ARG(pairs && centres && stats && workspace && (M == 0 || (nn && bd)), "%s: null output or workspace", who);
     const int n_cells = g.n_cells();
-    const PairWs w = pair_carve(workspace, M, (size_t)n_cells);
-    AY_CHECK_ARG(workspace_bytes >= w.bytes, "ay_pair_counts: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
-    AY_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "ay_pair_counts: workspace not 16-byte aligned");
+    const PairWs w = pair_carve(workspace, M, (size_t)n_cells, windowed ? &mg : nullptr);
+    AY_CHECK_ARG(workspace_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.bytes);
+    AY_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace not 16-byte aligned", who);
     hipStream_t st = S(stream);
     const long long n_nn = (long long)M * C * 2;
     const long long most = n_nn > n_cells + 2 ? n_nn : n_cells + 2;
@@ -391,8 +529,16 @@ extern "C" int ay_pair_counts(const float* rows, int n_rows, int num_classes, in
     AY_CHECK_LAUNCH("pair_fill_kernel");
     if (M > 0) {
         const unsigned rblocks = (unsigned)(((long long)M + PAIR_THREADS - 1) / PAIR_THREADS);
-        hipLaunchKernelGGL(pair_count_kernel, dim3(rblocks), dim3(PAIR_THREADS), 0, st, rows, M, C, 4 * W - 1, 4 * H - 1, min_conf, rad, win, g, w.cell_of,
-                           w.cell_start, w.row_q, w.row_ck, bd, centres, stats);
+        if (windowed) {
+            const unsigned cblocks = pair_blocks((long long)mg.n_chunks() * mg.gx, INT_MAX);
+            hipLaunchKernelGGL(pair_window_bits_kernel, dim3(cblocks), dim3(PAIR_THREADS), 0, st, mask, mg, w.bits);
+            AY_CHECK_LAUNCH("pair_window_bits_kernel");
+            hipLaunchKernelGGL(pair_window_dist_kernel, dim3((unsigned)(((long long)M + PAIR_WINDOW_ROWS - 1) / PAIR_WINDOW_ROWS)), dim3(PAIR_THREADS), 0, st,
+                               rows, M, C, 4 * W - 1, 4 * H - 1, min_conf, r_max, mg, (const unsigned long long*)w.bits, w.wbd);
+            AY_CHECK_LAUNCH("pair_window_dist_kernel");
+        }
+        hipLaunchKernelGGL(pair_count_kernel, dim3(rblocks), dim3(PAIR_THREADS), 0, st, rows, M, C, 4 * W - 1, 4 * H - 1, min_conf, rad, win, g,
+                           (const int32_t*)w.wbd, w.cell_of, w.cell_start, w.row_q, w.row_ck, bd, centres, stats);
         AY_CHECK_LAUNCH("pair_count_kernel");
         const int n_chunks = (n_cells + PAIR_SCAN_CHUNK - 1) / PAIR_SCAN_CHUNK;
         hipLaunchKernelGGL(pair_scan_chunks_kernel, dim3(n_chunks), dim3(PAIR_THREADS), 0, st, w.cell_start, n_cells, w.chunk_sum);
@@ -411,4 +557,29 @@ extern "C" int ay_pair_counts(const float* rows, int n_rows, int num_classes, in
         AY_CHECK_LAUNCH("pair_search_kernel");
     }
     return AY_OK;
+}
+
+}  // namespace ay
+
+extern "C" size_t ay_pair_counts_workspace_bytes(int n_rows, int slide_h, int slide_w, int r_max_q, int cell_side_q) {
+    return ay::pair_workspace_bytes(n_rows, slide_h, slide_w, r_max_q, cell_side_q, false, 0);
+}
+
+extern "C" int ay_pair_counts(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf, const int32_t* radii_q,
+                              int n_radii, const int32_t* roi_q, int border, int cell_side_q, int64_t* pairs, int32_t* centres, int32_t* nn,
+                              int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes, ay_stream_t stream) {
+    return ay::pair_counts_run("ay_pair_counts", false, rows, n_rows, num_classes, slide_h, slide_w, min_conf, radii_q, n_radii, roi_q, border,
+                               cell_side_q, nullptr, 0, pairs, centres, nn, bd, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t ay_pair_counts_window_workspace_bytes(int n_rows, int slide_h, int slide_w, int r_max_q, int cell_side_q, int mask_cell) {
+    return ay::pair_workspace_bytes(n_rows, slide_h, slide_w, r_max_q, cell_side_q, true, mask_cell);
+}
+
+extern "C" int ay_pair_counts_window(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf, const int32_t* radii_q,
+                                     int n_radii, const int32_t* roi_q, int border, int cell_side_q, const uint8_t* mask, int mask_cell,
+                                     int64_t* pairs, int32_t* centres, int32_t* nn, int32_t* bd, int32_t* stats, void* workspace,
+                                     size_t workspace_bytes, ay_stream_t stream) {
+    return ay::pair_counts_run("ay_pair_counts_window", true, rows, n_rows, num_classes, slide_h, slide_w, min_conf, radii_q, n_radii, roi_q, border,
+                               cell_side_q, mask, mask_cell, pairs, centres, nn, bd, stats, workspace, workspace_bytes, stream);
 }

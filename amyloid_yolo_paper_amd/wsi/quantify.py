@@ -13,13 +13,13 @@ from .focus import _check_focus, focus_map, focus_summary
 from .grid import _whole, check_raster, probed
 from .load import stain_load
 from .segment import _check_segment, plaque_morphometry, segment_boxes
-from .spatial import PAIR_MAX_CLASSES, _check_spatial, spatial_stats
+from .spatial import PAIR_MAX_CLASSES, _check_spatial, _window_cell, spatial_stats, window_from_tissue
 from .tissue import tissue_counts
 
 
 def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
                     dab_thres=None, load=False, focus=False, min_sharpness=None, segment=False, seg_margin=None, core_thres=None,
-                    min_area=None, spatial_radii=None, **detect_region_kwargs):
+                    min_area=None, spatial_radii=None, spatial_window=False, spatial_min_tissue=0.5, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
 
     1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
@@ -80,7 +80,12 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
        ``spatial_stats(rows, (H, W), spatial_radii, C, min_conf, area=tissue.sum(), mpp=mpp)``: the cross-class pair counts within
        every radius, Ripley's K and L, the pair correlation g and the nearest-neighbour distribution G over the whole slide, with the
        tissue pixels as the area (THE PAIR RULE; see :func:`spatial_stats` for what a ragged tissue outline does to K).  The
-       arguments are checked before any launch.  Without it the result has the keys it had.
+       arguments are checked before any launch.  Without it the result has the keys it had.  With ``spatial_window=True`` (only
+       with ``spatial_radii``; ``cell >= 16``) the window is the tissue's outline and no rectangle: ``spatial_window`` =
+       ``window_from_tissue(tissue, (H, W), cell, spatial_min_tissue)``, a bool map [Gy,Gx] of the cells that are IN, and ``spatial``
+       = ``spatial_stats(..., window=spatial_window, window_cell=cell)`` (THE PAIR WINDOW RULE): a row is a centre at a radius only
+       if its whole disc lies over IN cells, ``area`` is the window's area and ``inside`` counts the rows in IN cells, so that the
+       intensity belongs to the same window.  ``spatial_window=False`` is the result as it was.
 
     The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
     if not segment and not (seg_margin is None and core_thres is None and min_area is None):
@@ -132,6 +137,12 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
     need = max(1, math.ceil(float(field_min_tissue) * (F * cell) ** 2))
     if spatial_radii is not None:       # refused before any launch (and before the model is touched), like everything above
         _check_spatial("quantify_region", (H, W), spatial_radii, 1, None, None)
+    if spatial_window:
+        if spatial_radii is None:
+            raise ValueError("quantify_region: spatial_window needs spatial_radii")
+        _window_cell("quantify_region", (H, W), cell)
+        if isinstance(spatial_min_tissue, bool) or not 0.0 <= float(spatial_min_tissue) <= 1.0:       # a NaN fails both comparisons
+            raise ValueError(f"quantify_region: spatial_min_tissue {spatial_min_tissue!r} is no fraction of a cell")
     num_classes = int(model.yolo_layers[0].num_classes)
     if spatial_radii is not None:
         _whole(num_classes, 1, PAIR_MAX_CLASSES, "quantify_region: the model's classes (spatial statistics)")
@@ -178,7 +189,10 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
             a = out["plaque"]["area_px"][counted & (r[:, 6] == c)]
             if len(a):
                 out["class_area_px"][c] = np.percentile(a, [25.0, 50.0, 75.0])
-    if spatial_radii is not None:
+    if spatial_window:
+        out["spatial_window"] = window_from_tissue(tissue, (H, W), cell, spatial_min_tissue)
+        out["spatial"] = spatial_stats(rows, (H, W), spatial_radii, num_classes, min_conf, mpp=mpp, window=out["spatial_window"], window_cell=cell)
+    elif spatial_radii is not None:
         out["spatial"] = spatial_stats(rows, (H, W), spatial_radii, num_classes, min_conf, area=int(tissue.sum(dtype=np.int64)), mpp=mpp)
     if mpp is not None:
         mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue

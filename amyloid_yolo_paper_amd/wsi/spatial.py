@@ -14,6 +14,7 @@ from .grid import _whole, check_rows, hip_device
 
 
 PAIR_MAX_CLASSES, PAIR_MAX_RADII, PAIR_MAX_RADIUS_Q, PAIR_MAX_SIDE = 8, 32, 32767, 1 << 21      # include/amyloid_yolo.h, THE PAIR RULE
+PAIR_WINDOW_MIN_CELL, PAIR_WINDOW_MAX_CELLS = 16, 1 << 26                                       # THE PAIR WINDOW RULE
 
 
 def spatial_radii_q(radii):
@@ -68,12 +69,56 @@ def _check_spatial(what, slide_hw, radii, num_classes, roi, area, mpp=None):
     return H, W, nc, rq, roi_q, float(area)
 
 
-def pair_counts_device(rows, slide_hw, radii_q, num_classes, min_conf=0.0, roi_q=None, border=True, cell_side_q=0):
+def _window_cell(what, slide_hw, cell):
+    """the mask cell side of THE PAIR WINDOW RULE -> (cell, Gy, Gx); ``ValueError`` below 16 px or beyond 2**26 cells"""
+    H, W = slide_hw
+    cell = _whole(cell, PAIR_WINDOW_MIN_CELL, PAIR_MAX_SIDE, f"{what}: window_cell")
+    gy, gx = -(-H // cell), -(-W // cell)
+    if gy * gx > PAIR_WINDOW_MAX_CELLS:
+        raise ValueError(f"{what}: window_cell {cell} gives {gy} x {gx} mask cells on the {H} x {W} slide, more than 2**26")
+    return cell, gy, gx
+
+
+def window_from_tissue(tissue, slide_hw, cell, min_tissue=0.5):
+    """The mask of THE PAIR WINDOW RULE from a tissue map (:func:`tissue_counts`, ``quantify_region(...)["tissue"]``) on the grid of
+    ``cell``-pixel cells over the (H, W) slide: cell (gy, gx) is IN iff ``tissue[gy, gx] >= max(1, ceil(min_tissue * n))``, n the
+    pixels of the cell inside the slide (the last cells of a row and column are cut by it).  Returns a bool array [Gy, Gx]."""
+    if slide_hw is None or isinstance(slide_hw, (str, bytes)) or np.ndim(slide_hw) != 1 or len(slide_hw) != 2:
+        raise ValueError(f"window_from_tissue: slide_hw {slide_hw!r} is no (H, W)")
+    H, W = (_whole(v, 1, PAIR_MAX_SIDE, "window_from_tissue: slide_hw") for v in slide_hw)
+    cell, gy, gx = _window_cell("window_from_tissue", (H, W), cell)
+    if isinstance(min_tissue, bool) or not 0.0 <= float(min_tissue) <= 1.0:       # a NaN fails both comparisons
+        raise ValueError(f"window_from_tissue: min_tissue {min_tissue!r} is no fraction of a cell")
+    t = tissue.detach().cpu().numpy() if torch.is_tensor(tissue) else np.asarray(tissue)
+    if t.shape != (gy, gx) or t.dtype.kind not in "iu":
+        raise ValueError(f"window_from_tissue: tissue {t.dtype} {t.shape} is no integer map of the {gy} x {gx} cells of {cell} px")
+    hs = np.minimum(cell, H - cell * np.arange(gy, dtype=np.int64))
+    ws = np.minimum(cell, W - cell * np.arange(gx, dtype=np.int64))
+    need = np.maximum(1, np.ceil(float(min_tissue) * (hs[:, None] * ws[None, :]).astype(np.float64))).astype(np.int64)
+    return t.astype(np.int64) >= need
+
+
+def window_area(window, slide_hw, cell, roi_q=None):
+    """the area of mask AND ROI in square pixels, on integers: the quarter-pixel positions of the slide that lie in an IN cell and
+    inside ``roi_q`` (None: the whole slide), divided by 16"""
+    H, W = slide_hw
+    m = np.asarray(window) != 0
+    X1, Y1, X2, Y2 = (0, 0, 4 * W - 1, 4 * H - 1) if roi_q is None else (int(v) for v in roi_q)
+    S = 4 * int(cell)
+    x0, y0 = S * np.arange(m.shape[1], dtype=np.int64), S * np.arange(m.shape[0], dtype=np.int64)
+    nx = np.maximum(np.minimum(np.minimum(x0 + S, 4 * W) - 1, X2) - np.maximum(x0, X1) + 1, 0)      # positions of a column inside the ROI
+    ny = np.maximum(np.minimum(np.minimum(y0 + S, 4 * H) - 1, Y2) - np.maximum(y0, Y1) + 1, 0)
+    return int(ny @ m.astype(np.int64) @ nx) / 16.0
+
+
+def pair_counts_device(rows, slide_hw, radii_q, num_classes, min_conf=0.0, roi_q=None, border=True, cell_side_q=0, window=None, window_cell=0):
     """``ay_pair_counts`` on rows that live on the device (float32 [M,7], contiguous) -> a dict of int tensors on the device, all views
     of ONE buffer ``buf`` (so that a caller reads back once): ``pairs`` int64 [C,C,B], ``centres`` int32 [C,B], ``stats`` int32
     [2C+3], ``bd`` int32 [M], ``nn`` int32 [M,C,2], and ``label`` int32 [M], the rows' ``cls_pred`` as integers (a torch copy, for
     the host formulas).  Launches only: nothing is read back here.  ``cell_side_q`` overrides the grid's
-    cell side (quarter pixels, at least the largest radius); the result does not depend on it."""
+    cell side (quarter pixels, at least the largest radius); the result does not depend on it.  With ``window`` (a uint8 or bool
+    device tensor [Gy, Gx], contiguous, non-zero = IN) and ``window_cell`` (its cell side in pixels) the call is
+    ``ay_pair_counts_window`` (THE PAIR WINDOW RULE); ``None`` calls ``ay_pair_counts`` exactly as before."""
     H, W = slide_hw
     M, nc = int(rows.shape[0]), int(num_classes)
     rq = np.ascontiguousarray(radii_q, np.int32)
@@ -87,13 +132,23 @@ def pair_counts_device(rows, slide_hw, radii_q, num_classes, min_conf=0.0, roi_q
            "nn": piece[4].view(M, nc, 2), "label": piece[5]}
     if M:       # cls_pred as an integer next to the outputs (a value that is no class becomes -1 or a number no class has)
         out["label"].copy_(torch.nan_to_num(rows[:, 6], nan=-1.0, posinf=-1.0, neginf=-1.0).clamp(-1.0, 255.0))
-    need = int(L.ay_pair_counts_workspace_bytes(M, H, W, int(rq[-1]) if B else 0, int(cell_side_q)))
-    ws = torch.empty(max(need, 16), device=rows.device, dtype=torch.uint8)
     i32p = C.POINTER(C.c_int32)
     roi_arg = None if roi_q is None else np.ascontiguousarray(roi_q, np.int32).ctypes.data_as(i32p)
-    check(L.ay_pair_counts(ptr(rows) if M else None, M, nc, H, W, C.c_float(min_conf), rq.ctypes.data_as(i32p), B, roi_arg, int(bool(border)),
-                           int(cell_side_q), ptr(out["pairs"]), ptr(out["centres"]), ptr(out["nn"]) if M else None, ptr(out["bd"]) if M else None,
-                           ptr(out["stats"]), ptr(ws), need, _lib.stream_ptr()), "ay_pair_counts")
+    head = (ptr(rows) if M else None, M, nc, H, W, C.c_float(min_conf), rq.ctypes.data_as(i32p), B, roi_arg, int(bool(border)), int(cell_side_q))
+    outs = (ptr(out["pairs"]), ptr(out["centres"]), ptr(out["nn"]) if M else None, ptr(out["bd"]) if M else None, ptr(out["stats"]))
+    if window is None:
+        need = int(L.ay_pair_counts_workspace_bytes(M, H, W, int(rq[-1]) if B else 0, int(cell_side_q)))
+        ws = torch.empty(max(need, 16), device=rows.device, dtype=torch.uint8)
+        check(L.ay_pair_counts(*head, *outs, ptr(ws), need, _lib.stream_ptr()), "ay_pair_counts")
+        return out
+    gy, gx = -(-H // max(int(window_cell), 1)), -(-W // max(int(window_cell), 1))
+    if not torch.is_tensor(window) or window.device != rows.device or window.dtype not in (torch.uint8, torch.bool) or \
+            tuple(window.shape) != (gy, gx) or not window.is_contiguous():
+        raise ValueError(f"pair_counts_device: window must be a contiguous uint8 or bool tensor [{gy}, {gx}] on {rows.device}")
+    mask = window.view(torch.uint8) if window.dtype == torch.bool else window       # (a bool tensor holds one byte, 0 or 1, per cell)
+    need = int(L.ay_pair_counts_window_workspace_bytes(M, H, W, int(rq[-1]) if B else 0, int(cell_side_q), int(window_cell)))
+    ws = torch.empty(max(need, 16), device=rows.device, dtype=torch.uint8)
+    check(L.ay_pair_counts_window(*head, ptr(mask), int(window_cell), *outs, ptr(ws), need, _lib.stream_ptr()), "ay_pair_counts_window")
     return out
 
 
@@ -127,7 +182,24 @@ def spatial_summaries(pairs, centres, inside, bd, nn, radii_q, area, mpp=None, l
     return out
 
 
-def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, border=True, area=None, mpp=None):
+def _check_window(what, slide_hw, window, window_cell):
+    """the host checks of ``spatial_stats(window=, window_cell=)`` -> (mask as the caller gave it, host bool mask, cell) or
+    (None, None, 0); no device is needed"""
+    if window is None and window_cell is None:
+        return None, None, 0
+    if window is None or window_cell is None:
+        raise ValueError(f"{what}: window and window_cell go together")
+    cell, gy, gx = _window_cell(what, slide_hw, window_cell)
+    dev_mask = torch.is_tensor(window)
+    kind = window.dtype in (torch.bool, torch.uint8) if dev_mask else np.asarray(window).dtype in (np.bool_, np.uint8)
+    if not kind or tuple(window.shape if dev_mask else np.shape(window)) != (gy, gx):
+        raise ValueError(f"{what}: window must be a bool or uint8 array [{gy}, {gx}]: the cells of {cell} px of the {slide_hw[0]} x "
+                         f"{slide_hw[1]} slide")
+    host = (window.detach().cpu().numpy() if dev_mask else np.asarray(window)) != 0
+    return window, host, cell
+
+
+def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, border=True, area=None, mpp=None, window=None, window_cell=None):
     """Spatial statistics of a slide's detections (``ay_pair_counts``, THE PAIR RULE in ``include/amyloid_yolo.h``): the cross-class
     pair counts within every radius, and Ripley's K and L, the pair correlation g and the nearest-neighbour distribution G from them.
 
@@ -140,32 +212,49 @@ def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, 
     the window, so that its whole disc was observed; its partners may lie anywhere.  ``border=False`` takes every row inside the
     window as a centre at every radius.  One call, one read-back.
 
+    ``window`` (a host or device array [Gy, Gx], bool or uint8, non-zero = IN) with ``window_cell`` (its cell side in pixels, an
+    integer >= 16; ``Gy = ceil(H / cell)``, ``Gx = ceil(W / cell)``) makes the window a MASK, e.g. :func:`window_from_tissue` of a
+    tissue map (THE PAIR WINDOW RULE, ``ay_pair_counts_window``): the border distance is then also measured to the nearest position
+    that lies in a zero cell or outside the slide, exactly, in integers, and capped at the largest radius; the window is mask AND
+    ``roi``.  A row in a zero cell is no centre and not ``inside``, but still a partner.  A wrong shape or type, a cell below 16 or one
+    of the two without the other is a ``ValueError``.
+
     Returns a dict.  Raw: ``pairs`` int64 [C,C,B] (ordered pairs, cumulative in k: over the eligible centres of class a, the
     counted rows of class b within ``r_k``, the centre itself excluded), ``centres`` int32 [C,B], ``nn`` int32 [M,C,2] = (d2 in
     quarter pixels squared, row index) of the nearest counted row of every class within the largest radius, ties to the lowest
     index, -1 where there is none, ``nn_index`` int32 [M,C], ``nn_distance`` float64 [M,C] in pixels (NaN where there is none),
     ``bd`` int32 [M] (quarter pixels to the window's border, -1 outside and for rows not counted), ``counted`` and ``inside`` [C],
-    ``below``, ``flagged``, ``flags``, ``radii`` (effective, px), ``radii_q``, ``roi_q``, ``area``.  Derived, float64 on the host, NaN
-    wherever a denominator is 0: ``intensity[b] = inside[b] / area`` (``area`` in px**2; default: the window's; callers pass
-    tissue pixels), ``K[a,b,k] = pairs / (centres[a,k] * intensity[b])``, ``L = sqrt(K / pi)``, ``L_minus_r``, ``g[k] = (K_k -
-    K_{k-1}) / (pi (r_k**2 - r_{k-1}**2))`` with ``K_{-1} = r_{-1} = 0``, and ``G[a,b,k]``: the share of the class-a rows with
-    ``bd >= R_k`` whose nearest b lies within ``r_k``.  With ``mpp`` also ``radii_um`` and ``K_um2``.  Under complete spatial
+    ``below``, ``flagged``, ``flags``, ``radii`` (effective, px), ``radii_q``, ``roi_q``, ``area``; with ``window`` also
+    ``window_area``: the positions of the slide in IN cells and inside ``roi``, over 16, counted on the host in integers.  Derived,
+    float64 on the host, NaN wherever a denominator is 0: ``intensity[b] = inside[b] / area`` (``area`` in px**2; default: the
+    window's, with ``window`` its ``window_area``; ``area=`` overrides), ``K[a,b,k] = pairs / (centres[a,k] * intensity[b])``,
+    ``L = sqrt(K / pi)``, ``L_minus_r``, ``g[k] = (K_k - K_{k-1}) / (pi (r_k**2 - r_{k-1}**2))`` with ``K_{-1} = r_{-1} = 0``, and
+    ``G[a,b,k]``: the share of the class-a rows with ``bd >= R_k`` whose nearest b lies within ``r_k``.  With ``mpp`` also ``radii_um`` and ``K_um2``.  Under complete spatial
     randomness ``K = pi r**2``, ``L - r = 0`` and ``g = 1``; clustering at a scale shows as larger values there.
 
-    Two limits.  The window is a RECTANGLE: with ``area=`` tissue pixels on a slide whose tissue outline is ragged, centres near a
-    tissue edge have part of their disc over glass, and K is biased low there.  Comparing ``K[a][b]`` with ``K[a][a]`` on the same
-    slide, or working inside a field (``roi=``) that is all tissue, is the robust use.  And the COST is the number of pairs within
-    3 x 3 grid cells of side ``r_max``: quadratic in ``r_max`` at a given density.
+    Limits.  Without ``window`` the window is a RECTANGLE: with ``area=`` tissue pixels on a slide whose tissue outline is ragged,
+    centres near a tissue edge have part of their disc over glass, and K is biased low there; ``window=`` removes that bias, and
+    comparing ``K[a][b]`` with ``K[a][a]`` on the same slide or working inside a field (``roi=``) that is all tissue stay robust
+    uses.  With ``window`` the outline's RESOLUTION is the mask cell (16 px at the finest): a cell is in or out as a whole.  And the
+    COST is the number of pairs within 3 x 3 grid cells of side ``r_max``: quadratic in ``r_max`` at a given density.
 
-    Out of scope: Monte-Carlo envelopes (random relabelling of the classes is the natural follow-up), per-field statistics (pass a
-    field as ``roi=``) and windows that are no rectangles."""
+    Out of scope: Monte-Carlo envelopes (random relabelling of the classes is the natural follow-up) and per-field statistics (pass a
+    field as ``roi=``)."""
+    given_area = area
     H, W, nc, rq, roi_q, area = _check_spatial("spatial_stats", slide_hw, radii, num_classes, roi, area, mpp)
+    window, mask, cell = _check_window("spatial_stats", (H, W), window, window_cell)
     check_rows("spatial_stats", rows)
     min_conf = float(min_conf)
     dev = hip_device("the spatial statistics have")
     rows = _slide_array(rows, 7, dev)
     M = int(rows.shape[0])
-    dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border)
+    if mask is not None:
+        w_area = window_area(mask, (H, W), cell, roi_q)
+        area = w_area if given_area is None else area
+        on_dev = window if torch.is_tensor(window) and window.device == rows.device else torch.from_numpy(mask.view(np.uint8)).to(rows.device)
+        dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border, 0, on_dev.contiguous(), cell)
+    else:
+        dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border)
     host = dv["buf"].cpu()                                              # the one read-back
     off = lambda t: (t.data_ptr() - dv["buf"].data_ptr()) // 4
     take = lambda t: host[off(t):off(t) + t.numel() * t.element_size() // 4]
@@ -177,5 +266,7 @@ def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, 
     out = {"pairs": pairs, "centres": centres, "nn": nn, "nn_index": nn[:, :, 1].copy(), "nn_distance": np.where(d2 >= 0, np.sqrt(np.abs(d2)) / 4.0, np.nan),
            "bd": bd, "counted": st[:nc].copy(), "inside": st[nc:2 * nc].copy(), "below": int(st[2 * nc]), "flagged": int(st[2 * nc + 1]),
            "flags": int(st[2 * nc + 2]), "radii": rq / 4.0, "radii_q": rq, "roi_q": roi_q, "area": area}
+    if mask is not None:
+        out["window_area"] = w_area
     out.update(spatial_summaries(pairs, centres, out["inside"], bd, nn, rq, area, mpp, labels))
     return out

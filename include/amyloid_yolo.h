@@ -843,6 +843,40 @@ int ay_pair_counts(const float* rows, int n_rows, int num_classes, int slide_h, 
                    int n_radii, const int32_t* roi_q, int border, int cell_side_q, int64_t* pairs, int32_t* centres, int32_t* nn,
                    int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes, ay_stream_t stream);
 
+/* THE PAIR WINDOW RULE (wsi.spatial_stats(window=...), wsi.quantify_region(spatial_window=True)): minus-sampling inside a window that
+ *   is no rectangle -- a tissue outline -- given as a mask on cells.  (THE WINDOW RULE is the sampler's.)  tests/
+ *   spatial_window_reference.py restates it by brute force over the OUT cells.
+ *   Input: THE PAIR RULE's, and mask uint8 [Gy][Gx] on the device (non-zero: IN) with its cell side mask_cell in pixels, an integer
+ *   >= AY_PAIR_WINDOW_MIN_CELL; Gx = ceil(W / mask_cell), Gy = ceil(H / mask_cell), Gx * Gy <= AY_PAIR_WINDOW_MAX_CELLS; Sc = 4 *
+ *   mask_cell quarter pixels.
+ *   OUT positions: position (x, y) of the unbounded quarter-pixel lattice is OUT iff it lies outside the slide (x < 0, x > 4W - 1, y < 0
+ *     or y > 4H - 1) or the mask cell (y / Sc, x / Sc) is zero.  The last cell of a row or column is cut by the slide.
+ *   For a counted row i at (qx, qy): d2out_i = the minimum over all OUT positions p of |q_i - p|^2, on integers; wbd_i = the largest
+ *     integer d in -1 .. R_{B-1} with d * d < d2out_i (so -1 in an OUT cell, and capped at the largest radius);
+ *     bd_i = min(THE PAIR RULE's bd_i, wbd_i): the window is mask AND ROI.
+ *   Everything after bd_i is THE PAIR RULE unchanged: with `border` a row is an eligible centre at k iff bd_i >= R_k (for the mask
+ *     that is R_k^2 < d2out_i: the closed disc holds no OUT position), without it iff bd_i >= 0; stats[C + c] counts the rows with
+ *     bd_i >= 0; the output bd is this bd_i, -1 for negatives; partners may lie anywhere, in OUT cells too.
+ *   With an all-IN mask and no ROI the nearest OUT position is the slide's edge at the rectangle's bd + 1: pairs, centres, nn and stats
+ *     are byte for byte ay_pair_counts', and bd is the rectangle's capped at R_{B-1}.
+ *   With both offsets capped at R_{B-1} + 1 <= 32768, dx^2 + dy^2 reaches 2^31: the kernel computes it in UNSIGNED 32 bits.  No float
+ *     reaches an output: wbd is an integer square root, a float estimate corrected on integers.
+ *
+ * ay_pair_counts_window: ay_pair_counts with `mask` (device) and `mask_cell` behind cell_side_q, under the same contract: kernel
+ *   launches only, every output reset by the call's own kernels, n_rows == 0 legal, no scratch.  Two more kernels run in front of
+ *   the count kernel: the OUT cells of every 64 mask rows of a column as the bits of one word (Gy * Gx / 8 bytes of workspace), and
+ *   per row, on 16 lanes, the minimum over the mask columns within R_{B-1}, the vertical distance in a column read off its words.
+ *   mask == NULL, mask_cell < 16 (or beyond AY_PAIR_MAX_SIDE) and more than 2^26 mask cells are refused (ay_last_error).  workspace:
+ *   16-byte aligned, ay_pair_counts_window_workspace_bytes(n_rows, slide_h, slide_w, R_{B-1}, cell_side_q, mask_cell) bytes (0 for
+ *   arguments the call refuses). */
+#define AY_PAIR_WINDOW_MIN_CELL 16
+#define AY_PAIR_WINDOW_MAX_CELLS 67108864
+size_t ay_pair_counts_window_workspace_bytes(int n_rows, int slide_h, int slide_w, int r_max_q, int cell_side_q, int mask_cell);
+int ay_pair_counts_window(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf, const int32_t* radii_q,
+                          int n_radii, const int32_t* roi_q, int border, int cell_side_q, const uint8_t* mask, int mask_cell, int64_t* pairs,
+                          int32_t* centres, int32_t* nn, int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes,
+                          ay_stream_t stream);
+
 /* ---- stain normalisation for whole-slide detection (wsi.stain_stats, wsi.StainMap, wsi.detect_region(stain=...); csrc/ay_stain.hip) --
  * Amyloid IHC slides are hematoxylin + DAB and differ in stain strength from batch to batch and from scanner to scanner.  The slide's
  * optical densities are unmixed on a fixed two-stain basis, each stain is scaled by a gain that brings its strength to a target's,
