@@ -1,6 +1,7 @@
 """NumPy restatement of THE PAIR RULE of include/amyloid_yolo.h (TEST INFRASTRUCTURE ONLY): float32 for the centre and the multiply by
 four, integers after them; the pairs by brute force over ALL pairs (int64, chunks of 512 rows), a second time as a plain Python loop
-over every pair for tiny cases, and the host formulas (K, L, g, G) as loops.
+over every pair for tiny cases, a third time over a cell grid of side R_max for the sizes at which all pairs are too many
+(pair_counts_binned), and the host formulas (K, L, g, G) as loops.
 
 Nothing here comes from the product: the conversions of radii and windows are restated too."""
 import math
@@ -98,6 +99,47 @@ def pair_counts(rows, H, W, C, min_conf, rq, roi=None, border=True):
             best = db[np.arange(len(me)), j]
             hit = best <= r2[-1]
             nn[me[hit], b, 0], nn[me[hit], b, 1] = best[hit], idx[j[hit]]
+    return pairs, centres, nn, bd, stats
+
+
+def pair_counts_binned(rows, H, W, C, min_conf, rq, roi=None, border=True):
+    """the same rule over a cell grid of side R_max (quarter pixels), for sizes at which all pairs are too many: a partner within
+    R_max of a centre lies in the 3 x 3 cells around the centre's, so a cell's rows are compared with the rows of those nine cells
+    only, in int64, exactly as pair_counts compares a chunk with all rows.  tests/test_spatial_cpu.py shows the two equal in every
+    output."""
+    rq, qx, qy, cls, eligible, bd, stats, centres = _head(rows, H, W, C, min_conf, rq, roi, border)
+    M, B = len(cls), len(rq)
+    r2, S = rq * rq, int(rq[-1])
+    pairs, nn = np.zeros((C, C, B), np.int64), np.full((M, C, 2), -1, np.int32)
+    idx = np.flatnonzero(cls >= 0)
+    if len(idx) == 0:
+        return pairs, centres, nn, bd, stats
+    gx, gy = int(qx[idx].max()) // S + 1, int(qy[idx].max()) // S + 1
+    cell = (qy[idx] // S) * gx + qx[idx] // S
+    order = np.argsort(cell, kind="stable")
+    sidx, start = idx[order], np.searchsorted(cell[order], np.arange(gx * gy + 1))
+    far = np.int64(1) << 62
+    for c in np.unique(cell):
+        me = sidx[start[c]:start[c + 1]]
+        y, x = divmod(int(c), gx)
+        near = [sidx[start[v * gx + max(x - 1, 0)]:start[v * gx + min(x + 1, gx - 1) + 1]] for v in range(max(y - 1, 0), min(y + 1, gy - 1) + 1)]
+        nb = np.sort(np.concatenate(near))                           # ascending: the first minimum below is the lowest row index
+        d2 = (qx[me][:, None] - qx[nb][None, :]) ** 2 + (qy[me][:, None] - qy[nb][None, :]) ** 2   # int64 [cell, neighbourhood]
+        d2[me[:, None] == nb[None, :]] = far                         # j != i
+        pc = cls[nb]
+        onehot = (pc[:, None] == np.arange(C)[None, :]).astype(np.float64)
+        for k in range(B):                                           # equality counts
+            n = ((d2 <= r2[k]).astype(np.float64) @ onehot).astype(np.int64)                        # [cell, C] partners per class (exact)
+            for a in range(C):
+                pairs[a, :, k] += n[eligible[me, k] & (cls[me] == a)].sum(0)
+        for b in range(C):
+            if not (pc == b).any():
+                continue
+            db = np.where(pc[None, :] == b, d2, far)
+            j = db.argmin(1)
+            best = db[np.arange(len(me)), j]
+            hit = best <= r2[-1]
+            nn[me[hit], b, 0], nn[me[hit], b, 1] = best[hit], nb[j[hit]]
     return pairs, centres, nn, bd, stats
 
 

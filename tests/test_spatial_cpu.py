@@ -24,6 +24,38 @@ def test_brute_force_equals_the_pair_loop(M, border):
         np.testing.assert_array_equal(x, y)
 
 
+def assert_same_outputs(a, b):
+    for x, y in zip(a, b):
+        assert x.dtype == y.dtype and x.shape == y.shape
+        np.testing.assert_array_equal(x, y)
+
+
+@pytest.mark.parametrize("M,border", [(M, True) for M in sr.SIZES] + [(M, False) for M in sr.SIZES if M <= 257])
+def test_the_cell_grid_formulation_equals_the_brute_force_on_the_clustered_cases(M, border):
+    """pair_counts_binned (the reference of the sizes all pairs are too many for) against pair_counts, every output, on the cases the
+    GPU tests take"""
+    rows, rq, want = sr.clustered_case(M, border)
+    assert_same_outputs(sr.pair_counts_binned(rows, H, W, sr.CLASSES, 0.5, rq, None, border), want)
+    if M == 257:                                                   # a window of the caller's; one radius (one cell side for all)
+        roi = sr.roi_q((300.0, 200.5, 3800.25, 2900.0), H, W)
+        assert_same_outputs(sr.pair_counts_binned(rows, H, W, 3, 0.5, rq, roi, border), sr.pair_counts(rows, H, W, 3, 0.5, rq, roi, border))
+        assert_same_outputs(sr.pair_counts_binned(rows, H, W, 3, 0.5, rq[2:3], None, border), sr.pair_counts(rows, H, W, 3, 0.5, rq[2:3], None, border))
+
+
+@pytest.mark.parametrize("border", [True, False])
+def test_the_cell_grid_formulation_equals_the_brute_force_on_the_lattices(border):
+    """pairs at exactly R_k (3-4-5 and 5-12-13 on a lattice 1 px apart), partners exactly on cell borders, duplicates at one position"""
+    cases = [(sr.lattice_rows(9, 10.0, C=1, x0=60.0, y0=60.0), 200, 200, 1, sr.radii_q((10, 15))),
+             (sr.lattice_rows(16, 1.0, C=2, side=6.0, x0=20.0, y0=24.0), 64, 64, 2, sr.radii_q((5, 13))),
+             (sr.lattice_rows(16, 1.0, C=2, side=6.0, x0=20.0, y0=24.0), 64, 64, 2, sr.radii_q((4.75, 13))),
+             (sr.lattice_rows(12, 8.0, C=2, x0=0.0, y0=8.0), 100, 100, 2, sr.radii_q((1, 3.5, 8))),     # 32 quarter pixels: the cell side
+             (sr.points([[100.25, 50.5]] * 100, cls=np.arange(100) % 3), 200, 300, 3, sr.radii_q((0.25, 2)))]
+    for rows, H_, W_, C_, rq in cases:
+        want = sr.pair_counts(rows, H_, W_, C_, 0.0, rq, None, border)
+        assert want[0].sum() > 0
+        assert_same_outputs(sr.pair_counts_binned(rows, H_, W_, C_, 0.0, rq, None, border), want)
+
+
 def test_the_clustered_cases_are_not_idle():
     for M in (257, 4097):
         rows, rq, res = sr.clustered_case(M)          # (check_not_idle runs inside)
