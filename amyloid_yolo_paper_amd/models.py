@@ -292,6 +292,7 @@ class Darknet(nn.Module):
         sig = (self._param_signature(), self.precision, str(device))
         if self._prep is not None and self._prep["sig"] == sig:
             return self._prep
+        self._check_16bit_layers()  # refusals come before the first launch
         L = _lib.lib()
         st = _lib.stream_ptr()
         prep = {"sig": sig, "layers": {}}
@@ -322,10 +323,6 @@ class Darknet(nn.Module):
                 w0[:, :27] = w.reshape(32, 27)
                 entry["w0_bf16"] = w0.to(self._act_dtype).contiguous()
             if self._mfma and not entry["stem"]:
-                assert e["cin"] % 16 == 0, f"layer {i}: cin {e['cin']} is not a multiple of 16"
-                # blocked bf16 values are sized and strided in 16-channel planes of ceil16(channels); the kernels write
-                # cout_pad = ceil32(cout) channels: a BN layer with filters % 32 == 16 would write one plane per image too many
-                assert not e["bn"] or cout % 32 == 0, f"layer {i}: the bf16 path needs a multiple of 32 filters in conv+BN layers (got {cout}); use precision='fp32'"
                 nbytes = L.ay_packed_weight_bytes(cpad, e["cin"], e["k"])
                 packed = torch.empty(nbytes, device=device, dtype=torch.uint8)
                 check(self._fn("ay_pack_conv_weights")(ptr(w), ptr(packed), cout, cpad, e["cin"], e["k"], st), "ay_pack_conv_weights")
@@ -334,6 +331,21 @@ class Darknet(nn.Module):
         torch.cuda.current_stream().synchronize()  # temporaries (g,b_,mu,var,bias) die here
         self._prep = prep
         return prep
+
+    def _check_16bit_layers(self):
+        """what the 16-bit kernels cannot run, refused by layer index without touching the device (precision='fp32' runs these graphs)"""
+        if not self._mfma:
+            return
+        for i, e in enumerate(self._graph):
+            if e["type"] != "convolutional" or (i == 0 and (e["cin"], e["cout"], e["k"], e["stride"]) == (3, 32, 3, 1)):
+                continue
+            if e["cin"] % 16 != 0:
+                raise NotImplementedError(f"layer {i}: the 16-bit path needs a multiple of 16 input channels (got {e['cin']}); use precision='fp32'")
+            # blocked 16-bit values are sized and strided in 16-channel planes of ceil16(channels); the kernels write
+            # cout_pad = ceil32(cout) channels: a BN layer with filters % 32 == 16 would write one plane per image too many
+            if e["bn"] and e["cout"] % 32 != 0:
+                raise NotImplementedError(f"layer {i}: the 16-bit path needs a multiple of 32 filters in conv+BN layers (got {e['cout']}); "
+                                          "use precision='fp32'")
 
     # ------------------------------------------------------------------ storage type of the MFMA path
     @property
@@ -497,9 +509,12 @@ class Darknet(nn.Module):
             elif k == _lib.OP_CONCAT_UPSAMPLE and mfma:
                 check(L.ay_concat_upsample_bf16(at(o.src), o.c1, o.up1, at(o.src2), o.c2, at(o.dst), B, d.hout, d.wout, st),
                       "ay_concat_upsample_bf16")
-            elif k == _lib.OP_CONCAT_UPSAMPLE:
-                assert o.up1 == 1 and o.c2 == 0  # fp32 routes ride the convolution loader; only a lone x2 upsample is copied
+            elif k == _lib.OP_CONCAT_UPSAMPLE and o.c2 == 0 and o.up1 == 1:  # fp32: a lone x2 upsample that no convolution's loader reads
                 bufs[o.dst].copy_(bufs[o.src].repeat_interleave(2, 2).repeat_interleave(2, 3))
+            elif k == _lib.OP_CONCAT_UPSAMPLE:  # fp32: a two-source route that something other than a convolution reads
+                ctot = o.c1 + o.c2
+                check(L.ay_copy_channels_f32(at(o.src), at(o.dst), B, o.c1, ctot, 0, d.hout, d.wout, o.up1, st), "ay_copy_channels_f32")
+                check(L.ay_copy_channels_f32(at(o.src2), at(o.dst), B, o.c2, ctot, o.c1, d.hout, d.wout, 0, st), "ay_copy_channels_f32")
             elif k == _lib.OP_DECODE:
                 check(L.ay_yolo_decode(at(o.src), int(mfma), ptr(out), B, o.num_anchors, o.num_classes, o.grid, S, o.anchors_wh, N,
                                        o.row_offset, st), "ay_yolo_decode")
@@ -515,7 +530,8 @@ class Darknet(nn.Module):
         bf16 / fp16: the op list ``ay_plan_create`` takes.  fp32 and the split modes (host executor only, ``ay_plan_create`` never sees it): every
         convolution is an ``OP_CONV`` for ``ay_conv_fwd_f32`` / ``ay_conv_fwd_split``, whose loader reads ``src`` (``PLAN_INPUT`` = the image) with
         ``c1`` channels, x2 nearest-upsampled when ``up1``, followed by the channels of ``src2`` when set; a lazy upsample
-        that anything else reads is an ``OP_CONCAT_UPSAMPLE`` with ``c2 = 0`` (a tensor copy)."""
+        that anything else reads is an ``OP_CONCAT_UPSAMPLE`` with ``c2 = 0`` (a tensor copy), a two-source route that anything else
+        reads -- a shortcut -- one with ``c2 > 0`` (two channel copies, ``ay_copy_channels_f32``)."""
         mfma, graph = self._mfma, self._graph
         ops, op_layer, values, val = [], [], [], {}
 
@@ -553,12 +569,28 @@ class Darknet(nn.Module):
             v = val[i]
             if v[0] == "t":
                 return v[1]
-            assert v[0] == "up", f"layer {i}: a folded route is read by something other than a convolution"
+            if v[0] == "cat":   # a folded route that something other than a convolution's loader reads as well: a copy
+                return concat(i)
+            if v[0] != "up":
+                raise NotImplementedError(f"layer {i}: its output is never materialised ({v[0]}), but a later layer reads it")
             src = resolve(v[1])  # lazy upsample -> materialise
             h = size_of(i)
             dst = new_value(i)
             op(_lib.OP_CONCAT_UPSAMPLE, src=src, dst=dst, c1=graph[i]["channels"], up1=1, c2=0,
                conv=ConvDesc(B, 0, 0, h, h, h, h, 1, 1, 0, 0, 0))
+            val[i] = ("t", dst)
+            return dst
+
+        def concat(i):
+            """materialise the two-source route i = [a (x2 when a lazy upsample) | b]: -> id of its value"""
+            a, b_ = graph[i]["srcs"]
+            up = val[a][0] == "up"
+            s1 = resolve(val[a][1]) if up else resolve(a)
+            s2 = resolve(b_)
+            h = size_of(i)
+            dst = new_value(i)
+            op(_lib.OP_CONCAT_UPSAMPLE, src=s1, src2=s2, dst=dst, c1=graph[a]["channels"], up1=int(up),
+               c2=graph[b_]["channels"], conv=ConvDesc(B, 0, 0, h, h, h, h, 1, 1, 0, 0, 0))
             val[i] = ("t", dst)
             return dst
 
@@ -608,7 +640,7 @@ class Darknet(nn.Module):
                     o = op(_lib.OP_CONV1X1_CAT, src=s1, src2=s2, dst=dst, conv=d, c1=graph[ra]["channels"])
                 elif mfma:
                     if e["src"] < 0:
-                        raise NotImplementedError("bf16 path expects the 3->32 3x3 stem as layer 0")
+                        raise NotImplementedError(f"layer {i}: the 16-bit path expects the 3->32 3x3 stride-1 stem as layer 0; use precision='fp32'")
                     src = resolve(e["src"])
                     if fuse:
                         res = resolve(graph[i + 1]["b"])
@@ -645,22 +677,15 @@ class Darknet(nn.Module):
                     if not mfma or self._cat_foldable(i, val):
                         val[i] = ("cat", srcs)  # [a (x2 when a lazy upsample) | b]: read by the loader of the next convolution
                     else:
-                        a, b_ = srcs
-                        up = val[a][0] == "up"
-                        s1 = resolve(val[a][1]) if up else resolve(a)
-                        s2 = resolve(b_)
-                        h = size_of(i)
-                        dst = new_value(i)
-                        op(_lib.OP_CONCAT_UPSAMPLE, src=s1, src2=s2, dst=dst, c1=graph[a]["channels"], up1=int(up),
-                           c2=graph[b_]["channels"], conv=ConvDesc(B, 0, 0, h, h, h, h, 1, 1, 0, 0, 0))
-                        val[i] = ("t", dst)
+                        concat(i)
                 else:
-                    raise NotImplementedError("route with more than two sources")
+                    raise NotImplementedError(f"layer {i}: route with more than two sources")
             elif t == "yolo":
                 y = self.module_list[i][0]
                 head = resolve(e["src"])
                 G = size_of(i)
-                assert y.num_anchors <= 6
+                if y.num_anchors > 6:   # anchors_wh of the op descriptor (include/amyloid_yolo.h) holds six
+                    raise NotImplementedError(f"layer {i}: a detection layer with {y.num_anchors} anchors; an op carries at most 6")
                 o = op(_lib.OP_DECODE, src=head, num_anchors=y.num_anchors, num_classes=y.num_classes, grid=G, row_offset=row,
                        conv=ConvDesc(B, 0, 0, G, G, G, G, 1, 1, 0, 0, 0))
                 for k, v in enumerate(float(v) for a in y.anchors for v in a):
@@ -744,7 +769,8 @@ class Darknet(nn.Module):
             return t.clone()
         B, P, H, W, _ = t.shape
         c = self._graph[i]["channels"]
-        o = torch.empty(B, c, H, W, device=t.device, dtype=torch.float32)
+        # all P planes are converted: the converter strides images by ceil16(channels) planes, and a head value has ceil32(channels) / 16
+        o = torch.empty(B, P * 16, H, W, device=t.device, dtype=torch.float32)
         fn = {torch.bfloat16: L.ay_blocked_bf16_to_nchw_f32, torch.float16: L.ay_blocked_f16_to_nchw_f32}.get(t.dtype, L.ay_blocked_f32_to_nchw_f32)
-        check(fn(ptr(t), ptr(o), B, c, H, W, _lib.stream_ptr()), "blocked_to_nchw")
-        return o
+        check(fn(ptr(t), ptr(o), B, P * 16, H, W, _lib.stream_ptr()), "blocked_to_nchw")
+        return o if P * 16 == c else o[:, :c].contiguous()

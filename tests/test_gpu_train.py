@@ -47,46 +47,52 @@ def _trimmed_rel_l2(g, ref, keep=0.98):
     return float(np.linalg.norm(e[idx]) / max(np.linalg.norm(np.asarray(ref, np.float64).reshape(-1)[idx]), 1e-30))
 
 
-def _contract_spread(tmp_cfg_dir):
-    """What the fp32 contract itself leaves open, measured on the CPU oracle: the training step of every TRAIN_CASE evaluated twice --
-    convolution sums in fp32 (ATen's order, = the reference) and in float64 -- and, per checked layer, the trimmed relative L2
-    distance of the two filter gradients; the maximum over the cases (a flip is a chance event of a case) and, walking from the
-    loss down, over the layers above (a layer's gradient carries every flip between it and the loss).  The HIP step is a third
-    evaluation of the same contract in yet another summation order: it is held to a small multiple of this spread."""
-    if _SPREAD:
-        return _SPREAD
+def contract_spread(cfg, layers, steps):
+    """What the fp32 contract itself leaves open on the graph of `cfg`, measured on the CPU oracle: every training step of `steps`
+    = [(x, targets)] evaluated twice -- convolution sums in fp32 (ATen's order, = the reference) and in float64 -- and, per layer of
+    `layers`, the trimmed relative L2 distance of the two filter gradients; the maximum over the steps (a flip is a chance event of
+    a step) and, walking from the loss down, over the layers above (a layer's gradient carries every flip between it and the
+    loss).  -> {layer: spread}"""
     from oracle.darknet_oracle import OracleDarknet
-    per_layer = {li: 0.0 for li in GRAD_LAYERS}
-    for name, C_, S, B, seed in gc.TRAIN_CASES:
+    per_layer = {li: 0.0 for li in layers}
+    for x, tg in steps:
         grads = []
         for f64 in (False, True):
-            cfg = cfg_gen.write_cfg(C_, tmp_cfg_dir)
             o = OracleDarknet(cfg)
             o.set_params(synth.synth_params(parse_config.parse_model_config(cfg), seed=7))
             o.conv_f64 = f64
             o.require_grad()
-            loss, _ = o.forward(torch.from_numpy(gc.model_inputs(S, B, 10)), torch.from_numpy(gc.train_targets(B, C_, S, seed)), train_bn=True)
+            loss, _ = o.forward(x, tg, train_bn=True)
             loss.backward()
-            grads.append({li: o.params[li]["weight"].grad.numpy() for li in GRAD_LAYERS})
-        for li in GRAD_LAYERS:
+            grads.append({li: o.params[li]["weight"].grad.numpy() for li in layers})
+        for li in layers:
             per_layer[li] = max(per_layer[li], _trimmed_rel_l2(grads[0][li], grads[1][li]))
-    run = 0.0
-    for li in sorted(GRAD_LAYERS, reverse=True):
+    run, out = 0.0, {}
+    for li in sorted(layers, reverse=True):
         run = max(run, per_layer[li])
-        _SPREAD[li] = run
+        out[li] = run
+    return out
+
+
+def _contract_spread(tmp_cfg_dir):
+    """contract_spread of the YOLOv3 cfg over the TRAIN_CASES (the maximum over the cases, which differ in their class count), on
+    GRAD_LAYERS.  The HIP step is a third evaluation of the same contract in yet another summation order: it is held to a small
+    multiple of this spread."""
+    if _SPREAD:
+        return _SPREAD
+    per_case = [contract_spread(cfg_gen.write_cfg(C_, tmp_cfg_dir), GRAD_LAYERS,
+                                [(torch.from_numpy(gc.model_inputs(S, B, 10)), torch.from_numpy(gc.train_targets(B, C_, S, seed)))])
+                for name, C_, S, B, seed in gc.TRAIN_CASES]
+    # the running maximum from the loss down commutes with the maximum over the cases
+    _SPREAD.update({li: max(c[li] for c in per_case) for li in GRAD_LAYERS})
     return _SPREAD
 
 
-@pytest.mark.parametrize("case", gc.TRAIN_CASES, ids=lambda c: c[0])
-def test_train_step_vs_reference(golden_dir, tmp_cfg_dir, case):
-    """loss within 1e-4, the 13 per-layer metrics within 2e-4, sampled gradients within 2e-3 of the layer's gradient
-    scale (fp32 sums over up to 10^5 terms in a different order), BN running statistics within 1e-4."""
-    name, C_, S, B, seed = case
-    z = np.load(os.path.join(golden_dir, name + ".npz"))
-    m = _model(C_, tmp_cfg_dir)
-    m.train()
-    tg = torch.from_numpy(gc.train_targets(B, C_, S, seed))
-    x = torch.from_numpy(gc.model_inputs(S, B, 10))
+def check_train_step(m, z, x, tg, layers, tight_layers, spread):
+    """One fp32 training step of the HIP model `m` on (x, tg) against the reference results `z` (the keys of tests/golden/train_*.npz:
+    out, loss, metric_keys, metrics and per layer of `layers` gw / gb | ggamma, gbeta, rmean, rvar); bars in
+    test_train_step_vs_reference.  `tight_layers`: the linear heads.  `spread`: contract_spread of the graph on `layers`."""
+    B, S, C_ = x.shape[0], x.shape[2], m.yolo_layers[0].num_classes
     loss, out = m(x, tg)
     assert not out.is_cuda and out.shape == (B, m.num_boxes(S), 5 + C_)
     # train-mode outputs: batch statistics over as few as B*G*G = 27..32 samples per channel divide a 1e-6 relative
@@ -97,22 +103,12 @@ def test_train_step_vs_reference(golden_dir, tmp_cfg_dir, case):
     keys = list(z["metric_keys"])
     got = np.array([[yl.metrics[k] for k in keys] for yl in m.yolo_layers])
     close(got, z["metrics"], 2e-4, "metrics")
-    # Gradients.  The three linear heads (no LeakyReLU between them and the loss) must match to 2e-4 of the layer's
-    # gradient scale.  Below a LeakyReLU the comparison is inherently looser: a pre-activation within ~1e-5 of zero
-    # takes slope 1 on one side and 0.1 on the other, and a different fp32 summation order in the convolution flips
-    # the sign of a handful of such elements per step (17 of ~10^7 in this case, scripts/dbg_train.py lists them).
-    # Each flip changes dz at one element by up to 10x and spreads from there, so those layers are held to
-    # 10 % of the gradient scale element-wise (one flipped sample of 32 moves a whole filter row) and 3 % in relative L2; the kernels themselves are pinned tightly,
-    # one by one, in test_backward_kernels_vs_autograd below.
-    # On top of those flip allowances every filter gradient is held, in TRIMMED relative L2 (the 2 % of the elements with the largest
-    # error left out: the flipped rows), to 2.5x what the contract itself leaves open at that depth (_contract_spread: 3e-5 at layer
-    # 80, 0.4 % at 73, 0.8 % from 42 down) -- a kernel that is 2 % off in a deep layer fails this, where the flat 3 % let it pass.
-    spread = _contract_spread(tmp_cfg_dir)
 
     def check_grad(g, ref, tight, what, trimmed_bar=None):
         g, ref = np.asarray(g, np.float64), np.asarray(ref, np.float64)
         scale = max(np.abs(ref).max(), 1e-12)
         if tight:
+            print(f"{what}: {np.abs(g - ref).max() / scale:.2e} of the scale (bar 2e-4)")
             assert np.abs(g - ref).max() <= 2e-4 * scale, (what, float(np.abs(g - ref).max() / scale))
         else:
             assert np.abs(g - ref).max() <= 1e-1 * scale, (what, float(np.abs(g - ref).max() / scale))
@@ -122,13 +118,13 @@ def test_train_step_vs_reference(golden_dir, tmp_cfg_dir, case):
             print(f"{what}: trimmed rel L2 {t:.2e} (bar {trimmed_bar:.2e}), rel L2 {np.linalg.norm(g - ref) / np.linalg.norm(ref):.2e}")
             assert t <= trimmed_bar, (what, t, trimmed_bar)
 
-    for li in GRAD_LAYERS:
+    for li in layers:
         conv = m.module_list[li][0]
         g = conv.weight.grad.cpu().numpy()
         ref = z[f"gw{li}"]
         if ref.shape != g.shape:
             g = g.reshape(-1)[:: max(1, g.size // 65536)]
-        tight = li in (81, 93, 105)
+        tight = li in tight_layers
         check_grad(g, ref, tight, f"dW{li}", trimmed_bar=max(2.5 * spread[li], 2e-4))
         if conv.bias is not None:
             check_grad(conv.bias.grad.cpu().numpy(), z[f"gb{li}"], tight, f"db{li}")
@@ -139,6 +135,30 @@ def test_train_step_vs_reference(golden_dir, tmp_cfg_dir, case):
             close(bn.running_mean.cpu().numpy(), z[f"rmean{li}"], 1e-4, "running_mean")
             close(bn.running_var.cpu().numpy(), z[f"rvar{li}"], 1e-4, "running_var")
             assert int(bn.num_batches_tracked) == 1
+
+
+@pytest.mark.parametrize("case", gc.TRAIN_CASES, ids=lambda c: c[0])
+def test_train_step_vs_reference(golden_dir, tmp_cfg_dir, case):
+    """loss within 1e-4, the 13 per-layer metrics within 2e-4, sampled gradients within 2e-3 of the layer's gradient
+    scale (fp32 sums over up to 10^5 terms in a different order), BN running statistics within 1e-4.
+
+    Gradients.  The three linear heads (no LeakyReLU between them and the loss) must match to 2e-4 of the layer's
+    gradient scale.  Below a LeakyReLU the comparison is inherently looser: a pre-activation within ~1e-5 of zero
+    takes slope 1 on one side and 0.1 on the other, and a different fp32 summation order in the convolution flips
+    the sign of a handful of such elements per step (17 of ~10^7 in this case, scripts/dbg_train.py lists them).
+    Each flip changes dz at one element by up to 10x and spreads from there, so those layers are held to
+    10 % of the gradient scale element-wise (one flipped sample of 32 moves a whole filter row) and 3 % in relative L2; the kernels themselves are pinned tightly,
+    one by one, in test_backward_kernels_vs_autograd below.
+    On top of those flip allowances every filter gradient is held, in TRIMMED relative L2 (the 2 % of the elements with the largest
+    error left out: the flipped rows), to 2.5x what the contract itself leaves open at that depth (_contract_spread: 3e-5 at layer
+    80, 0.4 % at 73, 0.8 % from 42 down) -- a kernel that is 2 % off in a deep layer fails this, where the flat 3 % let it pass."""
+    name, C_, S, B, seed = case
+    z = np.load(os.path.join(golden_dir, name + ".npz"))
+    m = _model(C_, tmp_cfg_dir)
+    m.train()
+    tg = torch.from_numpy(gc.train_targets(B, C_, S, seed))
+    x = torch.from_numpy(gc.model_inputs(S, B, 10))
+    check_train_step(m, z, x, tg, GRAD_LAYERS, (81, 93, 105), _contract_spread(tmp_cfg_dir))
 
 
 def test_backward_kernels_vs_autograd():

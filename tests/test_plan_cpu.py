@@ -48,9 +48,37 @@ def create(ops, vbytes, S, N, dtype=0):
     return rc, h
 
 
+def check_plan_arena(ops, vbytes, S, N, dtype=0):
+    """ay_plan_create on a 16-bit op list: accepted, every value read after it is written, offsets aligned, and no two values whose
+    lifetimes overlap share bytes.  -> arena size in bytes"""
+    L = _lib.lib()
+    rc, h = create(ops, vbytes, S, N, dtype)
+    assert rc == 0, L.ay_last_error()
+    try:
+        arena = L.ay_plan_workspace_bytes(h)
+        off = [L.ay_plan_value_offset(h, v) for v in range(len(vbytes))]
+        assert arena >= max(vbytes) and all(o % 256 == 0 for o in off)
+        # no two values whose lifetimes overlap share bytes
+        born, last = {}, {}
+        for i, o in enumerate(ops):
+            for v in reads_of(o):
+                assert v in born, (i, v)
+                last[v] = i
+            if o.kind != _lib.OP_DECODE:
+                born[o.dst] = i
+                last.setdefault(o.dst, i)
+        vals = sorted(born)
+        for a in vals:
+            for b in vals:
+                if a < b and born[a] <= last[b] and born[b] <= last[a]:
+                    assert off[a] + vbytes[a] <= off[b] or off[b] + vbytes[b] <= off[a], (a, b)
+        return arena
+    finally:
+        L.ay_plan_destroy(h)
+
+
 @pytest.mark.parametrize("opts", [dict(), dict(fuse_blocks=False, fold_routes=False), dict(stem_mode="fp32"), dict(precision="fp16")], ids=str)
 def test_lowering_and_arena(tmp_cfg_dir, opts):
-    L = _lib.lib()
     m = Darknet(cfg_gen.write_cfg(3, tmp_cfg_dir))
     m.precision = "bf16"
     for k, v in opts.items():
@@ -67,29 +95,8 @@ def test_lowering_and_arena(tmp_cfg_dir, opts):
         assert kinds.count(_lib.OP_CONCAT_UPSAMPLE) == 2 and kinds.count(_lib.OP_RESBLOCK) == 0
     if opts.get("stem_mode") == "fp32":
         assert kinds[0] == _lib.OP_STEM
-    rc, h = create(ops, vbytes, S, m.num_boxes(S), int(m.precision == "fp16"))
-    assert rc == 0, L.ay_last_error()
-    try:
-        arena = L.ay_plan_workspace_bytes(h)
-        off = [L.ay_plan_value_offset(h, v) for v in range(len(vbytes))]
-        assert arena < 0.25 * sum(vbytes)                          # lifetimes are short: a few layers live at a time
-        assert arena >= max(vbytes) and all(o % 256 == 0 for o in off)
-        # no two values whose lifetimes overlap share bytes
-        born, last = {}, {}
-        for i, o in enumerate(ops):
-            for v in reads_of(o):
-                assert v in born, (i, v)
-                last[v] = i
-            if o.kind != _lib.OP_DECODE:
-                born[o.dst] = i
-                last.setdefault(o.dst, i)
-        vals = sorted(born)
-        for a in vals:
-            for b in vals:
-                if a < b and born[a] <= last[b] and born[b] <= last[a]:
-                    assert off[a] + vbytes[a] <= off[b] or off[b] + vbytes[b] <= off[a], (a, b)
-    finally:
-        L.ay_plan_destroy(h)
+    arena = check_plan_arena(ops, vbytes, S, m.num_boxes(S), int(m.precision == "fp16"))
+    assert arena < 0.25 * sum(vbytes)                              # lifetimes are short: a few layers live at a time
 
 
 @pytest.mark.parametrize("classes", [2, 3])
