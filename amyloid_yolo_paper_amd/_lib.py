@@ -103,6 +103,7 @@ _SIGS = {
     "ay_plan_op_reversed": (_I, [_P, _I]),
     "ay_conv_set_traversal": (None, [_I]),
     "ay_conv_get_traversal": (_I, []),
+    "ay_conv_deal_probe": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "ay_plan_workspace_bytes": (_SZ, [_P]),
     "ay_plan_value_offset": (_SZ, [_P, _I]),
     "ay_plan_forward": (_I, [_P, _P, _P, _P, _P]),

@@ -37,18 +37,22 @@ int conv_num_cus() {
 // on that stream starts -- so a set must never be shared by two streams, whose launches may overlap: every (device, stream)
 // pair owns DEAL_SETS sets of its own, up to DEAL_STREAMS streams per device; further streams deal statically.  A set pointer
 // baked into a captured graph node stays valid under the same rule: replay the graph on the stream it was captured on, or on
-// any stream as long as nothing else on the CAPTURE stream runs concurrently.
+// any stream as long as nothing else on the CAPTURE stream runs concurrently.  The owners' table is at file scope so that
+// ay_conv_deal_probe reads it under the same mutex.
+namespace {
+struct DealTable {  // of one device; guarded by g_deal_mu
+    unsigned* base = nullptr;
+    hipStream_t streams[DEAL_STREAMS] = {};
+    unsigned seq[DEAL_STREAMS] = {};
+    int n = 0;
+};
+std::mutex g_deal_mu;
+DealTable g_deal_tables[64];
+}  // namespace
+
 unsigned* next_deal_set(hipStream_t st) {
-    struct PerDevice {
-        unsigned* base = nullptr;
-        hipStream_t streams[DEAL_STREAMS] = {};
-        unsigned seq[DEAL_STREAMS] = {};
-        int n = 0;
-    };
-    static std::mutex mu;
-    static PerDevice devs[64];
-    std::lock_guard<std::mutex> lock(mu);
-    PerDevice& pd = devs[current_device()];
+    std::lock_guard<std::mutex> lock(g_deal_mu);
+    DealTable& pd = g_deal_tables[current_device()];
     if (!pd.base) {
         void* p = nullptr;
         if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_deal)) != hipSuccess) return nullptr;  // this device's copy of the symbol
@@ -96,6 +100,33 @@ void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* 
 static thread_local int t_traversal_reverse = 0;
 int conv_traversal_reverse() { return t_traversal_reverse; }
 }  // namespace ay
+
+// Tests and debugging only (synchronous): the dealing state of the current device as next_deal_set left it.  Reads the table, never
+// registers `stream`, never advances a rotation.
+extern "C" int ay_conv_deal_probe(ay_stream_t stream, int32_t* slot, uint32_t* launches, int32_t* nonzero_words) {
+    using namespace ay;
+    AY_CHECK_ARG(slot && launches && nonzero_words, "ay_conv_deal_probe: null argument");
+    if (hipDeviceSynchronize() != hipSuccess) {
+        set_error("ay_conv_deal_probe: device synchronisation failed");
+        return AY_ERR_LAUNCH;
+    }
+    static unsigned host[DEAL_STREAMS * DEAL_SETS][16];  // 64 KiB: under the mutex, not on the stack
+    std::lock_guard<std::mutex> lock(g_deal_mu);
+    const DealTable& pd = g_deal_tables[current_device()];
+    int k = 0;
+    while (k < pd.n && pd.streams[k] != (hipStream_t)stream) ++k;
+    *slot = k < pd.n ? k : -1;
+    *launches = k < pd.n ? pd.seq[k] : 0u;
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_deal), sizeof(host)) != hipSuccess) {
+        set_error("ay_conv_deal_probe: reading the counter sets failed");
+        return AY_ERR_LAUNCH;
+    }
+    int nz = 0;
+    for (int i = 0; i < DEAL_STREAMS * DEAL_SETS; ++i)
+        for (int j = 0; j < 16; ++j) nz += host[i][j] != 0;
+    *nonzero_words = nz;
+    return AY_OK;
+}
 extern "C" void ay_conv_set_traversal(int reverse) { ay::t_traversal_reverse = reverse != 0; }
 extern "C" int ay_conv_get_traversal(void) { return ay::t_traversal_reverse; }
 namespace ay {

@@ -96,6 +96,20 @@ int ay_stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const flo
 void ay_conv_set_traversal(int reverse);
 int ay_conv_get_traversal(void);
 
+/* TESTS AND DEBUGGING ONLY -- the one convolution entry that synchronises: it waits for the current device, then reads the state of
+ * the dynamic item dealing there.  The rule it lets a test observe: a ring-convolution launch that deals dynamically takes one
+ * counter set (16 words: 8 per-XCD item counters, an exit counter) from the 64 that its (device, stream) pair owns, in rotation;
+ * up to 16 streams per device own sets, in the order of their first dynamic launch, for the life of the process; a launch on a
+ * further stream, and every launch that deals statically, takes none.  A set belongs to its launch from the launch's first
+ * workgroup to its last, which hands it back zeroed: with no launch in flight every word of every set is zero.  A captured kernel
+ * node keeps the pointer of the set it was given at capture -- a set of the CAPTURE stream -- so a replay is correct on the
+ * capture stream, or on any stream while no other library work runs on the capture stream.
+ *   slot           index of `stream` among the current device's owners, -1 if it owns no sets
+ *   launches       counter sets `stream` has taken so far (0 without an entry)
+ *   nonzero_words  non-zero 32-bit words in all sets of the device
+ * The call neither registers `stream` nor advances a rotation. */
+int ay_conv_deal_probe(ay_stream_t stream, int32_t* slot, uint32_t* launches, int32_t* nonzero_words);
+
 /* 3x3 (stride 1|2) and 1x1 convolution, blocked bf16 in, MFMA 32x32x16 bf16, fp32 accumulate,
  * fused scale/shift + leaky + residual epilogue; `residual` (blocked bf16, output shape) may be NULL. */
 int ay_conv_fwd_bf16(const ay_conv_desc* d, const void* src, const void* w_packed, const float* scale,
