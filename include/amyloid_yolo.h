@@ -630,7 +630,14 @@ int ay_plan_forward_timed(const ay_plan* plan, const float* x_nchw, void* worksp
  * valid rows per image -> rows_out [batch][max_rows][7], count_out[batch]: pairs of rows of class 0 or 1 whose truncated integer pixel
  * rectangles share a pixel are replaced by the rectangle of the covered pixels (min of the confidences), pass after pass until
  * nothing changes, exactly as the reference does -- with the pair order the reference leaves to a Python set made explicit: rows
- * in input order, merged rows appended.  One wavefront per image, rows in LDS; max_rows <= ay_merge_detections_max_rows(). */
+ * in input order, merged rows appended.  One wavefront per image, rows in LDS; max_rows <= ay_merge_detections_max_rows().
+ * count[b] is clamped to [0, max_rows] (ay_nms_merge counts every kept row, also those it had no room for); rows behind count[b]
+ * are not read.  Image b's rows lie at b * max_rows * 7 in both buffers; the rows of rows_out behind count_out[b] are NOT written
+ * (a caller that wants zeros there clears the buffer first).  Rows and order are exact -- input values are copied, sign of zero
+ * included, the label of a merged row is that of the lower-index row of the pair -- as long as every coordinate stays below 2^24 px:
+ * a merged corner is an integer stored as float.  Identical rows collapse to the first; +0.0 and -0.0 are the same value.
+ * Returns -1 (and launches nothing) for a null pointer, batch <= 0, max_rows outside 1 .. ay_merge_detections_max_rows() or
+ * rows == rows_out. */
 int ay_merge_detections_max_rows(void);
 int ay_merge_detections(const float* rows, const int* count, int batch, int max_rows, float* rows_out, int* count_out,
                         ay_stream_t stream);
