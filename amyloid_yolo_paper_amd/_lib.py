@@ -1,13 +1,18 @@
 """ctypes binding of libamyloid_yolo_hip.so (the C ABI declared in include/amyloid_yolo.h).
 
+The signatures (``_SIGS``) and the ``AY_*`` constants (``CONSTANTS``) are read from that header at import: a new entry point takes its
+prototype there and its definition in a ``.hip`` file, and no line here.  Only the structs are restated (tests/test_abi_cpu.py holds
+their fields against the header's).
+
 There is no CPU fallback: if the HIP library is missing or a call fails this raises.
 """
 import ctypes as C
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libamyloid_yolo_hip.so")
-ABI_VERSION = 2   # include/amyloid_yolo.h: AY_ABI_VERSION this binding's signatures (_SIGS) were written against
+HEADER_PATH = os.path.join(HERE, "..", "include", "amyloid_yolo.h")   # where build.py finds it
 
 
 class ConvDesc(C.Structure):
@@ -38,10 +43,6 @@ class AugWindowParams(C.Structure):
                 ("y0", C.c_int32), ("context", C.c_int32), ("fill", C.c_float), ("aug", AugParams)]
 
 
-PLAN_INPUT, PLAN_NONE = -1, -2
-OP_STEM_S2_FUSED, OP_STEM, OP_CONV, OP_RESBLOCK, OP_CONV1X1_CAT, OP_CONCAT_UPSAMPLE, OP_DECODE = 1, 2, 3, 4, 5, 6, 7
-
-
 class StainParams(C.Structure):
     """ay_stain_params (include/amyloid_yolo.h, THE STAIN RULE): the tables of one stain map, uploaded once per slide"""
     _fields_ = [("od", C.c_float * 256), ("D", C.c_float * 9), ("A", C.c_float * 9), ("T", C.c_float * 257)]
@@ -56,139 +57,60 @@ class AyError(RuntimeError):
     pass
 
 
-_P, _I, _F, _SZ, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
-_SIGS = {
-    "ay_version": (C.c_int, []),
-    "ay_last_error": (C.c_char_p, []),
-    "ay_pack_conv_weights_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_packed_weight_bytes": (_SZ, [_I, _I, _I]),
-    "ay_fold_bn": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P]),
-    "ay_stem_conv_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ay_stem_s2_fused_fwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
-    "ay_conv_fwd_bf16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
-    "ay_conv3x3_m16_fwd_bf16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
-    "ay_concat_upsample_bf16": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
-    "ay_blocked_bf16_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_blocked_f32_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_nchw_f32_to_blocked_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_conv_fwd_f32": (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "ay_conv_fwd_f32_valu": (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "ay_conv_fwd_split": (_I, [C.POINTER(ConvDesc), _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
-    "ay_yolo_decode": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _I, _P]),
-    "ay_head_decode_fwd_bf16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), _P, _I, _I, _P]),
-    "ay_head_decode_fwd_f16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), _P, _I, _I, _P]),
-    "ay_xywh2xyxy": (_I, [_P, _I64, _I, _P]),
-    "ay_box_iou": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
-    "ay_box_iou_pairwise": (_I, [_P, _I, _P, _I, _I, _P, _P]),
-    "ay_nms_workspace_bytes": (_SZ, [_I, _I]),
-    "ay_nms_filter": (_I, [_P, _I, _I, _I, _F, _P, _P, _SZ, _P]),
-    "ay_nms_sort_merge": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _SZ, _P]),
-    "ay_bn_train_fwd_f32": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "ay_bn_train_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "ay_bias_grad_f32": (_I, [_P, _P, _I, _I, _I, _P]),
-    "ay_bias_grad_f32_acc": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_conv_dgrad_f32": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P]),
-    "ay_conv_wgrad_f32": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P]),
-    "ay_add_f32": (_I, [_P, _P, _P, _SZ, _P]),
-    "ay_accumulate_f32": (_I, [_P, _P, _SZ, _P]),
-    "ay_copy_channels_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "ay_slice_accumulate_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "ay_yolo_loss_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
-    "ay_yolo_loss_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _F, _F, _P, _P, _P, _SZ, _P]),
-    "ay_conv1x1_cat_fwd_bf16": (_I, [C.POINTER(ConvDesc), _P, _I, _P, _P, _P, _P, _P, _P]),
-    "ay_resblock_supported": (_I, [_I]),
-    "ay_plan_create": (_I, [C.POINTER(PlanOp), _I, C.POINTER(C.c_size_t), _I, _I, _I, _I, C.POINTER(C.c_void_p)]),
-    "ay_plan_destroy": (None, [_P]),
-    "ay_plan_set_alternation": (_I, [_P, _I]),
-    "ay_plan_op_reversed": (_I, [_P, _I]),
-    "ay_conv_set_traversal": (None, [_I]),
-    "ay_conv_get_traversal": (_I, []),
-    "ay_conv_deal_probe": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
-    "ay_plan_workspace_bytes": (_SZ, [_P]),
-    "ay_plan_value_offset": (_SZ, [_P, _I]),
-    "ay_plan_forward": (_I, [_P, _P, _P, _P, _P]),
-    "ay_plan_forward_timed": (_I, [_P, _P, _P, _P, C.POINTER(C.c_float), _P]),
-    "ay_plan_profile_begin": (_I, [_P, C.POINTER(C.c_ubyte)]),
-    "ay_plan_profile_begin_every": (_I, [_P, C.POINTER(C.c_ubyte), _I]),
-    "ay_plan_profile_end": (_I, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
-    "ay_resblock_fwd_bf16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "ay_match_detections": (_I, [_P, _P, _I, _I, _P, _I, _F, _P, _P, _P]),
-    "ay_ingest_tiles_u8": (_I, [_P, _I, _I, _I, _I, _F, _P, _P]),
-    "ay_ingest_region_tiles_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _P, _P]),
-    "ay_ingest_region_tiles_step_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "ay_ingest_region_tiles_list_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, _I, _P, _P]),
-    "ay_augment_ingest_u8": (_I, [_P, _SZ, _P, _I, _I, _P, _P]),
-    "ay_augment_ingest_window_u8": (_I, [_P, _SZ, _P, _I, _I, _P, _P]),
-    "ay_tile_tissue_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "ay_build_targets_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "ay_build_targets": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
-    "ay_yolo_loss_giou_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _F, _F, _P, _P, _P, _SZ, _P]),
-    "ay_adam_flat": (_I, [_P, _P, _P, _P, _SZ, _F, _F, _F, _F, _I, _F, _P]),
-    "ay_bn_train_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ay_bn_train_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ay_bn_train_bwd_bf16_acc": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "ay_bn_train_fwd_bf16_zeroed_ws": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ay_bn_train_bwd_bf16_acc_zeroed_ws": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "ay_accumulate_bf16": (_I, [_P, _P, _SZ, _P]),
-    "ay_slice_accumulate_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "ay_zero_insert_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ay_pack_dgrad_weights_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_packed_dgrad_weight_bytes": (_SZ, [_I, _I, _I]),
-    "ay_pack_batch_block": (_I, []),
-    "ay_pack_batch_bf16": (_I, [_P, _P, _I, _P]),
-    "ay_stem_train_fwd_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "ay_stem_train_stats_workspace_bytes": (C.c_size_t, []),
-    "ay_stem_train_fwd_stats_bf16": (_I, [_P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _P]),
-    "ay_bn_train_apply_bf16": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ay_stem_train_wgrad_workspace_bytes": (C.c_size_t, []),
-    "ay_stem_train_wgrad_bf16": (_I, [_P, _P, _P, _I, _P, C.c_size_t, _I, _I, _I, _P]),
-    "ay_packed_dgrad_s2_weight_bytes": (C.c_size_t, [_I, _I]),
-    "ay_pack_dgrad_s2_weights_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_conv_dgrad_s2_bf16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _I, _P]),
-    "ay_conv_wgrad_bf16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P]),
-    "ay_conv_wgrad_bf16_acc": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P]),
-    "ay_conv_wgrad_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
-    "ay_conv_wgrad_bf16_ws": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P, C.c_size_t, _P]),
-    # IEEE-half twins of the inference entry points (same signatures)
-    "ay_pack_conv_weights_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_stem_conv_fwd_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ay_stem_s2_fused_fwd_f16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
-    "ay_conv_fwd_f16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
-    "ay_conv3x3_m16_fwd_f16": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
-    "ay_conv1x1_cat_fwd_f16": (_I, [C.POINTER(ConvDesc), _P, _I, _P, _P, _P, _P, _P, _P]),
-    "ay_resblock_fwd_f16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "ay_blocked_f16_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_nchw_f32_to_blocked_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ay_stream_fence": (_I, [_P]),
-    "ay_merge_detections_max_rows": (_I, []),
-    "ay_merge_detections": (_I, [_P, _P, _I, _I, _P, _P, _P]),
-    "ay_nms_merge": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _SZ, _P]),
-    "ay_seam_append": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P]),
-    "ay_seam_merge_workspace_bytes": (_SZ, [_I]),
-    "ay_seam_merge": (_I, [_P, _P, _I, _F, _P, _P, _P, _SZ, _P]),
-    "ay_ingest_region_tiles_views_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, C.POINTER(C.c_int), _I, _I, _P, _P]),
-    "ay_unview_rows": (_I, [_P, _I, C.POINTER(C.c_int), _I, _I, _I, _I, _P]),
-    "ay_view_votes": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P, _I, _P, _P]),
-    "ay_view_select": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "ay_slide_match_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "ay_slide_match": (_I, [_P, _I, _P, _I, C.POINTER(C.c_float), _I, C.POINTER(C.c_float), _F, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
-    "ay_burden_bin": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
-    "ay_field_select_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
-    "ay_field_select": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
-    "ay_pair_counts_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
-    "ay_pair_counts": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
-    "ay_pair_counts_window_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "ay_pair_counts_window": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ,
-                                   _P]),
-    "ay_stain_hist_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _P, _P]),
-    "ay_ingest_region_tiles_stain_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _P, _I, C.POINTER(C.c_int), _I, _P, _I, _P, _P]),
-    "ay_stain_apply_u8": (_I, [_P, _I, _I, _SZ, _I, _P, _P, _SZ, _P]),
-    "ay_stain_moments_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _P, _P, _P]),
-    "ay_stain_direction_hist_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "ay_stain_load_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
-    "ay_focus_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
-    "ay_box_segments_u8": (_I, [_P, _I, _I, _SZ, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
-}
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "ay_stream_t": C.c_void_p}
+
+
+def _ctype(decl, proto, is_return=False):
+    """One parameter (``const float* w``, ``size_t n``) or return type of a prototype -> its ctypes type.  Every pointer travels as
+    ``c_void_p`` (callers hand over ``byref``, ctypes arrays, ``c_void_p`` or None), except a returned ``const char*``."""
+    words = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split()
+    if "*" in words:
+        return C.c_char_p if is_return and words == ["char", "*"] else C.c_void_p
+    base = " ".join(words if is_return or len(words) == 1 else words[:-1])       # a parameter's last word is its name
+    if is_return and base == "void":
+        return None
+    if base not in _SCALARS:
+        raise AyError(f"{HEADER_PATH}: no ctypes type for `{decl.strip()}` in `{proto}`")
+    return _SCALARS[base]
+
+
+def parse_header(text):
+    """The text of include/amyloid_yolo.h -> (signatures, constants): ``name -> (restype, [argtypes])`` of every ``ret ay_name(args);``
+    and the value of every integer ``#define AY_*`` and of the enumerators.  A type outside the map above is an ``AyError`` that
+    names the prototype, never a default."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {name: int(value) for name, value in re.findall(r"^#define\s+(AY_\w+)\s+\(?(-?\d+)\)?\s*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for item in filter(None, map(str.strip, body.split(","))):
+            m = re.fullmatch(r"(AY_\w+)\s*=\s*(-?\d+)", item)
+            if not m:
+                raise AyError(f"{HEADER_PATH}: enumerator `{item}` has no integer value written out")
+            constants[m.group(1)] = int(m.group(2))
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w*][\w\s*]*?)\b(ay_\w+)\s*\(([^()]*)\)\s*;", text):
+        proto = " ".join(f"{ret}{name}({params})".split())
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (_ctype(ret, proto, is_return=True), [_ctype(p, proto) for p in params])
+    unread = set(re.findall(r"\b(ay_\w+)\s*\(", text)) - set(sigs)
+    if unread:
+        raise AyError(f"{HEADER_PATH}: cannot read the prototype of {sorted(unread)}")
+    return sigs, constants
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise AyError(f"{HEADER_PATH} is missing: the ctypes signatures and the AY_* constants are read from it")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+_SIGS, CONSTANTS = _read_header()
+ABI_VERSION = CONSTANTS["AY_ABI_VERSION"]      # lib() compares it with ay_version() of the library it loads
+PLAN_INPUT, PLAN_NONE = CONSTANTS["AY_PLAN_INPUT"], CONSTANTS["AY_PLAN_NONE"]
+(OP_STEM_S2_FUSED, OP_STEM, OP_CONV, OP_RESBLOCK, OP_CONV1X1_CAT, OP_CONCAT_UPSAMPLE, OP_DECODE) = (
+    CONSTANTS["AY_OP_" + n] for n in ("STEM_S2_FUSED", "STEM", "CONV", "RESBLOCK", "CONV1X1_CAT", "CONCAT_UPSAMPLE", "DECODE"))
 
 _lib = None
 

@@ -139,7 +139,7 @@ def match_slide(rows, targets, iou_thres=0.5, roi=None, cell_side=None):
                            ptr(best_target) if M else None, ptr(claim) if T else None, ptr(row_ign) if M else None,
                            ptr(tgt_ign) if T else None, ptr(stats), ptr(ws), ws.numel(), _lib.stream_ptr()), "ay_slide_match")
     st = stats.cpu().numpy()
-    if int(st[2 * K]) & 1:   # AY_SLIDE_FLAG_CLASS
+    if int(st[2 * K]) & _lib.CONSTANTS["AY_SLIDE_FLAG_CLASS"]:
         raise _lib.AyError("ay_slide_match: a target's class is no integer in 0 .. 4095")
     return {"tp": tp, "best_iou": best_iou, "best_target": best_target, "claim": claim, "row_ignored": row_ign.bool(),
             "target_ignored": tgt_ign.bool(), "eligible": torch.from_numpy(st[0:2 * K:2].copy()),

@@ -13,7 +13,8 @@ from .grid import check_bg_level, check_probe_stride, probed
 from .stream import STRIP_ROWS, ResidentStrips, StripStream
 
 
-BASIS_OD_SCALE, BASIS_OD_MAX, BASIS_MOMENT_WORDS, BASIS_DIR_BINS = 1024, 2466, 11, 512     # include/amyloid_yolo.h, THE BASIS RULE
+BASIS_OD_SCALE, BASIS_OD_MAX, BASIS_MOMENT_WORDS, BASIS_DIR_BINS = (                       # include/amyloid_yolo.h, THE BASIS RULE
+    _lib.CONSTANTS["AY_BASIS_" + n] for n in ("OD_SCALE", "OD_MAX", "MOMENT_WORDS", "DIR_BINS"))
 BASIS_STRIP = STRIP_ROWS    # rows of the (halved) slide per strip of estimate_basis: stain_stats'
 
 

@@ -10,8 +10,10 @@ from .._lib import check, ptr
 from ..stats import _slide_array
 from .grid import _whole, check_rows, hip_device, tile_grid
 
-BURDEN_MAX_CLASSES, BURDEN_MAX_FIELDS, BURDEN_MAX_FIELD_SIDE = 64, 64, 46340    # include/amyloid_yolo.h, THE BURDEN / FIELD RULE
-BURDEN_FLAG_NONFINITE, BURDEN_FLAG_CLASS = 1, 2
+_AY = _lib.CONSTANTS                                                            # include/amyloid_yolo.h, THE BURDEN / FIELD RULE
+BURDEN_MAX_CLASSES, BURDEN_MAX_FIELDS = _AY["AY_BURDEN_MAX_CLASSES"], _AY["AY_BURDEN_MAX_FIELDS"]
+BURDEN_FLAG_NONFINITE, BURDEN_FLAG_CLASS = _AY["AY_BURDEN_FLAG_NONFINITE"], _AY["AY_BURDEN_FLAG_CLASS"]
+BURDEN_MAX_FIELD_SIDE = 46340                                                   # THE FIELD RULE's bound on field * cell
 
 
 def _int_planes(a, dev):

@@ -6,13 +6,14 @@ import math
 import numpy as np
 import torch
 
-from .._lib import ptr
+from .._lib import CONSTANTS, ptr
 from ..stats import _slide_array
 from .colour import STAIN_BINS, StainBasis
 from .grid import _whole, check_raster, tile_grid
 
 
-LOAD_MIN_CELL, LOAD_MAX_SIDE, LOAD_FLAG_NONFINITE = 16, 1 << 24, 1       # include/amyloid_yolo.h, THE LOAD RULE
+LOAD_MIN_CELL, LOAD_FLAG_NONFINITE = CONSTANTS["AY_LOAD_MIN_CELL"], CONSTANTS["AY_LOAD_FLAG_NONFINITE"]
+LOAD_MAX_SIDE = 1 << 24                                                  # include/amyloid_yolo.h, THE LOAD RULE
 LOAD_MAX_CELLS = 1 << 26                                                 # 24 bytes per cell on the device
 
 

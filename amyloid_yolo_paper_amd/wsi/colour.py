@@ -11,7 +11,7 @@ from .. import _lib
 from .grid import hip_device
 
 
-STAIN_BINS = 512        # include/amyloid_yolo.h, THE STAIN RULE: bins of 1/64 OD
+STAIN_BINS = _lib.CONSTANTS["AY_STAIN_BINS"]        # include/amyloid_yolo.h, THE STAIN RULE: bins of 1/64 OD
 
 
 class StainBasis:

@@ -141,9 +141,9 @@ def _detect_region_overlap(model, stream, per_call, conf_thres, nms_thres, seam_
                                ptr(slide_rows), ptr(slide_tile), ptr(slide_count), capacity, _lib.stream_ptr()), "ay_seam_append")
         t0 += B
     M, flags = (int(v) for v in slide_count.cpu())
-    if flags & 1:
+    if flags & _lib.CONSTANTS["AY_SEAM_FLAG_MAX_DET"]:
         raise _lib.AyError(f"detect_region: a tile holds more than max_det={max_det} detections; raise max_det or conf_thres")
-    if flags & 2:
+    if flags & _lib.CONSTANTS["AY_SEAM_FLAG_CAPACITY"]:
         raise _lib.AyError(f"detect_region: more than seam_capacity={capacity} detections on the slide; raise seam_capacity")
     if M == 0:
         return []

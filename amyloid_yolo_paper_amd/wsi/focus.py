@@ -11,7 +11,8 @@ from .grid import _whole, check_rows, tile_grid
 from .stream import StripStream
 
 
-FOCUS_MIN_CELL, FOCUS_MAX_SIDE, FOCUS_FLAG_NONFINITE = 16, 1 << 24, 1    # include/amyloid_yolo.h, THE FOCUS RULE: THE LOAD RULE's
+FOCUS_MIN_CELL, FOCUS_FLAG_NONFINITE = _lib.CONSTANTS["AY_FOCUS_MIN_CELL"], _lib.CONSTANTS["AY_FOCUS_FLAG_NONFINITE"]
+FOCUS_MAX_SIDE = 1 << 24                                                 # include/amyloid_yolo.h, THE FOCUS RULE: THE LOAD RULE's
 FOCUS_MAX_PIXELS = 1 << 43                                               # H * W below it: s2 fits int64
 
 

@@ -13,8 +13,10 @@ from .grid import _whole, check_rows, tile_grid
 from .stream import StripStream
 
 
-SEG_COLS, SEG_MAX_SIDE, SEG_MAX_MARGIN = 20, 255, 127                    # include/amyloid_yolo.h, THE SEGMENT RULE
-SEG_NONFINITE, SEG_EMPTY, SEG_LARGE, SEG_NOT_RESIDENT, SEG_INTERNAL = 1, 2, 4, 8, 16
+_AY = _lib.CONSTANTS                                                      # include/amyloid_yolo.h, THE SEGMENT RULE
+SEG_COLS, SEG_MAX_SIDE, SEG_MAX_MARGIN = _AY["AY_SEG_COLS"], _AY["AY_SEG_MAX_SIDE"], _AY["AY_SEG_MAX_MARGIN"]
+SEG_NONFINITE, SEG_EMPTY, SEG_LARGE, SEG_NOT_RESIDENT, SEG_INTERNAL = (
+    _AY["AY_SEG_NONFINITE"], _AY["AY_SEG_EMPTY"], _AY["AY_SEG_LARGE"], _AY["AY_SEG_NOT_RESIDENT"], _AY["AY_SEG_INTERNAL"])
 
 
 def _check_segment(what, raster, shrink, bg_level, thres, core_thres, stain, basis, margin, min_area):

@@ -13,8 +13,10 @@ from ..stats import _slide_array
 from .grid import _whole, check_rows, hip_device
 
 
-PAIR_MAX_CLASSES, PAIR_MAX_RADII, PAIR_MAX_RADIUS_Q, PAIR_MAX_SIDE = 8, 32, 32767, 1 << 21      # include/amyloid_yolo.h, THE PAIR RULE
-PAIR_WINDOW_MIN_CELL, PAIR_WINDOW_MAX_CELLS = 16, 1 << 26                                       # THE PAIR WINDOW RULE
+PAIR_MAX_CLASSES, PAIR_MAX_RADII, PAIR_MAX_RADIUS_Q, PAIR_MAX_SIDE = (                          # include/amyloid_yolo.h, THE PAIR RULE
+    _lib.CONSTANTS["AY_PAIR_" + n] for n in ("MAX_CLASSES", "MAX_RADII", "MAX_RADIUS_Q", "MAX_SIDE"))
+PAIR_WINDOW_MIN_CELL, PAIR_WINDOW_MAX_CELLS = (                                                 # THE PAIR WINDOW RULE
+    _lib.CONSTANTS["AY_PAIR_WINDOW_" + n] for n in ("MIN_CELL", "MAX_CELLS"))
 
 
 def spatial_radii_q(radii):

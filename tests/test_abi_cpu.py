@@ -29,6 +29,80 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().ay_version() == _lib.ABI_VERSION == 2   # include/amyloid_yolo.h: AY_ABI_VERSION
 
 
+def test_derived_signatures_equal_the_frozen_table():
+    """tests/golden/abi_sigs.json is the hand-written ctypes table this binding carried before it read the header, dumped from that
+    table (every POINTER(...) entry as void*, as it now travels): the signatures read from the header equal it entry by entry"""
+    import json
+    names = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64,
+             "void*": ctypes.c_void_p, "char*": ctypes.c_char_p, "void": None}
+    with open(os.path.join(REPO, "tests", "golden", "abi_sigs.json")) as f:
+        frozen = json.load(f)
+    assert len(frozen) == 128 and sorted(frozen) == sorted(_lib._SIGS)
+    for name, (res, args) in frozen.items():
+        got_res, got_args = _lib._SIGS[name]
+        assert got_res is names[res], name
+        assert len(got_args) == len(args) and all(g is names[a] for g, a in zip(got_args, args)), name
+    assert _lib._SIGS["ay_last_error"][0] is ctypes.c_char_p and _lib._SIGS["ay_plan_destroy"][0] is None
+
+
+def test_parser_refuses_a_type_it_does_not_know():
+    good = "#define AY_TWO (-2)\nenum { AY_OP_A = 1, AY_OP_B = 7 };\nsize_t ay_ok(const float* x, unsigned n, ay_stream_t stream);\n"
+    sigs, constants = _lib.parse_header(good)
+    assert sigs == {"ay_ok": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p])}
+    assert constants == {"AY_TWO": -2, "AY_OP_A": 1, "AY_OP_B": 7}
+    for bad in ("int ay_bad(const float* x, long long n, ay_stream_t stream);", "int ay_bad(int n, ay_params by_value);",
+                "short ay_bad(int n);", "int ay_bad(int n, void (*callback)(int));"):
+        with pytest.raises(_lib.AyError, match="ay_bad"):
+            _lib.parse_header(good + bad)
+    with pytest.raises(_lib.AyError, match="AY_OP_C"):
+        _lib.parse_header("enum { AY_OP_A = 1, AY_OP_C };")
+
+
+def test_constants_keep_their_names_and_values():
+    """every name that used to be a literal next to a `# include/amyloid_yolo.h` comment, with the value that literal had"""
+    from amyloid_yolo_paper_amd import wsi
+    assert (_lib.ABI_VERSION, _lib.PLAN_INPUT, _lib.PLAN_NONE) == (2, -1, -2)
+    assert (_lib.OP_STEM_S2_FUSED, _lib.OP_STEM, _lib.OP_CONV, _lib.OP_RESBLOCK, _lib.OP_CONV1X1_CAT, _lib.OP_CONCAT_UPSAMPLE,
+            _lib.OP_DECODE) == (1, 2, 3, 4, 5, 6, 7)
+    frozen = dict(STAIN_BINS=512, SEG_COLS=20, SEG_MAX_SIDE=255, SEG_MAX_MARGIN=127, SEG_NONFINITE=1, SEG_EMPTY=2, SEG_LARGE=4,
+                  SEG_NOT_RESIDENT=8, SEG_INTERNAL=16, FOCUS_MIN_CELL=16, FOCUS_MAX_SIDE=1 << 24, FOCUS_FLAG_NONFINITE=1,
+                  LOAD_MIN_CELL=16, LOAD_MAX_SIDE=1 << 24, LOAD_FLAG_NONFINITE=1, BURDEN_MAX_CLASSES=64, BURDEN_MAX_FIELDS=64,
+                  BURDEN_MAX_FIELD_SIDE=46340, BURDEN_FLAG_NONFINITE=1, BURDEN_FLAG_CLASS=2, BASIS_OD_SCALE=1024, BASIS_OD_MAX=2466,
+                  BASIS_MOMENT_WORDS=11, BASIS_DIR_BINS=512, PAIR_MAX_CLASSES=8, PAIR_MAX_RADII=32, PAIR_MAX_RADIUS_Q=32767,
+                  PAIR_MAX_SIDE=1 << 21, PAIR_WINDOW_MIN_CELL=16, PAIR_WINDOW_MAX_CELLS=1 << 26)
+    for name, value in frozen.items():
+        got = getattr(wsi, name)
+        assert type(got) is int and got == value, name
+    assert _lib.CONSTANTS["AY_SEAM_FLAG_MAX_DET"] == 1 and _lib.CONSTANTS["AY_SEAM_FLAG_CAPACITY"] == 2
+    assert _lib.CONSTANTS["AY_SLIDE_FLAG_CLASS"] == 1
+
+
+def header_struct_fields(text, name):
+    """[(field, array length or None)] of `typedef struct name { ... } name;`, in order"""
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), text, flags=re.S).group(1)
+    return [(m.group(1), int(m.group(2)) if m.group(2) else None)
+            for stmt in body.split(";") if stmt.strip() for piece in stmt.split(",")
+            for m in [re.search(r"(\w+)\s*(?:\[(\d+)\])?\s*$", piece)]]
+
+
+def test_ctypes_structs_carry_the_headers_fields():
+    with open(os.path.join(REPO, "include", "amyloid_yolo.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    structs = {"ay_conv_desc": _lib.ConvDesc, "ay_plan_op": _lib.PlanOp, "ay_aug_params": _lib.AugParams,
+               "ay_aug_window_params": _lib.AugWindowParams, "ay_stain_params": _lib.StainParams,
+               "ay_stain_basis_params": _lib.StainBasisParams}
+    for name, cls in structs.items():
+        mirror = [(f, t._length_ if issubclass(t, ctypes.Array) else None) for f, t in cls._fields_]
+        assert mirror == header_struct_fields(text, name), name
+    assert header_struct_fields(text, "ay_aug_params")[3] == ("inv", 6) and len(header_struct_fields(text, "ay_plan_op")) == 21
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "nope.h"))
+    with pytest.raises(_lib.AyError, match="nope.h"):
+        _lib._read_header()
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
