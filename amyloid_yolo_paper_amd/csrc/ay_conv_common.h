@@ -464,6 +464,10 @@ void fill_args(ConvArgs& a, const ay_conv_desc* d, const void* src, const void* 
 // workgroups of a persistent launch over n_items items: 8 XCDs x min(items per XCD, wgs_per_cu x CUs per XCD); 0: n_items is
 // not in 1 .. 0x7fffffff
 unsigned persistent_grid(long long n_items, int wgs_per_cu = 1);
+// m = floor(2^32 / d) (0xffffffff for d <= 1) for the kernels' multiply-high division: q = __umulhi(n, m), r = n - q * d, then
+// if (r >= d) ++q, r -= d.  One correction suffices for every 32-bit n: m > 2^32 / d - 1, so n * m / 2^32 > n / d - n / 2^32 >
+// n / d - 1 and q is floor(n / d) or one less.
+unsigned mulhi_divisor(unsigned d);
 
 // One launch of a persistent ring kernel (512 threads) over n_items items of `a`: the counter set (dynamic dealing) or none
 // (static dealing: each workgroup takes every slots-th item of its XCD's range), the grid, the launch.  `what` names the launch

@@ -142,6 +142,8 @@ unsigned persistent_grid(long long n_items, int wgs_per_cu) {
     return (unsigned)(8 * (per_xcd < cu_slots ? per_xcd : cu_slots));
 }
 
+unsigned mulhi_divisor(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ULL / d); }
+
 bool phase_clock_read(hipStream_t st, const void* ticks, unsigned long long* t, int n) {  // synchronous: timing experiments only
     void* dev = nullptr;  // this device's copy of the tick array
     if (!ticks || !(conv_dbg() & DBG_CLOCK) || hipGetSymbolAddress(&dev, ticks) != hipSuccess) return false;

@@ -9,7 +9,7 @@
 //   C  layer 1: 2 chunks x 9 taps of v_mfma_f32_32x32x16_bf16 from those slabs; its filters (36 KiB) stay in LDS for the
 //      whole kernel
 //   D  conv_epilogue (affine, leaky, bf16, 16-byte stores)
-#include "ay_conv_common.h"
+#include "ay_stem_window.h"
 
 namespace ay {
 
@@ -31,7 +31,7 @@ struct StemFusedArgs {
     const float* shift0;
     int leaky0;
     int H, W;
-    unsigned m_tx, m_tpi;   // v2: floor(2^32 / tiles_x), floor(2^32 / tiles per image) (0xffffffff for a divisor of 1)
+    unsigned m_tx, m_tpi;   // v2: mulhi_divisor of tiles_x, of tiles per image
     ConvArgs c1;            // layer 1 as a ConvArgs (src unused)
 };
 
@@ -281,15 +281,9 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_kernel(StemFusedArgs s, in
 //     separate loops, so each keeps its own constants in registers:
 //   * a consumer wave holds its 18 filter fragments of layer 1 (72 VGPRs) for the whole kernel: only pixel fragments come from LDS
 //   * stem slabs keep even and odd pixel columns apart, so the stride-2 reads of layer 1 are contiguous 16-byte cells
-//   * the image tile arrives by 16-byte buffer DMA (11 wave instructions per tile instead of 35 of 4 bytes; lanes outside the
-//     image read out of the descriptor's range = zeros): the window starts 4 columns left of the tile so that every piece is
-//     16-byte aligned in HBM (needs W % 4 == 0; other widths take v1).  Item coordinates come from one multiply-high division per
-//     item, computed when its tile is issued and kept in a register queue for the two later iterations that use them
-//   * the tile is stored [row][channel][column]: the 27 taps of a stem pixel are a 9 x 3 grid (rho = 3 kh + ci, kw) in it, and
-//     the K = 32 slots are ORDERED so that the 8 taps of lane half 1 are those of half 0 moved down 3 (K-step 0) or 2 (K-step
-//     1) grid rows: every LDS read of the stem is one per-lane base + an immediate; the 5 spare slots carry zero filters and
-//     re-read taps of the same or the next pixel row (finite whenever the image is).  Producers hold scale / shift in
-//     registers, LeakyReLU is max(t, slope t), two values per convert
+//   * the image window (12 rows: 11 used), its DMA, the item coordinates and the order of the K = 32 tap slots are those of
+//     ay_stem_window.h (other widths than W % 4 == 0 take v1).  Producers hold scale / shift in registers, LeakyReLU is
+//     max(t, slope t), two values per convert
 template <typename DT>
 __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s, int n_items) {
     DT::enter();
@@ -302,13 +296,9 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
     constexpr int ROWP = 2 * HALFW;                       // slab row: [even columns 33][odd columns 33] cells of 16 B
     constexpr int S_POS = SH * ROWP;                      // 594 cells; the lanes of the last block beyond pixel 584 write behind them
     constexpr int S_POSP = S_POS + NBLK * 32 - S_PIX;     // 617
-    constexpr int IH = SH + 3;                            // 12 image rows 2*y0-2 .. (11 used + 1 that only zero filters see)
-    constexpr int IW = 72;                                // image columns 2*x0-4 .. 2*x0+67 (used: 2*x0-2 .. 2*x0+64)
+    typedef StemWindow<SH + 3> Win;                       // image rows 2*y0-2 .., columns 2*x0-4 .. 2*x0+67 (used: 2*x0-2 .. 2*x0+64)
     constexpr int XOFF = 2;                               // window column of image column 2*x0-2
-    constexpr int ROW_PIECES = IW / 4;                    // 16-byte pieces per row
-    constexpr int IMG_PIECES = IH * 3 * ROW_PIECES;       // 648: [row][channel][column piece]
-    constexpr int IMG_DMAS = (IMG_PIECES + 63) / 64;      // 11 wave-wide DMA instructions per tile: one per wave (waves 11-15: none)
-    constexpr int IMG_BYTES = IMG_DMAS * 1024;
+    constexpr int IMG_BYTES = Win::IMG_BYTES;             // 11 wave-wide DMA instructions per tile: one per wave (waves 11-15: none)
     constexpr int NIB = 3;
     constexpr int SLAB = 2 * S_POSP * 16;                 // one 16-channel chunk of stem output: [half][cell][8 ch]
     constexpr int SET = 2 * SLAB;                         // both chunks
@@ -317,9 +307,8 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
     constexpr int OFF_SS1 = OFF_STEM + 2 * SET;
     constexpr int LDS_BYTES = OFF_SS1 + 1024;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    static_assert(IMG_DMAS <= 16, "one tile DMA per wave");
+    static_assert(Win::IMG_DMAS <= 16, "one tile DMA per wave");
     constexpr int MT = 1, NT = 1;
-    constexpr unsigned OOB = 0x80000000u;
 
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     __builtin_amdgcn_s_setprio(2);
@@ -337,11 +326,8 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
     struct Coord { int b, y0, x0; };
     auto coord_of = [&](int k) __attribute__((always_inline)) {   // item k of this workgroup -> image, tile origin
         const unsigned it = (unsigned)rg.item_of(rg.first_item() + k * rg.slots);
-        unsigned b = __umulhi(it, s.m_tpi), r = it - b * tiles_per_img;
-        if (r >= tiles_per_img) ++b, r -= tiles_per_img;
-        unsigned ty = __umulhi(r, s.m_tx), tx = r - ty * (unsigned)a.tiles_x;
-        if (tx >= (unsigned)a.tiles_x) ++ty, tx -= (unsigned)a.tiles_x;
-        return Coord{(int)b, (int)ty * TH, (int)tx * TW};
+        const StemTile t = stem_item_tile(it, (unsigned)a.tiles_x, tiles_per_img, s.m_tx, s.m_tpi);
+        return Coord{t.b, t.ty * TH, t.tx * TW};
     };
 
     if (tid < BN) {
@@ -350,19 +336,18 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
         ss1[128 + tid] = a.shift[tid];
     }
     const unsigned lds_base = lds_addr_of(lds);
-    // this lane's piece of a tile: piece u = wave*64 + lane -> (row, channel, 4 columns)
+    // this lane's piece of a tile: piece u = wave*64 + lane -> (row, channel, 4 columns).  stem_piece's rule, written out: the function
+    // moves the product H * W (profiles/stem_window_codegen.txt)
     const int pu = wave * 64 + lane;
-    const bool pu_ok = wave < IMG_DMAS && pu < IMG_PIECES;
-    const int pu_col = (pu % ROW_PIECES) * 4, pu_ci = (pu / ROW_PIECES) % 3, pu_row = pu / (ROW_PIECES * 3);
+    const bool pu_ok = wave < Win::IMG_DMAS && pu < Win::IMG_PIECES;
+    const int pu_col = (pu % Win::ROW_PIECES) * 4, pu_ci = (pu / Win::ROW_PIECES) % 3, pu_row = pu / (Win::ROW_PIECES * 3);
     const int plane_elems = s.H * s.W;
-    const int pu_gofs = pu_ci * plane_elems + pu_row * s.W + pu_col;   // relative to image pixel (2*y0-2, 2*x0-4) of channel 0
+    const StemPiece piece{pu_ok, pu_row, pu_col, pu_ci * plane_elems + pu_row * s.W + pu_col};
     auto issue_image = [&](const Coord& t, int slot_i) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rs =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.x) + (size_t)t.b * 3 * plane_elems, 0, 3 * plane_elems * 4, 0x00020000);
-        const int ybase = 2 * t.y0 - 2, xbase = 2 * t.x0 - 4;
-        const bool ok = pu_ok && (unsigned)(ybase + pu_row) < (unsigned)s.H && (unsigned)(xbase + pu_col) < (unsigned)s.W;
-        const unsigned vo = ok ? (unsigned)((pu_gofs + ybase * s.W + xbase) * 4) : OOB;
-        dma16_buf(rs, vo, 0u, lds_base + (wave < IMG_DMAS ? slot_i * IMG_BYTES + wave * 1024 : OFF_SCRATCH));
+        const unsigned vo = stem_piece_voff(piece, 2 * t.y0 - 2, 2 * t.x0 - 4, s.H, s.W);
+        dma16_buf(rs, vo, 0u, lds_base + (wave < Win::IMG_DMAS ? slot_i * IMG_BYTES + wave * 1024 : OFF_SCRATCH));
     };
 
     // ---- prologue: tiles of items 0 and 1 in flight, tile 0 landed.  Coordinate queue: cA = item k, cB = item k+1 at loop entry
@@ -385,22 +370,15 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
     // of item k-1 from set (k-1) & 1; the tile of item k+2 is issued by every wave into buffer (k+2) % 3 = the one item k-1 was
     // read from in iteration k-1.  Both loops pass the same nk + 1 barriers.
     if (wave < 8) {
-        // tap grid of a stem pixel in the tile: rho = 3 kh + ci (9 rows of IW floats), kw.  K slots (tap = rho*3 + kw, -1: zero filter):
-        //   step 0, half 0: rows 0,1 and (2,0) (2,1); half 1: the same 3 rows down
-        //   step 1, half 0: rows 6,7 and (2,2) (5,2); half 1: the same 2 rows down = row 8 (real), row 9, (4,2), (7,2) (zero filters)
-        auto slotA = [](int e) constexpr { return e; };                                        // taps 0..7 = rows 0,1,(2,0),(2,1)
-        auto slotC = [](int e) constexpr { return e < 6 ? 18 + e : (e == 6 ? 2 * 3 + 2 : 5 * 3 + 2); };
-        auto goff = [](int t) constexpr { return (t / 3) * IW + t % 3; };                       // float offset of grid tap t
-        auto kref = [](int t) constexpr { return ((t / 3) % 3) * 9 + (t / 9) * 3 + t % 3; };   // its index ci*9 + kh*3 + kw in w0
         vec8 wa[2];
-        {
-            const uint16_t* wr = s.w0 + c * 32;   // filters of output channel c
+        {   // filters of output channel c in slot order (the rule: ay_stem_window.h), written out: profiles/stem_window_codegen.txt
+            const uint16_t* wr = s.w0 + c * 32;
             uint16_t w0v[8], w1v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                w0v[e] = hh ? wr[kref(slotA(e) + 9)] : wr[kref(slotA(e))];
-                const int td = slotC(e) + 6;      // half 1 of step 1: real only for grid row 8
-                w1v[e] = hh ? (td / 3 == 8 ? wr[kref(td)] : (uint16_t)0) : wr[kref(slotC(e))];
+                w0v[e] = hh ? wr[tap_kref(slot_tap(8 + e))] : wr[tap_kref(slot_tap(e))];
+                const uint16_t w1h = slot_live(24 + e) ? wr[tap_kref(slot_tap(24 + e))] : (uint16_t)0;   // half 1 of step 1: grid row 8 only
+                w1v[e] = hh ? w1h : wr[tap_kref(slot_tap(16 + e))];
             }
             wa[0] = __builtin_bit_cast(vec8, make_uint4(w0v[0] | (unsigned)w0v[1] << 16, w0v[2] | (unsigned)w0v[3] << 16,
                                                            w0v[4] | (unsigned)w0v[5] << 16, w0v[6] | (unsigned)w0v[7] << 16));
@@ -425,9 +403,9 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
             const int P = (wave + 8 * j) * 32 + c;
             const int sy = P / SW, sx = P - sy * SW;
             const bool inside = P < S_PIX;
-            const int px = inside ? sy * 3 * IW + sx + XOFF : XOFF;
-            pbase0[j] = px + hh * 3 * IW;
-            pbase1[j] = px + hh * 2 * IW;
+            const int px = inside ? stem_pixel_off(sy, sx, XOFF) : XOFF;
+            pbase0[j] = px + hh * 3 * Win::IW;
+            pbase1[j] = px + hh * 2 * Win::IW;
             pcell[j] = (inside ? sy * ROWP + (sx & 1) * HALFW + (sx >> 1) : S_POS + (P - S_PIX)) * 16 + hh * 8;
         }
         for (int k = 0; k <= nk; ++k) {
@@ -445,21 +423,7 @@ __global__ void __launch_bounds__(1024) stem_s2_fused_v2_kernel(StemFusedArgs s,
                 // every stem pixel of the tile is a real one unless the tile touches the image border
                 const bool interior = 2 * y0 - 1 >= 0 && 2 * y0 - 1 + SH <= s.H && 2 * x0 - 1 >= 0 && 2 * x0 - 1 + SW <= s.W;
                 auto block = [&](int j) __attribute__((always_inline)) {
-                    const float* p0 = img + pbase0[j];
-                    const float* p1 = img + pbase1[j];
-                    f32x2 v0[4], v1[4];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        v0[jj] = f32x2{p0[goff(slotA(2 * jj))], p0[goff(slotA(2 * jj + 1))]};
-                        v1[jj] = f32x2{p1[goff(slotC(2 * jj))], p1[goff(slotC(2 * jj + 1))]};
-                    }
-                    const uint4 b0 = make_uint4(DT::pack2(v0[0]), DT::pack2(v0[1]), DT::pack2(v0[2]), DT::pack2(v0[3]));
-                    const uint4 b1 = make_uint4(DT::pack2(v1[0]), DT::pack2(v1[1]), DT::pack2(v1[2]), DT::pack2(v1[3]));
-                    f32x16 acc;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                    acc = DT::mfma32(wa[0], __builtin_bit_cast(vec8, b0), acc);
-                    acc = DT::mfma32(wa[1], __builtin_bit_cast(vec8, b1), acc);
+                    const f32x16 acc = stem_pixel_mfma<DT>(img + pbase0[j], img + pbase1[j], wa);
                     bool real = true;
                     if (!interior) {   // border tile: pixels outside the image are the zero padding of layer 1
                         const int P = (wave + 8 * j) * 32 + c;
@@ -586,7 +550,7 @@ static int stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const
     s.H = h;
     s.W = w;
     // any other image (width not a multiple of 4, unaligned, 2 GiB and more) takes the serial-phase kernel (8x32 items)
-    const bool v2 = w % 4 == 0 && (reinterpret_cast<uintptr_t>(x_nchw) & 15) == 0 && 3LL * h * w * 4 < 0x7fffffffLL;
+    const bool v2 = stem_window_ok(x_nchw, h, w);
     // layer 1: 3x3 stride 2 over the stem's 32 channels (never in memory: no src), 64 filters in one channel group
     ay_conv_desc d1{};
     d1.batch = batch, d1.cin = 32, d1.cout = d1.cout_pad = 64;
@@ -595,9 +559,8 @@ static int stem_s2_fused_fwd(const float* x_nchw, const void* stem_w_bf16, const
     ConvArgs& a = s.c1;
     fill_args(a, &d1, nullptr, w1_packed, scale1, shift1, nullptr, out_blocked, v2 ? 4 : 8, 32, 64);
     a.dbg = conv_dbg();
-    auto magic = [](unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ULL / d); };
-    s.m_tx = magic((unsigned)a.tiles_x);
-    s.m_tpi = magic((unsigned)(a.tiles_x * a.tiles_y));
+    s.m_tx = mulhi_divisor((unsigned)a.tiles_x);
+    s.m_tpi = mulhi_divisor((unsigned)(a.tiles_x * a.tiles_y));
     const long long n_items = (long long)a.tiles_x * a.tiles_y * batch;
     const dim3 grid(persistent_grid(n_items));   // static dealing
     AY_CHECK_ARG(grid.x, "ay_stem_s2_fused_fwd: grid");

@@ -6,45 +6,25 @@
 // 16-channel bf16 plane (1.07 GB written and read twice per step at B=32 / 1024^2 for 3 useful channels) and ran the generic
 // kernels on it: conversion 1.26 + forward 1.0-1.5 + weight gradient 1.5 ms per step.  Both kernels here read the image once.
 //
-// Same tile mechanics as the fused inference stem (ay_stem_fused.hip, v2): an item is 8 x 64 stem pixels; its (8+2) x (64+2) x 3
-// fp32 window arrives by 16-byte buffer-descriptor DMA into a ring of LDS buffers, stored [row][channel][column] with the window
-// starting 4 columns left of the tile (every piece 16-byte aligned, out-of-image lanes read zeros through the descriptor's range
-// check; needs W % 4 == 0), so the 27 taps of a pixel are a 9 x 3 grid (rho = 3 kh + ci, kw) of floats.
-#include "ay_conv_common.h"
+// Both take the image through the window of ay_stem_window.h (11 rows: 10 used; needs W % 4 == 0): an item is 8 x 64 stem pixels, its
+// window goes into a ring of LDS buffers.  Particular to this file: the forward keeps the batch statistics in registers, the weight
+// gradient reads its dz fragments transposed.
+#include "ay_stem_window.h"
 
 namespace ay {
 
 namespace stemtr {
 constexpr int TH = 8, TW = 64;                 // stem pixels per item
-constexpr int IH = TH + 3;                      // window rows y0-1 .. y0+9: 10 used + 1 that only zero-filter slots read
-constexpr int IW = 72;                          // window columns x0-4 .. x0+67 (used x0-1 .. x0+64)
+typedef StemWindow<TH + 3> Win;               // window rows y0-1 .. y0+9, columns x0-4 .. x0+67 (used x0-1 .. x0+64)
 constexpr int XOFF = 3;                         // window column of image column x-1 for tile column 0
-constexpr int ROW_PIECES = IW / 4;
-constexpr int IMG_PIECES = IH * 3 * ROW_PIECES; // 594 pieces of 16 bytes
-constexpr int IMG_DMAS = (IMG_PIECES + 63) / 64;  // 10 wave-wide DMA instructions
-constexpr int IMG_BYTES = IMG_DMAS * 1024;
-constexpr unsigned OOB = 0x80000000u;
-
-// K slots of the 32-wide reduction over taps (forward: the MFMA's K; weight gradient: its N): slot = step*16 + half*8 + e holds grid
-// tap t = rho*3 + kw (rho = 3 kh + ci), ordered so that half 1 of a step is half 0 moved down 3 (step 0) or 2 (step 1) grid rows;
-// the five spare slots of (step 1, half 1) alias real taps and carry zero filters / are dropped.
-__host__ __device__ constexpr int slot_tap(int slot) {
-    const int step = slot >> 4, half = (slot >> 3) & 1, e = slot & 7;
-    if (step == 0) return e + 9 * half;                                   // rows 0,1,(2,0),(2,1) | rows 3,4,(5,0),(5,1)
-    const int c = e < 6 ? 18 + e : (e == 6 ? 8 : 17);                     // rows 6,7,(2,2),(5,2)
-    return half ? c + 6 : c;                                              // | row 8, row 9 (spare), (4,2) (spare), (7,2) (spare)
-}
-__host__ __device__ constexpr bool slot_live(int slot) {
-    const int step = slot >> 4, half = (slot >> 3) & 1;
-    return !(step == 1 && half == 1) || slot_tap(slot) / 3 == 8;
-}
-__host__ __device__ constexpr int tap_goff(int t) { return (t / 3) * IW + t % 3; }               // float offset of grid tap t from the pixel
-__host__ __device__ constexpr int tap_kref(int t) { return ((t / 3) % 3) * 9 + (t / 9) * 3 + t % 3; }  // ci*9 + kh*3 + kw
+constexpr int IW = Win::IW, IMG_DMAS = Win::IMG_DMAS, IMG_BYTES = Win::IMG_BYTES;
+constexpr unsigned OOB = Win::OOB;
+static_assert(IMG_DMAS <= 16, "at most two tile DMAs per wave");
 
 struct Args {
     const float* x;          // [B][3][H][W]
     int B, H, W, tiles_x, tiles_y;
-    unsigned m_tx, m_tpi;    // floor(2^32 / tiles_x), floor(2^32 / tiles per image); 0xffffffff for a divisor of 1
+    unsigned m_tx, m_tpi;    // mulhi_divisor of tiles_x, of tiles per image
     const uint16_t* w0;      // forward: bf16 [32 cout][32], index ci*9 + kh*3 + kw (27..31 unused)
     uint8_t* z;              // forward: [B][2][H][W][16] bf16
     const uint8_t* dz;       // weight gradient: [B][2][H][W][16] bf16
@@ -56,12 +36,8 @@ struct Coord {
     int b, y0, x0;
 };
 __device__ __forceinline__ Coord coord_of(const Args& a, unsigned it) {
-    const unsigned tpi = (unsigned)(a.tiles_x * a.tiles_y);
-    unsigned b = __umulhi(it, a.m_tpi), r = it - b * tpi;
-    if (r >= tpi) ++b, r -= tpi;
-    unsigned ty = __umulhi(r, a.m_tx), tx = r - ty * (unsigned)a.tiles_x;
-    if (tx >= (unsigned)a.tiles_x) ++ty, tx -= (unsigned)a.tiles_x;
-    return Coord{(int)b, (int)ty * TH, (int)tx * TW};
+    const StemTile t = stem_item_tile(it, (unsigned)a.tiles_x, (unsigned)(a.tiles_x * a.tiles_y), a.m_tx, a.m_tpi);
+    return Coord{t.b, t.ty * TH, t.tx * TW};
 }
 }  // namespace stemtr
 
@@ -87,30 +63,20 @@ __global__ void __launch_bounds__(512, 4) stem_train_fwd_kernel(stemtr::Args a, 
     const unsigned lds_base = lds_addr_of(lds);
     const int plane_elems = a.H * a.W;
 
-    // tile pieces of this wave: pieces wave and wave + 8 (the second only for waves 0, 1); per lane (row, channel, 4 columns)
-    int pu_gofs[2], pu_row[2], pu_col[2];
-    bool pu_ok[2];
+    // tile pieces of this wave: pieces wave and wave + 8 (the second only for waves 0, 1)
+    StemPiece piece[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int pu = (wave + 8 * j) * 64 + lane;
-        pu_ok[j] = wave + 8 * j < IMG_DMAS && pu < IMG_PIECES;
-        pu_col[j] = (pu % ROW_PIECES) * 4;
-        const int ci = (pu / ROW_PIECES) % 3;
-        pu_row[j] = pu / (ROW_PIECES * 3);
-        pu_gofs[j] = ci * plane_elems + pu_row[j] * a.W + pu_col[j];
-    }
+    for (int j = 0; j < 2; ++j) piece[j] = stem_piece<Win>(wave + 8 * j, lane, plane_elems, a.W);
     auto issue_image = [&](const Coord& t, int buf) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rs =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x) + (size_t)t.b * 3 * plane_elems, 0, 3 * plane_elems * 4, 0x00020000);
-        const int ybase = t.y0 - 1, xbase = t.x0 - 4;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const bool ok = pu_ok[j] && (unsigned)(ybase + pu_row[j]) < (unsigned)a.H && (unsigned)(xbase + pu_col[j]) < (unsigned)a.W;
-            const unsigned vo = ok ? (unsigned)((pu_gofs[j] + ybase * a.W + xbase) * 4) : OOB;
+            const unsigned vo = stem_piece_voff(piece[j], t.y0 - 1, t.x0 - 4, a.H, a.W);
             dma16_buf(rs, vo, 0u, lds_base + (wave + 8 * j < IMG_DMAS ? buf * IMG_BYTES + (wave + 8 * j) * 1024 : OFF_SCRATCH));
         }
     };
-    // filters of output channel c in slot order
+    // filters of output channel c in slot order (the rule: ay_stem_window.h), written out: profiles/stem_window_codegen.txt
     bf16x8 wa[2];
     {
         const uint16_t* wr = a.w0 + c * 32;
@@ -133,7 +99,7 @@ __global__ void __launch_bounds__(512, 4) stem_train_fwd_kernel(stemtr::Args a, 
     int pbase0[2], pbase1[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int px = wave * 3 * IW + 32 * j + c + XOFF;
+        const int px = stem_pixel_off(wave, 32 * j + c, XOFF);
         pbase0[j] = px + hh * 3 * IW;
         pbase1[j] = px + hh * 2 * IW;
     }
@@ -168,7 +134,7 @@ __global__ void __launch_bounds__(512, 4) stem_train_fwd_kernel(stemtr::Args a, 
             __builtin_amdgcn_make_buffer_rsrc(a.z + (size_t)cA.b * 2 * out_plane_bytes, 0, (int)(2 * out_plane_bytes), 0x00020000);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const float* p0 = img + pbase0[j];
+            const float* p0 = img + pbase0[j];   // stem_pixel_mfma (ay_stem_window.h), written out: profiles/stem_window_codegen.txt
             const float* p1 = img + pbase1[j];
             f32x2 v0[4], v1[4];
 #pragma unroll
@@ -300,11 +266,9 @@ __global__ void __launch_bounds__(512) stem_train_wgrad_kernel(stemtr::Args a, i
         lane_row[i] = lane_col[i] = 0;
         if (qn < IMG_DMAS) {
             const int pu = qn * 64 + lane;
-            if (pu < IMG_PIECES) {
-                lane_col[i] = (pu % ROW_PIECES) * 4;
-                const int ci = (pu / ROW_PIECES) % 3;
-                lane_row[i] = pu / (ROW_PIECES * 3);
-                lane_off[i] = (unsigned)((ci * plane_elems + lane_row[i] * a.W + lane_col[i]) * 4);   // from image pixel (y0-1, x0-4)
+            if (pu < Win::IMG_PIECES) {
+                const StemPiece pc = stem_piece<Win>(qn, lane, plane_elems, a.W);
+                lane_row[i] = pc.row, lane_col[i] = pc.col, lane_off[i] = (unsigned)(pc.gofs * 4);   // from image pixel (y0-1, x0-4)
             }
         } else if (qn < NPIECE) {
             const int u = (qn - IMG_DMAS) * 64 + lane;
@@ -324,6 +288,7 @@ __global__ void __launch_bounds__(512) stem_train_wgrad_kernel(stemtr::Args a, i
             const int qn = i * 8 + wave;
             if (qn < IMG_DMAS) {
                 const int ybase = t.y0 - 1, xbase = t.x0 - 4;
+                // stem_piece_voff's rule on the table shared with the dz pieces (offsets in bytes, OOB = no piece)
                 const bool ok = lane_off[i] != OOB && (unsigned)(ybase + lane_row[i]) < (unsigned)a.H && (unsigned)(xbase + lane_col[i]) < (unsigned)a.W;
                 const unsigned vo = ok ? lane_off[i] + (unsigned)((ybase * a.W + xbase) * 4) : OOB;
                 dma16_buf(rx, vo, 0u, lds_base + buf * STAGE + qn * 1024);
@@ -348,7 +313,7 @@ __global__ void __launch_bounds__(512) stem_train_wgrad_kernel(stemtr::Args a, i
 #pragma unroll
         for (int s = 0; s < 16; ++s)
             if (s == n) off = tap_goff(slot_tap(nt * 16 + s));
-        boff[nt] = off + XOFF + 8 * g;
+        boff[nt] = off + stem_pixel_off(0, 8 * g, XOFF);
     }
     f32x4 acc[2][2];
 #pragma unroll
@@ -383,7 +348,7 @@ __global__ void __launch_bounds__(512) stem_train_wgrad_kernel(stemtr::Args a, i
                 const short v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 __builtin_memcpy(&af[mt], v, 16);
             }
-            const float* px = img + wave * 3 * IW + 32 * j;
+            const float* px = img + stem_pixel_off(wave, 32 * j, 0);
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const float* s = px + boff[nt];
@@ -438,9 +403,8 @@ static bool stem_train_setup(stemtr::Args& a, const float* x, int batch, int h, 
     a.B = batch, a.H = h, a.W = w;
     a.tiles_x = (w + TW - 1) / TW;
     a.tiles_y = (h + TH - 1) / TH;
-    auto magic = [](unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ULL / d); };
-    a.m_tx = magic((unsigned)a.tiles_x);
-    a.m_tpi = magic((unsigned)(a.tiles_x * a.tiles_y));
+    a.m_tx = mulhi_divisor((unsigned)a.tiles_x);
+    a.m_tpi = mulhi_divisor((unsigned)(a.tiles_x * a.tiles_y));
     *n_items = (long long)a.tiles_x * a.tiles_y * batch;
     *grid = persistent_grid(*n_items, wgs_per_cu);
     return *grid != 0;
@@ -451,8 +415,7 @@ static bool stem_train_setup(stemtr::Args& a, const float* x, int batch, int h, 
 using namespace ay;
 
 static int stem_train_args_ok(const float* x, int batch, int h, int w, const char* who) {
-    if (!(x && batch > 0 && h > 0 && w > 0 && w % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && 3LL * h * w * 4 < 0x7fffffffLL &&
-          2LL * h * w * 32 < 0x7fffffffLL)) {
+    if (!(x && batch > 0 && h > 0 && w > 0 && stem_window_ok(x, h, w) && 2LL * h * w * 32 < 0x7fffffffLL)) {
         set_error("%s: needs a 16-byte aligned image with W %% 4 == 0 below 2 GiB per image (%dx%d)", who, h, w);
         return AY_ERR_ARG;
     }

@@ -26,7 +26,7 @@ struct WgradArgs {
     int B, cin, cout, CIP, COP, hin, win, ho, wo;
     int nseg_x, total_segs;
     int ncob, ncib, ks;      // workgroup grid: ncob x ncib filter tiles x ks split-K slices, flattened into blockIdx.x (see the kernel)
-    unsigned m_nseg, m_ho;   // floor(2^32 / nseg_x), floor(2^32 / ho) (0xffffffff for a divisor of 1): multiply-high division in the K loop
+    unsigned m_nseg, m_ho;   // mulhi_divisor of nseg_x, of ho: multiply-high division in the K loop
     float* slab;       // split-K partial filters [gridDim.z][dw_elems] (plain stores, summed in fixed order by wgrad_reduce_kernel);
     size_t dw_elems;   // nullptr: the partial sums are added to dw with fp32 atomics
     int dbg;           // instrumented build only: the AY_DBG bits (ay_phase_clock.h), of which this kernel honours DBG_CLOCK
@@ -463,9 +463,8 @@ extern "C" int ay_conv_wgrad_bf16_ws(const ay_conv_desc* d, const void* x_blocke
     a.ho = d->hout;
     a.wo = d->wout;
     a.nseg_x = (d->wout + 31) / 32;
-    auto magic = [](unsigned dv) { return dv <= 1 ? 0xffffffffu : (unsigned)(0x100000000ULL / dv); };
-    a.m_nseg = magic((unsigned)a.nseg_x);
-    a.m_ho = magic((unsigned)d->hout);
+    a.m_nseg = mulhi_divisor((unsigned)a.nseg_x);
+    a.m_ho = mulhi_divisor((unsigned)d->hout);
     const long long total = (long long)d->batch * d->hout * a.nseg_x;
     AY_CHECK_ARG(total > 0 && total < 0x7fffffffLL, "ay_conv_wgrad_bf16: too many segments");
     a.total_segs = (int)total;
