@@ -11,15 +11,14 @@ usage: python scripts/bench_augment.py [--batch 32] [--tile 1536] [--size 1024] 
 import argparse
 import os
 import statistics
-import sys
 import tempfile
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
-from amyloid_yolo_paper_amd import _lib, augment as ag, synth
+from amyloid_yolo_paper_amd import _lib, augment as ag
 from amyloid_yolo_paper_amd._lib import check, ptr
 
 ap = argparse.ArgumentParser()
@@ -35,18 +34,13 @@ ap.add_argument("--n_cpu", type=int, default=8)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
+report = harness.Report()
+say = report.say
 
 L = _lib.lib()
 dev = torch.device("cuda:0")
 B, T, S = a.batch, a.tile, a.size
-base = (synth.synth_tiles(4, T, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
+base = harness.synthetic_tiles(T)
 tiles = torch.from_numpy(np.ascontiguousarray(np.stack([base[i % 4] for i in range(B)]))).to(dev)
 sizes = [(T, T)] * B
 tables = {"identity": ag.identity_params(sizes), "full": ag.sample_params(np.random.default_rng(0), sizes)}
@@ -62,22 +56,11 @@ runs = {
 traffic = B * 3 * S * S * 4 + tiles.numel()
 say(f"# augment ingest on {torch.cuda.get_device_name(0)}: B={B}, {T}^2 uint8 -> {S}^2 fp32; output {B * 3 * S * S * 4 / 1e6:.0f} MB + source "
     f"{tiles.numel() / 1e6:.0f} MB; {a.reps} x ({a.calls} calls between two events after a warm call), median [min, max]")
-times = {k: [] for k in runs}
-for rep in range(a.reps):          # the three alternate inside every repeat
-    for name, f in runs.items():
-        f()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.calls):
-            f()
-        e1.record()
-        torch.cuda.synchronize()
-        times[name].append(e0.elapsed_time(e1) / a.calls)
+times = dict(zip(runs, harness.time_calls(list(runs.values()), 0, a.reps, per=a.calls, lead=1)))     # the three alternate inside every repeat
 med = {}
 for name, v in times.items():
     med[name] = statistics.median(v)
-    say(f"{name:32s} {med[name] * 1e3:8.1f} us  [{min(v) * 1e3:.1f}, {max(v) * 1e3:.1f}]   {traffic / med[name] / 1e9:.2f} TB/s of output + source")
+    say(f"{name:32s} {harness.fmt_square(v, us=True)}   {traffic / med[name] / 1e9:.2f} TB/s of output + source")
 runs["ay_ingest_tiles_u8"]()
 runs["ay_augment_ingest_u8 identity"]()
 torch.cuda.synchronize()
@@ -114,7 +97,4 @@ if not a.no_loader:
             dt = time.time() - t0
             say(f"loader, {a.n_cpu} workers, {T}^2 PNG tiles, {'raw uint8 form' if raw else 'host fp32 form '}: {n / dt:7.1f} images/s "
                 f"({n} images in {dt:.2f} s; for information, depends on the box's CPUs)")
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+report.write(a.out)

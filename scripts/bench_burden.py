@@ -1,5 +1,5 @@
-"""Time of the slide-level burden calls (ay_burden_bin, ay_field_select) on the synthetic slide of scripts/bench_slide_match.py: about
-250 k detection rows of 8..47-px boxes on a 70 000-px square, C = 2 classes, cell = 128 px (a 547 x 547 map), field = 8 cells, top_k =
+"""Time of the slide-level burden calls (ay_burden_bin, ay_field_select) on the synthetic slide of scripts/bench_slide_match.py
+(harness.slide_rows, the class modulo 2): about 250 k detection rows of 8..47-px boxes on a 70 000-px square, C = 2 classes, cell = 128 px (a 547 x 547 map), field = 8 cells, top_k =
 5, inputs, outputs and workspace resident on the device.  The tissue plane is a disc of full cells (cell^2 pixels each) that covers
 the middle of the slide, need_tissue = half a field.
 CALL time: after WARM warm calls, REPS times, two device events around the call(s); both calls are kernel launches only, so this is
@@ -12,11 +12,9 @@ usage: rocprofv3 --kernel-trace --stats -d DIR -o burden --output-format csv -- 
 import argparse
 import ctypes as C
 import math
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
@@ -36,34 +34,15 @@ ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 -
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def synthetic_rows(M, side, seed=0, T=50000):
-    """the rows of bench_slide_match.synthetic_slide: four in five are jittered sightings of one of T objects of 8..47 px, the rest
-    boxes of the same sizes anywhere; the object's class modulo 2"""
-    rng = np.random.default_rng(seed)
-    xy = rng.uniform(0, side, (T, 2))
-    tb = np.concatenate([xy, xy + rng.uniform(8, 47, (T, 2))], 1)
-    cls = rng.integers(0, 3, T) % 2
-    g = rng.integers(0, T, M)
-    box = tb[g] + rng.normal(0, 3.0, (M, 4))
-    anywhere = rng.uniform(size=M) < 0.2
-    p = rng.uniform(0, side, (M, 2))
-    box[anywhere] = np.concatenate([p, p + rng.uniform(8, 47, (M, 2))], 1)[anywhere]
-    return np.concatenate([box, rng.uniform(0.5, 1, (M, 2)), cls[g][:, None]], 1).astype(np.float32)
-
+report = harness.Report()
+say = report.say
 
 L = _lib.lib()
 dev = torch.device("cuda:0")
 M, NC, cell, F, K, side = a.rows, 2, a.cell, a.field, a.top_k, a.side
 gy = gx = -(-side // cell)
-rows_h = synthetic_rows(M, side)
+rows_h = harness.slide_rows(M, 50000, side)[0]
+rows_h[:, 6] %= 2                    # C = 2: the object's class modulo 2
 one_cell_h = rows_h.copy()          # the same boxes, every centre moved into the cell in the middle of the map
 centre = (rows_h[:, 0:2] + rows_h[:, 2:4]) / 2
 target = (np.array([gx // 2, gy // 2], np.float32) + 0.5) * cell
@@ -96,24 +75,11 @@ def both():
 
 
 if a.calls_only:
-    for _ in range(a.calls_only):
-        both()
-    torch.cuda.synchronize()
-    sys.exit(0)
+    harness.calls_only(a.calls_only, both)
 
 
 def timed(fn):
-    for _ in range(a.warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = harness.time_calls([fn], a.warm, a.reps)[0]
     return f"{min(ms):8.3f} .. {max(ms):.3f} ms (median {statistics.median(ms):.3f})"
 
 
@@ -130,17 +96,9 @@ say(f"ay_field_select (row pass, column pass, selection)        {timed(select)}"
 say(f"    n_found {n_found.cpu().tolist()}, picks (fy, fx, n, t) of class 0: {fields[0].cpu().tolist()}")
 say(f"both calls                                                {timed(both)}")
 if a.kernel_stats:
-    import csv
-    import glob
-    table = list(csv.DictReader(open(glob.glob(os.path.join(a.kernel_stats, "**", "*_kernel_stats.csv"), recursive=True)[0])))
-    ours = [r for r in table if "burden_" in r["Name"]]
-    calls = max(int(r["Calls"]) for r in ours if "burden_select" in r["Name"])     # one selection kernel per call of both
+    ours, _ = harness.kernel_table(a.kernel_stats, ["burden_"])
+    _, calls = harness.kernel_table(a.kernel_stats, ["burden_select"])     # one selection kernel per call of both
     say(f"# KERNEL time per call of both, from a kernel trace of {calls} calls (total per call; the column pass runs twice, the tissue plane first):")
-    for r in sorted(ours, key=lambda r: -float(r["TotalDurationNs"])):
-        say(f"  {r['Name'].split('(')[0][:60]:60s} {float(r['TotalDurationNs']) / calls / 1e3:8.1f} us")
-    say(f"  {'sum of the six launches':60s} {sum(float(r['TotalDurationNs']) for r in ours) / calls / 1e3:8.1f} us")
+    harness.say_kernel_table(say, ours, calls, "sum of the six launches")
     say("# for scale: ay_slide_match takes 0.254 ms and ay_seam_merge 0.95 ms of kernels on slides of this size (DESIGN.md section 8)")
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+report.write(a.out)

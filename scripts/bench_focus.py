@@ -1,10 +1,10 @@
-"""Cost of the focus pass (THE FOCUS RULE, include/amyloid_yolo.h) on the synthetic strip of scripts/bench_load.py: one resident strip
+"""Cost of the focus pass (THE FOCUS RULE, include/amyloid_yolo.h) on the synthetic strip (harness.synthetic_strip): one resident strip
 of TX 1536-px tiles, one process, five calls taken in turn inside one timed loop:
   ay_tile_tissue_u8      one tile row (the floor: a minimum and a compare per pixel)
   ay_stain_load_u8       cells only (cell 128): the yardstick, a read stream over the same bytes with the same items
   ay_focus_u8            cells only (cell 128) | boxes only | both
 The strip lies at rows STRIP_ROW .. of a 70 000-px square slide and the focus calls own all of its rows but the first and the last (what
-a strip of wsi.focus_map owns); the rows are scripts/bench_load.py's (250 000 boxes of 8..47 px all over the slide: most miss the strip).
+a strip of wsi.focus_map owns); the rows are harness.slide_rows' (250 000 boxes of 8..47 px all over the slide: most miss the strip).
 CALL time: after WARM warm rounds, REPS rounds, two device events around each call; median (min .. max).  Calls are kernel launches
 only, so this is launch overhead plus kernels.  GB/s of READS: 3 B per source pixel of the strip over the median (the focus cell pass
 reads two halo rows per band of 32 on top, 6 % more than that; the box pass reads only the pixels of its boxes: for it the figure is
@@ -16,15 +16,12 @@ ratios between the calls of one run are the yardstick either way.
 usage: timeout 300 python scripts/bench_focus.py [TX] [--reps 20] [--warm 3] [--copies 4] [--out profiles/focus.txt]
        (the whole run takes a few seconds; the time limit keeps a hung device from holding a shared machine)"""
 import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+import harness
 import torch
 
-from amyloid_yolo_paper_amd import _lib, synth
+from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd._lib import check, ptr
 from amyloid_yolo_paper_amd.wsi import StainMap, tile_grid
 
@@ -37,48 +34,16 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
 a = ap.parse_args()
 TX, tile, BG, CELL, THRES_BIN, SIDE, STRIP_ROW = a.tx, 1536, 170, 128, 10, 70000, 20 * 1536
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def fmt(ms):
-    return "%.3f ms (%.3f .. %.3f)" % (statistics.median(ms), min(ms), max(ms))
-
-
-def slide_rows(M=250000, T=50000, side=float(SIDE), seed=0):
-    """the rows of scripts/bench_load.py (the same draws in the same order)"""
-    rng = np.random.default_rng(seed)
-    xy = rng.uniform(0, side, (T, 2))
-    tb = np.concatenate([xy, xy + rng.uniform(8, 47, (T, 2))], 1)
-    cls = rng.integers(0, 3, T)
-    g = rng.integers(0, T, M)
-    box = tb[g] + rng.normal(0, 3.0, (M, 4))
-    anywhere = rng.uniform(size=M) < 0.2
-    p = rng.uniform(0, side, (M, 2))
-    box[anywhere] = np.concatenate([p, p + rng.uniform(8, 47, (M, 2))], 1)[anywhere]
-    return np.concatenate([box, rng.uniform(0.5, 1, (M, 2)), cls[g][:, None]], 1).astype(np.float32)
-
+report = harness.Report()
+say = report.say
 
 dev = torch.device("cuda:0")
-base = (synth.synth_tiles(4, tile, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)     # bench_stain.py's strip
-strip = torch.from_numpy(np.concatenate([base[i % 4] for i in range(TX)], 1)).to(dev)
-strips = [strip] + [strip.clone() for _ in range(a.copies - 1)]
-turn = [0]
-
-
-def next_strip():
-    """the copy this call reads: the one read longest ago"""
-    turn[0] += 1
-    return ptr(strips[turn[0] % len(strips)])
-
-
+strip = torch.from_numpy(harness.synthetic_strip(TX, tile)).to(dev)
+strips = harness.Rotation(strip, a.copies)
+next_strip = strips.next            # the pointer of the copy this call reads: the one read longest ago
 H, W = strip.shape[:2]
 assert STRIP_ROW + H <= SIDE
-rows_h = slide_rows(side=float(W))          # the focus pass takes whole rows of the slide: the slide is as wide as the strip
+rows_h = harness.slide_rows(250000, 50000, float(W))[0]          # the focus pass takes whole rows of the slide: the slide is as wide as the strip
 rows = torch.from_numpy(rows_h).to(dev)
 M = len(rows_h)
 on_strip = int(((rows_h[:, 3] > STRIP_ROW) & (rows_h[:, 1] < STRIP_ROW + H) & (rows_h[:, 2] > 0) & (rows_h[:, 0] < W)).sum())
@@ -108,25 +73,15 @@ calls = [("ay_tile_tissue_u8           ", lambda: check(L.ay_tile_tissue_u8(next
          ("ay_focus_u8 cells only      ", lambda: focus(cells[0], None)),
          ("ay_focus_u8 boxes only      ", lambda: focus(None, boxes[0])),
          ("ay_focus_u8 cells+boxes     ", lambda: focus(cells[1], boxes[1]))]
-ms = [[] for _ in calls]
-for i in range(a.warm + a.reps):
-    for k, (_, call) in enumerate(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if i >= a.warm:
-            ms[k].append(e0.elapsed_time(e1))
+ms = harness.time_calls([call for _, call in calls], a.warm, a.reps)
 reads = strip.numel()
 for k, (name, _) in enumerate(calls):
     rate = "" if "boxes only" in name else ", %.0f GB/s of reads" % (reads / statistics.median(ms[k]) / 1e6)
-    say("%s: %s per strip%s" % (name, fmt(ms[k]), rate))
+    say("%s: %s per strip%s" % (name, harness.fmt_round(ms[k]), rate))
 med = [statistics.median(m) for m in ms]
 say("focus cells only / ay_stain_load_u8 cells only = %.2f, focus cells only / ay_tile_tissue_u8 = %.2f, focus cells+boxes / cells only = %.2f (medians)"
     % (med[2] / med[1], med[2] / med[0], med[4] / med[2]))
-spread = lambda m: (max(m) - min(m)) / statistics.median(m)
-say("repeat spread (max - min) / median: load cells only %.1f %%, focus cells only %.1f %%" % (100 * spread(ms[1]), 100 * spread(ms[2])))
+say("repeat spread (max - min) / median: load cells only %.1f %%, focus cells only %.1f %%" % (100 * harness.spread(ms[1]), 100 * harness.spread(ms[2])))
 # the passes counted the same pixels: the evaluated pixels are tissue, the two focus calls agree, the boxes two ways
 n = a.warm + a.reps
 tissue = int(counts.sum())
@@ -136,6 +91,4 @@ assert torch.equal(cells[0], cells[1]) and torch.equal(boxes[0], boxes[1]) and i
 s = cells[0].sum((0, 1)).tolist()
 say("tissue pixels of the strip: %d of %d; evaluated: %d; variance of the Laplacian over the strip: %.1f; boxes with an evaluated pixel: %d; "
     "the passes agree" % (tissue, H * W, evaluated, s[2] / s[0] - (s[1] / s[0]) ** 2, int((boxes[0][:, 0] > 0).sum())))
-if a.out:
-    with open(a.out, "a" if a.append else "w") as f:
-        f.write("\n".join(lines) + "\n")
+report.write(a.out, append=a.append)

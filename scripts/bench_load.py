@@ -1,10 +1,10 @@
-"""Cost of the amyloid load pass (THE LOAD RULE, include/amyloid_yolo.h) on the synthetic strip of scripts/bench_stain.py: one
+"""Cost of the amyloid load pass (THE LOAD RULE, include/amyloid_yolo.h) on the synthetic strip (harness.synthetic_strip): one
 resident strip of TX 1536-px tiles, one process, five calls taken in turn inside one timed loop:
   ay_tile_tissue_u8      one tile row (the floor: a minimum and a compare per pixel)
   ay_stain_hist_u8       the yardstick: the same bytes, both stains unmixed, two LDS adds per tissue pixel
   ay_stain_load_u8       cells only (cell 128) | boxes only | both
 The strip lies at rows STRIP_ROW .. of a 70 000-px square slide, and the rows are those of scripts/bench_slide_match.py's synthetic
-slide (250 000 boxes of 8..47 px all over the slide: most miss the strip, as most miss any strip of a real slide).
+slide (harness.slide_rows; 250 000 boxes of 8..47 px all over the slide: most miss the strip, as most miss any strip of a real slide).
 CALL time: after WARM warm rounds, REPS rounds, two device events around each call; median (min .. max).  Calls are kernel launches
 only, so this is launch overhead plus kernels.  GB/s of READS: 3 B per source pixel of the strip over the median (the box pass
 reads only the pixels of its boxes: for it the figure is not a bandwidth and is not printed).  bg_level 170 as in bench_stain.py.
@@ -16,15 +16,12 @@ which at most one is the box pass: at least 0.45 GB of other copies);
 usage: timeout 300 python scripts/bench_load.py [TX] [--reps 20] [--warm 3] [--copies 4] [--out profiles/load.txt]
        (the whole run takes a few seconds; the time limit keeps a hung device from holding a shared machine)"""
 import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+import harness
 import torch
 
-from amyloid_yolo_paper_amd import _lib, synth
+from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd._lib import check, ptr
 from amyloid_yolo_paper_amd.wsi import StainMap, tile_grid
 
@@ -36,48 +33,16 @@ ap.add_argument("--copies", type=int, default=4, help="copies of the strip the c
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 TX, tile, BG, CELL, THRES_BIN, SIDE, STRIP_ROW = a.tx, 1536, 170, 128, 10, 70000, 20 * 1536
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def fmt(ms):
-    return "%.3f ms (%.3f .. %.3f)" % (statistics.median(ms), min(ms), max(ms))
-
-
-def slide_rows(M=250000, T=50000, side=float(SIDE), seed=0):
-    """the rows of scripts/bench_slide_match.py's synthetic_slide (the same draws in the same order)"""
-    rng = np.random.default_rng(seed)
-    xy = rng.uniform(0, side, (T, 2))
-    tb = np.concatenate([xy, xy + rng.uniform(8, 47, (T, 2))], 1)
-    cls = rng.integers(0, 3, T)
-    g = rng.integers(0, T, M)
-    box = tb[g] + rng.normal(0, 3.0, (M, 4))
-    anywhere = rng.uniform(size=M) < 0.2
-    p = rng.uniform(0, side, (M, 2))
-    box[anywhere] = np.concatenate([p, p + rng.uniform(8, 47, (M, 2))], 1)[anywhere]
-    return np.concatenate([box, rng.uniform(0.5, 1, (M, 2)), cls[g][:, None]], 1).astype(np.float32)
-
+report = harness.Report()
+say = report.say
 
 dev = torch.device("cuda:0")
-base = (synth.synth_tiles(4, tile, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)     # bench_stain.py's strip
-strip = torch.from_numpy(np.concatenate([base[i % 4] for i in range(TX)], 1)).to(dev)
-strips = [strip] + [strip.clone() for _ in range(a.copies - 1)]
-turn = [0]
-
-
-def next_strip():
-    """the copy this call reads: the one read longest ago"""
-    turn[0] += 1
-    return ptr(strips[turn[0] % len(strips)])
-
-
+strip = torch.from_numpy(harness.synthetic_strip(TX, tile)).to(dev)
+strips = harness.Rotation(strip, a.copies)
+next_strip = strips.next            # the pointer of the copy this call reads: the one read longest ago
 H, W = strip.shape[:2]
 assert W <= SIDE and STRIP_ROW + H <= SIDE
-rows_h = slide_rows()
+rows_h = harness.slide_rows(250000, 50000, float(SIDE))[0]
 rows = torch.from_numpy(rows_h).to(dev)
 M = len(rows_h)
 on_strip = int(((rows_h[:, 3] > STRIP_ROW) & (rows_h[:, 1] < STRIP_ROW + H) & (rows_h[:, 2] > 0) & (rows_h[:, 0] < W)).sum())
@@ -106,25 +71,15 @@ calls = [("ay_tile_tissue_u8           ", lambda: check(L.ay_tile_tissue_u8(next
          ("ay_stain_load_u8 cells only ", lambda: load(cells[0], None)),
          ("ay_stain_load_u8 boxes only ", lambda: load(None, boxes[0])),
          ("ay_stain_load_u8 cells+boxes", lambda: load(cells[1], boxes[1]))]
-ms = [[] for _ in calls]
-for i in range(a.warm + a.reps):
-    for k, (_, call) in enumerate(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if i >= a.warm:
-            ms[k].append(e0.elapsed_time(e1))
+ms = harness.time_calls([call for _, call in calls], a.warm, a.reps)
 reads = strip.numel()
 for k, (name, _) in enumerate(calls):
     rate = "" if "boxes only" in name else ", %.0f GB/s of reads" % (reads / statistics.median(ms[k]) / 1e6)
-    say("%s: %s per strip%s" % (name, fmt(ms[k]), rate))
+    say("%s: %s per strip%s" % (name, harness.fmt_round(ms[k]), rate))
 med = [statistics.median(m) for m in ms]
 say("cells only / ay_stain_hist_u8 = %.2f, cells only / ay_tile_tissue_u8 = %.2f, cells+boxes / cells only = %.2f (medians)"
     % (med[2] / med[1], med[2] / med[0], med[4] / med[2]))
-spread = lambda m: (max(m) - min(m)) / statistics.median(m)
-say("repeat spread (max - min) / median: hist %.1f %%, cells only %.1f %%" % (100 * spread(ms[1]), 100 * spread(ms[2])))
+say("repeat spread (max - min) / median: hist %.1f %%, cells only %.1f %%" % (100 * harness.spread(ms[1]), 100 * harness.spread(ms[2])))
 # the passes counted the same pixels: tissue three ways, positives against the histogram's tail, the boxes two ways
 n = a.warm + a.reps
 tissue = int(counts.sum())
@@ -132,6 +87,4 @@ assert int(hist[1024]) == tissue * n and int(cells[0][:, :, 0].sum()) == tissue 
 assert int(cells[0][:, :, 1].sum()) == int(hist[512 + THRES_BIN:1024].sum()) and torch.equal(boxes[0], boxes[1]) and int(flags.item()) == 0
 say("tissue pixels of the strip: %d of %d; positive: %d; boxes with a pixel on the strip: %d; the three passes agree" %
     (tissue, H * W, int(cells[0][:, :, 1].sum()) // n, int((boxes[0][:, 0] > 0).sum())))
-if a.out:
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+report.write(a.out)

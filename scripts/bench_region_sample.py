@@ -17,14 +17,13 @@ import argparse
 import ctypes as C
 import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
-from amyloid_yolo_paper_amd import _lib, augment as ag, synth
+from amyloid_yolo_paper_amd import _lib, augment as ag
 from amyloid_yolo_paper_amd._lib import check, ptr
 from amyloid_yolo_paper_amd.wsi import SlideSampler
 
@@ -41,19 +40,14 @@ ap.add_argument("--step_ms", type=float, default=None)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
+report = harness.Report()
+say = report.say
 
 L = _lib.lib()
 dev = torch.device("cuda:0")
 B, T, S, R = a.batch, a.tile, a.size, a.raster
 sp = _lib.stream_ptr
-base = (synth.synth_tiles(4, T, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
+base = harness.synthetic_tiles(T)
 tiles = torch.from_numpy(np.ascontiguousarray(np.stack([base[i % 4] for i in range(B)]))).to(dev)
 table = ag.sample_params(np.random.default_rng(0), [(T, T)] * B)
 up = lambda recs: torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(dev)
@@ -80,22 +74,11 @@ runs["(c) window kernel, context 1, resident raster"] = lambda: check(L.ay_augme
 
 say(f"# region sampling on {torch.cuda.get_device_name(0)}: B={B}, {T}^2 windows -> {S}^2 fp32, default ranges; raster {R}^2; "
     f"{a.reps} x ({a.calls} calls between two events after a warm call), median [min, max]")
-times = {k: [] for k in runs}
-for rep in range(a.reps):          # all of them alternate inside every repeat
-    for name, f in runs.items():
-        f()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.calls):
-            f()
-        e1.record()
-        torch.cuda.synchronize()
-        times[name].append(e0.elapsed_time(e1) / a.calls)
+times = dict(zip(runs, harness.time_calls(list(runs.values()), 0, a.reps, per=a.calls, lead=1)))     # all of them alternate inside every repeat
 med = {k: statistics.median(v) for k, v in times.items()}
 ref = med["(a) ay_augment_ingest_u8, this tree"]
 for name, v in times.items():
-    say(f"{name:48s} {med[name] * 1e3:8.1f} us  [{min(v) * 1e3:.1f}, {max(v) * 1e3:.1f}]   {med[name] / ref:.3f} x (a)")
+    say(f"{name:48s} {harness.fmt_square(v, us=True)}   {med[name] / ref:.3f} x (a)")
 list(runs.values())[0]()
 runs["(b) window kernel, context 0, same tiles"]()
 torch.cuda.synchronize()
@@ -143,7 +126,4 @@ if a.step_ms:
     say(f"host side {host:.1f} ms (plan + staging) against the {a.step_ms:.1f} ms training step at B={B}, {S}^2: "
         f"{'hidden behind the step by staging one batch ahead' if host < a.step_ms else 'NOT hidden: the host side is longer than the step'}; "
         f"(c) is {100 * med['(c) window kernel, context 1, resident raster'] / a.step_ms:.2f} % of the step")
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+report.write(a.out)

@@ -1,6 +1,6 @@
 """Cost of plaque segmentation (THE SEGMENT RULE, include/amyloid_yolo.h; csrc/ay_segment.hip), one process, the contenders of every
 part taken in turn inside one timed loop, median (min .. max) over the rounds:
-  (a) ordinary boxes   4 096 boxes of 44 .. 52 px, margin 8, on a resident synthetic strip (scripts/bench_load.py's, TX tiles):
+  (a) ordinary boxes   4 096 boxes of 44 .. 52 px, margin 8, on a resident synthetic strip (harness.synthetic_strip, TX tiles):
                        ay_box_segments_u8 beside ay_stain_load_u8's box pass on the same rows.  The box pass is the yardstick: it
                        reads the same pixels without labelling them.  The calls rotate over COPIES copies of the strip.
   (b) worst windows    one 255 x 255 window per call: full, checkerboard, one-pixel spiral, serpentine (and an empty one: the floor of
@@ -11,16 +11,14 @@ part taken in turn inside one timed loop, median (min .. max) over the rounds:
 bg_level 170 as in the other benches on the synthetic tiles.
 usage: timeout 600 python scripts/bench_segment.py [TX] [TY] [--reps 20] [--warm 3] [--copies 3] [--out profiles/segment.txt]"""
 import argparse
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
-from amyloid_yolo_paper_amd import _lib, synth
+from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd._lib import check, ptr
 from amyloid_yolo_paper_amd.wsi import StainMap, segment_boxes, stain_load
 
@@ -33,16 +31,8 @@ ap.add_argument("--copies", type=int, default=3)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 TX, TY, tile, BG, THRES_BIN, CORE_BIN, MARGIN, N_BOXES = a.tx, a.ty, 1536, 170, 10, 64, 8, 4096
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def fmt(ms):
-    return "%.3f ms (%.3f .. %.3f)" % (statistics.median(ms), min(ms), max(ms))
+report = harness.Report()
+say = report.say
 
 
 def boxes_in(n, H, W, seed, y_hi=None):
@@ -56,43 +46,23 @@ def boxes_in(n, H, W, seed, y_hi=None):
     return rows
 
 
-def timed(calls, reps, warm):
-    ms = [[] for _ in calls]
-    for i in range(warm + reps):
-        for k, call in enumerate(calls):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            e1.synchronize()
-            if i >= warm:
-                ms[k].append(e0.elapsed_time(e1))
-    return ms
-
-
 dev = torch.device("cuda:0")
 L, sp = _lib.lib(), _lib.stream_ptr()
 identity = StainMap.identity()
 params = identity.params
-base = (synth.synth_tiles(4, tile, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-strip_h = np.concatenate([base[i % 4] for i in range(TX)], 1)
+strip_h = harness.synthetic_strip(TX, tile)
 say("%s; bg_level %d, thres_bin %d, core_bin %d, margin %d; %d warm + %d timed rounds" % (torch.cuda.get_device_name(0), BG, THRES_BIN, CORE_BIN,
                                                                                          MARGIN, a.warm, a.reps))
 
 # ---- (a) ordinary boxes on a resident strip ---------------------------------------------------------------------------------------
-strips = [torch.from_numpy(strip_h).to(dev) for _ in range(a.copies)]
+strips = harness.Rotation(torch.from_numpy(strip_h).to(dev), a.copies)
+next_strip = strips.next
 H, W = strip_h.shape[:2]
 rows_h = boxes_in(N_BOXES, H, W, 1)
 rows = torch.from_numpy(rows_h).to(dev)
 seg = torch.zeros(N_BOXES, 20, device=dev, dtype=torch.int32)
 box = torch.zeros(N_BOXES, 4, device=dev, dtype=torch.int64)
 flags = torch.zeros(1, device=dev, dtype=torch.int32)
-turn = [0]
-
-
-def next_strip():
-    turn[0] += 1
-    return ptr(strips[turn[0] % len(strips)])
 
 
 def segments(region, h, w, r, n, out):
@@ -100,18 +70,18 @@ def segments(region, h, w, r, n, out):
                                ptr(flags), sp), "ay_box_segments_u8")
 
 
-ms = timed([lambda: segments(next_strip(), H, W, rows, N_BOXES, seg),
-            lambda: check(L.ay_stain_load_u8(next_strip(), H, W, W * 3, 1, 0, 0, H, W, BG, ptr(params), 1, THRES_BIN, 128, None, ptr(rows), N_BOXES,
-                                             ptr(box), ptr(flags), sp), "ay_stain_load_u8")], a.reps, a.warm)
+ms = harness.time_calls([lambda: segments(next_strip(), H, W, rows, N_BOXES, seg),
+                         lambda: check(L.ay_stain_load_u8(next_strip(), H, W, W * 3, 1, 0, 0, H, W, BG, ptr(params), 1, THRES_BIN, 128, None, ptr(rows),
+                                                          N_BOXES, ptr(box), ptr(flags), sp), "ay_stain_load_u8")], a.warm, a.reps)
 s = seg.cpu().numpy()
 say("(a) %d boxes of 44 .. 52 px on a resident strip of %d x %d, over %d copies" % (N_BOXES, H, W, a.copies))
-say("    ay_box_segments_u8           : %s per call, %.2f us per box" % (fmt(ms[0]), 1e3 * statistics.median(ms[0]) / N_BOXES))
-say("    ay_stain_load_u8 boxes only  : %s per call, %.2f us per box" % (fmt(ms[1]), 1e3 * statistics.median(ms[1]) / N_BOXES))
+say("    ay_box_segments_u8           : %s per call, %.2f us per box" % (harness.fmt_round(ms[0]), 1e3 * statistics.median(ms[0]) / N_BOXES))
+say("    ay_stain_load_u8 boxes only  : %s per call, %.2f us per box" % (harness.fmt_round(ms[1]), 1e3 * statistics.median(ms[1]) / N_BOXES))
 say("    segments / box pass = %.2f (medians); %d rows with a selected component, median area %d px, median %d positive pixels per window, "
     "flags %d" % (statistics.median(ms[0]) / statistics.median(ms[1]), int((s[:, 7] > 0).sum()), int(np.median(s[s[:, 7] > 0, 7])) if (s[:, 7] > 0).any() else 0,
                   int(np.median(s[:, 5])), int(flags.item())))
 assert not int(flags.item()) and (s[:, 0] == 0).all()
-del strips
+del strips, next_strip
 
 # ---- (b) the worst windows, one per call ----------------------------------------------------------------------------------------------
 n = 255
@@ -153,12 +123,12 @@ def window_call(k):
                                ptr(outs[k]), ptr(flags), sp), "ay_box_segments_u8")
 
 
-ms = timed([lambda k=k: window_call(k) for k in range(len(patterns))], a.reps, a.warm)
+ms = harness.time_calls([lambda k=k: window_call(k) for k in range(len(patterns))], a.warm, a.reps)
 say("(b) one 255 x 255 window per call (one workgroup; two launches)")
 for k, (name, m) in enumerate(patterns):
     o = outs[k].cpu().numpy()[0]
     assert o[0] == 0 and o[5] == int(m.sum()) and o[7] == (int(m.sum()) if m.any() else 0)
-    say("    %-13s: %s, %d positive pixels in one component" % (name, fmt(ms[k]), int(o[7])))
+    say("    %-13s: %s, %d positive pixels in one component" % (name, harness.fmt_round(ms[k]), int(o[7])))
 
 # ---- (c) end to end on a slide in host memory ---------------------------------------------------------------------------------------
 raster = np.concatenate([np.roll(strip_h, 97 * j, 1) for j in range(TY)], 0)
@@ -180,9 +150,7 @@ for what, rws in (("boxes all over the slide ", boxes_in(N_BOXES, SH, SW, 2)), (
                 visited = res["strips"]
                 assert res["flags"] == 0
     for name, v in wall.items():
-        say("    %s %s: %s" % (what, name, fmt(v)))
+        say("    %s %s: %s" % (what, name, harness.fmt_round(v)))
     say("    %s segment_boxes visited %d of %d strips; segment_boxes / stain_load = %.2f (medians)"
         % (what, visited[0], visited[1], statistics.median(wall["segment_boxes"]) / statistics.median(wall["stain_load   "])))
-if a.out:
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+report.write(a.out)

@@ -14,13 +14,9 @@ usage: rocprofv3 --kernel-trace --stats -d DIR -o slide --output-format csv -- p
        python scripts/bench_slide_match.py [--rows 250000] [--targets 50000] [--reps 9] [--kernel-stats DIR] [--out profiles/slide_match.txt]"""
 import argparse
 import ctypes as C
-import os
-import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+import harness
 import torch
 
 from amyloid_yolo_paper_amd import _lib
@@ -38,34 +34,13 @@ ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 -
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def synthetic_slide(M, T, side, seed=0):
-    """T annotations of 8..47 px; four rows in five are jittered sightings of an annotation (several per annotation), the rest
-    boxes of the same sizes anywhere on the slide; three classes, scores in (0.5, 1)"""
-    rng = np.random.default_rng(seed)
-    xy = rng.uniform(0, side, (T, 2))
-    tb = np.concatenate([xy, xy + rng.uniform(8, 47, (T, 2))], 1)
-    cls = rng.integers(0, 3, T)
-    g = rng.integers(0, T, M)
-    box = tb[g] + rng.normal(0, 3.0, (M, 4))
-    anywhere = rng.uniform(size=M) < 0.2
-    p = rng.uniform(0, side, (M, 2))
-    box[anywhere] = np.concatenate([p, p + rng.uniform(8, 47, (M, 2))], 1)[anywhere]
-    rows = np.concatenate([box, rng.uniform(0.5, 1, (M, 2)), cls[g][:, None]], 1).astype(np.float32)
-    return rows, np.concatenate([cls[:, None], tb], 1).astype(np.float32)
-
+report = harness.Report()
+say = report.say
 
 L = _lib.lib()
 dev = torch.device("cuda:0")
 M, T = a.rows, a.targets
-rows_h, targets_h = synthetic_slide(M, T, a.side)
+rows_h, targets_h = harness.slide_rows(M, T, a.side)
 rows, targets = torch.from_numpy(rows_h).to(dev), torch.from_numpy(targets_h).to(dev)
 KMAX = 3
 tp = torch.empty(KMAX, M, device=dev, dtype=torch.uint8)
@@ -85,10 +60,7 @@ def call(thres, roi, cell_side):
 
 
 if a.calls_only:
-    for _ in range(a.calls_only):
-        call([0.3, 0.5, 0.75], None, 0.0)
-    torch.cuda.synchronize()
-    sys.exit(0)
+    harness.calls_only(a.calls_only, lambda: call([0.3, 0.5, 0.75], None, 0.0))
 
 say(f"# ay_slide_match on {torch.cuda.get_device_name(0)}: {M} rows against {T} targets of 8..47 px on a {a.side:.0f}-px square; "
     f"CALL time = {a.reps} x (two events around one call, after {a.warm} warm calls), median [min, max]; it holds the call's host read "
@@ -98,20 +70,10 @@ cases = [("K=1 (0.5)", [0.5], None, 0.0), ("K=3 (0.3, 0.5, 0.75)", [0.3, 0.5, 0.
          ("K=3, cell side 1024", [0.3, 0.5, 0.75], None, 1024.0), ("K=3, cell side 8192", [0.3, 0.5, 0.75], None, 8192.0)]
 ref_bytes = None
 for name, thres, roi, side in cases:
-    for _ in range(a.warm):
-        call(thres, roi, side)
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call(thres, roi, side)
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = harness.time_calls([lambda: call(thres, roi, side)], a.warm, a.reps)[0]
     st = stats.cpu().numpy()
     K = len(thres)
-    say(f"call, {name:38s} {statistics.median(ms):8.3f} ms  [{min(ms):.3f}, {max(ms):.3f}]   eligible / claimed per k: "
+    say(f"call, {name:38s} {harness.fmt_square(ms)}   eligible / claimed per k: "
         f"{[(int(st[2 * k]), int(st[2 * k + 1])) for k in range(K)]}, oversize targets {int(st[2 * K + 1])}")
     if K == 3 and roi is None:   # the cell side must not show in the result
         b = tp.cpu().numpy().tobytes() + claim.cpu().numpy().tobytes() + best_target.cpu().numpy().tobytes() + best_iou.cpu().numpy().tobytes()
@@ -127,17 +89,8 @@ for _ in range(3):
 say(f"stats.match_slide from host arrays, wall: {min(wall):.2f} ms (best of 3; upload of {rows_h.nbytes / 1e6:.1f} + {targets_h.nbytes / 1e6:.1f} MB, "
     f"allocation, call, counts back)")
 if a.kernel_stats:
-    import csv
-    import glob
-    table = list(csv.DictReader(open(glob.glob(os.path.join(a.kernel_stats, "**", "*_kernel_stats.csv"), recursive=True)[0])))
-    ours = [r for r in table if "slide_" in r["Name"] or "grid_" in r["Name"]]   # (the reduction and the scan are ay_box_grid.h's)
-    calls = max(int(r["Calls"]) for r in ours)
+    ours, calls = harness.kernel_table(a.kernel_stats, ["slide_", "grid_"])   # (the reduction and the scan are ay_box_grid.h's)
     say(f"# KERNEL time per call at K=3, from a kernel trace of {calls} calls (mean per dispatch):")
-    for r in sorted(ours, key=lambda r: -float(r["TotalDurationNs"])):
-        say(f"  {r['Name'].split('(')[0][:60]:60s} {float(r['TotalDurationNs']) / calls / 1e3:8.1f} us")
-    say(f"  {'sum of the six kernels':60s} {sum(float(r['TotalDurationNs']) for r in ours) / calls / 1e3:8.1f} us")
+    harness.say_kernel_table(say, ours, calls, "sum of the six kernels")
     say("# for scale: ay_seam_merge takes 0.95 ms of kernels on its 258 633 rows of such boxes (profiles/seam_*.txt)")
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+report.write(a.out)

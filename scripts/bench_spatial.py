@@ -18,12 +18,10 @@ usage: rocprofv3 --kernel-trace --stats -d DIR -o spatial --output-format csv --
        python scripts/bench_spatial.py [--rows 200000] [--reps 9] [--kernel-stats DIR] [--out profiles/spatial.txt]"""
 import argparse
 import ctypes as C
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
@@ -42,22 +40,8 @@ ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 -
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def synthetic_slide(M, side, seed=0):
-    rng = np.random.default_rng(seed)
-    parents = rng.uniform(0, side, (2000, 2))
-    xy = parents[rng.integers(0, 2000, M)] + rng.normal(0, 150.0, (M, 2))
-    loose = rng.uniform(size=M) < 0.25
-    xy[loose] = rng.uniform(0, side, (int(loose.sum()), 2))
-    wh = rng.uniform(8, 60, (M, 2))
-    return np.concatenate([xy - wh / 2, xy + wh / 2, rng.uniform(0.5, 1, (M, 2)), rng.integers(0, 2, (M, 1))], 1).astype(np.float32)
+report = harness.Report()
+say = report.say
 
 
 def visits(rows_h, side, r_max_q, cell_side_q):
@@ -78,7 +62,7 @@ def visits(rows_h, side, r_max_q, cell_side_q):
 L = _lib.lib()
 dev = torch.device("cuda:0")
 M, side, NC, B = a.rows, a.side, 2, 16
-rows_h = synthetic_slide(M, side)
+rows_h = harness.clustered_rows(M, side)
 rows = torch.from_numpy(rows_h).to(dev)
 pairs = torch.empty(NC, NC, B, device=dev, dtype=torch.int64)
 centres = torch.empty(NC, B, device=dev, dtype=torch.int32)
@@ -97,31 +81,13 @@ def workspace(r_max_q, cell_side_q):
     return torch.empty(int(L.ay_pair_counts_workspace_bytes(M, side, side, r_max_q, cell_side_q)), device=dev, dtype=torch.uint8)
 
 
-def timed(fn):
-    for _ in range(a.warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms), min(ms), max(ms)
-
-
 def radii(r_max_px):
     return [4 * r_max_px * (k + 1) // B for k in range(B)]
 
 
 if a.calls_only:
     ws = workspace(4 * a.r_max, 0)
-    for _ in range(a.calls_only):
-        call(radii(a.r_max), 1, 0, ws)
-    torch.cuda.synchronize()
-    sys.exit(0)
+    harness.calls_only(a.calls_only, lambda: call(radii(a.r_max), 1, 0, ws))
 
 say(f"# ay_pair_counts on {torch.cuda.get_device_name(0)}: {M} clustered rows, C = {NC}, B = {B}, on a {side}-px square; CALL time = {a.reps} x "
     f"(two events around one call, after {a.warm} warm calls), median [min, max]; a call is seven kernel launches")
@@ -135,8 +101,9 @@ for r_max in (64, 256, 1024):
         ws = workspace(rq[-1], cs)
         call(rr, 0, cs, ws)
         within = int(pairs.view(-1)[:NC * NC * len(rr)].view(NC, NC, len(rr))[:, :, -1].sum().item())
-        med, lo, hi = timed(lambda: call(rr, 1, cs, ws))
-        say(f"call, {name:20s} {med:8.3f} ms  [{lo:.3f}, {hi:.3f}]   cells {S / 4:g} px ({g} x {g}), partners visited {n_vis:.4g} "
+        ms = harness.time_calls([lambda: call(rr, 1, cs, ws)], a.warm, a.reps)[0]
+        med = statistics.median(ms)
+        say(f"call, {name:20s} {harness.fmt_square(ms)}   cells {S / 4:g} px ({g} x {g}), partners visited {n_vis:.4g} "
             f"({n_vis / (med * 1e-3):.3g} pair tests/s), within r_max {within:.4g} ({within / (med * 1e-3):.3g} /s)")
 
 # the sibling search on the same grid header: every row against every row as a target
@@ -155,8 +122,8 @@ def match():
                            ptr(row_ign), ptr(tgt_ign), ptr(mstats), ptr(mws), mws.numel(), _lib.stream_ptr()), "ay_slide_match")
 
 
-med, lo, hi = timed(match)
-say(f"call, ay_slide_match, the rows as rows and targets, K = 1: {med:8.3f} ms  [{lo:.3f}, {hi:.3f}]   (holds a host read and memsets)")
+ms = harness.time_calls([match], a.warm, a.reps)[0]
+say(f"call, ay_slide_match, the rows as rows and targets, K = 1: {harness.fmt_square(ms)}   (holds a host read and memsets)")
 wall = []
 for _ in range(3):
     torch.cuda.synchronize()
@@ -166,16 +133,7 @@ for _ in range(3):
 say(f"wsi.spatial_stats from host rows at r_max 256 px, wall: {min(wall):.2f} ms (best of 3; upload of {rows_h.nbytes / 1e6:.1f} MB, allocation, "
     f"call, one read-back of {(M * (2 * NC + 2) * 4) / 1e6:.1f} MB, K / L / g / G on the host)")
 if a.kernel_stats:
-    import csv
-    import glob
-    table = list(csv.DictReader(open(glob.glob(os.path.join(a.kernel_stats, "**", "*_kernel_stats.csv"), recursive=True)[0])))
-    ours = [r for r in table if "pair_" in r["Name"] or "grid_" in r["Name"]]
-    calls = max(int(r["Calls"]) for r in ours)
+    ours, calls = harness.kernel_table(a.kernel_stats, ["pair_", "grid_"])
     say(f"# KERNEL time per call at r_max {a.r_max} px, from a kernel trace of {calls} calls (mean per dispatch):")
-    for r in sorted(ours, key=lambda r: -float(r["TotalDurationNs"])):
-        say(f"  {r['Name'].split('(')[0][:60]:60s} {float(r['TotalDurationNs']) / calls / 1e3:8.1f} us")
-    say(f"  {'sum of the seven kernels':60s} {sum(float(r['TotalDurationNs']) for r in ours) / calls / 1e3:8.1f} us")
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+    harness.say_kernel_table(say, ours, calls, "sum of the seven kernels")
+report.write(a.out)

@@ -10,10 +10,9 @@ LAYER TIMES (`--layer-times N`): device events around every convolution launch o
 usage: python scripts/bench_split.py [--batch 8] [--size 1024] [--rounds 4] [--per 5] [--warm 2] [--layers 5] [--layer-times 0]
                                      [--out FILE (appended)]"""
 import argparse
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
@@ -38,13 +37,8 @@ MODES = a.modes.split(",")
 assert MODES[0] == "fp32", "the first mode is the reference of the ratios"
 assert a.rounds * a.per >= 20, "at least 20 timed forwards per mode"
 
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
+report = harness.Report()
+say = report.say
 
 if not torch.cuda.is_available():
     sys.exit("bench_split.py measures on the GPU: no HIP device")
@@ -75,20 +69,9 @@ x = torch.from_numpy(synth.synth_tiles(B, S, start=0)).to(dev)
 say(f"# split-bf16 precisions against precision='fp32' on {torch.cuda.get_device_name(0)}: yolov3-custom ({a.classes} classes), B = {B} at "
     f"{S}^2, one process; {a.warm} warm forwards per mode, then {a.rounds} rounds of [{' | '.join(MODES)}] x {a.per} forwards between "
     f"two device events (forward_device: convolution stack + decode)")
-for p in MODES:
-    for _ in range(a.warm):
-        models[p].forward_device(x)
-torch.cuda.synchronize()
-blocks = {p: [] for p in MODES}
-for _ in range(a.rounds):
-    for p in MODES:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.per):
-            models[p].forward_device(x)
-        e1.record()
-        torch.cuda.synchronize()
-        blocks[p].append(e0.elapsed_time(e1) / a.per)
+forwards = [lambda p=p: models[p].forward_device(x) for p in MODES]
+harness.time_calls(forwards, a.warm, 0)
+blocks = dict(zip(MODES, harness.time_calls(forwards, 0, a.rounds, per=a.per)))
 rate = {p: B * 1e3 * len(blocks[p]) / sum(blocks[p]) for p in MODES}
 for p in MODES:
     ms = blocks[p]
@@ -152,7 +135,4 @@ if a.layer_times:
     for key, v in sorted(shapes.items(), key=lambda kv: -kv[1][2]):
         say(f"{str(key):28s} {v[0]:3d} {v[1]:8.1f} " + " ".join(f"{t:8.3f}" for t in v[2:]) + "  " + " ".join(f"{v[2] / t:11.2f}" for t in v[3:]))
     say("all convolutions" + " " * 25 + " ".join(f"{sum(v[2 + j] for v in shapes.values()):8.3f}" for j in range(len(MODES))))
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "a") as fh:
-        fh.write("\n".join(lines) + "\n")
+report.write(a.out, append=True)

@@ -9,13 +9,11 @@ kernel launches only, so this is launch overhead plus kernel.  The synthetic til
 usage: python scripts/bench_stain.py [TY TX] [--reps 20] [--warm 3] [--detect-reps 3] [--out profiles/stain.txt]"""
 import argparse
 import ctypes as C
-import os
 import statistics
-import sys
 import tempfile
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
@@ -33,36 +31,11 @@ ap.add_argument("--out", default=None)
 a = ap.parse_args()
 TY, TX = a.grid
 tile, S, BG = 1536, 1024, 170
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def timed_pair(first, second):
-    """both calls alternating, REPS times each behind WARM warm rounds -> two lists of milliseconds"""
-    out = ([], [])
-    for i in range(a.warm + a.reps):
-        for k, call in enumerate((first, second)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            e1.synchronize()
-            if i >= a.warm:
-                out[k].append(e0.elapsed_time(e1))
-    return out
-
-
-def fmt(ms):
-    return "%.3f ms (%.3f .. %.3f)" % (statistics.median(ms), min(ms), max(ms))
-
+report = harness.Report()
+say = report.say
 
 dev = torch.device("cuda:0")
-base = (synth.synth_tiles(4, tile, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)     # bench_wsi.py's raster
-row = np.concatenate([base[i % 4] for i in range(TX)], 1)
+row = harness.synthetic_strip(TX, tile)
 raster = np.concatenate([np.roll(row, 97 * j, 1) for j in range(TY)], 0)
 say("raster %s, %.3f GB; tile %d -> %d; %d warm + %d timed calls per side" % (raster.shape, raster.nbytes / 1e9, tile, S, a.warm, a.reps))
 
@@ -81,11 +54,11 @@ params = stain.params
 # ---- 1. the cut ----
 plain = lambda: check(L.ay_ingest_region_tiles_list_u8(ptr(strip), H, W, W * 3, 1, tile, ptr(origins), TX, S, ptr(out), sp), "list")
 mapped = lambda: check(L.ay_ingest_region_tiles_stain_u8(ptr(strip), H, W, W * 3, 1, tile, ptr(origins), TX, ids, 1, ptr(params), S, ptr(out), sp), "stain")
-t_plain, t_stain = timed_pair(plain, mapped)
+t_plain, t_stain = harness.time_calls([plain, mapped], a.warm, a.reps)
 stores = out.numel() * 4
 for name, ms in (("plain list cut", t_plain), ("stain cut     ", t_stain)):
     m = statistics.median(ms)
-    say("CUT    %s: %s per call of %d tiles = %.1f us per tile, %.0f GB/s of stores" % (name, fmt(ms), TX, m * 1e3 / TX, stores / m / 1e6))
+    say("CUT    %s: %s per call of %d tiles = %.1f us per tile, %.0f GB/s of stores" % (name, harness.fmt_round(ms), TX, m * 1e3 / TX, stores / m / 1e6))
 say("CUT    stain / plain = %.2f (medians)" % (statistics.median(t_stain) / statistics.median(t_plain)))
 
 # ---- 2. the statistics ----
@@ -93,10 +66,10 @@ counts = torch.empty(TX, device=dev, dtype=torch.int32)
 hist = torch.zeros(1025, device=dev, dtype=torch.int64)
 tissue = lambda: check(L.ay_tile_tissue_u8(ptr(strip), H, W, W * 3, 1, tile, tile, 1, TX, BG, ptr(counts), sp), "tissue")
 histo = lambda: check(L.ay_stain_hist_u8(ptr(strip), H, W, W * 3, 1, BG, ptr(params), ptr(hist), sp), "hist")
-t_tissue, t_hist = timed_pair(tissue, histo)
+t_tissue, t_hist = harness.time_calls([tissue, histo], a.warm, a.reps)
 reads = strip.numel()
 for name, ms in (("ay_tile_tissue_u8", t_tissue), ("ay_stain_hist_u8 ", t_hist)):
-    say("STATS  %s: %s per strip, %.0f GB/s of reads" % (name, fmt(ms), reads / statistics.median(ms) / 1e6))
+    say("STATS  %s: %s per strip, %.0f GB/s of reads" % (name, harness.fmt_round(ms), reads / statistics.median(ms) / 1e6))
 assert int(hist[1024]) == int(counts.sum()) * (a.warm + a.reps)       # the histogram accumulates; both count the same tissue
 say("STATS  tissue pixels of the strip: %d of %d" % (int(counts.sum()), H * W))
 
@@ -125,6 +98,4 @@ for name, st in (("without stain", None), ("with stain   ", stain)):
     s = statistics.median(wall[st])
     say("DETECT %s: %.3f s (%.3f .. %.3f), %.1f tiles/s, %d rows" % (name, s, min(wall[st]), max(wall[st]), TY * TX / s, rows[st]))
 say("DETECT with / without = %.3f (medians)" % (statistics.median(wall[stain]) / statistics.median(wall[None])))
-if a.out:
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+report.write(a.out)

@@ -1,6 +1,6 @@
 """Cost of the two passes of the stain basis estimate (THE BASIS RULE, include/amyloid_yolo.h) on the synthetic strip of
-scripts/bench_stain.py and scripts/bench_load.py: one resident strip of TX 1536-px tiles, one process, four calls taken in turn inside
-one timed loop:
+scripts/bench_stain.py and scripts/bench_load.py (harness.synthetic_strip): one resident strip of TX 1536-px tiles, one process, four
+calls taken in turn inside one timed loop:
   ay_tile_tissue_u8             one tile row (the floor: a minimum and a compare per pixel)
   ay_stain_hist_u8              the yardstick: the same bytes, both stains unmixed in fp32, two LDS adds per tissue pixel
   ay_stain_moments_u8           pass 1: nine integer multiply-adds per selected pixel in registers, 11 atomics per workgroup
@@ -17,15 +17,13 @@ The ratios between the calls of one run are the yardstick either way.
 usage: timeout 300 python scripts/bench_stain_basis.py [TX] [--reps 20] [--warm 3] [--copies 4] [--out profiles/stain_basis.txt]
        (the whole run takes a few seconds; the time limit keeps a hung device from holding a shared machine)"""
 import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np
 import torch
 
-from amyloid_yolo_paper_amd import _lib, synth, wsi
+from amyloid_yolo_paper_amd import _lib, wsi
 from amyloid_yolo_paper_amd._lib import check, ptr
 from amyloid_yolo_paper_amd.wsi import StainMap
 
@@ -37,31 +35,13 @@ ap.add_argument("--copies", type=int, default=4, help="copies of the strip the c
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 TX, tile, BG, BETA_Q = a.tx, 1536, 170, 154
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def fmt(ms):
-    return "%.3f ms (%.3f .. %.3f)" % (statistics.median(ms), min(ms), max(ms))
-
+report = harness.Report()
+say = report.say
 
 dev = torch.device("cuda:0")
-base = (synth.synth_tiles(4, tile, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)     # bench_stain.py's strip
-strip = torch.from_numpy(np.concatenate([base[i % 4] for i in range(TX)], 1)).to(dev)
-strips = [strip] + [strip.clone() for _ in range(a.copies - 1)]
-turn = [0]
-
-
-def next_strip():
-    """the copy this call reads: the one read longest ago"""
-    turn[0] += 1
-    return ptr(strips[turn[0] % len(strips)])
-
-
+strip = torch.from_numpy(harness.synthetic_strip(TX, tile)).to(dev)
+strips = harness.Rotation(strip, a.copies)
+next_strip = strips.next            # the pointer of the copy this call reads: the one read longest ago
 H, W = strip.shape[:2]
 say("%s: strip %d x %d, %.3f GB; bg_level %d, beta_q %d; %d warm + %d timed rounds; the calls rotate over %d cop%s of the strip"
     % (torch.cuda.get_device_name(0), H, W, strip.numel() / 1e9, BG, BETA_Q, a.warm, a.reps, a.copies,
@@ -90,24 +70,14 @@ calls = [("ay_tile_tissue_u8         ", lambda: check(L.ay_tile_tissue_u8(next_s
          ("ay_stain_moments_u8       ", lambda: pass1(moments)),
          ("ay_stain_direction_hist_u8", lambda: check(L.ay_stain_direction_hist_u8(next_strip(), H, W, W * 3, 1, BG, BETA_Q, *plane, ptr(odq), ptr(dirs), sp),
                                                       "ay_stain_direction_hist_u8"))]
-ms = [[] for _ in calls]
-for i in range(a.warm + a.reps):
-    for k, (_, call) in enumerate(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        if i >= a.warm:
-            ms[k].append(e0.elapsed_time(e1))
+ms = harness.time_calls([call for _, call in calls], a.warm, a.reps)
 reads = strip.numel()
 for k, (name, _) in enumerate(calls):
-    say("%s: %s per strip, %.0f GB/s of reads" % (name, fmt(ms[k]), reads / statistics.median(ms[k]) / 1e6))
+    say("%s: %s per strip, %.0f GB/s of reads" % (name, harness.fmt_round(ms[k]), reads / statistics.median(ms[k]) / 1e6))
 med = [statistics.median(m) for m in ms]
 say("moments / ay_stain_hist_u8 = %.2f, moments / ay_tile_tissue_u8 = %.2f, direction hist / ay_stain_hist_u8 = %.2f, "
     "direction hist / ay_tile_tissue_u8 = %.2f (medians)" % (med[2] / med[1], med[2] / med[0], med[3] / med[1], med[3] / med[0]))
-spread = lambda m: (max(m) - min(m)) / statistics.median(m)
-say("repeat spread (max - min) / median: moments %.1f %%, direction hist %.1f %%" % (100 * spread(ms[2]), 100 * spread(ms[3])))
+say("repeat spread (max - min) / median: moments %.1f %%, direction hist %.1f %%" % (100 * harness.spread(ms[2]), 100 * harness.spread(ms[3])))
 # the passes counted the same pixels
 n = a.warm + a.reps
 tissue = int(counts.sum())
@@ -115,7 +85,4 @@ m, d = moments.cpu().numpy(), dirs.cpu().numpy()
 assert int(hist[1024]) == tissue * n and np.array_equal(m, first * n) and int(first[0]) == tissue
 assert int(d[513]) == int(first[1]) * n == int(d[:513].sum())
 say("tissue pixels of the strip: %d of %d; selected: %d; outside the half plane: %d; the passes agree" % (tissue, H * W, first[1], d[512] // n))
-if a.out:
-    kept = [ln for ln in (open(a.out).read().splitlines() if os.path.exists(a.out) else []) if ln.startswith("normalisation gap")]
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines + kept) + "\n")
+report.write(a.out, keep_prefix="normalisation gap")

@@ -11,8 +11,8 @@ no blob is rightly unwanted.
 --views V (1, 2, 4 or 8; default 1 = off): every tile runs in the first V dihedral views (wsi.detect_region(views=range(V)): 4 = the
 flips, 8 = all); --min-views K keeps the detections at least K views agree on.  The report then counts images (tiles x V) as well,
 and how many tiles leave the NMS LDS paths (more than 1 024 / 4 096 candidates, now that a tile holds V times the rows)."""
-import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sys, time
+import harness
 import numpy as np, torch
 from amyloid_yolo_paper_amd import cfg_gen, synth
 from amyloid_yolo_paper_amd.models import Darknet
@@ -41,9 +41,7 @@ for i, p in synth.synth_params(parse_config.parse_model_config(cfg), seed=7).ite
         if k in p:
             sd[f"module_list.{i}.{name}"].copy_(torch.from_numpy(p[k]))
 m = m.to(dev).eval()
-base = synth.synth_tiles(4, 1536, start=0)                       # [4,3,1536,1536] float
-base = (base * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-row = np.concatenate([base[i % 4] for i in range(TX)], 1)
+row = harness.synthetic_strip(TX, tile)
 raster = np.concatenate([np.roll(row, 97 * j, 1) for j in range(TY)], 0)
 if opts["--blank"] > 0:
     raster[:, (TX - round(opts["--blank"] * TX)) * tile:] = 255

@@ -5,7 +5,7 @@ region_tiles_cut_u8_kernel<V, Origins>, in a trace); 3 repeats x (1 warm call + 
 usage: python scripts/profile_tissue_kernels.py
        rocprofv3 --kernel-trace --stats -d DIR -o tk --output-format csv -- python scripts/profile_tissue_kernels.py
        python scripts/profile_tissue_kernels.py --trace DIR     (per kernel, the dispatch durations of DIR's kernel trace; no GPU)"""
-import os, sys
+import sys
 if "--trace" in sys.argv:
     import csv, glob, collections
     files = glob.glob(sys.argv[sys.argv.index("--trace") + 1] + "/**/*kernel_trace.csv", recursive=True)
@@ -19,15 +19,14 @@ if "--trace" in sys.argv:
         v = sorted(v)
         print("%-70s n=%3d  min %8.1f  median %8.1f  max %8.1f us" % (n[:70], len(v), v[0], v[len(v) // 2], v[-1]))
     sys.exit(0)
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import numpy as np, torch
-from amyloid_yolo_paper_amd import _lib, synth
+from amyloid_yolo_paper_amd import _lib
 from amyloid_yolo_paper_amd._lib import check, ptr
 L = _lib.lib()
 dev = torch.device("cuda:0")
 tile, S, TX = 1536, 1024, 32
-base = (synth.synth_tiles(4, 1536, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-row = np.ascontiguousarray(np.concatenate([base[i % 4] for i in range(TX)], 1))
+row = np.ascontiguousarray(harness.synthetic_strip(TX, tile))
 W = row.shape[1]
 strip = torch.from_numpy(row).to(dev)
 off = torch.empty(row.size + 16, dtype=torch.uint8, device=dev); off[1:1 + row.size] = strip.reshape(-1)
@@ -45,13 +44,8 @@ runs = {
  "grid ingest (the entry without a step)": lambda: check(L.ay_ingest_region_tiles_u8(ptr(strip), tile, W, W * 3, 1, tile, 1, TX, S, ptr(out), sp())),
  "list ingest full grid": lambda: check(L.ay_ingest_region_tiles_list_u8(ptr(strip), tile, W, W * 3, 1, tile, ptr(origins), TX, S, ptr(out2), sp())),
 }
+times = harness.time_calls(list(runs.values()), 0, 3, per=10, lead=1)
 for rep in range(3):
-    for name, f in runs.items():
-        f(); torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(10):
-            f()
-        b.record(); torch.cuda.synchronize()
-        print("rep %d  %-52s %8.1f us per call (events, 10 calls)" % (rep, name, a.elapsed_time(b) * 100), flush=True)
+    for name, ms in zip(runs, times):
+        print("rep %d  %-52s %8.1f us per call (events, 10 calls)" % (rep, name, ms[rep] * 1e3), flush=True)
 print("list == step:", torch.equal(out, out2), " counts[:4]", counts[:4].tolist(), " source bytes", row.size)

@@ -7,7 +7,7 @@ call + 10 calls between two events) each.
 usage: python scripts/profile_views_kernels.py
        rocprofv3 --kernel-trace --stats -d DIR -o vk --output-format csv -- python scripts/profile_views_kernels.py
        python scripts/profile_views_kernels.py --trace DIR     (per kernel, the dispatch durations of DIR's kernel trace; no GPU)"""
-import os, sys
+import sys
 if "--trace" in sys.argv:
     import csv, glob, collections
     files = glob.glob(sys.argv[sys.argv.index("--trace") + 1] + "/**/*kernel_trace.csv", recursive=True)
@@ -21,16 +21,15 @@ if "--trace" in sys.argv:
         v = sorted(v)
         print("%-70s n=%3d  min %8.1f  median %8.1f  max %8.1f us" % (n[:70], len(v), v[0], v[len(v) // 2], v[-1]))
     sys.exit(0)
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 import ctypes as C
 import numpy as np, torch
-from amyloid_yolo_paper_amd import _lib, synth, utils, views
+from amyloid_yolo_paper_amd import _lib, utils, views
 from amyloid_yolo_paper_amd._lib import check, ptr
 L = _lib.lib()
 dev = torch.device("cuda:0")
 tile, S, TX, NT = 1536, 1024, 32, 8
-base = (synth.synth_tiles(4, 1536, start=0) * 255).astype(np.uint8).transpose(0, 2, 3, 1)
-row = np.ascontiguousarray(np.concatenate([base[i % 4] for i in range(TX)], 1))
+row = np.ascontiguousarray(harness.synthetic_strip(TX, tile))
 W = row.shape[1]
 strip = torch.from_numpy(row).to(dev)
 origins = torch.tensor([(i * tile * 4, 0) for i in range(NT)], dtype=torch.int32, device=dev)   # 8 tiles spread over the strip
@@ -78,15 +77,10 @@ runs = {
  "view_votes": votes,
  "view_select": select,
 }
+times = harness.time_calls(list(runs.values()), 0, 3, per=10, lead=1)
 for rep in range(3):
-    for name, f in runs.items():
-        f(); torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(10):
-            f()
-        b.record(); torch.cuda.synchronize()
-        print("rep %d  %-60s %8.1f us per call (events, 10 calls)" % (rep, name[:60], a.elapsed_time(b) * 100), flush=True)
+    for name, ms in zip(runs, times):
+        print("rep %d  %-60s %8.1f us per call (events, 10 calls)" % (rep, name[:60], ms[rep] * 1e3), flush=True)
 ingest((0,))(); torch.cuda.synchronize()
 print("views (0,) == list:", torch.equal(out[:NT], ref), " count", state["r"][2].tolist(), " cand", state["r"][3].tolist(),
       " votes popcount histogram", np.bincount([bin(v).count("1") for v in state["v"].cpu().numpy().ravel()], minlength=9).tolist())
