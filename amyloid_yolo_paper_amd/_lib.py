@@ -4,6 +4,10 @@ The signatures (``_SIGS``) and the ``AY_*`` constants (``CONSTANTS``) are read f
 prototype there and its definition in a ``.hip`` file, and no line here.  Only the structs are restated (tests/test_abi_cpu.py holds
 their fields against the header's).
 
+``include/amyloid_yolo.h`` is a frozen list of prototypes (tests/golden/abi_sigs.json, ``AY_ABI_VERSION``).  Entry points added after
+the freeze are declared in the headers of ``MORE_HEADER_PATHS`` and read into a second table, ``_SIGS_MORE``; their constants join
+``CONSTANTS``, and ``lib()`` binds both tables.
+
 There is no CPU fallback: if the HIP library is missing or a call fails this raises.
 """
 import ctypes as C
@@ -13,6 +17,7 @@ import re
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libamyloid_yolo_hip.so")
 HEADER_PATH = os.path.join(HERE, "..", "include", "amyloid_yolo.h")   # where build.py finds it
+MORE_HEADER_PATHS = (os.path.join(HERE, "..", "include", "amyloid_yolo_spatial_sim.h"),)
 
 
 class ConvDesc(C.Structure):
@@ -99,14 +104,22 @@ def parse_header(text):
     return sigs, constants
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
-        raise AyError(f"{HEADER_PATH} is missing: the ctypes signatures and the AY_* constants are read from it")
-    with open(HEADER_PATH) as f:
+def _read_header(path=None):
+    path = HEADER_PATH if path is None else path
+    if not os.path.exists(path):
+        raise AyError(f"{path} is missing: the ctypes signatures and the AY_* constants are read from it")
+    with open(path) as f:
         return parse_header(f.read())
 
 
 _SIGS, CONSTANTS = _read_header()
+_SIGS_MORE = {}
+for _path in MORE_HEADER_PATHS:
+    _sigs, _constants = _read_header(_path)
+    if set(_sigs) & (set(_SIGS) | set(_SIGS_MORE)) or set(_constants) & set(CONSTANTS):
+        raise AyError(f"{_path} declares a name that an earlier header has")
+    _SIGS_MORE.update(_sigs)
+    CONSTANTS.update(_constants)
 ABI_VERSION = CONSTANTS["AY_ABI_VERSION"]      # lib() compares it with ay_version() of the library it loads
 PLAN_INPUT, PLAN_NONE = CONSTANTS["AY_PLAN_INPUT"], CONSTANTS["AY_PLAN_NONE"]
 (OP_STEM_S2_FUSED, OP_STEM, OP_CONV, OP_RESBLOCK, OP_CONV1X1_CAT, OP_CONCAT_UPSAMPLE, OP_DECODE) = (
@@ -117,6 +130,11 @@ _lib = None
 
 def exported_symbols():
     return sorted(_SIGS)
+
+
+def exported_symbols_more():
+    """the entry points declared behind the frozen header (``MORE_HEADER_PATHS``)"""
+    return sorted(_SIGS_MORE)
 
 
 def lib():
@@ -133,7 +151,7 @@ def lib():
         if have != ABI_VERSION:   # a stale .so would take e.g. ay_plan_create's out pointer for a dtype: refuse it before any call
             raise AyError(f"{LIB_PATH} exports ABI version {have}, this binding needs {ABI_VERSION}: rebuild it "
                           "(python -m amyloid_yolo_paper_amd.build --force)")
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_MORE.items()):
             fn = getattr(l, name)  # AttributeError here = header/library mismatch
             fn.restype = res
             fn.argtypes = args

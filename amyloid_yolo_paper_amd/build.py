@@ -35,7 +35,7 @@ def _stale(target, deps):
 
 def build_library(force=False, verbose=True):
     hipcc = _hipcc()
-    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "amyloid_yolo.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", h) for h in ("amyloid_yolo.h", "amyloid_yolo_spatial_sim.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

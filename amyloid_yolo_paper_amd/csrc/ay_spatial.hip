@@ -50,9 +50,26 @@
 //   The decomposition first built kept, per mask cell, the nearest OUT row above and below (8 bytes a cell, one more kernel): on a
 //   16-px mask writing them was the largest part of what the window added.  Reading the words in the distance kernel instead makes
 //   the call faster at small radii and leaves it level at large ones, with 1/64 of the workspace (profiles/spatial_window.txt).
+//
+// RELABEL: THE RELABEL RULE (ay_pair_counts_relabel; stated in include/amyloid_yolo_spatial_sim.h, restated by tests/
+// spatial_envelope_reference.py): the counts of THE PAIR RULE (or THE PAIR WINDOW RULE) under S labellings of the counted rows, given as
+// a table uint8 [M][stride] in row order.  Positions, bd, eligibility and the pairs within every radius are those of one labelling, so
+// the front end is the plain call's up to the scatter (steps 1 .. 3, with a, b in front when there is a mask; the count kernel's
+// centres go to the workspace), the sorted arrays sqx, sqy, skmax, sorig are used as they are, and two kernels stand in for step 4.
+// Both read the table only through sorig.
+//   5. relabel_centres_kernel: per simulation and label the histogram of the rows' largest k (LDS, a lane per simulation), its suffix
+//      sum = the eligible centres, and the rows with bd >= 0.
+//   6. relabel_search_kernel: ONE pair walk for all simulations.  A wavefront per centre, its 64 lanes 64 simulations; the geometry
+//      of a partner is wave-uniform, its 64 labels one read of 64 bytes; a lane books the pair in its own LDS column [la][lb][k] as
+//      +1 at the first bin and -1 behind the centre's last, and the prefix sum over k at the flush goes to sim_pairs (64-bit atomics).
+//      LDS: a column has A x C x B int32 entries, at most 256 = 64 KiB for one wavefront; relabel_plan says which shapes keep all C
+//      centre labels in the column (C x C x B <= 256: C = 2 at every B, C = 3 up to B = 28, C = 4 up to B = 16, C = 8 up to B = 4)
+//      and which walk the pairs in passes over the centre's label.  At C = 2, B = 16 a wavefront takes 16 KiB, a workgroup of four 64
+//      KiB: two workgroups, eight wavefronts per CU of 160 KiB.  Cost: profiles/spatial_envelope.txt.
 #include <limits.h>
 
 #include "ay_box_grid.h"
+#include "../../include/amyloid_yolo_spatial_sim.h"
 
 namespace ay {
 
@@ -431,8 +448,190 @@ __global__ void __launch_bounds__(PAIR_THREADS) __attribute__((amdgpu_num_sgpr(9
     }
 }
 
+// ---- THE RELABEL RULE (ay_pair_counts_relabel; the header of this file, RELABEL): the two kernels behind the scatter
+constexpr int RELABEL_LANES = 64;            // the simulations of a chunk: the lanes of a wavefront
+constexpr int RELABEL_COLUMN = 256;          // the int32 entries of one lane's column that 64 KiB of LDS hold for one wavefront
+constexpr int RELABEL_LDS = RELABEL_COLUMN * RELABEL_LANES * 4;
+constexpr int RELABEL_WAVES = PAIR_THREADS / 64;
+constexpr int RELABEL_UNROLL = 4;            // partner label reads in flight per wavefront
+constexpr int RELABEL_ROWS = 1024;           // sorted rows of one workgroup of relabel_centres_kernel
+constexpr int RELABEL_FLUSH = 1 << 30;       // pairs a wavefront books between two flushes (see relabel_search_kernel)
+constexpr int RELABEL_BLOCKS = 1024;         // the search's workgroups, all chunks and passes together: 256 CUs x 4
+
+struct PairRelabel {
+    const uint8_t* labels;
+    int S, stride;
+    int64_t* sim_pairs;
+    int32_t *sim_centres, *sim_inside;
+};
+
+// which shapes take which path.  A lane's column holds [A][C][B] entries, A the centre classes of one pass: A = C (one pass, every
+// pair walked once) where C * C * B <= 256, else the largest A with A * C * B <= 256 and ceil(C / A) passes over the pair walk, each
+// booking the centres labelled a0 .. a0 + A - 1 (A = 1 at C = 8, B = 32: eight passes, a column of exactly 256 entries).  C * B <=
+// 256 always, so every legal shape has a plan.  A workgroup has as many wavefronts (1 .. 4) as 64 KiB hold columns for.
+struct RelabelPlan {
+    int A, passes, cols, waves, chunks;   // cols = A * C * B entries of a lane's column
+    size_t lds() const { return (size_t)waves * cols * RELABEL_LANES * 4; }
+};
+static inline RelabelPlan relabel_plan(int C, int B, int S) {
+    RelabelPlan p;
+    p.A = RELABEL_COLUMN / (C * B) < C ? RELABEL_COLUMN / (C * B) : C;
+    p.passes = (C + p.A - 1) / p.A;
+    p.cols = p.A * C * B;
+    p.waves = RELABEL_COLUMN / p.cols < RELABEL_WAVES ? RELABEL_COLUMN / p.cols : RELABEL_WAVES;
+    p.chunks = (S + RELABEL_LANES - 1) / RELABEL_LANES;
+    return p;
+}
+// the simulations of one workgroup of relabel_centres_kernel: its table [C][B + 1][SL] must fit 64 KiB (not at C = 8, B = 32 with 64)
+static inline int relabel_centres_sims(int C, int B) { return C * (B + 1) * RELABEL_LANES * 4 <= RELABEL_LDS ? RELABEL_LANES : RELABEL_LANES / 2; }
+
+// per simulation s and class a: the counted rows labelled a that are eligible at k (a histogram over the rows' largest k in LDS, a
+// suffix sum at the end) and those with bd >= 0.  A workgroup takes RELABEL_ROWS sorted rows and SL simulations; a lane is a
+// simulation (with SL = 32 the two halves of a wavefront take two rows).  A row with kmax >= 0 has bd >= R_0 > 0 under the border
+// rule and bd >= 0 without it, so `inside` is the histogram's total plus the rows with kmax < 0 and bd >= 0 (slot B).  A label >= C
+// on a counted row books nothing and sets AY_PAIR_RELABEL_FLAG_LABEL.
+__global__ void __launch_bounds__(PAIR_THREADS) relabel_centres_kernel(int C, int B, int SL, const int32_t* __restrict__ cell_start, int n_cells,
+                                                                        const int8_t* __restrict__ skmax, const int32_t* __restrict__ sorig,
+                                                                        const int32_t* __restrict__ bd, const uint8_t* __restrict__ labels, int S,
+                                                                        int stride, int32_t* __restrict__ sim_centres, int32_t* __restrict__ sim_inside,
+                                                                        int32_t* __restrict__ stats) {
+    extern __shared__ int relabel_tab[];   // [C][B + 1][SL]
+    __shared__ int bad;
+    const int n = cell_start[n_cells], base = blockIdx.x * RELABEL_ROWS, end = min(base + RELABEL_ROWS, n);
+    if (base >= n) return;
+    const int tid = threadIdx.x, per_wave = RELABEL_LANES / SL, sl = tid & (SL - 1), s = blockIdx.y * SL + sl;
+    for (int e = tid; e < C * (B + 1) * SL; e += PAIR_THREADS) relabel_tab[e] = 0;
+    if (tid == 0) bad = 0;
+    __syncthreads();
+    if (s < S) {
+        for (int p = base + (tid >> 6) * per_wave + (tid & 63) / SL; p < end; p += RELABEL_WAVES * per_wave) {
+            const int kmax = skmax[p], i = sorig[p];
+            const int la = labels[(size_t)i * stride + s];
+            if (la >= C) atomicOr(&bad, 1);
+            else if (kmax >= 0) atomicAdd(&relabel_tab[(la * (B + 1) + kmax) * SL + sl], 1);
+            else if (bd[i] >= 0) atomicAdd(&relabel_tab[(la * (B + 1) + B) * SL + sl], 1);
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < SL * C; e += PAIR_THREADS) {   // (the simulation moves fastest: the reads of a wavefront take 64 banks)
+        const int l = e & (SL - 1), a = e / SL, sim = blockIdx.y * SL + l;
+        if (sim >= S) continue;
+        int run = 0;
+        for (int k = B - 1; k >= 0; --k) {   // eligible at k: every row whose largest k is k or more
+            run += relabel_tab[(a * (B + 1) + k) * SL + l];
+            if (run) atomicAdd(&sim_centres[((size_t)sim * C + a) * B + k], run);
+        }
+        run += relabel_tab[(a * (B + 1) + B) * SL + l];
+        if (run) atomicAdd(&sim_inside[(size_t)sim * C + a], run);
+    }
+    if (tid == 0 && bad) atomicOr(&stats[2 * C + 2], AY_PAIR_RELABEL_FLAG_LABEL);
+}
+
+// a lane's column: prefix sums over k of every [slot][b], added to the simulation's pairs with 64-bit atomics, and zeroed
+__device__ __forceinline__ void relabel_flush(int* __restrict__ acc, int lane, int A, int a0, int C, int B, bool live, int s, int64_t* __restrict__ sim_pairs) {
+    for (int slot = 0; slot < A && a0 + slot < C; ++slot)
+        for (int b = 0; b < C; ++b) {
+            int run = 0;
+            unsigned long long* out = (unsigned long long*)sim_pairs + (((size_t)s * C + (a0 + slot)) * C + b) * B;
+            for (int k = 0; k < B; ++k) {
+                const int e = ((slot * C + b) * B + k) * RELABEL_LANES + lane;
+                run += acc[e];
+                acc[e] = 0;
+                if (live && run) atomicAdd(out + k, (unsigned long long)run);
+            }
+        }
+}
+
+// the pair walk of pair_search_kernel with a WAVEFRONT per centre and a simulation per lane (chunk blockIdx.y of 64 simulations, pass
+// blockIdx.z over the centre's label: relabel_plan).  The partners of a run are taken 64 at a time, a lane each: d2 on integers and
+// the first bin k as the number of squared radii below d2 (32 compares against kernel arguments: no table, the LDS is the columns').
+// The partners with k <= kmax of the centre are then walked one by one, wave-uniform (ballot, readlane): a partner's 64 labels are
+// one coalesced read of 64 bytes, RELABEL_UNROLL partners in flight.  Lane s adds +1 at [la - a0][lb][k] and -1 at [..][kmax + 1]
+// (nothing behind the last bin) of ITS OWN column acc[entry][lane] in LDS: the prefix sum over k at the flush is the pair's share of
+// the bins k .. kmax.  No lane reads another's words, so there is no barrier, and with the lane as the fastest index no bank
+// conflict; the adds are LDS add instructions without a result, not read-modify-write chains.
+// NO COUNTER WRAPS.  Every booked pair moves one entry of a column by +1 and at most one by -1, so after n pairs every entry and every
+// prefix sum lies in -n .. n.  `booked` counts the partners a wavefront walked since its last flush (wave-uniform, an upper bound for
+// every lane); it is tested after every 64 partners, so a wavefront flushes before it passes RELABEL_FLUSH + 64 + RELABEL_UNROLL < 2^31,
+// and once more at its end.
+__global__ void __launch_bounds__(PAIR_THREADS) relabel_search_kernel(PairRadii rad, int r_max, int C, int A, PairGrid g, const int32_t* __restrict__ cell_start,
+                                                                       const int32_t* __restrict__ sqx, const int32_t* __restrict__ sqy,
+                                                                       const int8_t* __restrict__ skmax, const int32_t* __restrict__ sorig,
+                                                                       const uint8_t* __restrict__ labels, int S, int stride,
+                                                                       int64_t* __restrict__ sim_pairs) {
+    extern __shared__ int relabel_acc[];   // [waves][A][C][B][64]
+    const int B = rad.n, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), waves = blockDim.x >> 6;
+    const int cols = A * C * B, a0 = blockIdx.z * A, s = blockIdx.y * RELABEL_LANES + lane;
+    const bool live = s < S;
+    int* acc = relabel_acc + (size_t)wave * cols * RELABEL_LANES;
+    for (int e = 0; e < cols; ++e) acc[e * RELABEL_LANES + lane] = 0;
+    const int n = cell_start[g.n_cells()];   // the counted rows
+    int booked = 0;
+    for (int p = blockIdx.x * waves + wave; p < n; p += gridDim.x * waves) {
+        const int kmax = skmax[p];
+        if (kmax < 0) continue;   // (wave-uniform) eligible nowhere: no centre
+        const int qxi = sqx[p], qyi = sqy[p], i = sorig[p];
+        const int la = live ? labels[(size_t)i * stride + s] : 255;
+        const int slot = la - a0;
+        const bool mine = la < C && slot >= 0 && slot < A;   // (a label >= C: no centre in this simulation)
+        if (__ballot(mine) == 0) continue;                   // no simulation of the chunk has this centre in the pass
+        const int cx = qxi / g.S, cy = qyi / g.S;
+        const int xa = max(cx - 1, 0), xb = min(cx + 1, g.gx - 1);
+        int lo[3], hi[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int y = cy - 1 + r;
+            const bool in = y >= 0 && y < g.gy;
+            lo[r] = in ? cell_start[y * g.gx + xa] : 0;
+            hi[r] = in ? cell_start[y * g.gx + xb + 1] : 0;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            for (int q0 = lo[r]; q0 < hi[r]; q0 += RELABEL_LANES) {
+                const int q = q0 + lane;
+                int dx = 0, dy = 0, j = 0;
+                bool hit = q < hi[r] && q != p;
+                if (hit) dx = sqx[q] - qxi, dy = sqy[q] - qyi, j = sorig[q];
+                hit = hit && abs(dx) <= r_max && abs(dy) <= r_max;   // (then both squares fit int32)
+                const int d2 = hit ? dx * dx + dy * dy : 0;
+                int k = 0;   // the number of radii with R_k^2 < d2: the partner's first bin (B beyond the largest radius)
+#pragma unroll
+                for (int t = 0; t < AY_PAIR_MAX_RADII; ++t) k += (rad.r[t] <= AY_PAIR_MAX_RADIUS_Q ? rad.r[t] * rad.r[t] : INT_MAX) < d2 ? 1 : 0;
+                unsigned long long m = __ballot(hit && k <= kmax);
+                while (m) {   // (wave-uniform)
+                    int jj[RELABEL_UNROLL], kk[RELABEL_UNROLL], lb[RELABEL_UNROLL];
+                    bool valid[RELABEL_UNROLL];
+                    int l = 0;
+#pragma unroll
+                    for (int u = 0; u < RELABEL_UNROLL; ++u) {
+                        valid[u] = m != 0;
+                        if (m) l = __builtin_ctzll(m), m &= m - 1;
+                        jj[u] = __builtin_amdgcn_readlane(j, l), kk[u] = __builtin_amdgcn_readlane(k, l);   // (past the last: the one before again)
+                    }
+#pragma unroll
+                    for (int u = 0; u < RELABEL_UNROLL; ++u) lb[u] = live ? labels[(size_t)jj[u] * stride + s] : 255;
+#pragma unroll
+                    for (int u = 0; u < RELABEL_UNROLL; ++u) {
+                        if (valid[u] && mine && lb[u] < C) {   // (a label >= C: no partner in this simulation)
+                            int* col = acc + (size_t)((slot * C + lb[u]) * B) * RELABEL_LANES + lane;
+                            __hip_atomic_fetch_add(col + kk[u] * RELABEL_LANES, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            if (kmax + 1 < B) __hip_atomic_fetch_add(col + (kmax + 1) * RELABEL_LANES, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                    }
+                    booked += RELABEL_UNROLL;
+                }
+                if (booked >= RELABEL_FLUSH) {   // (wave-uniform; between two partners, each booked whole)
+                    relabel_flush(acc, lane, A, a0, C, B, live, s, sim_pairs);
+                    booked = 0;
+                }
+            }
+        }
+    }
+    relabel_flush(acc, lane, A, a0, C, B, live, s, sim_pairs);
+}
+
 struct PairWs {
-    int32_t *cell_of, *row_ck, *sqx, *sqy, *sorig, *cell_start, *cursor, *chunk_sum, *wbd;
+    int32_t *cell_of, *row_ck, *sqx, *sqy, *sorig, *cell_start, *cursor, *chunk_sum, *wbd, *obs_centres;
     int2* row_q;
     unsigned long long* bits;
     uint8_t* scls;
@@ -441,7 +640,7 @@ struct PairWs {
 };
 
 // mask: the mask grid of the window call, NULL for the plain call (whose workspace is then what it was)
-static PairWs pair_carve(void* ws, int n_rows, size_t n_cells, const PairMask* mask) {
+static PairWs pair_carve(void* ws, int n_rows, size_t n_cells, const PairMask* mask, bool relabel = false) {
     PairWs w;
     WsCarver cv(ws);
     const size_t m = (size_t)(n_rows > 0 ? n_rows : 1);
@@ -461,6 +660,7 @@ static PairWs pair_carve(void* ws, int n_rows, size_t n_cells, const PairMask* m
         w.wbd = cv.take<int32_t>(m);
         w.bits = cv.take<unsigned long long>((size_t)mask->gx * mask->n_chunks());
     }
+    w.obs_centres = relabel ? cv.take<int32_t>(AY_PAIR_MAX_CLASSES * AY_PAIR_MAX_RADII) : nullptr;   // the count kernel's centres [C][B]
     w.bytes = cv.bytes();
     return w;
 }
@@ -475,20 +675,21 @@ static inline unsigned pair_blocks(long long n, long long cap) {
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-static size_t pair_workspace_bytes(int n_rows, int H, int W, int r_max, int cell_side, bool windowed, int mask_cell) {
+static size_t pair_workspace_bytes(int n_rows, int H, int W, int r_max, int cell_side, bool windowed, int mask_cell, bool relabel = false) {
     PairGrid g;
     PairMask mg;
     if (!pair_dims_ok(n_rows, H, W, r_max, cell_side) || !pair_grid(n_rows, H, W, r_max, cell_side, &g)) return 0;
     if (windowed && !pair_mask_grid(H, W, mask_cell, &mg)) return 0;
-    return pair_carve(nullptr, n_rows, (size_t)g.n_cells(), windowed ? &mg : nullptr).bytes;
+    return pair_carve(nullptr, n_rows, (size_t)g.n_cells(), windowed ? &mg : nullptr, relabel).bytes;
 }
 
-// both entry points: `who` names the one in the messages; windowed adds the two kernels of THE PAIR WINDOW RULE and hands their
-// wbd to the count kernel
+// the three entry points: `who` names the one in the messages; windowed adds the two kernels of THE PAIR WINDOW RULE and hands their
+// wbd to the count kernel.  With `rl` (ay_pair_counts_relabel) pairs, centres and nn are NULL: the front end is the same up to the
+// scatter (the count kernel's centres go to the workspace), and the two relabel kernels stand in for pair_search_kernel.
 static int pair_counts_run(const char* who, bool windowed, const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf,
                            const int32_t* radii_q, int n_radii, const int32_t* roi_q, int border, int cell_side_q, const uint8_t* mask, int mask_cell,
                            int64_t* pairs, int32_t* centres, int32_t* nn, int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes,
-                           ay_stream_t stream) {
+                           ay_stream_t stream, const PairRelabel* rl = nullptr) {
     const int M = n_rows, C = num_classes, B = n_radii, H = slide_h, W = slide_w;
     AY_CHECK_ARG(M >= 0 && (M == 0 || rows), "%s: n_rows %d%s", who, M, rows ? "" : " with null rows");
     AY_CHECK_ARG(C >= 1 && C <= AY_PAIR_MAX_CLASSES, "%s: num_classes %d outside 1 .. %d", who, C, AY_PAIR_MAX_CLASSES);
@@ -516,15 +717,31 @@ static int pair_counts_run(const char* who, bool windowed, const float* rows, in
                      AY_PAIR_WINDOW_MIN_CELL, AY_PAIR_MAX_SIDE);
         AY_CHECK_ARG(pair_mask_grid(H, W, mask_cell, &mg), "%s: mask_cell %d gives more than 2^26 mask cells on a %d x %d slide", who, mask_cell, H, W);
     }
-    AY_CHECK_ARG(pairs && centres && stats && workspace && (M == 0 || (nn && bd)), "%s: null output or workspace", who);
+    if (rl) {
+        AY_CHECK_ARG(rl->S >= 1 && rl->S <= AY_PAIR_RELABEL_MAX_SIMS, "%s: n_sims %d outside 1 .. %d", who, rl->S, AY_PAIR_RELABEL_MAX_SIMS);
+        AY_CHECK_ARG(rl->stride >= rl->S, "%s: label_stride %d below n_sims %d", who, rl->stride, rl->S);
+        AY_CHECK_ARG(M == 0 || rl->labels, "%s: null labels", who);
+        AY_CHECK_ARG(rl->sim_pairs && rl->sim_centres && rl->sim_inside && stats && workspace && (M == 0 || bd), "%s: null output or workspace", who);
+    } else {
+        AY_CHECK_ARG(pairs && centres && stats && workspace && (M == 0 || (nn && bd)), "%s: null output or workspace", who);
+    }
     const int n_cells = g.n_cells();
-    const PairWs w = pair_carve(workspace, M, (size_t)n_cells, windowed ? &mg : nullptr);
+    const PairWs w = pair_carve(workspace, M, (size_t)n_cells, windowed ? &mg : nullptr, rl != nullptr);
     AY_CHECK_ARG(workspace_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.bytes);
     AY_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace not 16-byte aligned", who);
     hipStream_t st = S(stream);
-    const long long n_nn = (long long)M * C * 2;
-    const long long most = n_nn > n_cells + 2 ? n_nn : n_cells + 2;
-    hipLaunchKernelGGL(pair_fill_kernel, dim3(pair_blocks(most, 4096)), dim3(PAIR_THREADS), 0, st, w.cell_start, w.cursor, n_cells + 2, pairs, C * C * B,
+    long long n_nn = (long long)M * C * 2;
+    int n_pairs = C * C * B;
+    if (rl) {   // the simulations' pairs are zeroed where the plain call zeroes its own; the other two outputs by a second launch
+        pairs = rl->sim_pairs, n_pairs *= rl->S, centres = w.obs_centres, nn = nullptr, n_nn = 0;
+        hipLaunchKernelGGL(pair_fill_kernel, dim3(pair_blocks((long long)rl->S * C * B, 4096)), dim3(PAIR_THREADS), 0, st, (int32_t*)nullptr,
+                           (int32_t*)nullptr, 0, (int64_t*)nullptr, 0, rl->sim_centres, rl->S * C * B, rl->sim_inside, rl->S * C, (int32_t*)nullptr, 0ll,
+                           (int32_t*)nullptr, 0);
+        AY_CHECK_LAUNCH("pair_fill_kernel");
+    }
+    const long long cells_or_rows = (long long)M > n_cells + 2 ? (long long)M : n_cells + 2;
+    const long long most = rl ? (n_pairs > cells_or_rows ? n_pairs : cells_or_rows) : (n_nn > n_cells + 2 ? n_nn : n_cells + 2);
+    hipLaunchKernelGGL(pair_fill_kernel, dim3(pair_blocks(most, 4096)), dim3(PAIR_THREADS), 0, st, w.cell_start, w.cursor, n_cells + 2, pairs, n_pairs,
                        centres, C * B, stats, 2 * C + 3, nn, n_nn, bd, M);
     AY_CHECK_LAUNCH("pair_fill_kernel");
     if (M > 0) {
@@ -551,6 +768,21 @@ static int pair_counts_run(const char* who, bool windowed, const float* rows, in
         hipLaunchKernelGGL(pair_scatter_kernel, dim3(rblocks), dim3(PAIR_THREADS), 0, st, M, (const int32_t*)w.cell_of, (const int32_t*)w.cell_start,
                            w.cursor, (const int2*)w.row_q, (const int32_t*)w.row_ck, w.sqx, w.sqy, w.scls, w.skmax, w.sorig);
         AY_CHECK_LAUNCH("pair_scatter_kernel");
+        if (rl) {
+            const int SL = relabel_centres_sims(C, B);
+            hipLaunchKernelGGL(relabel_centres_kernel, dim3((unsigned)(((long long)M + RELABEL_ROWS - 1) / RELABEL_ROWS), (unsigned)((rl->S + SL - 1) / SL)),
+                               dim3(PAIR_THREADS), (size_t)C * (B + 1) * SL * 4, st, C, B, SL, (const int32_t*)w.cell_start, n_cells, (const int8_t*)w.skmax,
+                               (const int32_t*)w.sorig, (const int32_t*)bd, rl->labels, rl->S, rl->stride, rl->sim_centres, rl->sim_inside, stats);
+            AY_CHECK_LAUNCH("relabel_centres_kernel");
+            const RelabelPlan pl = relabel_plan(C, B, rl->S);
+            const long long want = ((long long)M + pl.waves - 1) / pl.waves, cap = RELABEL_BLOCKS / (pl.chunks * pl.passes);
+            const unsigned bx = (unsigned)(want < 1 ? 1 : (want > cap ? (cap < 1 ? 1 : cap) : want));
+            hipLaunchKernelGGL(relabel_search_kernel, dim3(bx, (unsigned)pl.chunks, (unsigned)pl.passes), dim3(64 * pl.waves), pl.lds(), st, rad, r_max, C,
+                               pl.A, g, (const int32_t*)w.cell_start, (const int32_t*)w.sqx, (const int32_t*)w.sqy, (const int8_t*)w.skmax,
+                               (const int32_t*)w.sorig, rl->labels, rl->S, rl->stride, rl->sim_pairs);
+            AY_CHECK_LAUNCH("relabel_search_kernel");
+            return AY_OK;
+        }
         hipLaunchKernelGGL(pair_search_kernel, dim3(pair_blocks((long long)M * PAIR_GROUP, PAIR_SEARCH_BLOCKS)), dim3(PAIR_THREADS), pair_search_lds(C, B), st, rad,
                            r_max, C, g, (const int32_t*)w.cell_start, (const int32_t*)w.sqx, (const int32_t*)w.sqy, (const uint8_t*)w.scls,
                            (const int8_t*)w.skmax, (const int32_t*)w.sorig, pairs, nn);
@@ -582,4 +814,21 @@ extern "C" int ay_pair_counts_window(const float* rows, int n_rows, int num_clas
                                      size_t workspace_bytes, ay_stream_t stream) {
     return ay::pair_counts_run("ay_pair_counts_window", true, rows, n_rows, num_classes, slide_h, slide_w, min_conf, radii_q, n_radii, roi_q, border,
                                cell_side_q, mask, mask_cell, pairs, centres, nn, bd, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t ay_pair_counts_relabel_workspace_bytes(int n_rows, int num_classes, int n_radii, int slide_h, int slide_w, int r_max_q,
+                                                         int cell_side_q, int mask_cell, int n_sims) {
+    if (num_classes < 1 || num_classes > AY_PAIR_MAX_CLASSES || n_radii < 1 || n_radii > AY_PAIR_MAX_RADII || n_sims < 1 ||
+        n_sims > AY_PAIR_RELABEL_MAX_SIMS)
+        return 0;
+    return ay::pair_workspace_bytes(n_rows, slide_h, slide_w, r_max_q, cell_side_q, mask_cell != 0, mask_cell, true);
+}
+
+extern "C" int ay_pair_counts_relabel(const float* rows, int n_rows, int num_classes, int slide_h, int slide_w, float min_conf,
+                                      const int32_t* radii_q, int n_radii, const int32_t* roi_q, int border, int cell_side_q, const uint8_t* mask,
+                                      int mask_cell, const uint8_t* labels, int n_sims, int label_stride, int64_t* sim_pairs, int32_t* sim_centres,
+                                      int32_t* sim_inside, int32_t* bd, int32_t* stats, void* workspace, size_t workspace_bytes, ay_stream_t stream) {
+    const ay::PairRelabel rl = {labels, n_sims, label_stride, sim_pairs, sim_centres, sim_inside};
+    return ay::pair_counts_run("ay_pair_counts_relabel", mask != nullptr, rows, n_rows, num_classes, slide_h, slide_w, min_conf, radii_q, n_radii, roi_q,
+                               border, cell_side_q, mask, mask_cell, nullptr, nullptr, nullptr, bd, stats, workspace, workspace_bytes, stream, &rl);
 }

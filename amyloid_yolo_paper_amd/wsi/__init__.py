@@ -36,6 +36,7 @@ the tests and benchmark scripts reach as ``wsi._x``):
   ``burden``    :func:`burden_map`, :func:`densest_fields` (THE BURDEN RULE, THE FIELD RULE)
   ``spatial``   :func:`spatial_stats`: pair counts, Ripley's K and L, g, nearest neighbours (THE PAIR RULE); :func:`window_from_tissue`:
                 a tissue-shaped window for them (THE PAIR WINDOW RULE)
+                :func:`spatial_envelope`, :func:`relabel_table`: the band of K and L under random labelling (THE RELABEL RULE)
   ``colour``    :class:`StainBasis`, :class:`StainStats`, :class:`StainMap`: the host side of THE STAIN RULE
   ``stain``     :func:`stain_stats`, :func:`normalize_region`: its passes
   ``basis``     :func:`estimate_basis`: the slide's own two stain vectors (THE BASIS RULE)
@@ -62,7 +63,9 @@ from .sampler import SlideBatchPlan, SlideSampler  # noqa: F401
 from .segment import (SEG_COLS, SEG_EMPTY, SEG_INTERNAL, SEG_LARGE, SEG_MAX_MARGIN, SEG_MAX_SIDE, SEG_NONFINITE, SEG_NOT_RESIDENT,  # noqa: F401
                       plaque_morphometry, segment_boxes)
 from .spatial import (PAIR_MAX_CLASSES, PAIR_MAX_RADII, PAIR_MAX_RADIUS_Q, PAIR_MAX_SIDE, PAIR_WINDOW_MAX_CELLS, PAIR_WINDOW_MIN_CELL,  # noqa: F401
-                      pair_counts_device, spatial_radii_q, spatial_roi_q, spatial_stats, spatial_summaries, window_area, window_from_tissue)
+                      PAIR_RELABEL_FLAG_LABEL, PAIR_RELABEL_MAX_SIMS, envelope_summaries, pair_counts_device, pair_counts_relabel_device,
+                      relabel_keys, relabel_table, spatial_envelope, spatial_radii_q, spatial_roi_q, spatial_stats, spatial_summaries,
+                      window_area, window_from_tissue)
 from .stain import normalize_region, stain_stats  # noqa: F401
 from .stream import RegionTileStream, StripStream  # noqa: F401
 from .tissue import tissue_counts, tissue_mask  # noqa: F401

@@ -13,13 +13,15 @@ from .focus import _check_focus, focus_map, focus_summary
 from .grid import _whole, check_raster, probed
 from .load import stain_load
 from .segment import _check_segment, plaque_morphometry, segment_boxes
+from . import spatial as _spatial
 from .spatial import PAIR_MAX_CLASSES, _check_spatial, _window_cell, spatial_stats, window_from_tissue
 from .tissue import tissue_counts
 
 
 def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=0.5, mpp=None, min_conf=0.0, stain_stats=None,
                     dab_thres=None, load=False, focus=False, min_sharpness=None, segment=False, seg_margin=None, core_thres=None,
-                    min_area=None, spatial_radii=None, spatial_window=False, spatial_min_tissue=0.5, **detect_region_kwargs):
+                    min_area=None, spatial_radii=None, spatial_window=False, spatial_min_tissue=0.5, spatial_envelope=None, spatial_seed=0,
+                    spatial_rank=1, **detect_region_kwargs):
     """What a slide carries: :func:`detect_region`, then per class the count map, the tissue of every map cell and the densest fields.
 
     1. Runs ``detect_region(model, raster, **detect_region_kwargs)`` unchanged and concatenates its ``(ty, tx, boxes)`` result in
@@ -85,7 +87,11 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
        ``window_from_tissue(tissue, (H, W), cell, spatial_min_tissue)``, a bool map [Gy,Gx] of the cells that are IN, and ``spatial``
        = ``spatial_stats(..., window=spatial_window, window_cell=cell)`` (THE PAIR WINDOW RULE): a row is a centre at a radius only
        if its whole disc lies over IN cells, ``area`` is the window's area and ``inside`` counts the rows in IN cells, so that the
-       intensity belongs to the same window.  ``spatial_window=False`` is the result as it was.
+       intensity belongs to the same window.  ``spatial_window=False`` is the result as it was.  With ``spatial_envelope`` = the
+       number of simulations (only with ``spatial_radii``; a model of two classes at least) also ``spatial_envelope`` =
+       ``spatial_envelope(rows, (H, W), spatial_radii, C, spatial_envelope, spatial_seed, spatial_rank, min_conf, ...)`` with the
+       window and area that ``spatial`` gets: the band of K and L under random relabelling of the classes and the global test
+       ``p_mad`` (THE RELABEL RULE; see :func:`spatial_envelope` for what that null is).  ``None`` is the result as it was.
 
     The numbers are counts and areas; mapping them to CERAD categories is a clinical choice and not made here."""
     if not segment and not (seg_margin is None and core_thres is None and min_area is None):
@@ -143,9 +149,13 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         _window_cell("quantify_region", (H, W), cell)
         if isinstance(spatial_min_tissue, bool) or not 0.0 <= float(spatial_min_tissue) <= 1.0:       # a NaN fails both comparisons
             raise ValueError(f"quantify_region: spatial_min_tissue {spatial_min_tissue!r} is no fraction of a cell")
+    if spatial_envelope is not None:
+        if spatial_radii is None:
+            raise ValueError("quantify_region: spatial_envelope needs spatial_radii")
+        _spatial._check_envelope("quantify_region", spatial_envelope, spatial_seed, spatial_rank)
     num_classes = int(model.yolo_layers[0].num_classes)
     if spatial_radii is not None:
-        _whole(num_classes, 1, PAIR_MAX_CLASSES, "quantify_region: the model's classes (spatial statistics)")
+        _whole(num_classes, 2 if spatial_envelope is not None else 1, PAIR_MAX_CLASSES, "quantify_region: the model's classes (spatial statistics)")
     rows = cat_rows(detect_region(model, raster, **detect_region_kwargs))
     view, s, t, _ = probed(raster, cell, shrink, 0, d)
     tissue = tissue_counts(view, t, s, 0, bg_level) * np.int32(d * d)
@@ -194,6 +204,10 @@ def quantify_region(model, raster, cell=128, field=8, top_k=5, field_min_tissue=
         out["spatial"] = spatial_stats(rows, (H, W), spatial_radii, num_classes, min_conf, mpp=mpp, window=out["spatial_window"], window_cell=cell)
     elif spatial_radii is not None:
         out["spatial"] = spatial_stats(rows, (H, W), spatial_radii, num_classes, min_conf, area=int(tissue.sum(dtype=np.int64)), mpp=mpp)
+    if spatial_envelope is not None:       # the window and the area that `spatial` got
+        how = dict(window=out["spatial_window"], window_cell=cell) if spatial_window else dict(area=int(tissue.sum(dtype=np.int64)))
+        out["spatial_envelope"] = _spatial.spatial_envelope(rows, (H, W), spatial_radii, num_classes, spatial_envelope, spatial_seed, spatial_rank,
+                                                            min_conf, mpp=mpp, **how)
     if mpp is not None:
         mm2 = lambda px: np.where(px > 0, px, np.nan).astype(np.float64) * float(mpp) ** 2 * 1e-6      # NaN where there is no tissue
         out["density_per_mm2"] = bm["counts"].cpu().numpy().astype(np.float64) / mm2(tissue)[None]

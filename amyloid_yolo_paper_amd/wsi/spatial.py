@@ -1,6 +1,7 @@
 """Spatial statistics: :func:`spatial_stats` counts the cross-class pairs of a slide's detections within every radius and finds every
 row's nearest neighbour of every class (``ay_pair_counts``, THE PAIR RULE), and turns them into Ripley's K and L, the pair correlation
-and the nearest-neighbour distribution on the host."""
+and the nearest-neighbour distribution on the host.  :func:`spatial_envelope` holds the observed K and L against the band of random
+labellings of the same positions (``ay_pair_counts_relabel``, THE RELABEL RULE): one pair walk for all simulations."""
 import ctypes as C
 import math
 
@@ -17,6 +18,8 @@ PAIR_MAX_CLASSES, PAIR_MAX_RADII, PAIR_MAX_RADIUS_Q, PAIR_MAX_SIDE = (          
     _lib.CONSTANTS["AY_PAIR_" + n] for n in ("MAX_CLASSES", "MAX_RADII", "MAX_RADIUS_Q", "MAX_SIDE"))
 PAIR_WINDOW_MIN_CELL, PAIR_WINDOW_MAX_CELLS = (                                                 # THE PAIR WINDOW RULE
     _lib.CONSTANTS["AY_PAIR_WINDOW_" + n] for n in ("MIN_CELL", "MAX_CELLS"))
+PAIR_RELABEL_MAX_SIMS, PAIR_RELABEL_FLAG_LABEL = (                                              # include/amyloid_yolo_spatial_sim.h, THE RELABEL RULE
+    _lib.CONSTANTS["AY_PAIR_RELABEL_" + n] for n in ("MAX_SIMS", "FLAG_LABEL"))
 
 
 def spatial_radii_q(radii):
@@ -240,23 +243,43 @@ def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, 
     uses.  With ``window`` the outline's RESOLUTION is the mask cell (16 px at the finest): a cell is in or out as a whole.  And the
     COST is the number of pairs within 3 x 3 grid cells of side ``r_max``: quadratic in ``r_max`` at a given density.
 
-    Out of scope: Monte-Carlo envelopes (random relabelling of the classes is the natural follow-up) and per-field statistics (pass a
-    field as ``roi=``)."""
+    Whether an observed ``K[a][b]`` means anything is :func:`spatial_envelope`'s question: the band of K and L under random
+    relabelling of the classes, and a global test.  Out of scope: per-field statistics (pass a field as ``roi=``)."""
+    return _spatial_run("spatial_stats", rows, slide_hw, radii, num_classes, min_conf, roi, border, area, mpp, window, window_cell)[0]
+
+
+def _counted_label(rows, num_classes, min_conf):
+    """THE PAIR RULE's tests on device rows [M,7], as torch launches: int32 [M], the class of every counted row and -1 for the others
+    (two fp32 operations for the centre, comparisons after them: the same decisions as the kernels')"""
+    cx, cy, lab = (rows[:, 0] + rows[:, 2]) * 0.5, (rows[:, 1] + rows[:, 3]) * 0.5, rows[:, 6]
+    ok = torch.isfinite(cx) & torch.isfinite(cy) & (lab >= 0) & (lab < num_classes) & (lab == torch.floor(lab))
+    ok &= rows[:, 4] >= float(np.float32(min_conf))                    # (the kernels take min_conf as fp32)
+    return torch.where(ok, lab, torch.full_like(lab, -1.0)).to(torch.int32)
+
+
+def _spatial_run(what, rows, slide_hw, radii, num_classes, min_conf, roi, border, area, mpp, window, window_cell, counted_labels=False):
+    """:func:`spatial_stats` -> (its dict, labels, context).  With ``counted_labels`` the label piece of the one read-back holds the
+    class of the COUNTED rows (-1 for the others) and ``labels`` is that int array [M]; ``context`` is what a second call on the same
+    rows needs (:func:`spatial_envelope`)."""
     given_area = area
-    H, W, nc, rq, roi_q, area = _check_spatial("spatial_stats", slide_hw, radii, num_classes, roi, area, mpp)
-    window, mask, cell = _check_window("spatial_stats", (H, W), window, window_cell)
-    check_rows("spatial_stats", rows)
+    H, W, nc, rq, roi_q, area = _check_spatial(what, slide_hw, radii, num_classes, roi, area, mpp)
+    window, mask, cell = _check_window(what, (H, W), window, window_cell)
+    check_rows(what, rows)
     min_conf = float(min_conf)
     dev = hip_device("the spatial statistics have")
     rows = _slide_array(rows, 7, dev)
     M = int(rows.shape[0])
+    on_dev = None
     if mask is not None:
         w_area = window_area(mask, (H, W), cell, roi_q)
         area = w_area if given_area is None else area
         on_dev = window if torch.is_tensor(window) and window.device == rows.device else torch.from_numpy(mask.view(np.uint8)).to(rows.device)
-        dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border, 0, on_dev.contiguous(), cell)
+        on_dev = on_dev.contiguous()
+        dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border, 0, on_dev, cell)
     else:
         dv = pair_counts_device(rows, (H, W), rq, nc, min_conf, roi_q, border)
+    if counted_labels and M:
+        dv["label"].copy_(_counted_label(rows, nc, min_conf))
     host = dv["buf"].cpu()                                              # the one read-back
     off = lambda t: (t.data_ptr() - dv["buf"].data_ptr()) // 4
     take = lambda t: host[off(t):off(t) + t.numel() * t.element_size() // 4]
@@ -264,11 +287,187 @@ def spatial_stats(rows, slide_hw, radii, num_classes=2, min_conf=0.0, roi=None, 
     centres, st = take(dv["centres"]).view(nc, len(rq)).numpy().copy(), take(dv["stats"]).numpy().copy()
     bd, nn = take(dv["bd"]).numpy().copy(), take(dv["nn"]).view(M, nc, 2).numpy().copy()
     d2 = nn[:, :, 0].astype(np.float64)
-    labels = np.where(bd >= 0, take(dv["label"]).numpy(), -1)          # G asks rows with bd >= R_k >= 1 only: those are counted
+    all_labels = take(dv["label"]).numpy().copy()
+    labels = np.where(bd >= 0, all_labels, -1)                         # G asks rows with bd >= R_k >= 1 only: those are counted
     out = {"pairs": pairs, "centres": centres, "nn": nn, "nn_index": nn[:, :, 1].copy(), "nn_distance": np.where(d2 >= 0, np.sqrt(np.abs(d2)) / 4.0, np.nan),
            "bd": bd, "counted": st[:nc].copy(), "inside": st[nc:2 * nc].copy(), "below": int(st[2 * nc]), "flagged": int(st[2 * nc + 1]),
            "flags": int(st[2 * nc + 2]), "radii": rq / 4.0, "radii_q": rq, "roi_q": roi_q, "area": area}
     if mask is not None:
         out["window_area"] = w_area
     out.update(spatial_summaries(pairs, centres, out["inside"], bd, nn, rq, area, mpp, labels))
+    context = {"rows": rows, "slide_hw": (H, W), "num_classes": nc, "radii_q": rq, "roi_q": roi_q, "border": border, "min_conf": min_conf,
+               "window": on_dev, "window_cell": cell, "area": area}
+    return out, all_labels, context
+
+
+# ---- THE RELABEL RULE (include/amyloid_yolo_spatial_sim.h): the label table on the host, the device call, the envelopes ------------------
+_MASK64 = (1 << 64) - 1
+_KEY_SIM, _KEY_ROW, _KEY_MIX1, _KEY_MIX2 = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+
+
+def relabel_keys(seed, s, n):
+    """THE RELABEL RULE's keys of simulation ``s`` for the counted rows t = 0 .. n-1: a uint64 array, all arithmetic modulo 2**64"""
+    z = np.uint64((int(seed) + int(s) * _KEY_SIM) & _MASK64) + np.arange(n, dtype=np.uint64) * np.uint64(_KEY_ROW)      # (arrays wrap silently)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(_KEY_MIX1)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(_KEY_MIX2)
+    return z ^ (z >> np.uint64(31))
+
+
+def _check_envelope(what, n_sim, seed, rank):
+    """the host checks of the simulation arguments -> (n_sim, seed, rank)"""
+    n_sim = _whole(n_sim, 1, PAIR_RELABEL_MAX_SIMS - 1, f"{what}: n_sim")
+    rank = _whole(rank, 1, max(n_sim // 2, 1), f"{what}: rank")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= _MASK64:
+        raise ValueError(f"{what}: seed {seed!r} is no integer in 0 .. 2**64 - 1")
+    return n_sim, int(seed), rank
+
+
+def relabel_table(labels, num_classes, n_sim, seed):
+    """The label table of THE RELABEL RULE: uint8 [M, n_sim + 1].  ``labels`` int [M] is the class of every counted row, in row order,
+    and -1 (or any value outside 0 .. C-1) for a row that is not counted: such a row gets 255 in every column.  Column 0 is the
+    observed labelling; column s >= 1 deals the observed classes out again by the rank of the rows' keys (a pure function of
+    ``(seed, s, t)``, t the row's position among the counted rows): a uniform permutation, so every column keeps the class totals.
+    Host NumPy: one stable argsort of uint64 keys per simulation."""
+    nc = _whole(num_classes, 1, PAIR_MAX_CLASSES, "relabel_table: num_classes")
+    n_sim, seed, _ = _check_envelope("relabel_table", n_sim, seed, 1)
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.dtype.kind not in "iu":
+        raise ValueError(f"relabel_table: labels {lab.dtype} {lab.shape} is no integer array [M]")
+    lab = lab.astype(np.int64)
+    idx = np.flatnonzero((lab >= 0) & (lab < nc))
+    observed = lab[idx]
+    table = np.full((len(lab), n_sim + 1), 255, np.uint8)
+    table[idx, 0] = observed
+    by_rank = np.sort(observed, kind="stable").astype(np.uint8)         # rank r holds the class c with cum_c <= r < cum_{c+1}
+    col = np.empty(len(idx), np.uint8)
+    for s in range(1, n_sim + 1):
+        col[np.argsort(relabel_keys(seed, s, len(idx)), kind="stable")] = by_rank
+        table[idx, s] = col
+    return table
+
+
+def pair_counts_relabel_device(rows, slide_hw, radii_q, num_classes, table, min_conf=0.0, roi_q=None, border=True, cell_side_q=0, window=None,
+                               window_cell=0):
+    """``ay_pair_counts_relabel`` on rows that live on the device (float32 [M,7], contiguous) and a label table uint8 [M, S] (a device
+    tensor, or a host array that is uploaded; 1 <= S <= 1024) -> a dict of int tensors on the device, all views of ONE buffer ``buf``:
+    ``sim_pairs`` int64 [S,C,C,B], ``sim_centres`` int32 [S,C,B], ``sim_inside`` int32 [S,C], ``stats`` int32 [2C+3], ``bd`` int32
+    [M].  The table's stride is padded to a multiple of 64 (with 255), so that the 64 labels a wavefront reads of a row are one
+    aligned line.  One call, launches only: nothing is read back here.  ``window`` / ``window_cell`` as :func:`pair_counts_device`
+    takes them (THE PAIR WINDOW RULE); ``cell_side_q`` does not show in the result."""
+    H, W = slide_hw
+    M, nc = int(rows.shape[0]), int(num_classes)
+    rq = np.ascontiguousarray(radii_q, np.int32)
+    B = len(rq)
+    tab = table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table, np.uint8))
+    if tab.dtype != torch.uint8 or tab.dim() != 2 or int(tab.shape[0]) != M:
+        raise ValueError(f"pair_counts_relabel_device: table must be uint8 [{M}, S], got {tab.dtype} {tuple(tab.shape)}")
+    S = int(tab.shape[1])
+    stride = max((S + 63) & ~63, 64)
+    padded = torch.full((max(M, 1), stride), 255, device=rows.device, dtype=torch.uint8)
+    if M and S:
+        padded[:M, :S] = tab.to(rows.device)
+    L = _lib.lib()
+    sizes = [2 * S * nc * nc * B, S * nc * B, S * nc, 2 * nc + 3, M]
+    offs = np.concatenate([[0], np.cumsum([(n + 3) & ~3 for n in sizes])])       # every piece starts on 16 bytes
+    buf = torch.empty(max(int(offs[-1]), 4), device=rows.device, dtype=torch.int32)
+    piece = [buf[int(o):int(o) + n] for o, n in zip(offs[:-1], sizes)]
+    out = {"buf": buf, "sim_pairs": piece[0].view(torch.int64).view(S, nc, nc, B), "sim_centres": piece[1].view(S, nc, B),
+           "sim_inside": piece[2].view(S, nc), "stats": piece[3], "bd": piece[4], "labels": padded}
+    i32p = C.POINTER(C.c_int32)
+    roi_arg = None if roi_q is None else np.ascontiguousarray(roi_q, np.int32).ctypes.data_as(i32p)
+    mask, cell = None, 0
+    if window is not None:
+        cell = int(window_cell)
+        gy, gx = -(-H // max(cell, 1)), -(-W // max(cell, 1))
+        if not torch.is_tensor(window) or window.device != rows.device or window.dtype not in (torch.uint8, torch.bool) or \
+                tuple(window.shape) != (gy, gx) or not window.is_contiguous():
+            raise ValueError(f"pair_counts_relabel_device: window must be a contiguous uint8 or bool tensor [{gy}, {gx}] on {rows.device}")
+        mask = window.view(torch.uint8) if window.dtype == torch.bool else window
+    need = int(L.ay_pair_counts_relabel_workspace_bytes(M, nc, B, H, W, int(rq[-1]) if B else 0, int(cell_side_q), cell, S))
+    ws = torch.empty(max(need, 16), device=rows.device, dtype=torch.uint8)
+    check(L.ay_pair_counts_relabel(ptr(rows) if M else None, M, nc, H, W, C.c_float(min_conf), rq.ctypes.data_as(i32p), B, roi_arg, int(bool(border)),
+                                   int(cell_side_q), ptr(mask), cell, ptr(padded), S, stride, ptr(out["sim_pairs"]), ptr(out["sim_centres"]),
+                                   ptr(out["sim_inside"]), ptr(out["bd"]) if M else None, ptr(out["stats"]), ptr(ws), need, _lib.stream_ptr()),
+          "ay_pair_counts_relabel")
+    return out
+
+
+def envelope_summaries(sim_pairs, sim_centres, sim_inside, radii_q, area, rank):
+    """The host formulas of :func:`spatial_envelope`, float64, from the counts of the S + 1 patterns (index 0: the observed one)."""
+    pairs, centres, inside = np.asarray(sim_pairs, np.float64), np.asarray(sim_centres, np.float64), np.asarray(sim_inside, np.float64)
+    n = len(pairs) - 1
+    r = np.asarray(radii_q, np.int64) / 4.0
+    with np.errstate(all="ignore"):
+        intensity = inside / area if area > 0 else np.full(inside.shape, np.nan)
+        den = centres[:, :, None, :] * intensity[:, None, :, None]
+        K = np.where(den > 0, pairs / den, np.nan)
+        LR = np.sqrt(K / math.pi) - r
+
+        def band(v):        # the rank-th smallest and largest over the simulations, NaN where any simulation is NaN
+            v = np.sort(v[1:], axis=0)                                  # (NaN sorts last)
+            bad = np.isnan(v[-1])
+            return np.where(bad, np.nan, v[rank - 1]), np.where(bad, np.nan, v[n - rank])
+
+        K_lo, K_hi = band(K)
+        L_lo, L_hi = band(LR)
+        total = np.zeros(LR.shape[1:])
+        for s in range(n + 1):                                          # in this order: the sum is the same float on every run
+            total = total + LR[s]
+        Lbar = total / (n + 1)
+        finite = np.isfinite(LR).all(0)                                 # the radii where every pattern is finite
+        T = np.where(finite[None], np.abs(LR - Lbar[None]), -np.inf).max(-1)
+        some = finite.any(-1)
+        T = np.where(some[None], T, np.nan)
+        p_mad = np.where(some, (1 + (T[1:] >= T[0][None]).sum(0)) / (n + 1), np.nan)
+        out = {"K_sim": K, "L_minus_r_sim": LR, "K_lo": K_lo, "K_hi": K_hi, "L_lo": L_lo, "L_hi": L_hi, "K_mean": K[1:].mean(0),
+               "L_mean": LR[1:].mean(0), "outside": (LR[0] > L_hi) | (LR[0] < L_lo), "T": T, "p_mad": p_mad}
+    return out
+
+
+def spatial_envelope(rows, slide_hw, radii, num_classes=2, n_sim=99, seed=0, rank=1, min_conf=0.0, roi=None, border=True, area=None, mpp=None,
+                     window=None, window_cell=None):
+    """Random-labelling envelopes for :func:`spatial_stats`: is an observed ``K[a][b]`` more than its class densities predict?
+
+    THE NULL.  The positions are FIXED and the labels EXCHANGEABLE: every simulation keeps every counted row where it is and deals the
+    observed classes out again among the counted rows, uniformly at random (THE RELABEL RULE, ``include/amyloid_yolo_spatial_sim.h``;
+    the class totals stay).  For ``a != b`` this tests whether the two classes are labelled independently of where they lie (do CAA
+    vessels and cored plaques occur together more often than their densities predict); for ``a == b`` whether class a is a random
+    subset of all objects.  It does NOT test complete spatial randomness: objects that cluster as a whole give a flat result here as
+    long as the classes are mixed at random among them.  The band ``*_lo .. *_hi`` is POINTWISE: at each radius on its own a share
+    ``alpha_pointwise`` of null patterns falls outside it, and over many radii far more do somewhere; it is no simultaneous band.
+    ``p_mad`` is the simultaneous test.
+
+    Arguments as :func:`spatial_stats`, with ``num_classes`` >= 2, ``n_sim`` = S in 1 .. 1023 simulations, ``seed`` in 0 .. 2**64 - 1
+    (the table is a pure function of it) and ``rank`` in 1 .. max(S // 2, 1); ``ValueError`` otherwise, before any launch.  Runs
+    :func:`spatial_stats` unchanged for the observed pattern, builds the label table on the host (:func:`relabel_table`: column 0 the
+    observed labelling, from that call's read-back), makes ONE more call for all S + 1 labellings (``ay_pair_counts_relabel``: the
+    pair walk is shared, only the class indices a pair is booked under differ) and reads back once more; the rest is float64 on the
+    host.
+
+    Returns a dict: ``observed`` (the dict of :func:`spatial_stats`), ``sim_pairs`` int64 [S+1,C,C,B], ``sim_centres`` int32
+    [S+1,C,B], ``sim_inside`` int32 [S+1,C] (index 0 is the observed pattern), ``n_sim``, ``seed``, ``rank``, ``flags`` (of the
+    relabel call); ``K_sim`` and ``L_minus_r_sim`` [S+1,C,C,B] with ``K_s = pairs_s / (centres_s[a,k] * inside_s[b] / area)``, NaN
+    where the denominator is 0 (``K_sim[0]`` equals ``observed["K"]``); ``K_lo``, ``K_hi`` and ``L_lo``, ``L_hi`` (of ``L - r``): the
+    ``rank``-th smallest and largest over the simulations 1 .. S, NaN where any simulation is NaN; ``K_mean``, ``L_mean`` over the
+    simulations; ``alpha_pointwise = 2 rank / (S + 1)``; ``outside`` bool [C,C,B]: the observed ``L - r`` above ``L_hi`` or below
+    ``L_lo``; and the global maximum-absolute-deviation test: with ``Lbar`` the mean of ``L_minus_r_sim`` over all S + 1 patterns,
+    ``T[s,a,b] = max_k |L_minus_r_sim[s] - Lbar|`` over the radii at which every pattern is finite, and ``p_mad[a,b] = (1 + #{s >= 1:
+    T_s >= T_0}) / (S + 1)``, NaN where there is no such radius.
+
+    Out of scope: envelopes for g and G (G needs the nearest neighbours of every simulation), simulations of complete spatial
+    randomness (new positions inside the window), and a label table made on the device."""
+    nc = _whole(num_classes, 2, PAIR_MAX_CLASSES, "spatial_envelope: num_classes (two classes at least)")
+    n_sim, seed, rank = _check_envelope("spatial_envelope", n_sim, seed, rank)
+    observed, labels, cx = _spatial_run("spatial_envelope", rows, slide_hw, radii, nc, min_conf, roi, border, area, mpp, window, window_cell, True)
+    table = relabel_table(labels, nc, n_sim, seed)
+    dv = pair_counts_relabel_device(cx["rows"], cx["slide_hw"], cx["radii_q"], nc, table, cx["min_conf"], cx["roi_q"], cx["border"], 0, cx["window"],
+                                    cx["window_cell"])
+    host = dv["buf"].cpu()                                              # the second read-back
+    S1, B = n_sim + 1, len(cx["radii_q"])
+    off = lambda t: (t.data_ptr() - dv["buf"].data_ptr()) // 4
+    take = lambda t: host[off(t):off(t) + t.numel() * t.element_size() // 4]
+    out = {"observed": observed, "sim_pairs": take(dv["sim_pairs"]).view(torch.int64).view(S1, nc, nc, B).numpy().copy(),
+           "sim_centres": take(dv["sim_centres"]).view(S1, nc, B).numpy().copy(), "sim_inside": take(dv["sim_inside"]).view(S1, nc).numpy().copy(),
+           "n_sim": n_sim, "seed": seed, "rank": rank, "flags": int(take(dv["stats"])[2 * nc + 2]), "alpha_pointwise": 2.0 * rank / (n_sim + 1)}
+    out.update(envelope_summaries(out["sim_pairs"], out["sim_centres"], out["sim_inside"], cx["radii_q"], cx["area"], rank))
     return out

@@ -845,6 +845,8 @@ int ay_field_select(const int32_t* counts, int num_classes, int gy, int gx, cons
  *     bd int32 [M]: bd_i; -1 for rows not counted and for any negative value.  stats int32 [2C + 3] = rows counted per class, counted
  *     rows with bd_i >= 0 per class, rows below, rows flagged, flag bits; sum(stats[:C]) + below + flagged == M.
  *   Integer sums and minima with an index tie-break: a function of the inputs alone, the same bytes on every run.
+ *   THE RELABEL RULE (include/amyloid_yolo_spatial_sim.h, ay_pair_counts_relabel) counts the same pairs under many labellings of the
+ *   counted rows at once: the null band of random labelling that an observed K[a][b] is held against.
  *
  * ay_pair_counts: rows and every output on the device; radii_q (n_radii int32) and roi_q (4 int32, or NULL) on the HOST: they travel
  *   as kernel arguments.  Kernel launches only -- no memset node, no allocation, no host read, no synchronisation -- so the call can
